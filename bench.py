@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s (+ Mrays/s) of the MI355X wavefront path tracer on BASELINE.json's configs.
 
-    python bench.py --gpus N --steps K --warmup W          (N = 1: plain process)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N = 1: plain process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 The timed workload (`value`, `config.workload`) is the one BASELINE.json's north star quotes its targets on: C4 =
@@ -10,10 +10,14 @@ and it is the same workload for every N so that the N = 1 value of a scaling run
 A step is one whole frame: every rank renders its interleaved row bands of the frame on its own GPU (scene already
 resident in HBM), copies them to the host and rank 0 assembles the frame (shared-memory frame, or a gloo gather; no RCCL:
 pixels are independent).  Total work is fixed as N grows, so scaling is reported as "strong".
-At N = 1 the same run also times C2 and C3 at full size and C5 on a stated 64-spp slice (fewer steps) and reports them under
-`other_configs`.  After the timed loop — outside the timed region, like the `cpu_baseline` leg — the oracle renders a 64 x 8
-window of the LAST TIMED FRAME at the workload's full strata and the line carries `parity_window` (bit-exact or not, max
-per-pixel L2 error); a failed window makes the process exit non-zero after the line is printed.
+A plain run sets up, warms up, times exactly K frames and prints the headline (`value`, `ms_per_step`, the stage times of
+the timed frames).  `--dump-outputs DIR` writes the last timed frame to DIR/frame.npy (float32) before the line is printed;
+with the same arguments the scene and the seed, hence the frame, are the same from run to run.
+`--full` adds everything beyond the headline, each outside the timed region: one untimed frame with the pass overlap off
+(`stages_ms_serial`) and one instrumented frame (ray counts, `roofline`); at N = 1 C2 and C3 at full size and C5 on a stated
+64-spp slice (fewer steps) under `other_configs`, and the `cpu_baseline` leg; and the oracle renders a 64 x 8 window of the
+LAST TIMED FRAME at the workload's full strata, so that the line carries `parity_window` (bit-exact or not, max per-pixel L2
+error); a failed window makes the process exit non-zero after the line is printed.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -35,6 +39,8 @@ PARITY_WINDOWS = {"c1": (96, 120, 64, 8), "c2": (480, 500, 64, 8), "c3": (300, 7
                   "c4xl": (900, 600, 64, 8)}
 # configs timed on a stated slice of their spp when they ride along in `other_configs` (samples are i.i.d. passes: SURVEY.md §8d)
 ALSO_STRATA = {"c5": (8, 8)}
+# --dump-outputs writes at most this many bytes; a larger frame is written as a fixed, seeded sample of its pixels
+DUMP_LIMIT = 64 << 20
 
 
 def parse():
@@ -43,7 +49,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default=DEFAULT_CONFIG, help="c1..c5 (BASELINE.json configs[0..4]); default c4 = the north-star workload; c4xl = C4's generator at 16.8 M triangles (not a BASELINE config)")
-    ap.add_argument("--also", default=None, help="comma-separated configs timed after the main one at N = 1 (default: c2,c3,c5 when --config is c4; c5 on a 64-spp slice)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: serial-stage and instrumented frames, roofline, other configs, CPU baseline and the oracle's parity window")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed frame to DIR/frame.npy (float32)")
+    ap.add_argument("--also", default=None, help="with --full: comma-separated configs timed after the main one at N = 1 (default: c2,c3,c5 when --config is c4; c5 on a 64-spp slice)")
     ap.add_argument("--also-steps", type=int, default=2)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -53,8 +62,8 @@ def parse():
     ap.add_argument("--samples-per-pass", type=int, default=0)
     ap.add_argument("--integrator", default="path", choices=["path", "direct"],
                     help="path = src/pathintegrator.rs (the BASELINE metric); direct = direct_lighting_integrator (src/directlighting.rs:14-47)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-window", action="store_true", help="skip the oracle's window of the timed frame (developer A/B runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity-window", action="store_true", help="with --full: skip the oracle's window of the timed frame (developer A/B runs)")
     ap.add_argument("--cpu-sample", type=int, nargs=3, default=None, metavar=("W", "H", "MSAA"), help="CPU baseline sample (default per config)")
     ap.add_argument("--allow-shared-gpus", action="store_true",
                     help="rehearsal only: let more ranks than visible GPUs share devices round-robin (the JSON then says so)")
@@ -117,6 +126,21 @@ def parity_window(config_name, frame, window, sx, sy, depth, seed, integrator="p
     return {"rect": [x0, y0, w, h], "spp": sx * sy, "strata": [sx, sy], "samples": int(ost["samples"]), "bit_exact": exact,
             "max_l2": float(l2.max()), "tolerance_l2": 1e-4, "oracle_panics": int(ost["panics"]), "oracle_s": dt,
             "frame": "the last frame of the timed loop", "window_mean_radiance": [float(x) for x in ref.reshape(-1, 3).mean(axis=0)]}
+
+
+def dump_outputs(out_dir, frame):
+    """The frame as <out_dir>/frame.npy (float32, H x W x RGB).  A frame larger than DUMP_LIMIT is written as a fixed, seeded
+    sample of its pixels instead: frame.npy (K x RGB) and their row-major indices, frame_pixel_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    k = (DUMP_LIMIT - 4096) // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "frame.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
 
 
 def device_identity(torch, ordinal):
@@ -190,8 +214,9 @@ class Workload:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def measure(self, steps, warmup):
-        """W untimed frames, then exactly `steps` frames between barriers; returns rank 0's report (None elsewhere)."""
+    def measure(self, steps, warmup, full=True):
+        """W untimed frames, then exactly `steps` frames between barriers; returns rank 0's report (None elsewhere) and keeps
+        the last timed frame in `self.timed_frame` (rank 0).  Without `full` the report is the headline of the timed frames alone."""
         from pbrs_amd import roofline
         torch, dist, world, rank = self.torch, self.dist, self.world, self.rank
         # the first frame allocates the path state (tens of GB): it is never a timed one, whatever --warmup says
@@ -229,6 +254,11 @@ class Workload:
             t = torch.tensor([elapsed, gather_ms], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed, gather_ms = float(t[0].item()), float(t[1].item())
+        self.timed_frame = timed_frame
+        if not full:
+            if rank != 0:
+                return None
+            return self.headline(steps, elapsed, stage_ms, launches, gather_ms, per_frame, per_rank)
 
         # Untimed: one frame with every pass on one stream, for per-stage milliseconds that are exclusive times (in the timed frames a pass's
         # late bounces run on a second stream beside the next pass's first bounces: their event brackets overlap and do not add up)
@@ -254,11 +284,11 @@ class Workload:
         frames_agree = bool((np.isnan(frame) == np.isnan(timed_frame)).all() and
                             (frame.view(np.uint32)[~np.isnan(frame)] == timed_frame.view(np.uint32)[~np.isnan(timed_frame)]).all())
 
+        line = self.headline(steps, elapsed, stage_ms, launches, gather_ms, per_frame, per_rank)
+        times = line["stages_ms_per_step"]
         samples_per_step = float(W) * H * spp
         assert counts[2] == samples_per_step, (counts, samples_per_step)
         rays_per_step = counts[0] + counts[1]
-        times = {k: v / steps for k, v in stage_ms.items()}
-        times.update({k: v // steps for k, v in launches.items()})
         # HBM bytes per launch cannot be collected in-process (rocprofv3 owns the counters): the last measured figures for
         # this workload are read from profiles/ (tools/round_artifacts.sh -> tools/traffic_from_pmc.py), full-size runs only.
         traffic_doc, traffic_src = None, None
@@ -297,18 +327,7 @@ class Workload:
         n_b = [float(x) for x in counts[5:5 + nb]]
         s_b = [float(x) for x in counts[5 + nb:5 + 2 * nb]]
         last = max([i for i, x in enumerate(n_b) if x > 0] + [0])
-        return {
-            "value": samples_per_step * steps / elapsed / 1e6,
-            "unit": "Msamples/s",
-            "steps": steps,
-            "ms_per_step": elapsed / steps * 1e3,
-            "config": {"workload": (f"BASELINE configs[{int(self.name[1]) - 1}] ({self.name})" if self.name in ("c1", "c2", "c3", "c4", "c5") else
-                                    f"{self.name} (not a BASELINE config: C4's generator at 16.8 M triangles, a scene ten times the Infinity Cache)") +
-                                   f": {W}x{H}, {spp} spp ({sx}x{sy} strata), "
-                                   f"path depth {depth}, frame tiled over {world} GPU(s) in interleaved {self.tiling.BAND_ROWS}-row bands",
-                       "scene": self.name, "width": W, "height": H, "spp": spp, "depth": depth, "seed": self.args.seed,
-                       "integrator": self.args.integrator, "scene_bytes_in_hbm": self.hs.nbytes,
-                       "full_size": self.full_size and self.name in ("c1", "c2", "c3", "c4", "c5")},
+        line.update({
             "mrays_per_s": rays_per_step * steps / elapsed / 1e6,
             "rays_per_step": rays_per_step,
             "closest_rays_per_step": counts[0],
@@ -322,14 +341,6 @@ class Workload:
             "invalid_samples": counts[3],
             "frame_mean_radiance": [float(x) for x in timed_frame.reshape(-1, 3).mean(axis=0)],
             "parity_window": window,
-            "gather_ms": gather_ms,
-            # which instantiations of the traversal kernels the timed frames ran (include/pbrs_gpu.h, pbrs_stats::kernel_features_*)
-            "kernel_features": {"extend": int(per_frame[-1]["kernel_features_extend"]) if per_frame[-1] else None,
-                                "shadow": int(per_frame[-1]["kernel_features_shadow"]) if per_frame[-1] else None,
-                                "bits": "1 analytic shapes, 2 shading check, 4 scanned TLAS, 8 several node steps per round, 16 four-wide nodes, "
-                                        "32 full further node steps (scene outside the guarded range of the division-free box test), 64 scene arrays in LDS, 128 TLAS in LDS, 256 (extend) the TLAS extent followed to the letter (a ParallelQuad next to a mesh)"},
-            "per_rank": per_rank,
-            "band_imbalance": max(r["rows"] for r in per_rank) / (sum(r["rows"] for r in per_rank) / len(per_rank)),
             "roofline_inconsistent": inconsistent or False,
             "roofline": {
                 "bound": roofline.bound_of(dom), "kernel": dom["kernel"], "achieved": dom["achieved_GBps"], "peak": roofline.HBM_PEAK_GBS, "unit": "GB/s",
@@ -366,13 +377,42 @@ class Workload:
                         "salu_issue_frac = scalar instructions x 4.25 cycles over the same slots (they issue beside other waves' vector work)",
             },
             "traversal": trav,
-            "stages_ms_per_step": times,
             "stages_overlap": "a render of several passes runs each pass's late bounces on a second stream beside the next pass's first bounces "
                               "(pbrs_set_pass_overlap): stages_ms_per_step are HIP-event brackets on the launching stream over the timed frames and "
                               "include the time a kernel shares the chip with the other stream's, so they do not add up to ms_total; "
                               "stages_ms_serial is one untimed frame with the overlap off (rank 0), where they do",
             "stages_ms_serial": serial_times,
             "stages": rep,
+        })
+        return line
+
+    def headline(self, steps, elapsed, stage_ms, launches, gather_ms, per_frame, per_rank):
+        """Rank 0's report of the timed frames alone: rate, time per step, workload, per-rank split and stage times."""
+        W, H, sx, sy, depth, spp, world = self.W, self.H, self.sx, self.sy, self.depth, self.sx * self.sy, self.world
+        samples_per_step = float(W) * H * spp
+        times = {k: v / steps for k, v in stage_ms.items()}
+        times.update({k: v // steps for k, v in launches.items()})
+        return {
+            "value": samples_per_step * steps / elapsed / 1e6,
+            "unit": "Msamples/s",
+            "steps": steps,
+            "ms_per_step": elapsed / steps * 1e3,
+            "config": {"workload": (f"BASELINE configs[{int(self.name[1]) - 1}] ({self.name})" if self.name in ("c1", "c2", "c3", "c4", "c5") else
+                                    f"{self.name} (not a BASELINE config: C4's generator at 16.8 M triangles, a scene ten times the Infinity Cache)") +
+                                   f": {W}x{H}, {spp} spp ({sx}x{sy} strata), "
+                                   f"path depth {depth}, frame tiled over {world} GPU(s) in interleaved {self.tiling.BAND_ROWS}-row bands",
+                       "scene": self.name, "width": W, "height": H, "spp": spp, "depth": depth, "seed": self.args.seed,
+                       "integrator": self.args.integrator, "scene_bytes_in_hbm": self.hs.nbytes,
+                       "full_size": self.full_size and self.name in ("c1", "c2", "c3", "c4", "c5")},
+            "gather_ms": gather_ms,
+            # which instantiations of the traversal kernels the timed frames ran (include/pbrs_gpu.h, pbrs_stats::kernel_features_*)
+            "kernel_features": {"extend": int(per_frame[-1]["kernel_features_extend"]) if per_frame[-1] else None,
+                                "shadow": int(per_frame[-1]["kernel_features_shadow"]) if per_frame[-1] else None,
+                                "bits": "1 analytic shapes, 2 shading check, 4 scanned TLAS, 8 several node steps per round, 16 four-wide nodes, "
+                                        "32 full further node steps (scene outside the guarded range of the division-free box test), 64 scene arrays in LDS, 128 TLAS in LDS, 256 (extend) the TLAS extent followed to the letter (a ParallelQuad next to a mesh)"},
+            "per_rank": per_rank,
+            "band_imbalance": max(r["rows"] for r in per_rank) / (sum(r["rows"] for r in per_rank) / len(per_rank)),
+            "stages_ms_per_step": times,
         }
 
     def close(self):
@@ -413,12 +453,14 @@ def main():
 
     ctx = pbrs_amd.Context(ordinal)
     main_wl = Workload(args, args.config, ctx, torch, dist, dev, world, rank)
-    result = main_wl.measure(args.steps, args.warmup)
+    result = main_wl.measure(args.steps, args.warmup, full=args.full)
     main_wl.close()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_wl.timed_frame)
 
     others = {}
     also = args.also if args.also is not None else ("c2,c3,c5" if args.config == DEFAULT_CONFIG and not (args.width or args.height or args.strata or args.depth) else "")
-    if world == 1:
+    if world == 1 and args.full:
         for name in [c for c in also.split(",") if c]:
             wl = Workload(args, name, ctx, torch, dist, dev, world, rank, strata=ALSO_STRATA.get(name))
             r = wl.measure(args.also_steps, 1)
@@ -456,14 +498,15 @@ def main():
                   "rays_per_sample", "paths_at_bounce", "shadow_rays_at_bounce", "invalid_samples", "frame_mean_radiance", "parity_window", "gather_ms",
                   "per_rank", "band_imbalance", "kernel_features",
                   "roofline_inconsistent", "roofline", "traversal", "stages_ms_per_step", "stages_overlap", "stages_ms_serial", "stages"):
-            line[k] = result[k]
+            if k in result:  # a plain run reports the headline only
+                line[k] = result[k]
         if others:
             line["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sample = tuple(args.cpu_sample) if args.cpu_sample else CPU_SAMPLES[args.config]
             line["cpu_baseline"] = cpu_baseline(args.config, result["config"]["depth"], args.seed, sample, args.integrator)
         print(json.dumps(line), flush=True)
-        windows = [("main", result["parity_window"])] + [(n, o["parity_window"]) for n, o in others.items()]
+        windows = [("main", result.get("parity_window"))] + [(n, o["parity_window"]) for n, o in others.items()]
         failed = [n for n, w in windows if w is not None and not (w["bit_exact"] and w["timed_frame_equals_instrumented_frame"])]
     else:
         failed = []

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Runs on the GPU box (through gpurun): the round's measured artifacts under gpurun_out/artifacts_<tag>/, per config —
-#   kernel_stats_<cfg>.csv           rocprofv3 --kernel-trace --stats of `python3 bench.py --config <cfg> --also ""` (for c4: the default
-#                                    workload of `python3 bench.py` without its C2 / C3 extras, so that per-kernel averages are of ONE workload)
+#   kernel_stats_<cfg>.csv           rocprofv3 --kernel-trace --stats of `python3 bench.py --full --config <cfg> --also ""` (for c4: the default
+#                                    workload of `python3 bench.py --full` without its C2 / C3 extras, so that per-kernel averages are of ONE workload)
 #   bench_under_rocprof_<cfg>.json   the JSON line of that same run
 #   pmc_<set>_<cfg>.txt              per-kernel counter sums of separate --pmc passes (no trace domains besides --kernel-trace): L2 memory-side
 #                                    bytes (1-4), the SQ's instruction and wave-cycle counts (5, 6), the L1's accesses and the busy cycles of
 #                                    the texture address / data units (7, 8)
 #   traffic_<cfg>.json               HBM bytes per launch per kernel (tools/traffic_from_pmc.py)
-#   bench.json                       the plain default bench line (no profiler), last
+#   bench.json                       the default `bench.py --full` line (no profiler), last
 #   PBRS_SKIP_PLAIN_BENCH=1 skips the closing plain bench (a call that collects one config's counters and nothing else)
 # usage: tools/round_artifacts.sh TAG [cfg ...]      (default: c4 c2 c3).  Copy what should be judged into profiles/ afterwards.
 set -o pipefail
@@ -21,7 +21,7 @@ for cfg in $cfgs; do
   extra=""; [ $cfg = c5 ] && extra="--strata 8 8"   # C5 rides along as a 64-spp slice of its 4096 spp (bench.py ALSO_STRATA): the same slice here
   echo "== $cfg: kernel trace"; date +%T
   rm -rf $out/trace_$cfg
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$cfg -o t -- python3 $R/bench.py --config $cfg $extra --also "" --steps 3 --warmup 1 --no-cpu-baseline > $out/trace_$cfg.log 2>&1 || { tail -5 $out/trace_$cfg.log; exit 1; }
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$cfg -o t -- python3 $R/bench.py --full --config $cfg $extra --also "" --steps 3 --warmup 1 --no-cpu-baseline > $out/trace_$cfg.log 2>&1 || { tail -5 $out/trace_$cfg.log; exit 1; }
   grep '^{"metric"' $out/trace_$cfg.log > $out/bench_under_rocprof_$cfg.json
   cp $(find $out/trace_$cfg -name '*kernel_stats.csv' | head -1) $out/kernel_stats_$cfg.csv
   rm -rf $out/trace_$cfg
@@ -44,6 +44,6 @@ for cfg in $cfgs; do
 done
 if [ -z "$PBRS_SKIP_PLAIN_BENCH" ]; then
   echo "== plain default bench"; date +%T
-  cd $R && timeout -k 10 600 python3 bench.py > $out/bench.log 2>&1; grep '^{"metric"' $out/bench.log > $out/bench.json
+  cd $R && timeout -k 10 600 python3 bench.py --full > $out/bench.log 2>&1; grep '^{"metric"' $out/bench.log > $out/bench.json
 fi
 ls -la $out
