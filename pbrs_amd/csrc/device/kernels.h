@@ -17,9 +17,6 @@
 #include "lights.h"
 #include "textures.h"
 #include "traverse.h"
-#ifdef PBRS_DEV_OVERRIDES
-#include "experimental/closest_wide.h"
-#endif
 
 struct PathState {
     // Path records by queue position i, structure-of-float4-arrays, ping-pong by bounce parity (k_shade reads set b & 1
@@ -346,26 +343,13 @@ PD void wave_append_slow(bool slow, uint32_t item, uint32_t* list, uint32_t* cou
     base = __shfl(base, leader, 64);
     if (slow) list[base + lane_prefix(m)] = item;
 }
-#ifndef PBRS_WIDE_EXTEND_WAVES  // min waves per SIMD asked of the register allocator for the wide-walk kernels
-#define PBRS_WIDE_EXTEND_WAVES 5
-#endif
-#ifndef PBRS_WIDE_SHADOW_WAVES
+#ifndef PBRS_WIDE_SHADOW_WAVES  // min waves per SIMD asked of the register allocator for the wide-walk kernels
 #define PBRS_WIDE_SHADOW_WAVES 5
 #endif
 #ifndef PBRS_WIDE_NODE_STEPS  // node steps per loop round of the wide walks in scenes with long walks
 #define PBRS_WIDE_NODE_STEPS 2u
 #endif
-template <uint32_t ARITY, bool STATS, uint32_t FEAT>  // ARITY 0: the binary walks; 4: the walks over four-wide nodes (device/wide.h)
-struct ClosestSel {
-#ifdef PBRS_DEV_OVERRIDES
-    typedef ClosestWalkW<FEAT> type;  // device/experimental/closest_wide.h
-#endif
-};
-template <bool STATS, uint32_t FEAT>
-struct ClosestSel<0u, STATS, FEAT> {
-    typedef ClosestWalk<STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP | PBRS_FEAT_EXTENT))> type;
-};
-template <uint32_t ARITY, bool STATS, uint32_t FEAT>
+template <uint32_t ARITY, bool STATS, uint32_t FEAT>  // ARITY 0: the binary walk; 4: the walk over four-wide nodes (device/wide.h)
 struct AnySel {
     typedef AnyWalkW<FEAT> type;
 };
@@ -425,15 +409,14 @@ PD DevScene stage_top(const DevScene& G, uint32_t* lds_base) {
 
 // Persistent: every wave keeps pulling rays from the queue until it is empty; a lane whose walk ends is
 // handed a new ray at the next refill, the walks of the other lanes continue where they were.
-// `indirect` (binary-walk kernels working off a slow list): the queue positions to trace, `count` of them.
+// `indirect` (binary-walk kernels working off a slow list): the queue positions to trace, `count` of them.  (k_extend walks binary
+// only: the host passes null for `indirect` and the slow list.)
 template <bool STATS, uint32_t FEAT>
-__global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_WIDE) ? PBRS_WIDE_EXTEND_WAVES : (FEAT & PBRS_FEAT_SHADING_CHECK) ? PBRS_TRAV_WAVES : PBRS_LEAN_EXTEND_WAVES)
+__global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_SHADING_CHECK) ? PBRS_TRAV_WAVES : PBRS_LEAN_EXTEND_WAVES)
     k_extend(DevScene G, PathState st, uint32_t set, const uint32_t* count, uint32_t n_direct, uint32_t* next, GlobalCounters* gc, const uint32_t* indirect,
              uint32_t* slow_list, uint32_t* slow_count, uint32_t split) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
     const DevScene S = (!STATS && (FEAT & PBRS_FEAT_LDS_SCENE)) ? stage_scene(G, lds_stack) : (!STATS && (FEAT & PBRS_FEAT_LDS_TOP)) ? stage_top(G, lds_stack) : G;
-    constexpr uint32_t ARITY = PBRS_WALK_ARITY(STATS, FEAT);
-    constexpr bool WIDE = ARITY != 0u;
     const uint32_t n = count ? *count : n_direct;
     const float4* q0 = st.q[set][0];
     const float4* q1 = st.q[set][1];
@@ -441,7 +424,7 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_WIDE) ? PBR
     Cnt<STATS> cnt;
     cnt.init();
     uint32_t nrays = 0, nhit = 0;
-    typename ClosestSel<ARITY, STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP | PBRS_FEAT_EXTENT))>::type walk;
+    ClosestWalk<STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP | PBRS_FEAT_EXTENT))> walk;
     walk.mode = PBRS_WALK_IDLE;
     PBRS_KP_DECL(walk);
     PBRS_TT_DECL;
@@ -451,10 +434,6 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_WIDE) ? PBR
         uint64_t live = __ballot(walk.mode == PBRS_WALK_NODE || walk.mode == PBRS_WALK_LEAF || walk.mode == PBRS_WALK_XFER);
         if ((uint32_t)__popcll(live) < S.refill_below) {
             PBRS_KP_WAVE(1);
-            if constexpr (WIDE) {
-                wave_append_slow(walk.mode == PBRS_WALK_SLOW, item & 0x7fffffffu, slow_list, slow_count);
-                if (walk.mode == PBRS_WALK_SLOW) walk.mode = PBRS_WALK_IDLE;
-            }
             if (walk.mode == PBRS_WALK_DONE) {  // finished walks are retired in batches, at refill time
                 walk.finish(cnt);  // a walk that ended inside an instance: its candidate meets the best hit here
                 const Hit& h = walk.best;
@@ -496,21 +475,13 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_WIDE) ? PBR
                     nrays++;
                     PBRS_KP_LANE(2, true);
                 }
-                if constexpr (WIDE) walk.scan_wave(S, stk);
-                else walk.scan_wave(S, cnt);
+                walk.scan_wave(S, cnt);
                 live = __ballot(walk.mode == PBRS_WALK_NODE || walk.mode == PBRS_WALK_LEAF || walk.mode == PBRS_WALK_XFER);
             }
-            if (live == 0) {
-                if constexpr (WIDE) {
-                    walk.forget_reciprocals();
-                    if (__ballot(walk.mode == PBRS_WALK_SLOW || walk.mode == PBRS_WALK_DONE)) continue;  // rays that ended in the refill itself
-                }
-                break;
-            }
+            if (live == 0) break;
         }
         PBRS_TT(0);
-        PBRS_STEP_WALK(walk, S, stk, cnt, PBRS_EXT_XFER_MIN, PBRS_EXT_LEAF_MIN, PBRS_WALK_NSTEPS(FEAT, ARITY), ((FEAT & PBRS_FEAT_FULL_STEPS) != 0u));
-        if constexpr (WIDE) walk.forget_reciprocals();
+        PBRS_STEP_WALK(walk, S, stk, cnt, PBRS_EXT_XFER_MIN, PBRS_EXT_LEAF_MIN, PBRS_WALK_NSTEPS(FEAT, 0u), ((FEAT & PBRS_FEAT_FULL_STEPS) != 0u));
     }
     flush_counters<STATS>(cnt, gc, true, nrays, nhit);
     if (!STATS) PBRS_KP_FLUSH(0, walk);
@@ -1317,10 +1288,10 @@ __global__ void k_sum_bounce_counts(const uint32_t* act, const unsigned long lon
 }
 
 // ---- parity-harness kernels --------------------------------------------------------------------------------------------
-// The walks the pipeline runs for the scene, chosen per stage exactly as run_pass chooses them: WIDE_ANY = occlusion queries go through
-// the four-wide any-hit walk of k_shadow (AnyWalkW, with its hand-off of refused rays to the binary walk); WIDE_CLOSEST = the
-// four-wide closest-hit walk (developer builds only).  info[0] / info[1]: rays the wide any-hit / closest-hit walk refused.
-template <bool WIDE_CLOSEST, bool WIDE_ANY>
+// The walks the pipeline runs for the scene (pbrs_gpu.hip, KernelPlan): closest hits through k_extend's binary walk; WIDE_ANY =
+// occlusion queries go through the four-wide any-hit walk of k_shadow (AnyWalkW, with its hand-off of refused rays to the binary
+// walk).  info[0]: rays the wide any-hit walk refused (info[1], the closest-hit walk's, stays 0).
+template <bool WIDE_ANY>
 __global__ void __launch_bounds__(256) k_intersect_rays(DevScene S, uint32_t n, const float4* origins, const float4* dirs, const float* tmax,
                                                        pbrs_hit_record* hits, uint8_t* occluded, uint32_t* info) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
@@ -1340,11 +1311,6 @@ __global__ void __launch_bounds__(256) k_intersect_rays(DevScene S, uint32_t n, 
         }
         if (hits) {
             Hit h;
-            bool slow = false;
-#ifdef PBRS_DEV_OVERRIDES
-            if constexpr (WIDE_CLOSEST) tlas_closest_wide(S, active, o, d, t_max, stk, h, slow);
-            else
-#endif
             if (S.exact_extent) tlas_closest<false, PBRS_FEAT_EXTENT>(S, active, o, d, t_max, stk, h, cnt);  // as the scene's k_extend
             else tlas_closest<false>(S, active, o, d, t_max, stk, h, cnt);
             if (active) {
@@ -1356,7 +1322,6 @@ __global__ void __launch_bounds__(256) k_intersect_rays(DevScene S, uint32_t n, 
                 r.b1 = h.b1;
                 r.b2 = h.b2;
                 hits[i] = r;
-                if (slow) atomicAdd(info + 1, 1u);
             }
         }
         if (occluded) {

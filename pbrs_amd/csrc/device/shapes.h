@@ -78,7 +78,7 @@ struct DevScene {
 #define PBRS_FEAT_SHADING_CHECK 2u  // some mesh needs the tangent check of blas.rs:193-200 evaluated per candidate hit
 #define PBRS_FEAT_FLAT_TLAS 4u      // the leaf copies at DevScene::flat_off are built: rays on the division-free box test scan the TLAS leaves
 #define PBRS_FEAT_ALL 7u
-#define PBRS_FEAT_EXTENT 256u        // closest-hit walk only, outside the kernel tables: the TLAS extent is the reference's ray.t_max to the letter, rises included
+#define PBRS_FEAT_EXTENT 256u        // closest-hit walk only (one k_extend each way, pbrs_gpu.hip kExtentFeatures): the TLAS extent is the reference's ray.t_max to the letter, rises included
                                     // (traverse.h, ClosestWalk::EXT): scenes with a ParallelQuad next to a mesh (pbrs_upload_scene)
 #define PBRS_FEAT_LONG_WALKS 8u     // kernels only (not a property of the walks): several node steps per loop round (kernels.h)
 #define PBRS_FEAT_WIDE 16u          // kernels only: the walks over four-wide nodes (device/wide.h); needs PBRS_FEAT_FLAT_TLAS

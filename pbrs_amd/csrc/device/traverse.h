@@ -95,7 +95,7 @@ PD bool slab_rs(const pbrs_node& n, const RaySpace& R, float t_max) {
 
 // The same test with an infinite extent, for a ray on the division-free test, returning t_low = max(lo_el, 0) as well: with a
 // finite extent t the reference's test is t_low <= min(hi_el, t), i.e. this result AND t_low <= t — which is how a closest-hit
-// walk re-evaluates a scanned TLAS leaf at its turn without fetching the box again (ClosestWalkW, FlatScan::run_tlow).
+// walk re-evaluates a scanned TLAS leaf at its turn without fetching the box again (FlatScan::run_tlow).
 PD bool slab_rs_tlow(const pbrs_node& n, const RaySpace& R, float& t_low) {
     float t0x = qdiv(R.o.x - n.min[0], R.d.x, R.nr.x), t0y = qdiv(R.o.y - n.min[1], R.d.y, R.nr.y), t0z = qdiv(R.o.z - n.min[2], R.d.z, R.nr.z);
     float t1x = qdiv(R.o.x - n.max[0], R.d.x, R.nr.x), t1y = qdiv(R.o.y - n.max[1], R.d.y, R.nr.y), t1z = qdiv(R.o.z - n.max[2], R.d.z, R.nr.z);
@@ -1076,7 +1076,7 @@ struct AnyWalkW : AnyWalk<false, FEAT> {
     }
     PD void xfer_step(const DevScene& S, LaneStack stk, Cnt<false>& cnt) {
         if (in_blas) {
-            const bool rebuilt = moved && !(inst_kind & 0x100u);  // (AnyWalk::xfer_step's first branch: see ClosestWalkW::xfer_step)
+            const bool rebuilt = moved && !(inst_kind & 0x100u);  // (AnyWalk::xfer_step's first branch, restated so that its second one is not compiled into this kernel twice)
             mode = PBRS_WALK_NODE;
             in_blas = false;
             leave_instance(S, stk, !moved ? PBRS_SPACE_WORLD : (inst_kind & 0x100u) ? PBRS_SPACE_TRANSLATED : PBRS_SPACE_MOVED, C);

@@ -16,6 +16,7 @@
 #include <map>
 #include <utility>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -27,9 +28,9 @@ namespace {
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kMaxDepth = 64;
 constexpr uint32_t kHeadWords = PBRS_WORK_HEADS * PBRS_WORK_HEAD_STRIDE;
-// per bounce: act, ns (u64), the slow-list lengths of k_extend and k_shadow; then four sets of work heads (the two stages, and
-// the binary-walk launches that work off their slow lists)
-constexpr uint32_t kCounterWords = (7 + 4 * kHeadWords) * (kMaxDepth + 2);  // ... and k_extend's split counts (u64)
+// per bounce: act, ns (u64), the slow-list length of k_shadow; then three sets of work heads (the two stages, and the binary-walk
+// launch that works off k_shadow's slow list)
+constexpr uint32_t kCounterWords = (4 + 3 * kHeadWords) * (kMaxDepth + 2);
 constexpr uint32_t kSlowGrid = 64;
 #ifndef PBRS_SPLIT_KEEP_PERCENT
 #define PBRS_SPLIT_KEEP_PERCENT 85u  // k_extend's queue split stays on where it keeps at most this share of a pass's rays for k_shade
@@ -43,16 +44,113 @@ struct StageEvent {
     hipEvent_t a, b;
 };
 
-// Developer overrides (A/B timing of kernel selection: tools/ab_env.sh) exist only in builds made with -DPBRS_DEV_OVERRIDES.
-// The shipped library never reads the environment: a bench line must not depend on the box it ran on.
-inline const char* dev_env(const char* name) {
+// Developer overrides (A/B timing of kernel selection: tools/ab_env.sh): environment variables that builds made with
+// -DPBRS_DEV_OVERRIDES read once per context (pbrs_create); every other build leaves the defaults, which bend nothing.  The shipped
+// library never reads the environment: a bench line must not depend on the box it ran on.
+struct DevOverrides {
+    bool overlap_passes = true;   // PBRS_OVERLAP_PASSES=0: every pass on the main stream, as in rounds 1-3
+    bool sort_classes = true;     // PBRS_SORT_CLASSES=0: no class sort
+    bool split_lambert = true;    // PBRS_SPLIT_LAMBERT=0: one general k_shade launch for all classes
+    bool split_fourier = true;    // PBRS_SPLIT_FOURIER=0: one launch of the Fourier variants over every class, as in round 2
+    bool split_queue = true;      // PBRS_SPLIT_QUEUE=0: k_extend never splits the path integrator's queue
+    bool wide_shadow = true;      // PBRS_WIDE without bit 1: k_shadow keeps the binary walk
+    bool lds_scene = true;        // PBRS_LDS_SCENE=0: the traversal kernels never stage the whole scene in LDS
+    bool lds_top = true;          // PBRS_LDS_TOP=0: ... nor the TLAS alone
+    bool raygen_tiles8 = true;    // PBRS_RAYGEN_TILES8=0: no 8 x 8 pixel tiles in the slot order
+    uint32_t shade_spec = ~0u;    // PBRS_SHADE_SPEC: a mask of the path integrator's k_shade specialisation
+    uint32_t shade_lds = ~0u;     // PBRS_SHADE_LDS: a mask of what k_shade stages in LDS
+    std::optional<bool> long_walks, full_steps;         // PBRS_LONG_WALKS / PBRS_FULL_STEPS
+    std::optional<uint32_t> overlap_from, refill_below;  // PBRS_OVERLAP_FROM / PBRS_REFILL_BELOW
+    std::optional<uint32_t> raygen_chunk;  // PBRS_RAYGEN_CHUNK: pixels per slot-order chunk (0: the sample index outermost, as in round 1)
+    size_t lds_min = 0;           // PBRS_LDS_MIN: dynamic LDS bytes the traversal kernels take at least (lowers their occupancy)
+};
+
 #ifdef PBRS_DEV_OVERRIDES
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
+const char* dev_env(const char* name) { return std::getenv(name); }
+
+DevOverrides read_dev_overrides() {
+    DevOverrides o;
+    auto flag = [](const char* name, bool& v) {
+        if (const char* e = dev_env(name)) v = std::atoi(e) != 0;
+    };
+    flag("PBRS_OVERLAP_PASSES", o.overlap_passes);
+    flag("PBRS_SORT_CLASSES", o.sort_classes);
+    flag("PBRS_SPLIT_LAMBERT", o.split_lambert);
+    flag("PBRS_SPLIT_FOURIER", o.split_fourier);
+    flag("PBRS_SPLIT_QUEUE", o.split_queue);
+    flag("PBRS_LDS_SCENE", o.lds_scene);
+    flag("PBRS_LDS_TOP", o.lds_top);
+    flag("PBRS_RAYGEN_TILES8", o.raygen_tiles8);
+    if (const char* e = dev_env("PBRS_WIDE")) o.wide_shadow = (std::atoi(e) & 2) != 0;
+    if (const char* e = dev_env("PBRS_SHADE_SPEC")) o.shade_spec = (uint32_t)std::atoi(e);
+    if (const char* e = dev_env("PBRS_SHADE_LDS")) o.shade_lds = (uint32_t)std::atoi(e);
+    if (const char* e = dev_env("PBRS_LONG_WALKS")) o.long_walks = std::atoi(e) != 0;
+    if (const char* e = dev_env("PBRS_FULL_STEPS")) o.full_steps = std::atoi(e) != 0;
+    if (const char* e = dev_env("PBRS_OVERLAP_FROM")) o.overlap_from = (uint32_t)std::atoi(e);
+    if (const char* e = dev_env("PBRS_REFILL_BELOW")) o.refill_below = (uint32_t)std::atoi(e);
+    if (const char* e = dev_env("PBRS_RAYGEN_CHUNK")) {
+        const long v = std::atol(e);
+        o.raygen_chunk = v > 0 ? (uint32_t)v : 0xffffffffu;
+    }
+    if (const char* e = dev_env("PBRS_LDS_MIN")) o.lds_min = (size_t)std::atol(e);
+    return o;
 }
+#endif
+
+typedef void (*extend_fn_t)(DevScene, PathState, uint32_t, const uint32_t*, uint32_t, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
+typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*);
+typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*);
+
+// What pbrs_upload_scene finds out about a scene that decides which kernels render it (plan_kernels).
+struct SceneFacts {
+    uint32_t features = 0;      // DevScene::features: PBRS_FEAT_ANALYTIC, _SHADING_CHECK, and _FLAT_TLAS where k_extend scans the TLAS leaves
+    bool tlas_scanned = false;  // the TLAS leaf copies exist (DevScene::n_flat): k_shadow scans them
+    bool exact_extent = false;  // DevScene::exact_extent: the closest-hit walks follow ray.t_max to the letter (PBRS_FEAT_EXTENT)
+    bool long_walks = false;    // a walk of PBRS_LONG_WALK_HEIGHT levels or more: the PBRS_FEAT_LONG_WALKS kernels
+    bool full_steps = false;    // ... whose further node steps are full ones (PBRS_FEAT_FULL_STEPS): coordinates outside the guarded range of the division-free box test
+    bool wide_ok = false;       // k_shadow may walk the four-wide nodes (a scanned TLAS, built wide nodes, a BLAS deep enough)
+    size_t stack_bytes = 0;     // a block's stack rows: DevScene::lds_off_words
+    size_t wide_stack_bytes = 0;  // ... of the four-wide walk: DevScene::wide_cap rows
+    size_t scene_bytes = 0;     // the arrays the walks read, as stage_scene copies them
+    size_t top_bytes = 0;       // the TLAS nodes, as stage_top copies them
+    uint32_t n_classes = 0;     // DevScene::n_classes
+    uint32_t lambert_class = 0; // shading class of the materials that are one untextured Lambertian DiffuseReflect (0: none)
+    uint32_t fourier_class = 0; // shading class of the materials that are one Fourier BSDF (0: none)
+    bool textured = false;      // some lobe evaluates a non-Solid texture: k_shade<.., true, ..>
+    bool fourier = false;       // some lobe is a Fourier BSDF: k_shade<.., PBRS_SHADE_FOURIER>
+    bool lambert = false;       // every lobe is an untextured Lambertian DiffuseReflect, at most one per material
+    uint32_t light_spec = 0;    // PBRS_SHADE_LIGHT_*: every area light has that shape
+    uint32_t shade_lds = 0;     // PBRS_SHADE_LDS_*: what fits k_shade's LDS budget
+    size_t shade_rec_bytes = 0, shade_tri_bytes = 0;  // what stage_shade_scene copies for PBRS_SHADE_LDS_RECORDS, and for _TRIS on top
+};
+
+// The kernels that render the uploaded scene, chosen once per upload (plan_kernels) from the tables below.
+template <class Fn>
+struct StageKernel {
+    Fn fn = nullptr;
+    uint32_t features = 0;  // the instantiation's PBRS_FEAT_* as pbrs_stats::kernel_features_* reports them (0x80000000: instrumented)
+    size_t lds = 0;         // dynamic LDS: the lanes' stack rows and what the kernel stages
+};
+struct ShadeLaunch {
+    shade_fn_t fn = nullptr;
+    size_t lds = 0;
+    uint32_t range = 0;  // the st.class_range entry the launch covers (PBRS_MAX_CLASSES: the classes before the last one), 0: the queue
+};
+struct IntegratorPlan {
+    enum Order { NO_ORDER, CLASS_SORT, CLASS_MAJOR } order = NO_ORDER;  // how the queue is ordered before k_shade
+    uint32_t last_class = 0;  // CLASS_MAJOR: the class that goes last, over PBRS_MAX_CLASSES classes
+    uint32_t n_shade = 0;     // one or two k_shade launches
+    ShadeLaunch shade[2];
+};
+struct KernelPlan {
+    StageKernel<extend_fn_t> extend[2];  // [instrumented]
+    StageKernel<shadow_fn_t> shadow[2];
+    bool wide_shadow = false;               // the timed k_shadow walks four-wide nodes ...
+    StageKernel<shadow_fn_t> shadow_slow;   // ... and this binary-walk kernel works off the rays it refused
+    bool split_queue = false;               // k_extend may split the path integrator's queue (one shading class; run_pass decides)
+    uint32_t lds_staging = 0;               // PBRS_FEAT_LDS_SCENE, PBRS_FEAT_LDS_TOP or 0: what the traversal kernels stage in LDS
+    IntegratorPlan integ[PBRS_INTEGRATOR_NORMALS + 1];
+};
 
 }  // namespace
 
@@ -86,7 +184,7 @@ struct pbrs_ctx {
     int cur_set = 0;
     hipStream_t main_stream = nullptr;  // the stream of set 0: the context's own, or the caller's (pbrs_set_stream)
     hipStream_t second_stream = nullptr;  // the late stream: the context's own, high priority, ordered against the main one by events
-    bool overlap_passes = true;  // PBRS_OVERLAP_PASSES=0 in developer builds: every pass on the main stream, as in rounds 1-3
+    bool overlap_passes = true;  // pbrs_set_pass_overlap (DevOverrides::overlap_passes): every pass on the main stream, as in rounds 1-3
     // The bounce from which a pass moves to the late stream (and the next pass starts behind it on the main one).  Same-box A/B lines in
     // profiles/r04m_ab_pass_overlap.log: scenes that live in every XCD's L2 gain most from bounce 2 on (C2 +1.9 %, C3 +1.5 %, C5 +3.3 %
     // against one stream; from 1: +1.3 / +1.2 / +2.7, from 3: 0 / +1.4 / +2.3), a scene that lives in the Infinity Cache from bounce 4 on
@@ -111,38 +209,20 @@ struct pbrs_ctx {
     std::vector<hipEvent_t> total_ev;  // 2
     pbrs_stats pending{};
     bool pending_counters = false, pending_times = false;
-    bool textured = false;  // the uploaded scene evaluates non-Solid textures: k_shade<.., true>
-    bool fourier = false;   // ... has a Fourier BSDF lobe: k_shade<.., true, PBRS_SHADE_FOURIER>
-    uint32_t lambert_class = 0;    // shading class of the Lambert-only materials (0: none)
-    uint32_t fourier_class = 0;    // shading class of the Fourier BSDF materials (0: none): k_shade's variants with that lobe run over it alone
-    uint32_t light_spec = 0;       // PBRS_SHADE_LIGHT_*: every area light has that shape
-    bool split_lambert = true;     // PBRS_SPLIT_LAMBERT=0 in the environment: one general k_shade launch for all classes (A/B timing)
-    uint32_t shade_spec = 0;       // PBRS_SHADE_*: what k_shade<PATH> may leave out for this scene
-    bool long_walks = false;       // a BLAS of PBRS_LONG_WALK_HEIGHT levels or more: the PBRS_FEAT_LONG_WALKS kernels
-    bool full_steps = false;       // ... whose further node steps are full ones (PBRS_FEAT_FULL_STEPS): a scene outside the guarded range of the division-free box test
-    uint64_t walk_bytes = 0;       // bytes of the arrays the walks read (nodes, wide nodes, triangle vertices, instances)
-    uint32_t shade_lds = 0;        // PBRS_SHADE_LDS_*: what k_shade<PATH>'s untextured variants stage in LDS for this scene (kernels.h)
-    size_t shade_lds_bytes = 0;
-    bool lds_top = false;          // ... or only the TLAS does (an unscanned one): the PBRS_FEAT_LDS_TOP kernels
-    size_t lds_top_bytes = 0;
-    bool lds_scene = false;        // ... and they fit next to a block's stack rows: the PBRS_FEAT_LDS_SCENE kernels (S.lds_*)
-    size_t lds_scene_bytes = 0;
-    bool shadow_flat = false;      // k_shadow scans the TLAS leaves (up to PBRS_FLAT_TLAS_MAX_ANYHIT instances; k_extend: S.features)
-    bool split_queue = true;       // k_extend splits the path integrator's queue of one-class scenes (shaded / terminal / dropped); PBRS_SPLIT_QUEUE=0 in developer builds
-    // ... which pays where many paths are dropped (an open scene: C4 shades in 84 instead of 117 ms per frame) and costs where
-    // none are (a closed box: the gathered records cost C2 4 %).  Decided once per uploaded scene, from the counts of the first
-    // pass rendered with the path integrator: 0 = not yet, 1 = split, 2 = do not.  The image does not depend on it.
+    DevOverrides dev;  // read in pbrs_create (-DPBRS_DEV_OVERRIDES builds)
+    KernelPlan plan;   // the kernels that render the uploaded scene (plan_kernels)
+    // k_extend splits the path integrator's queue of one-class scenes (shaded / terminal / dropped: KernelPlan::split_queue), which
+    // pays where many paths are dropped (an open scene: C4 shades in 84 instead of 117 ms per frame) and costs where none are (a
+    // closed box: the gathered records cost C2 4 %).  Decided once per uploaded scene, from the counts of the first pass rendered
+    // with the path integrator: 0 = not yet, 1 = split, 2 = do not.  The image does not depend on it.
     int split_decision = 0;
     // The counts travel to the host through a pinned buffer behind an event that later passes poll (hipEventQuery): no call of the
     // render path waits for them, so pbrs_render_tile_device stays asynchronous (also on a caller's stream, pbrs_set_stream).
     unsigned long long* split_host = nullptr;  // pinned: (paths kept, paths in all) of the probed pass
     hipEvent_t split_ev = nullptr;
     bool split_probe_in_flight = false;
-    bool wide_extend = false, wide_shadow = false;  // the stage runs the walks over four-wide nodes (device/wide.h), the binary walks after it for what they refuse
-    uint32_t* slow = nullptr;      // 2 * cap_slots: queue positions a wide-walk kernel handed to the binary-walk kernel
+    uint32_t* slow = nullptr;      // 2 * cap_slots: queue positions the wide-walk k_shadow handed to the binary-walk kernel
     bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
-    bool sort_classes = true;      // PBRS_SORT_CLASSES=0 in the environment turns the class sort off (A/B timing)
-    bool split_fourier = true;     // PBRS_SPLIT_FOURIER=0 in developer builds: one launch of the Fourier variants over every class, as in round 2
     uint64_t pending_closest = 0;
     pbrs_intersect_info last_intersect{};  // which walks the last pbrs_intersect_rays went through
 };
@@ -270,16 +350,6 @@ int ensure_work(pbrs_ctx* c, size_t n_slots, size_t n_pixels) {
     return PBRS_OK;
 }
 
-// wide-walk kernels: DevScene::wide_cap stack rows, and for closest hit one row per scanned TLAS leaf (entry distances)
-size_t lds_bytes_wide(const pbrs_ctx* c, bool closest) {
-    return (size_t)(c->S.wide_cap + (closest ? c->S.n_flat : 0u)) * kBlock * sizeof(uint32_t);
-}
-size_t lds_bytes(const pbrs_ctx* c) {
-    size_t b = (size_t)(c->stack_depth) * kBlock * sizeof(uint32_t);
-    if (const char* e = dev_env("PBRS_LDS_MIN")) b = b < (size_t)atol(e) ? (size_t)atol(e) : b;  // lowers the occupancy of the traversal kernels
-    return b;
-}
-
 uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p);
 
 int check_params(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p) {
@@ -370,7 +440,7 @@ struct Timer {
     }
 };
 
-RenderConst make_const(const pbrs_camera* cam, const pbrs_render_params* p) {
+RenderConst make_const(const pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p) {
     RenderConst rc{};
     rc.cam = *cam;
     rc.x0 = p->x0; rc.y0 = p->y0; rc.w = p->w; rc.h = p->h;
@@ -382,16 +452,9 @@ RenderConst make_const(const pbrs_camera* cam, const pbrs_render_params* p) {
     rc.integrator = p->integrator;
     // slot order of a pass (kernels.h, sample_of_slot): chunks of 4 K pixels, a multiple of the block and of the wave (C4:
     // 1156 Msamples/s with the sample index outermost, 1208-1211 with chunks of 256 ... 16 K pixels, 1202 with 64 K)
-    rc.chunk_pixels = 4096u;
-    if (const char* e = dev_env("PBRS_RAYGEN_CHUNK")) {  // developer override (A/B timing): 0 = sample index outermost, as in round 1
-        const long v = std::atol(e);
-        rc.chunk_pixels = v > 0 ? (uint32_t)v : 0xffffffffu;
-    }
+    rc.chunk_pixels = c->dev.raygen_chunk.value_or(4096u);
     if (rc.chunk_pixels > rc.n_pixels) rc.chunk_pixels = rc.n_pixels;  // one chunk: slot = k * P + pixel
-    rc.tiles8_per_row = (p->w % 8u == 0u && p->h % 8u == 0u) ? p->w / 8u : 0u;
-    if (const char* e = dev_env("PBRS_RAYGEN_TILES8")) {  // developer override (A/B timing)
-        if (std::atoi(e) == 0) rc.tiles8_per_row = 0u;
-    }
+    rc.tiles8_per_row = (c->dev.raygen_tiles8 && p->w % 8u == 0u && p->h % 8u == 0u) ? p->w / 8u : 0u;
     return rc;
 }
 
@@ -426,116 +489,188 @@ uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p) {
     return (uint32_t)k;
 }
 
-// The traversal kernels are instantiated per scene-feature set (device/shapes.h PBRS_FEAT_*): one table entry per valid combination,
-// filled at compile time; the instrumented variant exists for the full set only.  k_shadow never evaluates shading frames, so
-// PBRS_FEAT_SHADING_CHECK does not select it.  `wide`: the walks over four-wide nodes (scenes with a scanned TLAS); `indirect` /
-// `slow_*`: see kernels.h.
-typedef void (*extend_fn_t)(DevScene, PathState, uint32_t, const uint32_t*, uint32_t, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
-typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*);
-constexpr uint32_t kFeatCombos = 256u;  // PBRS_FEAT_* bits 0 .. 7
-constexpr bool extend_feat_ok(uint32_t f) {
+// The traversal kernels are instantiated per key (device/shapes.h PBRS_FEAT_*): one table entry per valid key, filled at compile
+// time; configure_kernels walks the tables and plan_kernels takes its pointers from them alone.  A key is a feature set, plus
+// kStatsKey for the instrumented variants, of which there is one per table and scene kind.  k_shadow never evaluates shading frames
+// nor follows the extent, so PBRS_FEAT_SHADING_CHECK and _EXTENT do not select it; k_extend walks binary nodes only (PBRS_FEAT_WIDE:
+// k_shadow's walk over four-wide nodes, scenes with a scanned TLAS).  `indirect` / `slow_*`: see kernels.h.
+constexpr uint32_t kStatsKey = 512u;  // above the PBRS_FEAT_* bits 0 .. 8
+constexpr uint32_t kTraversalKeys = 2u * kStatsKey;
+// a scene whose closest-hit walks follow the extent: no leaf scan, no staging, one k_extend each way
+constexpr uint32_t kExtentFeatures = PBRS_FEAT_ANALYTIC | PBRS_FEAT_SHADING_CHECK | PBRS_FEAT_EXTENT;
+constexpr uint32_t kShadowStatsFeatures = PBRS_FEAT_ANALYTIC | PBRS_FEAT_FLAT_TLAS;
+constexpr bool extend_key_ok(uint32_t k) {
+    const uint32_t f = k & ~kStatsKey;
+    if (f & PBRS_FEAT_EXTENT) return f == kExtentFeatures;
+    if (k & kStatsKey) return f == PBRS_FEAT_ALL;  // the instrumented kernel carries every feature
+    if (f & PBRS_FEAT_WIDE) return false;
     if ((f & PBRS_FEAT_FULL_STEPS) && !(f & PBRS_FEAT_LONG_WALKS)) return false;  // further node steps exist in the long-walk kernels only
-    if ((f & PBRS_FEAT_LDS_SCENE) && (f & (PBRS_FEAT_WIDE | PBRS_FEAT_FULL_STEPS))) return false;  // a scene of a few KB
-    if ((f & PBRS_FEAT_LDS_TOP) && (f & (PBRS_FEAT_LDS_SCENE | PBRS_FEAT_WIDE | PBRS_FEAT_FULL_STEPS | PBRS_FEAT_FLAT_TLAS))) return false;  // a TLAS too large to scan
-    if (f & PBRS_FEAT_WIDE) {
-#ifdef PBRS_DEV_OVERRIDES  // the four-wide closest-hit walk (device/experimental/closest_wide.h)
-        return (f & PBRS_FEAT_FLAT_TLAS) && !(f & PBRS_FEAT_FULL_STEPS);
-#else
-        return false;
-#endif
-    }
+    if ((f & PBRS_FEAT_LDS_SCENE) && (f & PBRS_FEAT_FULL_STEPS)) return false;  // a scene of a few KB
+    if ((f & PBRS_FEAT_LDS_TOP) && (f & (PBRS_FEAT_LDS_SCENE | PBRS_FEAT_FULL_STEPS | PBRS_FEAT_FLAT_TLAS))) return false;  // a TLAS too large to scan
     return true;
 }
-constexpr bool shadow_feat_ok(uint32_t f) {
-    if (f & PBRS_FEAT_SHADING_CHECK) return false;
+constexpr bool shadow_key_ok(uint32_t k) {
+    const uint32_t f = k & ~kStatsKey;
+    if (k & kStatsKey) return f == kShadowStatsFeatures;
+    if (f & (PBRS_FEAT_SHADING_CHECK | PBRS_FEAT_EXTENT)) return false;
     if ((f & PBRS_FEAT_FULL_STEPS) && !(f & PBRS_FEAT_LONG_WALKS)) return false;
     if ((f & PBRS_FEAT_LDS_SCENE) && (f & (PBRS_FEAT_WIDE | PBRS_FEAT_FULL_STEPS))) return false;
     if ((f & PBRS_FEAT_LDS_TOP) && (f & (PBRS_FEAT_LDS_SCENE | PBRS_FEAT_WIDE | PBRS_FEAT_FULL_STEPS | PBRS_FEAT_FLAT_TLAS))) return false;
     if ((f & PBRS_FEAT_WIDE) && !(f & PBRS_FEAT_FLAT_TLAS)) return false;
     return true;
 }
-template <uint32_t F>
+template <uint32_t K>
 constexpr extend_fn_t extend_fn_of() {
-    if constexpr (extend_feat_ok(F)) return &k_extend<false, F>;
+    if constexpr (extend_key_ok(K)) return &k_extend<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
     else return nullptr;
 }
-template <uint32_t F>
+template <uint32_t K>
 constexpr shadow_fn_t shadow_fn_of() {
-    if constexpr (shadow_feat_ok(F)) return &k_shadow<false, F>;
+    if constexpr (shadow_key_ok(K)) return &k_shadow<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
     else return nullptr;
 }
-template <uint32_t... F>
-const extend_fn_t* extend_table(std::integer_sequence<uint32_t, F...>) {
-    static const extend_fn_t t[sizeof...(F)] = {extend_fn_of<F>()...};
+template <uint32_t... K>
+const extend_fn_t* extend_table(std::integer_sequence<uint32_t, K...>) {
+    static const extend_fn_t t[sizeof...(K)] = {extend_fn_of<K>()...};
     return t;
 }
-template <uint32_t... F>
-const shadow_fn_t* shadow_table(std::integer_sequence<uint32_t, F...>) {
-    static const shadow_fn_t t[sizeof...(F)] = {shadow_fn_of<F>()...};
+template <uint32_t... K>
+const shadow_fn_t* shadow_table(std::integer_sequence<uint32_t, K...>) {
+    static const shadow_fn_t t[sizeof...(K)] = {shadow_fn_of<K>()...};
     return t;
 }
-const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kFeatCombos>{}); }
-const shadow_fn_t* shadow_fns() { return shadow_table(std::make_integer_sequence<uint32_t, kFeatCombos>{}); }
+const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
+const shadow_fn_t* shadow_fns() { return shadow_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
+template <class Fn>
+StageKernel<Fn> stage_kernel(const Fn* table, uint32_t key, size_t lds) {
+    return StageKernel<Fn>{table[key], (key & ~kStatsKey) | ((key & kStatsKey) ? 0x80000000u : 0u), lds};
+}
 
-int launch_extend(pbrs_ctx* c, bool stats, bool wide, uint32_t grid, size_t lds, uint32_t set, const uint32_t* count, uint32_t n_direct, uint32_t* heads,
-                  const uint32_t* indirect, uint32_t* slow_list, uint32_t* slow_count, uint32_t split) {
-    // k_extend scans the TLAS leaves only up to PBRS_FLAT_TLAS_MAX instances (S.features); the leaf copies may exist for
-    // k_shadow alone, and the instrumented variant, which carries every feature, must then walk the tree like the timed one
-    DevScene S = c->S;
-    if (!(S.features & PBRS_FEAT_FLAT_TLAS)) S.n_flat = 0u;
-    if (S.exact_extent) {  // the extent follows the tree: no leaf scan, no staging, one kernel each way (scenes with a ParallelQuad: no benchmark holds one)
-        constexpr uint32_t kF = PBRS_FEAT_ANALYTIC | PBRS_FEAT_SHADING_CHECK | PBRS_FEAT_EXTENT;
-        if (stats)
-            hipLaunchKernelGGL((k_extend<true, kF>), dim3(grid), dim3(kBlock), lds, c->stream, S, c->st, set, count, n_direct, heads, c->gcnt, indirect, slow_list, slow_count, split);
-        else
-            hipLaunchKernelGGL((k_extend<false, kF>), dim3(grid), dim3(kBlock), lds, c->stream, S, c->st, set, count, n_direct, heads, c->gcnt, indirect, slow_list, slow_count, split);
-        c->pending.kernel_features_extend = kF | (stats ? 0x80000000u : 0u);
-        return PBRS_OK;
-    }
-    if (stats) {
-        hipLaunchKernelGGL((k_extend<true, PBRS_FEAT_ALL>), dim3(grid), dim3(kBlock), lds, c->stream, S, c->st, set, count, n_direct, heads, c->gcnt, indirect, slow_list,
-                           slow_count, split);
-        c->pending.kernel_features_extend = PBRS_FEAT_ALL | 0x80000000u;
-        return PBRS_OK;
-    }
-    uint32_t feat = (c->S.features & PBRS_FEAT_ALL) | (c->long_walks ? PBRS_FEAT_LONG_WALKS : 0u) | ((c->long_walks && c->full_steps) ? PBRS_FEAT_FULL_STEPS : 0u);
-    if (wide) feat = (feat & ~PBRS_FEAT_FULL_STEPS) | PBRS_FEAT_WIDE;  // (developer builds; PBRS_FEAT_FLAT_TLAS is set: pbrs_upload_scene)
-    if (c->lds_scene && !wide) {
-        feat |= PBRS_FEAT_LDS_SCENE;
-        lds += c->lds_scene_bytes;
-    } else if (c->lds_top && !wide && !(feat & (PBRS_FEAT_FLAT_TLAS | PBRS_FEAT_FULL_STEPS))) {
-        feat |= PBRS_FEAT_LDS_TOP;
-        lds += c->lds_top_bytes;
-    }
-    const extend_fn_t fn = extend_fns()[feat];
-    if (!fn) return fail(c, PBRS_E_DEVICE, "no k_extend instantiation for this scene's feature set");
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), lds, c->stream, S, c->st, set, count, n_direct, heads, c->gcnt, indirect, slow_list, slow_count, split);
-    if (!indirect) c->pending.kernel_features_extend = feat;  // (a launch over a slow list is the stage's second kernel)
-    return PBRS_OK;
+// The k_shade instantiations (kernels.h: INTEG, TEX, SPEC) the plans choose from.
+struct ShadeKernel {
+    uint32_t integ;
+    bool tex;
+    uint32_t spec;
+    shade_fn_t fn;
+};
+template <uint32_t I, bool T, uint32_t SP>
+ShadeKernel shade_kernel() { return ShadeKernel{I, T, SP, &k_shade<I, T, SP>}; }
+constexpr uint32_t kShadeLdsAll = PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS;
+constexpr uint32_t kShadeFourierOnly = PBRS_SHADE_FOURIER | PBRS_SHADE_FOURIER_ONLY;
+const ShadeKernel kShadeKernels[] = {
+    // the path integrator's untextured variants, specialised on Lambert-only scenes and their light shape, with the shading records (and
+    // the triangle records) staged in LDS
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, 0u>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LAMBERT>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LAMBERT>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll | PBRS_SHADE_LAMBERT>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE>(),
+    // textures, the Fourier lobe, the Fourier materials' class alone
+    shade_kernel<PBRS_INTEGRATOR_PATH, true, 0u>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, true, PBRS_SHADE_FOURIER>(),
+    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeFourierOnly>(),
+    shade_kernel<PBRS_INTEGRATOR_DIRECT, false, 0u>(),
+    shade_kernel<PBRS_INTEGRATOR_DIRECT, true, 0u>(),
+    shade_kernel<PBRS_INTEGRATOR_DIRECT, true, PBRS_SHADE_FOURIER>(),
+    shade_kernel<PBRS_INTEGRATOR_DIRECT, false, kShadeFourierOnly>(),
+    // the visualisers
+    shade_kernel<PBRS_INTEGRATOR_MATERIALS, false, 0u>(),
+    shade_kernel<PBRS_INTEGRATOR_NORMALS, false, 0u>(),
+};
+shade_fn_t shade_fn(uint32_t integ, bool tex, uint32_t spec) {
+    for (const ShadeKernel& k : kShadeKernels)
+        if (k.integ == integ && k.tex == tex && k.spec == spec) return k.fn;
+    return nullptr;
 }
-int launch_shadow(pbrs_ctx* c, bool stats, bool wide, uint32_t grid, size_t lds, const uint32_t* count, uint32_t* heads, const uint32_t* indirect,
-                  uint32_t* slow_list, uint32_t* slow_count) {
-    if (stats) {
-        hipLaunchKernelGGL((k_shadow<true, PBRS_FEAT_ANALYTIC | PBRS_FEAT_FLAT_TLAS>), dim3(grid), dim3(kBlock), lds, c->stream, c->S, c->st, count, heads, c->gcnt + 1,
-                           indirect, slow_list, slow_count);
-        c->pending.kernel_features_shadow = PBRS_FEAT_ANALYTIC | PBRS_FEAT_FLAT_TLAS | 0x80000000u;
-        return PBRS_OK;
+
+// The kernels that render a scene, from what pbrs_upload_scene found out about it, bent by the developer overrides.  False where a
+// table lacks a kernel the choice names.
+bool plan_kernels(const SceneFacts& f, const DevOverrides& dev, KernelPlan& p) {
+    p = KernelPlan{};
+    const bool long_walks = dev.long_walks.value_or(f.long_walks);
+    const bool full_steps = dev.full_steps.value_or(f.full_steps);
+    const uint32_t steps = long_walks ? PBRS_FEAT_LONG_WALKS | (full_steps ? PBRS_FEAT_FULL_STEPS : 0u) : 0u;
+    p.wide_shadow = f.tlas_scanned && f.wide_ok && dev.wide_shadow;
+    // The arrays the walks read, staged in every block's LDS (kernels.h, stage_scene) where they fit next to the stack rows with
+    // eight blocks to a CU: scenes of a few KB whose walks are short (no wide nodes, lean-step choice irrelevant) ...
+    const bool lds_scene = dev.lds_scene && !p.wide_shadow && !full_steps && f.stack_bytes + f.scene_bytes <= kLdsBytesPerCU / 8;
+    // ... or the TLAS alone, where it is too large for the wave's shared scan (no leaf copies) and fits with seven blocks to a CU
+    const bool lds_top = dev.lds_top && !lds_scene && !f.tlas_scanned && !full_steps && f.stack_bytes + f.top_bytes + 512 <= kLdsBytesPerCU / 7;
+    p.lds_staging = lds_scene ? PBRS_FEAT_LDS_SCENE : lds_top ? PBRS_FEAT_LDS_TOP : 0u;
+    const size_t stack = std::max(f.stack_bytes, dev.lds_min);
+    const size_t staged = stack + (lds_scene ? f.scene_bytes : lds_top ? f.top_bytes : 0u);
+    if (f.exact_extent) {  // (scenes with a ParallelQuad next to a mesh: no benchmark holds one)
+        p.extend[0] = stage_kernel(extend_fns(), kExtentFeatures, stack);
+        p.extend[1] = stage_kernel(extend_fns(), kStatsKey | kExtentFeatures, stack);
+    } else {
+        p.extend[0] = stage_kernel(extend_fns(), (f.features & PBRS_FEAT_ALL) | steps | p.lds_staging, staged);
+        p.extend[1] = stage_kernel(extend_fns(), kStatsKey | PBRS_FEAT_ALL, stack);
     }
-    uint32_t feat = (c->S.features & PBRS_FEAT_ANALYTIC) | (c->shadow_flat ? PBRS_FEAT_FLAT_TLAS : 0u) | (c->long_walks ? PBRS_FEAT_LONG_WALKS : 0u) |
-                    ((c->long_walks && c->full_steps) ? PBRS_FEAT_FULL_STEPS : 0u);
-    if (wide) feat |= PBRS_FEAT_WIDE;  // (PBRS_FEAT_FLAT_TLAS is set: pbrs_upload_scene)
-    if (c->lds_scene && !wide) {
-        feat |= PBRS_FEAT_LDS_SCENE;
-        lds += c->lds_scene_bytes;
-    } else if (c->lds_top && !wide && !(feat & (PBRS_FEAT_FLAT_TLAS | PBRS_FEAT_FULL_STEPS))) {
-        feat |= PBRS_FEAT_LDS_TOP;
-        lds += c->lds_top_bytes;
+    const uint32_t shadow_feat = (f.features & PBRS_FEAT_ANALYTIC) | (f.tlas_scanned ? PBRS_FEAT_FLAT_TLAS : 0u) | steps;
+    if (p.wide_shadow) {
+        p.shadow[0] = stage_kernel(shadow_fns(), shadow_feat | PBRS_FEAT_WIDE, f.wide_stack_bytes);
+        p.shadow_slow = stage_kernel(shadow_fns(), shadow_feat, stack);
+    } else {
+        p.shadow[0] = stage_kernel(shadow_fns(), shadow_feat | p.lds_staging, staged);
     }
-    const shadow_fn_t fn = shadow_fns()[feat];
-    if (!fn) return fail(c, PBRS_E_DEVICE, "no k_shadow instantiation for this scene's feature set");
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kBlock), lds, c->stream, c->S, c->st, count, heads, c->gcnt + 1, indirect, slow_list, slow_count);
-    if (!indirect) c->pending.kernel_features_shadow = feat;
-    return PBRS_OK;
+    p.shadow[1] = stage_kernel(shadow_fns(), kStatsKey | kShadowStatsFeatures, stack);
+    bool ok = p.extend[0].fn && p.extend[1].fn && p.shadow[0].fn && p.shadow[1].fn && (!p.wide_shadow || p.shadow_slow.fn);
+    p.split_queue = f.n_classes <= 1u && dev.split_queue;
+
+    // k_shade.  The path integrator's untextured variants stage the scene's shading records (and triangle records) in LDS where they fit,
+    // and leave out what the scene's materials and lights do not need (the light shape alone does not pay: without the Lambert cut the
+    // kernel grows to 135-141 VGPRs, three waves per SIMD; C2 shade 110.5 -> 117.0 ms, C4 150.6 -> 169.3)
+    const uint32_t shade_lds = f.shade_lds & dev.shade_lds;
+    const uint32_t path_lds = (shade_lds == kShadeLdsAll || shade_lds == PBRS_SHADE_LDS_RECORDS) ? shade_lds : 0u;
+    const size_t path_lds_bytes = path_lds == kShadeLdsAll ? f.shade_rec_bytes + f.shade_tri_bytes : path_lds ? f.shade_rec_bytes : 0u;
+    uint32_t spec = f.lambert ? (PBRS_SHADE_LAMBERT | f.light_spec) & dev.shade_spec : 0u;
+    if (!(spec & PBRS_SHADE_LAMBERT)) spec = 0u;
+    auto shade = [&](IntegratorPlan& ip, uint32_t integ, bool tex, uint32_t sp, size_t lds, uint32_t range) {
+        ip.shade[ip.n_shade++] = ShadeLaunch{shade_fn(integ, tex, sp), lds, range};
+        ok = ok && ip.shade[ip.n_shade - 1].fn;
+    };
+    auto path_untextured = [&](IntegratorPlan& ip, uint32_t sp, uint32_t range) { shade(ip, PBRS_INTEGRATOR_PATH, false, sp | path_lds, path_lds_bytes, range); };
+    // several shading classes (and an integrator that shades): the queue is ordered by class first; counted as shade time
+    const bool sorted = f.n_classes > 1u && dev.sort_classes;
+    for (uint32_t i = PBRS_INTEGRATOR_PATH; i <= PBRS_INTEGRATOR_DIRECT; ++i) {
+        IntegratorPlan& ip = p.integ[i];
+        const bool path = i == PBRS_INTEGRATOR_PATH;
+        // ... and where one of the classes is Lambertian (and the integrator has a Lambert variant), class-major over the whole
+        // queue, so that the class gets a launch of that variant and the other classes one of the general kernel
+        const bool split = sorted && path && f.lambert_class && dev.split_lambert && !f.textured && !f.fourier;
+        // ... or a Fourier BSDF: its lobe's code (168 registers and scratch in k_shade's variants that carry it) then runs over
+        // the vertices on such a material only, the other classes take the kernels without it
+        const bool fsplit = sorted && f.fourier && f.fourier_class && dev.split_fourier;
+        ip.order = (split || fsplit) ? IntegratorPlan::CLASS_MAJOR : sorted ? IntegratorPlan::CLASS_SORT : IntegratorPlan::NO_ORDER;
+        ip.last_class = split ? f.lambert_class : fsplit ? f.fourier_class : 0u;
+        if (fsplit) {  // (one untextured Fourier lobe per material: the variant cut down to it)
+            shade(ip, i, false, kShadeFourierOnly, 0, f.fourier_class);
+            shade(ip, i, f.textured, 0u, 0, PBRS_MAX_CLASSES);
+        } else if (f.fourier && f.fourier_class && f.n_classes == 1u) {  // every material with lobes is a Fourier BSDF
+            shade(ip, i, false, kShadeFourierOnly, 0, 0u);
+        } else if (f.fourier) {  // some material is a Fourier BSDF: the kernels that carry the lobe (and textures)
+            shade(ip, i, true, PBRS_SHADE_FOURIER, 0, 0u);
+        } else if (f.textured) {  // some material evaluates a non-Solid texture per hit
+            shade(ip, i, true, 0u, 0, 0u);
+        } else if (!path) {
+            shade(ip, i, false, 0u, 0, 0u);
+        } else if (split) {
+            path_untextured(ip, PBRS_SHADE_LAMBERT | f.light_spec, f.lambert_class);
+            path_untextured(ip, 0u, PBRS_MAX_CLASSES);
+        } else {
+            path_untextured(ip, spec, 0u);
+        }
+    }
+    shade(p.integ[PBRS_INTEGRATOR_MATERIALS], PBRS_INTEGRATOR_MATERIALS, false, 0u, 0, 0u);
+    shade(p.integ[PBRS_INTEGRATOR_NORMALS], PBRS_INTEGRATOR_NORMALS, false, 0u, 0, 0u);
+    return ok;
 }
 
 // The split probe of an earlier pass (run_pass), if its counts have arrived: keep the queue split where it keeps at most
@@ -573,28 +708,31 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     uint32_t* act = c->counters;                 // act[b]: paths entering bounce b (b >= 1)
     // ns[b]: one 64-bit word per bounce: low half = paths whose light estimate waits for visibility, high half = shadow rays
     unsigned long long* ns = reinterpret_cast<unsigned long long*>(c->counters + stride);
+    uint32_t* slows = c->counters + 3 * stride;  // k_shadow's slow-list length per bounce
     // work-fetch heads of k_extend / k_shadow: kHeadWords words per bounce (one head per queue segment, kernels.h)
-    uint32_t* slowx = c->counters + 3 * stride;  // slow-list lengths per bounce: k_extend's, k_shadow's
-    uint32_t* slows = slowx + stride;
-    uint32_t* xhead = c->counters + 7 * stride;
+    uint32_t* xhead = c->counters + 4 * stride;
     uint32_t* shead = xhead + stride * kHeadWords;
-    uint32_t* xhead2 = shead + stride * kHeadWords;  // the binary-walk launches over the slow lists
-    uint32_t* shead2 = xhead2 + stride * kHeadWords;
-    const bool wide_x = c->wide_extend && !stats, wide_s = c->wide_shadow && !stats;
-    const size_t lds_wx = lds_bytes_wide(c, true), lds_ws = lds_bytes_wide(c, false);
+    uint32_t* shead2 = shead + stride * kHeadWords;  // the binary-walk launch over k_shadow's slow list
     uint32_t* neeq = c->neeq;
+    const KernelPlan& plan = c->plan;
+    const IntegratorPlan& ip = plan.integ[rc.integrator];
+    const StageKernel<extend_fn_t>& xk = plan.extend[stats];
+    const StageKernel<shadow_fn_t>& sk = plan.shadow[stats];
+    // k_extend scans the TLAS leaves only up to PBRS_FLAT_TLAS_MAX instances (S.features); the leaf copies may exist for k_shadow
+    // alone, and the instrumented variant, which carries every feature, must then walk the tree like the timed one
+    DevScene xS = c->S;
+    if (!(xS.features & PBRS_FEAT_FLAT_TLAS)) xS.n_flat = 0u;
     HIPCHK(c, hipMemsetAsync(c->counters, 0, kCounterWords * sizeof(uint32_t), c->stream));
     if (tm.begin(0)) return fail(c, PBRS_E_DEVICE, "event record failed");
     hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, c->stream, c->st, rc);
     tm.end();
-    const size_t lds = lds_bytes(c);
     poll_split_probe(c);
     // the direct-lighting integrator is at most two rays deep whatever `depth` says (directlighting.rs:15-17, :36, :49)
     const uint32_t n_bounces = rc.integrator == PBRS_INTEGRATOR_DIRECT      ? (rc.max_depth ? 2u : 0u)
                                : rc.integrator >= PBRS_INTEGRATOR_MATERIALS ? 1u  // the visualisers: one cast, no lights
                                                                             : rc.max_depth;
     // this pass counts what k_extend's queue split keeps (the first path-integrator pass of an uploaded one-class scene)
-    const bool probe_split = c->split_decision == 0 && !c->split_probe_in_flight && rc.integrator == PBRS_INTEGRATOR_PATH && c->S.n_classes <= 1u && c->split_queue && n_bounces > 0;
+    const bool probe_split = c->split_decision == 0 && !c->split_probe_in_flight && rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && n_bounces > 0;
     for (uint32_t b = 0; b < n_bounces; ++b) {
         if (handoff && b == c->overlap_from) HIPCHK(c, to_late_stream());
         // bounce b reads the path records of set b & 1 (k_raygen wrote set 0) and k_shade writes set (b + 1) & 1; the
@@ -603,108 +741,42 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         if (tm.begin(1)) return fail(c, PBRS_E_DEVICE, "event record failed");
         // the path integrator on a scene with one shading class (no class sort): k_extend splits its queue into the hits k_shade
         // shades, the paths that only end (emitter hits, misses that see the environment) and the misses nothing happens to
-        const uint32_t qsplit = (rc.integrator == PBRS_INTEGRATOR_PATH && c->S.n_classes <= 1u && c->split_queue && c->split_decision != 2) ? (1u | (b == 0 ? 2u : 0u)) : 0u;
-        int lrc = launch_extend(c, stats, wide_x, pgrid, wide_x ? lds_wx : lds, b & 1u, cnt_in, N, xhead + b * kHeadWords, nullptr, c->slow, slowx + b, qsplit);
-        if (!lrc && wide_x)  // what the wide walks refused (rays outside the guarded range of the division-free box test, overlong stacks)
-            lrc = launch_extend(c, false, false, pgrid < kSlowGrid ? pgrid : kSlowGrid, lds, b & 1u, slowx + b, 0u, xhead2 + b * kHeadWords, c->slow, nullptr, nullptr, qsplit);
-        if (lrc) return lrc;
+        const uint32_t qsplit = (rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && c->split_decision != 2) ? (1u | (b == 0 ? 2u : 0u)) : 0u;
+        hipLaunchKernelGGL(xk.fn, dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, c->st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr, nullptr,
+                           nullptr, qsplit);
+        c->pending.kernel_features_extend = xk.features;
         tm.end();
         if (tm.begin(2)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        // several shading classes (and an integrator that shades): order the queue by class first; counted as shade time
-        const uint32_t sorted = (c->S.n_classes > 1u && rc.integrator <= PBRS_INTEGRATOR_DIRECT && c->sort_classes) ? 1u : 0u;
-        // ... and where one of the classes is Lambertian (and the integrator has a Lambert variant), class-major over the whole
-        // queue, so that the class gets a launch of that variant and the other classes one of the general kernel
-        const bool split = sorted && c->lambert_class && c->split_lambert && !c->textured && !c->fourier && rc.integrator == PBRS_INTEGRATOR_PATH;
-        // ... or a Fourier BSDF: its lobe's code (168 registers and scratch in k_shade's variants that carry it) then runs over
-        // the vertices on such a material only, the other classes take the kernels without it
-        const bool fsplit = sorted && c->fourier && c->fourier_class && c->split_fourier && rc.integrator <= PBRS_INTEGRATOR_DIRECT;
+        // the queue in the order the plan asks for; a queue k_extend split: class-major over its two classes, class 1 = the kept paths, last
+        const IntegratorPlan::Order order = qsplit ? IntegratorPlan::CLASS_MAJOR : ip.order;
         const uint32_t n_tiles = (N + PBRS_SORT_TILE - 1) / PBRS_SORT_TILE;
-        if (split || qsplit || fsplit) {  // class-major over the whole queue; a queue k_extend split: class 1 = the kept paths, last
+        if (order == IntegratorPlan::CLASS_MAJOR) {
             if (qsplit) hipLaunchKernelGGL(k_class_count<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
             else hipLaunchKernelGGL(k_class_count<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
-            hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, c->st, cnt_in, N, qsplit ? 1u : fsplit ? c->fourier_class : c->lambert_class,
+            hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, c->st, cnt_in, N, qsplit ? 1u : ip.last_class,
                                (qsplit && probe_split) ? c->bounce_acc + 2 * PBRS_STATS_MAX_BOUNCES : nullptr);
             if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
             else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
-        } else if (sorted) {
+        } else if (order == IntegratorPlan::CLASS_SORT) {
             hipLaunchKernelGGL(k_class_sort, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
         }
-        {
-#define PBRS_LAUNCH_SHADE_LDS(I, T, SP, LDS)                                                                                              \
-    hipLaunchKernelGGL((k_shade<I, T, SP>), dim3(shade_grid), dim3(kBlock), LDS, c->stream, c->S, c->st, rc, b, shade_count, N, act + b + 1, neeq, ns + b, \
-                       sorted | split_sorted, shade_range)
-#define PBRS_LAUNCH_SHADE(I, T, SP) PBRS_LAUNCH_SHADE_LDS(I, T, SP, 0)
-// the path integrator's untextured variants: with the scene's shading records (and triangle records) staged in LDS where they fit
-#define PBRS_LAUNCH_SHADE_PATH(SP)                                                                                                               \
-    do {                                                                                                                                          \
-        if (c->shade_lds == (PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS))                                                                        \
-            PBRS_LAUNCH_SHADE_LDS(PBRS_INTEGRATOR_PATH, false, (SP) | PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS, c->shade_lds_bytes);           \
-        else if (c->shade_lds == PBRS_SHADE_LDS_RECORDS)                                                                                           \
-            PBRS_LAUNCH_SHADE_LDS(PBRS_INTEGRATOR_PATH, false, (SP) | PBRS_SHADE_LDS_RECORDS, c->shade_lds_bytes);                                 \
-        else                                                                                                                                       \
-            PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, false, SP);                                                                                    \
-    } while (0)
-            const uint32_t shade_grid = grid;
-            const uint2* shade_range = qsplit ? c->st.class_range + 1 : nullptr;  // a split queue: the kept paths
-            const uint32_t split_sorted = qsplit ? 1u : 0u;
-            const uint32_t* shade_count = cnt_in;
-            {
-            const bool direct = rc.integrator == PBRS_INTEGRATOR_DIRECT;
-            if (rc.integrator == PBRS_INTEGRATOR_MATERIALS) {
-                PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_MATERIALS, false, 0u);
-            } else if (rc.integrator == PBRS_INTEGRATOR_NORMALS) {
-                PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_NORMALS, false, 0u);
-            } else if (c->fourier && fsplit) {  // the Fourier materials' class under the kernels that carry the lobe, the rest without
-                shade_range = c->st.class_range + c->fourier_class;  // (one untextured Fourier lobe per material: the variant cut down to it)
-                if (direct) PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, false, PBRS_SHADE_FOURIER | PBRS_SHADE_FOURIER_ONLY);
-                else PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_FOURIER | PBRS_SHADE_FOURIER_ONLY);
-                shade_range = c->st.class_range + PBRS_MAX_CLASSES;
-                if (c->textured) {
-                    if (direct) PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, true, 0u);
-                    else PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, true, 0u);
-                } else {
-                    if (direct) PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, false, 0u);
-                    else PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, false, 0u);
-                }
-            } else if (c->fourier && c->fourier_class && c->S.n_classes == 1u) {  // every material with lobes is a Fourier BSDF
-                if (direct) PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, false, PBRS_SHADE_FOURIER | PBRS_SHADE_FOURIER_ONLY);
-                else PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_FOURIER | PBRS_SHADE_FOURIER_ONLY);
-            } else if (c->fourier) {  // some material is a Fourier BSDF: the kernels that carry the lobe (and textures)
-                if (direct) PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, true, PBRS_SHADE_FOURIER);
-                else PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, true, PBRS_SHADE_FOURIER);
-            } else if (c->textured) {  // some material evaluates a non-Solid texture per hit
-                if (direct) PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, true, 0u);
-                else PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_PATH, true, 0u);
-            } else if (direct) {
-                PBRS_LAUNCH_SHADE(PBRS_INTEGRATOR_DIRECT, false, 0u);
-            } else if (split) {
-                shade_range = c->st.class_range + c->lambert_class;
-                switch (c->light_spec) {
-                    case PBRS_SHADE_LIGHT_SPHERE: PBRS_LAUNCH_SHADE_PATH(PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE); break;
-                    case PBRS_SHADE_LIGHT_TRIANGLE: PBRS_LAUNCH_SHADE_PATH(PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE); break;
-                    default: PBRS_LAUNCH_SHADE_PATH(PBRS_SHADE_LAMBERT); break;
-                }
-                shade_range = c->st.class_range + PBRS_MAX_CLASSES;
-                PBRS_LAUNCH_SHADE_PATH(0u);
-            } else {  // the path integrator, specialised on what the scene's materials and lights are (c->shade_spec)
-                switch (c->shade_spec) {
-                    case PBRS_SHADE_LAMBERT: PBRS_LAUNCH_SHADE_PATH(PBRS_SHADE_LAMBERT); break;
-                    case PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE: PBRS_LAUNCH_SHADE_PATH(PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE); break;
-                    case PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE: PBRS_LAUNCH_SHADE_PATH(PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE); break;
-                    default: PBRS_LAUNCH_SHADE_PATH(0u); break;
-                }
-            }
-            }
-#undef PBRS_LAUNCH_SHADE_PATH
-#undef PBRS_LAUNCH_SHADE
-#undef PBRS_LAUNCH_SHADE_LDS
+        const uint32_t sorted = order != IntegratorPlan::NO_ORDER ? 1u : 0u;
+        for (uint32_t k = 0; k < ip.n_shade; ++k) {
+            const ShadeLaunch& l = ip.shade[k];
+            // one class range of a class-major queue; a split queue: the kept paths
+            const uint2* range = l.range ? c->st.class_range + l.range : qsplit ? c->st.class_range + 1 : nullptr;
+            hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), l.lds, c->stream, c->S, c->st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b, sorted, range);
         }
         tm.end();
         if (tm.begin(3)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        lrc = launch_shadow(c, stats, wide_s, pgrid, wide_s ? lds_ws : lds, reinterpret_cast<const uint32_t*>(ns + b), shead + b * kHeadWords, nullptr, c->slow, slows + b);
-        if (!lrc && wide_s)
-            lrc = launch_shadow(c, false, false, pgrid < kSlowGrid ? pgrid : kSlowGrid, lds, slows + b, shead2 + b * kHeadWords, c->slow, nullptr, nullptr);
-        if (lrc) return lrc;
+        hipLaunchKernelGGL(sk.fn, dim3(pgrid), dim3(kBlock), sk.lds, c->stream, c->S, c->st, reinterpret_cast<const uint32_t*>(ns + b), shead + b * kHeadWords, c->gcnt + 1,
+                           nullptr, c->slow, slows + b);
+        c->pending.kernel_features_shadow = sk.features;
+        if (plan.wide_shadow && !stats) {  // what the wide walks refused (rays outside the guarded range of the division-free box test, overlong stacks)
+            const StageKernel<shadow_fn_t>& slow = plan.shadow_slow;
+            hipLaunchKernelGGL(slow.fn, dim3(pgrid < kSlowGrid ? pgrid : kSlowGrid), dim3(kBlock), slow.lds, c->stream, c->S, c->st, slows + b, shead2 + b * kHeadWords,
+                               c->gcnt + 1, c->slow, nullptr, nullptr);
+        }
         hipLaunchKernelGGL(k_nee_resolve, dim3(sgrid), dim3(kBlock), 0, c->stream, c->st, neeq, reinterpret_cast<const uint32_t*>(ns + b));
         tm.end();
     }
@@ -741,7 +813,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     const uint32_t K = auto_samples_per_pass(c, p);
     rcode = ensure_work(c, (size_t)P * K, P);
     if (rcode) return rcode;
-    RenderConst rc = make_const(cam, p);
+    RenderConst rc = make_const(c, cam, p);
     const bool stats = p->collect_counters != 0;
     Timer tm{c, p->time_stages != 0};
     c->events_used = 0;
@@ -836,25 +908,18 @@ int collect(pbrs_ctx* c, pbrs_stats* out) {
 // The traversal kernels take their per-lane stacks from dynamic LDS.  The limit a kernel may ask for is per-function state
 // of the PROCESS (hipFuncSetAttribute), not of a context: it is raised once per device, to the most any scene may need
 // (pbrs_upload_scene refuses stacks above kLdsBytesPerCU / 2), so that contexts holding scenes with different stack depths
-// can render side by side — rewriting it per upload let the last upload decide for every context of the process.
+// can render side by side — rewriting it per upload let the last upload decide for every context of the process.  Every traversal
+// kernel a plan can name sits in the tables (plan_kernels).
 std::mutex g_kernel_cfg_mutex;
 bool g_kernel_cfg_done[64] = {};
 int configure_kernels(pbrs_ctx* c) {
     std::lock_guard<std::mutex> lock(g_kernel_cfg_mutex);
     if (c->device < 64 && g_kernel_cfg_done[c->device]) return PBRS_OK;
     const int cap = (int)(kLdsBytesPerCU / 2);
-    std::vector<const void*> traversal_kernels = {reinterpret_cast<const void*>(&k_extend<true, PBRS_FEAT_ALL>),
-                                                  reinterpret_cast<const void*>(&k_shadow<true, PBRS_FEAT_ANALYTIC | PBRS_FEAT_FLAT_TLAS>),
-                                                  reinterpret_cast<const void*>(&k_intersect_rays<false, false>),
-                                                  reinterpret_cast<const void*>(&k_intersect_rays<false, true>),
-#ifdef PBRS_DEV_OVERRIDES
-                                                  reinterpret_cast<const void*>(&k_intersect_rays<true, false>),
-                                                  reinterpret_cast<const void*>(&k_intersect_rays<true, true>),
-#endif
-    };
-    for (uint32_t f = 0; f < kFeatCombos; ++f) {
-        if (extend_fns()[f]) traversal_kernels.push_back(reinterpret_cast<const void*>(extend_fns()[f]));
-        if (shadow_fns()[f]) traversal_kernels.push_back(reinterpret_cast<const void*>(shadow_fns()[f]));
+    std::vector<const void*> traversal_kernels = {reinterpret_cast<const void*>(&k_intersect_rays<false>), reinterpret_cast<const void*>(&k_intersect_rays<true>)};
+    for (uint32_t k = 0; k < kTraversalKeys; ++k) {
+        if (extend_fns()[k]) traversal_kernels.push_back(reinterpret_cast<const void*>(extend_fns()[k]));
+        if (shadow_fns()[k]) traversal_kernels.push_back(reinterpret_cast<const void*>(shadow_fns()[k]));
     }
     for (const void* k : traversal_kernels) HIPCHK(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
     if (c->device < 64) g_kernel_cfg_done[c->device] = true;
@@ -915,11 +980,10 @@ int pbrs_create(int device_ordinal, pbrs_ctx** out) {
          hipEventCreateWithFlags(&c->pass_set[1].accumulated, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&c->pass_set[0].late, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&c->pass_set[1].late, hipEventDisableTiming) == hipSuccess;
-    if (const char* e = dev_env("PBRS_OVERLAP_PASSES")) c->overlap_passes = std::atoi(e) != 0;
-    if (const char* e = dev_env("PBRS_SORT_CLASSES")) c->sort_classes = std::atoi(e) != 0;
-    if (const char* e = dev_env("PBRS_SPLIT_LAMBERT")) c->split_lambert = std::atoi(e) != 0;
-    if (const char* e = dev_env("PBRS_SPLIT_FOURIER")) c->split_fourier = std::atoi(e) != 0;
-    if (const char* e = dev_env("PBRS_SPLIT_QUEUE")) c->split_queue = std::atoi(e) != 0;
+#ifdef PBRS_DEV_OVERRIDES
+    c->dev = read_dev_overrides();
+#endif
+    c->overlap_passes = c->dev.overlap_passes;
     for (int k = 0; ok && k < 2; ++k) {
         hipEvent_t ev = nullptr;
         ok = hipEventCreate(&ev) == hipSuccess;
@@ -1120,6 +1184,7 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     (void)hipStreamSynchronize(c->second_stream);
     free_scene(c);
     DevScene S{};
+    SceneFacts f{};
     int rc;
     // The division-free box test (device/traverse.h) is exact when every node coordinate b is finite, |b| <= 2^40 and (b == 0 or
     // |b| >= 2^-60) — the range of a ray's origin components (origin_in_range); otherwise every lane uses the literal divisions.
@@ -1188,15 +1253,13 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
             }
             S.n_classes = (uint32_t)std::min<size_t>(sigs.size(), PBRS_MAX_CLASSES - 1);
             // the class of the materials that are one untextured Lambertian DiffuseReflect (signature: kind 1, not Oren-Nayar)
-            c->lambert_class = 0;
             const std::string lam_sig = {(char)('a' + PBRS_BXDF_DIFFUSE), 'a', 'a', 'a', '-'};
             for (size_t at = 0; at < sigs.size() && at + 1 < PBRS_MAX_CLASSES - 1; ++at)
-                if (sigs[at] == lam_sig) c->lambert_class = (uint32_t)at + 1;
+                if (sigs[at] == lam_sig) f.lambert_class = (uint32_t)at + 1;
             // ... and of the materials that are one Fourier BSDF (material/src/lib.rs:451-475: whatever their tables, one signature)
-            c->fourier_class = 0;
             const std::string fou_sig = {(char)('a' + PBRS_BXDF_FOURIER), 'a', 'a', 'a', '-'};
             for (size_t at = 0; at < sigs.size() && at + 1 < PBRS_MAX_CLASSES - 1; ++at)
-                if (sigs[at] == fou_sig) c->fourier_class = (uint32_t)at + 1;
+                if (sigs[at] == fou_sig) f.fourier_class = (uint32_t)at + 1;
         }
         for (pbrs_instance& in : inst) {
             in.pad[0] = mat_class[in.material];
@@ -1262,36 +1325,22 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     S.has_env = (d->env_kind != PBRS_ENV_CONSTANT || !(S.env[0] <= 0.0f && S.env[1] <= 0.0f && S.env[2] <= 0.0f)) ? 1u : 0u;
     S.refill_below = max_blas_height >= PBRS_LONG_WALK_HEIGHT ? PBRS_REFILL_BELOW_LONG : PBRS_REFILL_BELOW_SHORT;
     S.refill_below_shadow = max_blas_height >= PBRS_LONG_WALK_HEIGHT ? PBRS_REFILL_BELOW_LONG_SHADOW : PBRS_REFILL_BELOW_SHORT;
-    if (const char* e = dev_env("PBRS_REFILL_BELOW")) S.refill_below = S.refill_below_shadow = (uint32_t)std::atoi(e);  // developer override (A/B timing)
+    if (c->dev.refill_below) S.refill_below = S.refill_below_shadow = *c->dev.refill_below;
     // long walks: the levels a ray actually walks — the deepest BLAS, plus the TLAS where it is not scanned
-    c->long_walks = (S.n_flat ? 0u : tlas_levels) + max_blas_height >= PBRS_LONG_WALK_HEIGHT;
-    if (const char* e = dev_env("PBRS_LONG_WALKS")) c->long_walks = std::atoi(e) != 0;  // developer override (A/B timing)
+    f.long_walks = (S.n_flat ? 0u : tlas_levels) + max_blas_height >= PBRS_LONG_WALK_HEIGHT;
     // lean further node steps for rays on the division-free box test; a scene whose coordinates leave its guarded range walks every
     // ray on the literal divisions, which the lean steps do not carry: full steps (kernels.h)
-    c->walk_bytes = walk_bytes;
-    c->full_steps = S.fast_slab == 0u;
-    if (const char* e = dev_env("PBRS_FULL_STEPS")) c->full_steps = std::atoi(e) != 0;  // developer override (A/B timing)
-    c->overlap_from = walk_bytes <= (4ull << 20) ? 2u : 4u;  // one XCD's L2 holds the arrays the walks read, or not (pbrs_ctx::overlap_from)
-    if (const char* e = dev_env("PBRS_OVERLAP_FROM")) c->overlap_from = (uint32_t)std::atoi(e);  // developer override (A/B timing)
+    f.full_steps = S.fast_slab == 0u;
+    c->overlap_from = c->dev.overlap_from.value_or(walk_bytes <= (4ull << 20) ? 2u : 4u);  // one XCD's L2 holds the arrays the walks read, or not (pbrs_ctx::overlap_from)
     // the leaf copies serve k_shadow up to PBRS_FLAT_TLAS_MAX_ANYHIT instances, k_extend up to PBRS_FLAT_TLAS_MAX
-    c->shadow_flat = S.n_flat != 0u;
-    const uint32_t flat_feature = (S.n_flat != 0u && d->n_instances <= PBRS_FLAT_TLAS_MAX) ? PBRS_FEAT_FLAT_TLAS : 0u;
-    S.features = flat_feature;
+    f.tlas_scanned = S.n_flat != 0u;
+    S.features = (S.n_flat != 0u && d->n_instances <= PBRS_FLAT_TLAS_MAX) ? PBRS_FEAT_FLAT_TLAS : 0u;
     // the walks over four-wide nodes: scenes whose TLAS the stage scans and whose coordinates admit the division-free box test
     // ... and that have a BLAS deep enough for it to matter (PBRS_WIDE_MIN_LEVELS wide nodes on the way down: meshes of a few
     // triangles are a leaf or two, where the binary walks at their six waves per SIMD are faster — C2: 105 against 140 ms)
-    // k_shadow gains (C4: 250 -> 236 ms per frame at five waves per SIMD); k_extend, whose wide walk needs 117 registers (four
-    // waves per SIMD, or 72 bytes of spills at five), loses against the binary walk at six (459 -> 506 ms) and keeps the binary
-    // walk: its wide kernels exist in developer builds only (PBRS_WIDE bit 0).
-    const bool wide_ok = S.fast_slab != 0u && S.wnodes != nullptr && wide_levels >= PBRS_WIDE_MIN_LEVELS;
-    c->wide_extend = false;
-    c->wide_shadow = c->shadow_flat && wide_ok;
-#ifdef PBRS_DEV_OVERRIDES
-    if (const char* e = dev_env("PBRS_WIDE")) {  // developer override (A/B timing): bit 0 k_extend, bit 1 k_shadow
-        c->wide_extend = flat_feature != 0u && wide_ok && (std::atoi(e) & 1);
-        c->wide_shadow = c->wide_shadow && (std::atoi(e) & 2);
-    }
-#endif
+    // k_shadow gains (C4: 250 -> 236 ms per frame at five waves per SIMD); k_extend keeps the binary walk (a four-wide closest-hit
+    // walk needed 117 registers, four waves per SIMD, and lost against the binary walk at six: 459 -> 506 ms)
+    f.wide_ok = S.fast_slab != 0u && S.wnodes != nullptr && wide_levels >= PBRS_WIDE_MIN_LEVELS;
     for (uint32_t i = 0; i < d->n_instances; ++i) {
         const pbrs_instance& in = d->instances[i];
         if (in.shape_kind == PBRS_SHAPE_MESH) {
@@ -1300,68 +1349,54 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
             S.features |= PBRS_FEAT_ANALYTIC;
         }
     }
+    f.features = S.features;
+    f.exact_extent = exact_extent;
+    f.n_classes = S.n_classes;
+    f.textured = textured;
+    f.fourier = fourier;
     // k_shade specialisation: every lobe an untextured Lambertian DiffuseReflect (at most one per material); every area light
     // of one shape
-    {
-        bool lambert = !textured;
-        for (uint32_t i = 0; i < d->n_materials && lambert; ++i) {
-            const pbrs_material& m = d->materials[i];  // its lobes only: the array also holds the visualisers' records
-            lambert = m.n_bxdfs <= 1;
-            for (uint32_t k = 0; k < m.n_bxdfs && lambert; ++k) {
-                const pbrs_bxdf& bx = d->bxdfs[m.first_bxdf + k];
-                lambert = bx.kind == PBRS_BXDF_DIFFUSE && bx.oren_nayar == 0 && bx.tex == 0;
-            }
+    f.lambert = !textured;
+    for (uint32_t i = 0; i < d->n_materials && f.lambert; ++i) {
+        const pbrs_material& m = d->materials[i];  // its lobes only: the array also holds the visualisers' records
+        f.lambert = m.n_bxdfs <= 1;
+        for (uint32_t k = 0; k < m.n_bxdfs && f.lambert; ++k) {
+            const pbrs_bxdf& bx = d->bxdfs[m.first_bxdf + k];
+            f.lambert = bx.kind == PBRS_BXDF_DIFFUSE && bx.oren_nayar == 0 && bx.tex == 0;
         }
-        uint32_t light_spec = 0u;
-        if (d->n_area_lights) {
-            const uint32_t k0 = d->area_lights[0].shape_kind;
-            bool same = true;
-            for (uint32_t i = 1; i < d->n_area_lights; ++i) same = same && d->area_lights[i].shape_kind == k0;
-            if (same && k0 == PBRS_SHAPE_SPHERE) light_spec = PBRS_SHADE_LIGHT_SPHERE;
-            if (same && k0 == PBRS_SHAPE_TRIANGLE) light_spec = PBRS_SHADE_LIGHT_TRIANGLE;
-        }
-        c->light_spec = light_spec;
-        // the light shape alone does not pay: without the Lambert cut the kernel grows to 135-141 VGPRs, three waves per SIMD
-        // (C2 shade 110.5 -> 117.0 ms, C4 150.6 -> 169.3)
-        uint32_t spec = lambert ? (PBRS_SHADE_LAMBERT | light_spec) : 0u;
-        if (const char* e = dev_env("PBRS_SHADE_SPEC")) spec &= (uint32_t)std::atoi(e);  // developer override (A/B timing): a mask
-        c->shade_spec = spec;
     }
-    // The arrays the walks read, staged in every block's LDS (kernels.h, stage_scene) where they fit next to the stack rows with
-    // eight blocks to a CU: scenes of a few KB whose walks are short (no wide nodes, lean-step choice irrelevant).
-    {
-        const size_t stack_bytes = (size_t)depth * kBlock * sizeof(uint32_t);
-        const size_t scene_bytes = n_scene_nodes * sizeof(pbrs_node) + (size_t)d->n_triangles * sizeof(pbrs_tri_verts) + (size_t)d->n_instances * sizeof(pbrs_instance) +
-                                   (size_t)d->n_shapes * sizeof(pbrs_shape);
-        c->lds_scene = !c->wide_shadow && !c->wide_extend && !c->full_steps && stack_bytes + scene_bytes <= kLdsBytesPerCU / 8;
-        if (const char* e = dev_env("PBRS_LDS_SCENE")) c->lds_scene = c->lds_scene && std::atoi(e) != 0;  // developer override (A/B timing)
-        c->lds_scene_bytes = c->lds_scene ? scene_bytes : 0;
-        // ... or the TLAS alone, where it is too large for the wave's shared scan (no leaf copies) and fits with seven blocks to a CU
-        const size_t top_bytes = (size_t)d->n_tlas_nodes * sizeof(pbrs_node);
-        c->lds_top = !c->lds_scene && S.n_flat == 0u && !c->full_steps && stack_bytes + top_bytes + 512 <= kLdsBytesPerCU / 7;
-        if (const char* e = dev_env("PBRS_LDS_TOP")) c->lds_top = c->lds_top && std::atoi(e) != 0;  // developer override (A/B timing)
-        c->lds_top_bytes = c->lds_top ? top_bytes : 0;
-        S.lds_off_words = depth * kBlock;
-        S.lds_nodes = c->lds_scene ? (uint32_t)n_scene_nodes : c->lds_top ? d->n_tlas_nodes : 0u;
-        S.lds_tris = c->lds_scene ? d->n_triangles : 0u;
-        S.lds_inst = c->lds_scene ? d->n_instances : 0u;
-        S.lds_shapes = c->lds_scene ? d->n_shapes : 0u;
+    if (d->n_area_lights) {
+        const uint32_t k0 = d->area_lights[0].shape_kind;
+        bool same = true;
+        for (uint32_t i = 1; i < d->n_area_lights; ++i) same = same && d->area_lights[i].shape_kind == k0;
+        if (same && k0 == PBRS_SHAPE_SPHERE) f.light_spec = PBRS_SHADE_LIGHT_SPHERE;
+        if (same && k0 == PBRS_SHAPE_TRIANGLE) f.light_spec = PBRS_SHADE_LIGHT_TRIANGLE;
     }
+    // what the traversal kernels may stage in LDS next to the stack rows (plan_kernels)
+    f.stack_bytes = (size_t)depth * kBlock * sizeof(uint32_t);
+    f.wide_stack_bytes = (size_t)S.wide_cap * kBlock * sizeof(uint32_t);
+    f.scene_bytes = n_scene_nodes * sizeof(pbrs_node) + (size_t)d->n_triangles * sizeof(pbrs_tri_verts) + (size_t)d->n_instances * sizeof(pbrs_instance) +
+                    (size_t)d->n_shapes * sizeof(pbrs_shape);
+    f.top_bytes = (size_t)d->n_tlas_nodes * sizeof(pbrs_node);
     // k_shade: the shading records (instances, shapes, materials, lobes, lights) in LDS where they are a few KB, the triangle records
     // too where everything is (kernels.h, stage_shade_scene); five blocks of the Lambert variants share a CU's 160 KB with the rest
     {
         S.n_inst = d->n_instances; S.n_shapes = d->n_shapes; S.n_tris = d->n_triangles; S.n_mats = d->n_materials; S.n_bxdfs = d->n_bxdfs;
-        const size_t rec = (size_t)d->n_instances * sizeof(pbrs_instance) + (size_t)d->n_shapes * sizeof(pbrs_shape) + (size_t)d->n_materials * sizeof(pbrs_material) +
-                           (size_t)d->n_bxdfs * sizeof(pbrs_bxdf) + (size_t)d->n_area_lights * sizeof(pbrs_area_light) + (size_t)d->n_delta_lights * sizeof(pbrs_delta_light);
-        const size_t tris = (size_t)d->n_triangles * (sizeof(pbrs_tri_verts) + sizeof(pbrs_tri_shade));
+        f.shade_rec_bytes = (size_t)d->n_instances * sizeof(pbrs_instance) + (size_t)d->n_shapes * sizeof(pbrs_shape) + (size_t)d->n_materials * sizeof(pbrs_material) +
+                            (size_t)d->n_bxdfs * sizeof(pbrs_bxdf) + (size_t)d->n_area_lights * sizeof(pbrs_area_light) + (size_t)d->n_delta_lights * sizeof(pbrs_delta_light);
+        f.shade_tri_bytes = (size_t)d->n_triangles * (sizeof(pbrs_tri_verts) + sizeof(pbrs_tri_shade));
         const size_t budget = 16u << 10;
-        c->shade_lds = rec + tris <= budget ? (PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS) : rec <= budget ? PBRS_SHADE_LDS_RECORDS : 0u;
-        if (const char* e = dev_env("PBRS_SHADE_LDS")) c->shade_lds &= (uint32_t)std::atoi(e);  // developer override (A/B timing): a mask
-        c->shade_lds_bytes = (c->shade_lds & PBRS_SHADE_LDS_TRIS) ? rec + tris : c->shade_lds ? rec : 0;
+        f.shade_lds = f.shade_rec_bytes + f.shade_tri_bytes <= budget ? (PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS) : f.shade_rec_bytes <= budget ? PBRS_SHADE_LDS_RECORDS : 0u;
     }
+    if (!plan_kernels(f, c->dev, c->plan)) return fail(c, PBRS_E_DEVICE, "no kernel instantiation for this scene's feature set");
+    // what the plan's traversal kernels stage (kernels.h, stage_scene / stage_top)
+    const bool lds_scene = c->plan.lds_staging == PBRS_FEAT_LDS_SCENE;
+    S.lds_off_words = depth * kBlock;
+    S.lds_nodes = lds_scene ? (uint32_t)n_scene_nodes : c->plan.lds_staging == PBRS_FEAT_LDS_TOP ? d->n_tlas_nodes : 0u;
+    S.lds_tris = lds_scene ? d->n_triangles : 0u;
+    S.lds_inst = lds_scene ? d->n_instances : 0u;
+    S.lds_shapes = lds_scene ? d->n_shapes : 0u;
     c->S = S;
-    c->textured = textured;
-    c->fourier = fourier;
     c->has_vis_records = vis_records;
     c->stack_depth = depth;
     c->has_scene = true;
@@ -1441,23 +1476,17 @@ int pbrs_intersect_rays(pbrs_ctx* c, uint32_t n, const float* origins, const flo
     TRY(hipMemcpyAsync(d_d, h_d.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
     TRY(hipMemcpyAsync(d_t, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     {
-        // the walks the pipeline runs for this scene: over four-wide nodes where the TLAS is scanned (the binary walks take what
-        // those refuse, as in the pipeline), else the binary walks
+        // the walks the pipeline runs for this scene: any-hit over four-wide nodes where k_shadow walks them (the binary walk takes
+        // what that one refuses, as in the pipeline), else the binary walks
         const uint32_t rows = std::max(c->stack_depth, c->S.wide_cap);
         const size_t lds = (size_t)(rows + c->S.n_flat) * kBlock * sizeof(uint32_t);
         const dim3 grid(std::min<uint32_t>((n + kBlock - 1) / kBlock, kPersistentBlocks));
-        // each query through the walk its stage runs in the pipeline (run_pass): occlusion through the four-wide any-hit walk whenever
-        // k_shadow takes it, closest hits through the binary walk (the four-wide closest walk exists in developer builds only)
-        c->last_intersect = pbrs_intersect_info{c->wide_shadow ? 1u : 0u, c->wide_extend ? 1u : 0u, 0u, 0u};
-#define PBRS_LAUNCH_RAYS(WC, WA) hipLaunchKernelGGL((k_intersect_rays<WC, WA>), grid, dim3(kBlock), lds, c->stream, c->S, n, d_o, d_d, d_t, d_h, d_occ, d_info)
-#ifdef PBRS_DEV_OVERRIDES
-        if (c->wide_extend && c->wide_shadow) PBRS_LAUNCH_RAYS(true, true);
-        else if (c->wide_extend) PBRS_LAUNCH_RAYS(true, false);
-        else
-#endif
-        if (c->wide_shadow) PBRS_LAUNCH_RAYS(false, true);
-        else PBRS_LAUNCH_RAYS(false, false);
-#undef PBRS_LAUNCH_RAYS
+        // each query through the walk its stage runs in the pipeline (KernelPlan): occlusion through the four-wide any-hit walk whenever
+        // k_shadow takes it, closest hits through the binary walk
+        const bool wide = c->plan.wide_shadow;
+        c->last_intersect = pbrs_intersect_info{wide ? 1u : 0u, 0u, 0u, 0u};
+        const auto fn = wide ? &k_intersect_rays<true> : &k_intersect_rays<false>;
+        hipLaunchKernelGGL(fn, grid, dim3(kBlock), lds, c->stream, c->S, n, d_o, d_d, d_t, d_h, d_occ, d_info);
     }
     TRY(hipGetLastError());
     if (hits_out) TRY(hipMemcpyAsync(hits_out, d_h, (size_t)n * sizeof(pbrs_hit_record), hipMemcpyDeviceToHost, c->stream));
@@ -1486,7 +1515,7 @@ int pbrs_camera_rays(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
     const uint32_t P = p->w * p->h;
     rc = ensure_work(c, P, P);
     if (rc) return rc;
-    RenderConst k = make_const(cam, p);
+    RenderConst k = make_const(c, cam, p);
     k.tiles8_per_row = 0u;  // one sample index, exported by pixel: slot = pixel
     k.pass_first_sample = sample_index;
     k.n_slots = P;
@@ -1535,7 +1564,7 @@ int pbrs_render_sample_radiance(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_
     const uint32_t P = p->w * p->h;
     rc = ensure_work(c, P, P);
     if (rc) return rc;
-    RenderConst k = make_const(cam, p);
+    RenderConst k = make_const(c, cam, p);
     k.tiles8_per_row = 0u;  // one sample index, exported by pixel: slot = pixel
     Timer tm{c, false};
     HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));

@@ -184,8 +184,7 @@ def test_a_raised_extent_reaches_a_mirrored_quad_hit(gpu_ctx):
         h_gpu, occ_gpu = gpu_ctx.intersect(o, d, t)
         assert not st["tie_mask"].any()
         assert h_ref["inst"][0] == 2 and h_ref["t"].view(np.uint32)[0] == np.float32(0.34959823).view(np.uint32)  # the quad, behind the raised extent
-        if not gpu_ctx.last_intersect_info()["wide_closest"]:  # (a developer build's four-wide closest walk in the ray harness does not follow the extent)
-            assert h_gpu["inst"][0] == h_ref["inst"][0] and h_gpu["t"].view(np.uint32)[0] == h_ref["t"].view(np.uint32)[0]
+        assert h_gpu["inst"][0] == h_ref["inst"][0] and h_gpu["t"].view(np.uint32)[0] == h_ref["t"].view(np.uint32)[0]
         assert (occ_ref == occ_gpu).all()
     for integrator, depth in (("path", 7), ("direct", 3)):
         ref, ost = osc.render(2, 2, depth, 11 + seed, integrator=integrator)
@@ -198,6 +197,45 @@ def test_a_raised_extent_reaches_a_mirrored_quad_hit(gpu_ctx):
                 assert st["instances"] + st["shadow_instances"] == ost["instances"]  # what the boxes decide, closest and any-hit walks together
             nan = np.isnan(ref)
             assert (nan == np.isnan(img)).all() and (img.view(np.uint32)[~nan] == ref.view(np.uint32)[~nan]).all(), (integrator, counters)
+
+
+def test_exact_extent_scene_with_a_stack_above_64_kb_renders(gpu_ctx):
+    """A scene with a ParallelQuad next to a mesh walks with the extent followed to the letter (PBRS_FEAT_EXTENT), whose TLAS entries
+    take two stack words: its stack has max(T, T - 1 + H) + T + 1 rows of 1 KB for a TLAS of T levels and a BLAS of H.  A TLAS grown
+    as a chain (one instance split off per level: spheres at geometrically growing distances) takes it beyond 64 KB, the portable
+    default limit of a kernel's dynamic LDS, which configure_kernels raises for every kernel in the tables; upload accepts stacks up to
+    80 KB.  Both variants of k_extend for such a scene render it, equal to the oracle bit for bit."""
+    def levels(nodes):  # levels of every subtree: children come after their parent
+        h = np.ones(len(nodes), dtype=np.int64)
+        for i in range(len(nodes) - 1, -1, -1):
+            if not nodes[i, 7] & 0x80000000:
+                h[i] = max(h[i + 1], h[nodes[i, 3]]) + 1
+        return h
+
+    sb = SceneBuilder()
+    sb.instance(scenes.quad_mesh(sb, (-4, 0, -4), (4, 0, -4), (-4, 0, 4), (4, 0, 4), (0, 1, 0)), sb.lambertian((0.6, 0.6, 0.5)))
+    sb.instance(sb.quad((-1.0, 0.2, 0.5), (0.0, 1.3, 0.0), (1.2, 0.0, 0.0)), sb.lambertian((0.7, 0.3, 0.2)))
+    for k in range(32):
+        sb.instance(sb.sphere((0, 0, 0), 0.4), sb.lambertian((0.2, 0.5, 0.7)), Transform().translate((5.0 * 2.2 ** k, 0.5, 0.0)))
+    light = sb.sphere((-2.0, 4.0, -1.0), 0.5)
+    sb.instance(light, sb.diffuse_light((8.0, 8.0, 7.0)))
+    sb.area_light((8.0, 8.0, 7.0), light)
+    sb.set_camera(64, 48, deg(50), (0.5, 2.5, -6.0), (0.5, 0.5, 0.5))
+    assert takes_the_exact_extent_walk(sb)
+    hs = pbrs_amd.HostScene(sb)
+    T, H = int(levels(hs.nodes("tlas"))[0]), int(levels(hs.nodes("blas")).max())
+    rows = max(T, T - 1 + H) + T + 1
+    assert 64 < rows <= 80, (T, H, rows)
+    gpu_ctx.upload(hs)
+    tile = (16, 12, 32, 24)
+    ref, ost = OracleScene(sb).render(2, 2, 5, 7, tile=tile)
+    assert ost["tlas_ties"] == 0 and ost["panics"] == 0 and np.isfinite(ref).all()
+    for counters in (True, False):
+        img, st = gpu_ctx.render(2, 2, 5, 7, tile=tile, counters=counters)
+        assert st["kernel_features_extend"] & 256, st["kernel_features_extend"]
+        if counters:
+            assert st["closest_rays"] == ost["closest_rays"] and st["shadow_rays"] == ost["shadow_rays"]
+        assert (img.view(np.uint32) == ref.view(np.uint32)).all(), counters
 
 
 def test_random_scenes_contain_parallel_quads():

@@ -1,6 +1,6 @@
 #!/bin/bash
-# developer tool (GPU box): full-size bench lines of library variants built with -DPBRS_DEV_OVERRIDES under PBRS_PAIR / PBRS_WIDE
-# settings (bit 0 k_extend, bit 1 k_shadow), parity window on.   usage: CFGS="c4" tools/ab_pair.sh lib "PBRS_GRID=3" "PBRS_CNODE=3" "PBRS_PAIR=3" "PBRS_WIDE=2" ...
+# developer tool (GPU box): full-size bench lines of library variants built with -DPBRS_DEV_OVERRIDES under developer
+# overrides such as PBRS_WIDE (bit 1, its only bit: k_shadow's four-wide walk), parity window on.   usage: CFGS="c4" tools/ab_pair.sh lib "PBRS_WIDE=0" "PBRS_WIDE=2" ...
 cfgs=${CFGS:-c4}
 lib=$1; shift
 for c in $cfgs; do for v in "$@"; do

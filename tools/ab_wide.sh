@@ -1,6 +1,6 @@
 #!/bin/bash
 # developer tool (GPU box): full-size bench lines of library variants built with -DPBRS_DEV_OVERRIDES, with and without the
-# wide-walk kernels (PBRS_WIDE=0 selects the binary-walk kernels of the same binary).  usage: CFGS="c4 c2" tools/ab_wide.sh w5 w4
+# four-wide k_shadow (PBRS_WIDE=0 selects the binary-walk kernel of the same binary; bit 1 is PBRS_WIDE's only bit).  usage: CFGS="c4 c2" tools/ab_wide.sh w5 w4
 cfgs=${CFGS:-c4 c2 c3}
 run() {  # label, env, lib
   line=$(env $2 PBRS_GPU_LIB=$PWD/pbrs_amd/lib/abl_$3.so timeout -k 10 300 python bench.py --full --config $c --also "" --steps ${STEPS:-2} --warmup 1 --no-cpu-baseline --no-parity-window $BENCH_EXTRA 2>&1 | grep '^{"metric"')
@@ -8,5 +8,5 @@ run() {  # label, env, lib
 }
 for c in $cfgs; do
   run "binary($1)" "PBRS_WIDE=0" $1
-  for v in "$@"; do run "wide($v)" "PBRS_WIDE=3" $v; done
+  for v in "$@"; do run "wide($v)" "PBRS_WIDE=2" $v; done
 done

@@ -1,6 +1,6 @@
 """Developer probe: what the traversal loops of k_extend / k_shadow execute, per ray.  Needs a library built with
 -DPBRS_PROBE_TRAV (tools/ablate.sh "tprobe:-DPBRS_PROBE_TRAV -DPBRS_DEV_OVERRIDES") selected through PBRS_GPU_LIB; PBRS_WIDE
-(bit 0 k_extend, bit 1 k_shadow) picks the walks.     python tools/trav_probe.py c4 [sx sy]"""
+(bit 1, its only bit: k_shadow's four-wide walk) picks the any-hit walk.     python tools/trav_probe.py c4 [sx sy]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pbrs_amd
