@@ -342,6 +342,43 @@ int pbrs_render_tile_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_par
 /* After a _device render with time_stages/collect_counters: waits for the stream and fills the stats. */
 int pbrs_collect_stats(pbrs_ctx*, pbrs_stats* stats_out);
 
+/* First-hit AOVs beside the image: per-pixel buffers of the render's own camera samples (the same jittered rays, all
+ * strata_x * strata_y sample indices, the tile / band packing of rgb_out).  For sample s of a pixel the first hit is the
+ * hit record of `scene.tlas.intersect` on its camera ray (bounce 0).  Every pointer may be NULL (not wanted); spp =
+ * strata_x * strata_y, sums are sequential f32 sums in sample-index order from +0, scaled like the radiance (`* (1.0f / spp)`):
+ *   albedo    3 x f32 row-major RGB: (sum_s a_s) * (1 / spp).  a_s = the colours of the lobes the hit's material pushes at that
+ *             hit summed in lobe order from +0 (a textured lobe: its texture at the hit's (u, v, pos); Uber drops a lobe whose
+ *             texture is black there; a Fourier lobe counts as (1, 1, 1)), each channel then clamped, fminf(fmaxf(x, 0), 1).
+ *             A miss and an emitter without lobes give 0.
+ *   normal    3 x f32: (sum_s n_s) * (1 / spp), n_s = the world-space shading normal of the hit (the normal PBRS_INTEGRATOR_NORMALS
+ *             shows), not renormalised; 0 for a miss.
+ *   coverage  f32: (float)n_hit * (1 / spp), n_hit = samples that hit something.
+ *   depth     f32: t of the nearest hit among the pixel's samples (smallest t; a tie keeps the lowest sample index), +inf if none.
+ *             t is the ray parameter of the reference: camera directions are not unit length (geometry/src/camera.rs:65-77),
+ *             so t is not a distance.
+ *   instance  u32: that hit's instance, an index into pbrs_scene_desc::instances; 0xffffffff if no sample hits.
+ *   material  u32: instances[instance].material; 0xffffffff if no sample hits.
+ *   prim      u32: that hit's primitive, numbered as pbrs_hit_record::prim; 0xffffffff if no sample hits.
+ * Pointers are host memory for pbrs_render_tile_aovs, device memory for pbrs_render_tile_aovs_device. */
+typedef struct pbrs_aov_buffers {
+    float* albedo;
+    float* normal;
+    float* coverage;
+    float* depth;
+    uint32_t* instance;
+    uint32_t* material;
+    uint32_t* prim;
+} pbrs_aov_buffers;
+/* pbrs_render_tile / pbrs_render_tile_device that also fill the requested AOVs (the image is the same, bit for bit).  Any
+ * integrator; the visualisers trace their one cast even at max_depth 0, PBRS_INTEGRATOR_PATH / _DIRECT with max_depth == 0
+ * trace no camera ray and return PBRS_E_INVALID when a buffer is requested.  `aovs` NULL or all-NULL: exactly the plain call.
+ * The AOV kernels' time counts in pbrs_stats::ms_total only.  The context keeps 40 B of AOV state per pixel (and, for the host
+ * variant, 44 B per pixel of staging); _device is asynchronous like pbrs_render_tile_device: valid after pbrs_collect_stats. */
+int pbrs_render_tile_aovs(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                          pbrs_stats* stats_out);
+int pbrs_render_tile_aovs_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_device,
+                                 const pbrs_aov_buffers* aovs_device, pbrs_stats* stats_out);
+
 /* ---- parity-harness entry points (the reference's own functions, batched) -------------------------- */
 typedef struct pbrs_hit_record {
     float t;

@@ -71,13 +71,32 @@ class RenderParams(C.Structure):
                 ("band_rows", C.c_uint32), ("band_count", C.c_uint32), ("band_index", C.c_uint32), ("integrator", C.c_uint32)]
 
 
+class AovBuffers(C.Structure):
+    """pbrs_aov_buffers: one pointer per first-hit AOV, NULL = not wanted (include/pbrs_gpu.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "coverage", "depth", "instance", "material", "prim")]
+
+
+# name -> (channels, dtype) of each AOV, in the order of pbrs_aov_buffers
+AOVS = {"albedo": (3, np.float32), "normal": (3, np.float32), "coverage": (1, np.float32), "depth": (1, np.float32),
+        "instance": (1, np.uint32), "material": (1, np.uint32), "prim": (1, np.uint32)}
+AOV_NAMES = ("albedo", "normal", "depth", "instance", "material", "prim", "coverage")
+
+
+def _aov_names(aovs):
+    names = tuple(aovs)
+    unknown = [n for n in names if n not in AOVS]
+    if unknown:
+        raise ValueError(f"unknown AOV name(s) {unknown}; known: {sorted(AOVS)}")
+    return names
+
+
 HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
 NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "exp": 6, "ln": 7, "hypot": 8, "div": 9,
                "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "box_quotient": 15}
 
 GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_stream", "pbrs_set_pass_overlap", "pbrs_upload_scene", "pbrs_render_tile",
                "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
-               "pbrs_numeric_eval", "pbrs_render_sample_radiance"]
+               "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error",
@@ -144,6 +163,8 @@ def gpu_lib():
         L.pbrs_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.pbrs_numeric_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pbrs_render_sample_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.pbrs_render_tile_aovs.argtypes = [C.c_void_p] * 6
+        L.pbrs_render_tile_aovs_device.argtypes = [C.c_void_p] * 6
         _gpu = L
     return _gpu
 
@@ -299,6 +320,35 @@ class Context:
         p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
         self._check(self._L.pbrs_render_tile_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr), None),
                     "pbrs_render_tile_device")
+
+    def render_aovs(self, strata_x, strata_y, depth, seed, aovs=AOV_NAMES, tile=None, samples_per_pass=0, counters=False,
+                    timing=False, bands=None, integrator="path"):
+        """render() plus first-hit AOVs of the same camera samples (include/pbrs_gpu.h, pbrs_aov_buffers) -> (rgb, {name: array},
+        stats).  albedo / normal: (h, w, 3) f32; coverage / depth: (h, w) f32; instance / material / prim: (h, w) u32."""
+        names = _aov_names(aovs)
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
+        out = np.empty((p.h, p.w, 3), dtype=np.float32)
+        bufs, arrays = AovBuffers(), {}
+        for n in names:
+            ch, dt = AOVS[n]
+            arrays[n] = np.empty((p.h, p.w, ch) if ch > 1 else (p.h, p.w), dtype=dt)
+            setattr(bufs, n, arrays[n].ctypes.data)
+        st = Stats()
+        self._check(self._L.pbrs_render_tile_aovs(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
+                                                  C.addressof(st)), "pbrs_render_tile_aovs")
+        return out, arrays, st.as_dict()
+
+    def render_aovs_device(self, rgb_device_ptr, aov_device_ptrs, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0,
+                           counters=False, timing=False, bands=None, integrator="path"):
+        """render_device() plus first-hit AOVs into caller-owned device memory: `aov_device_ptrs` = {name: pointer} (e.g.
+        tensor.data_ptr(); sizes as render_aovs returns them).  Asynchronous like render_device: valid after `collect_stats()`."""
+        _aov_names(aov_device_ptrs)
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
+        bufs = AovBuffers()
+        for n, ptr in aov_device_ptrs.items():
+            setattr(bufs, n, ptr)
+        self._check(self._L.pbrs_render_tile_aovs_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
+                                                         C.addressof(bufs), None), "pbrs_render_tile_aovs_device")
 
     def collect_stats(self):
         st = Stats()

@@ -22,6 +22,7 @@
 
 #include "../../include/pbrs_gpu.h"
 #include "device/kernels.h"
+#include "device/aov.h"
 
 namespace {
 
@@ -38,6 +39,7 @@ constexpr uint32_t kSlowGrid = 64;
 constexpr uint32_t kStreamGridCap = 4096;  // blocks of k_nee_resolve, whose work is counted on the device (kernels.h)
 constexpr uint32_t kPersistentBlocks = PBRS_PERSISTENT_BLOCKS;  // 256 CUs x up to 6 resident 256-thread blocks (VGPR/LDS permitting)
 constexpr size_t kLdsBytesPerCU = 160 * 1024;
+constexpr uint32_t kAovOutWords = 3 + 3 + 1 + 1 + 1 + 1 + 1;  // pbrs_aov_buffers: albedo, normal, coverage, depth, instance, material, prim
 
 struct StageEvent {
     int stage;  // 0 raygen, 1 extend, 2 shade, 3 shadow, 4 accumulate
@@ -225,6 +227,11 @@ struct pbrs_ctx {
     bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
     uint64_t pending_closest = 0;
     pbrs_intersect_info last_intersect{};  // which walks the last pbrs_intersect_rays went through
+    // first-hit AOVs (pbrs_render_tile_aovs*, device/aov.h): the per-pixel running state k_aov folds every pass into, and the host variant's
+    // staging for the finished buffers
+    size_t cap_aov_pixels = 0, cap_aov_out_pixels = 0;
+    float* aov_state = nullptr;  // PBRS_AOV_STATE_WORDS * cap_aov_pixels, planar
+    void* aov_out = nullptr;     // kAovOutWords * cap_aov_out_pixels: the seven buffers of pbrs_aov_buffers, one after the other
 };
 
 namespace {
@@ -348,6 +355,42 @@ int ensure_work(pbrs_ctx* c, size_t n_slots, size_t n_pixels) {
         c->cap_pixels = n_pixels;
     }
     return PBRS_OK;
+}
+
+// The AOV state (and, with `staging`, the host variant's output buffers) for n_pixels, as ensure_work allocates: a failure leaves
+// the context without them (cap_aov_* = 0), usable for every other call.
+int ensure_aov(pbrs_ctx* c, size_t n_pixels, bool staging) {
+    auto grow = [&](void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) -> int {
+        if (n_pixels <= cap) return PBRS_OK;
+        cap = 0;
+        if (*ptr) (void)hipFree(*ptr);
+        *ptr = nullptr;
+        const size_t total = n_pixels * bytes_per_pixel;
+        hipError_t e = hipMalloc(ptr, total);
+        if (e != hipSuccess) {
+            *ptr = nullptr;
+            c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
+            (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
+            return PBRS_E_DEVICE;
+        }
+        cap = n_pixels;
+        return PBRS_OK;
+    };
+    int rc = grow(reinterpret_cast<void**>(&c->aov_state), c->cap_aov_pixels, PBRS_AOV_STATE_WORDS * sizeof(float), "the AOV state");
+    if (rc || !staging) return rc;
+    return grow(&c->aov_out, c->cap_aov_out_pixels, kAovOutWords * sizeof(uint32_t), "the AOV buffers");
+}
+
+void free_aov(pbrs_ctx* c) {
+    if (c->aov_state) (void)hipFree(c->aov_state);
+    if (c->aov_out) (void)hipFree(c->aov_out);
+    c->aov_state = nullptr;
+    c->aov_out = nullptr;
+    c->cap_aov_pixels = c->cap_aov_out_pixels = 0;
+}
+
+bool any_aov(const pbrs_aov_buffers* a) {
+    return a && (a->albedo || a->normal || a->coverage || a->depth || a->instance || a->material || a->prim);
 }
 
 uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p);
@@ -687,7 +730,8 @@ void poll_split_probe(pbrs_ctx* c) {
 // One pass: kc sample indices starting at `first` for every pixel of the tile.
 // `handoff`: the pass moves to the late stream at bounce pbrs_ctx::overlap_from (at the latest for its k_accumulate: the late stream runs
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
-int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false) {
+// `aov`: the AOV state k_aov folds this pass's first hits into (null: no AOVs).
+int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false, float* aov = nullptr) {
     pbrs_ctx::PassSet& set = c->pass_set[c->cur_set];
     // the set's memory is free once the pass that used it last has accumulated (two passes back, on the late stream)
     if (handoff && set.in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, set.accumulated, 0));
@@ -746,6 +790,13 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
                            nullptr, qsplit);
         c->pending.kernel_features_extend = xk.features;
         tm.end();
+        // First-hit AOVs: bounce 0's rays (q[0], at their slots) and hit records, before bounce 1 overwrites them (k_shade writes set 0
+        // at bounce 1, k_extend the hit records).  Outside the stage brackets: counted in ms_total only.  The state is shared by the
+        // passes, so their k_aov launches must run in pass order on one stream: bounce 0 runs on the main stream for every pass unless
+        // overlap_from is 0 (a developer override), and then on the late stream for every pass — one stream either way, in pass order
+        // (render_common joins the late stream before k_aov_finalize).
+        if (b == 0 && aov)
+            hipLaunchKernelGGL(k_aov, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, c->st, aov, P, kc, rc.chunk_pixels, qsplit);
         if (tm.begin(2)) return fail(c, PBRS_E_DEVICE, "event record failed");
         // the queue in the order the plan asks for; a queue k_extend split: class-major over its two classes, class 1 = the kept paths, last
         const IntegratorPlan::Order order = qsplit ? IntegratorPlan::CLASS_MAJOR : ip.order;
@@ -804,7 +855,8 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     return PBRS_OK;
 }
 
-int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device) {
+// `aovs` (device pointers; null or all-null: none): the first-hit AOVs too, from the state ensure_aov allocated.
+int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device, const pbrs_aov_buffers* aovs = nullptr) {
     HIPCHK(c, hipSetDevice(c->device));  // before check_params: the automatic pass size reads THIS device's free memory
     int rcode = check_params(c, cam, p);
     if (rcode) return rcode;
@@ -826,6 +878,8 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     HIPCHK(c, hipMemsetAsync(c->nonfinite, 0, sizeof(unsigned long long), c->stream));
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[0], c->stream));
     HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
+    float* aov = any_aov(aovs) ? c->aov_state : nullptr;
+    if (aov) HIPCHK(c, hipMemsetAsync(aov, 0, PBRS_AOV_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     uint32_t passes = 0;
     // Where the render has more than one pass, passes alternate between the two pass sets and hand their late bounces to the second
     // stream: those are near-empty launches that end with the latency of their longest walks (C4: 47 ms per frame in kernels that leave
@@ -844,7 +898,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     for (uint32_t first = 0; first < spp; first += K) {
         uint32_t kc = spp - first < K ? spp - first : K;
         if (two) use_pass_set(c, (int)(passes & 1u));  // (also: back to the main stream)
-        rcode = run_pass(c, rc, first, kc, stats, tm, two);
+        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov);
         if (rcode) {
             use_pass_set(c, 0);
             return rcode;
@@ -857,6 +911,9 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
         HIPCHK(c, hipStreamWaitEvent(c->main_stream, last, 0));  // the late stream has run every pass's accumulation, in order
     }
     hipLaunchKernelGGL(k_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->sum, rgb_device, P, 1.0f / (float)spp);
+    if (aov)
+        hipLaunchKernelGGL(k_aov_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, aov, c->S.inst, P, rc.w, rc.tiles8_per_row,
+                           1.0f / (float)spp, *aovs);
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending.passes = passes;
@@ -1014,6 +1071,7 @@ void pbrs_destroy(pbrs_ctx* c) {
     if (c->second_stream) (void)hipStreamSynchronize(c->second_stream);
     free_scene(c);
     free_work(c);  // (leaves pass set 0 in use)
+    free_aov(c);
     if (c->counters) (void)hipFree(c->counters);
     if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
     for (int k = 0; k < 2; ++k)
@@ -1425,6 +1483,67 @@ int pbrs_render_tile(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
     rc = render_common(c, cam, p, c->rgb_dev);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * (size_t)p->w * p->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return collect(c, stats_out);
+}
+
+// The checks of the AOV entry points beyond render_common's: a render that traces no camera ray has no first hits to report.
+int check_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_aov_buffers* aovs) {
+    int rc = check_params(c, cam, p);
+    if (rc || !any_aov(aovs)) return rc;
+    if (p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0)
+        return fail(c, PBRS_E_INVALID, "AOVs requested from a render that traces no camera ray (max_depth 0)");
+    // before render_common's pass size reads the free memory
+    return ensure_aov(c, (size_t)p->w * p->h, false);
+}
+
+int pbrs_render_tile_aovs_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, const pbrs_aov_buffers* aovs_device,
+                                 pbrs_stats* stats_out) {
+    if (!c) return PBRS_E_INVALID;
+    if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = check_aovs(c, cam, p, aovs_device);
+    if (rc) return rc;
+    rc = render_common(c, cam, p, rgb_out_device, aovs_device);
+    if (rc) return rc;
+    if (stats_out) return collect(c, stats_out);
+    return PBRS_OK;
+}
+
+int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                          pbrs_stats* stats_out) {
+    if (!c) return PBRS_E_INVALID;
+    if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = check_aovs(c, cam, p, aovs_host);
+    if (rc) return rc;
+    const size_t P = (size_t)p->w * p->h;
+    const bool want = any_aov(aovs_host);
+    if (want) rc = ensure_aov(c, P, true);
+    if (rc) return rc;
+    rc = ensure_work(c, P * auto_samples_per_pass(c, p), P);
+    if (rc) return rc;
+    // device staging of the requested buffers, in the order of pbrs_aov_buffers
+    pbrs_aov_buffers dev{};
+    float* f = static_cast<float*>(c->aov_out);
+    if (want) {
+        dev.albedo = aovs_host->albedo ? f : nullptr;
+        dev.normal = aovs_host->normal ? f + 3 * P : nullptr;
+        dev.coverage = aovs_host->coverage ? f + 6 * P : nullptr;
+        dev.depth = aovs_host->depth ? f + 7 * P : nullptr;
+        dev.instance = aovs_host->instance ? reinterpret_cast<uint32_t*>(f + 8 * P) : nullptr;
+        dev.material = aovs_host->material ? reinterpret_cast<uint32_t*>(f + 9 * P) : nullptr;
+        dev.prim = aovs_host->prim ? reinterpret_cast<uint32_t*>(f + 10 * P) : nullptr;
+    }
+    rc = render_common(c, cam, p, c->rgb_dev, want ? &dev : nullptr);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (want) {
+        const void* src[7] = {dev.albedo, dev.normal, dev.coverage, dev.depth, dev.instance, dev.material, dev.prim};
+        void* dst[7] = {aovs_host->albedo, aovs_host->normal, aovs_host->coverage, aovs_host->depth, aovs_host->instance, aovs_host->material, aovs_host->prim};
+        const size_t words[7] = {3, 3, 1, 1, 1, 1, 1};
+        for (int k = 0; k < 7; ++k)
+            if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], src[k], words[k] * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
     return collect(c, stats_out);
 }
 

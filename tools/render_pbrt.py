@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals]"""
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs]
+
+--aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
+<out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import pbrs_amd
 
+aovs = "--aovs" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--aovs"]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -13,6 +19,15 @@ ctx = pbrs_amd.Context(0)
 ctx.upload(pbrs_amd.HostScene(ls))
 if integrator in ("materials", "normals"):  # --visualize-materials / --visualize-normals (src/main.rs:180-185): one ray per pixel
     msaa = 1
-img, st = ctx.render(msaa, msaa, depth, 1, integrator=integrator, timing=True)
+if aovs:
+    img, buf, st = ctx.render_aovs(msaa, msaa, depth, 1, aovs=("albedo", "normal", "depth"), integrator=integrator, timing=True)
+else:
+    img, st = ctx.render(msaa, msaa, depth, 1, integrator=integrator, timing=True)
 pbrs_amd.write_image(out, img)
+if aovs:
+    stem = out[:-4] if out.lower().endswith((".exr", ".png")) else out
+    for name in ("albedo", "normal", "depth"):
+        a = buf[name] if buf[name].ndim == 3 else np.repeat(buf[name][:, :, None], 3, axis=2)
+        pbrs_amd.write_image(f"{stem}.{name}.exr", a)
+        print(f"-> {stem}.{name}.exr")
 print(f"{img.shape[1]}x{img.shape[0]} at {msaa * msaa} spp in {st['ms_total']:.1f} ms -> {out}")
