@@ -379,6 +379,48 @@ int pbrs_render_tile_aovs(pbrs_ctx*, const pbrs_camera*, const pbrs_render_param
 int pbrs_render_tile_aovs_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_device,
                                  const pbrs_aov_buffers* aovs_device, pbrs_stats* stats_out);
 
+/* Filtered film: the image reconstructed with the scene's pixel filter (pbrt-v3's `Filter`, math/src/filter.rs) instead of
+ * the plain per-pixel mean of src/main.rs:205-208, which pbrs_render_tile[_device] keep.  The reference parses the filter and
+ * never applies it; the support and normalisation below are pbrt-v3's Film::AddSample / WriteImage.  All arithmetic is f32
+ * without fused multiply-add, in the order written; pn_* is include/pbrs_numeric.h, the factors are include/pbrs_filter.h.
+ *   Sample i of film pixel (col, row) sits at xs = (float)col + pn_fract(jx), ys = (float)row + pn_fract(jy): k_raygen's
+ *   jitter, the same draws.  For output pixel (px, py): ox = xs - ((float)px + 0.5f), oy = ys - ((float)py + 0.5f).
+ *   Support: the sample counts iff pn_abs(ox) <= rx && pn_abs(oy) <= ry (inclusive); outside it is skipped, inside it is
+ *   added even with weight 0.  Weight w = fx(ox) * fy(oy), each factor with its own axis's radius r:
+ *     BOX       1.0f                                                                   (pbrt-v3 default radius 0.5)
+ *     TRIANGLE  pn_max(r - pn_abs(o), 0.0f)                                            (2)
+ *     GAUSSIAN  pn_max(pn_exp((-alpha * o) * o) - pn_exp((-alpha * r) * r), 0.0f)     (2, alpha 2) — pbrt-v3's form: filter.rs:40-41
+ *               misses the first term's .exp() (every weight 0 there; the reference never calls it)
+ *     MITCHELL  x = pn_abs(2.0f * (o / r)), RN(1/6) * poly(x): filter.rs:72-90's coefficients, each computed in f32 from B, C in
+ *               the written order, the x > 1.0f branch or the other, Horner as float.rs:106-110 (fold from 0)   (2, B = C = 1/3)
+ *     LANCZOS   sinc(pn_abs(o) / tau) * sinc(pn_abs(o)), sinc(x) = pn_abs(x) < 1e-5f ? 1.0f : pn_sin(PN_PI * x) / (PN_PI * x)  (4, tau 3)
+ *   Per output pixel, from S = (+0, +0, +0), W = +0: for sample index i = 0 .. spp-1, for dy = -hy .. hy, for dx = -hx .. hx
+ *   (h = floor(r + 0.5) per axis), neighbour q = (px + dx, py + dy) inside the camera film (samples exist only there), each
+ *   sample of q inside the support: S.c = S.c + w * L.c per channel, then W = W + w.  Result: W == 0 gives 0, else
+ *   v = S.c * (1.0f / W), then v < 0 ? +0 : v (pbrt-v3's clamp of negative lobes; a NaN stays NaN, as in the plain image).
+ *   The sample index is the outer loop, so the result does not depend on the passes; a tile traces its pixels plus hx columns
+ *   and hy rows of halo (clipped to the film) and writes its own pixels, so a filtered tile is the same crop of the filtered
+ *   full frame, bit for bit.
+ * pbrs_stats: samples = samples traced, halo included; invalid_samples = the tile's own pixels only (the plain render's count);
+ * the filter stage's time counts in ms_accumulate.  The filter's weights use the render's own camera samples only (AOVs stay
+ * per-pixel means: pbrs_render_tile_aovs).
+ * Refused with PBRS_E_INVALID (the context stays usable): a NULL filter, band_count > 1, the visualiser integrators, an unknown
+ * kind, a radius that is not finite or not > 0, a non-finite parameter of the kind; a radius above PBRS_FILTER_MAX_RADIUS in
+ * either axis is PBRS_E_LIMIT. */
+enum pbrs_filter_kind { PBRS_FILTER_BOX = 0, PBRS_FILTER_TRIANGLE = 1, PBRS_FILTER_GAUSSIAN = 2, PBRS_FILTER_MITCHELL = 3, PBRS_FILTER_LANCZOS = 4 };
+#define PBRS_FILTER_MAX_RADIUS 4.0f
+typedef struct pbrs_pixel_filter {
+    uint32_t kind;     /* enum pbrs_filter_kind */
+    float radius[2];   /* pbrt-v3 "xwidth", "ywidth" (they are radii) */
+    float a, b;        /* GAUSSIAN: alpha, -; MITCHELL: B, C; LANCZOS: tau, -; else unused */
+    uint32_t pad;
+} pbrs_pixel_filter;   /* 24 B */
+/* pbrs_render_tile / pbrs_render_tile_device through the filter above; _device is asynchronous like pbrs_render_tile_device. */
+int pbrs_render_tile_filtered(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, const pbrs_pixel_filter*, float* rgb_out_host,
+                              pbrs_stats* stats_out);
+int pbrs_render_tile_filtered_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, const pbrs_pixel_filter*,
+                                     float* rgb_out_device, pbrs_stats* stats_out);
+
 /* ---- parity-harness entry points (the reference's own functions, batched) -------------------------- */
 typedef struct pbrs_hit_record {
     float t;

@@ -40,6 +40,11 @@ int pbrs_host_load_pbrt(const char* path, pbrs_loaded_scene** out);
 const pbrs_scene_spec* pbrs_loaded_scene_spec(const pbrs_loaded_scene*); /* borrowed, valid until _free */
 void pbrs_loaded_scene_free(pbrs_loaded_scene*);
 const char* pbrs_host_load_error(void);
+/* The scene's pixel filter (`Filter "box|triangle|gaussian|mitchell|sinc"`, scene/src/loader.rs:822-855 with pbrt-v3's
+ * "triangle"): xwidth / ywidth / alpha / B / C / tau with parse_filter's defaults; a file without `Filter` gives box 0.5
+ * (loader.rs:73-74).  An unknown filter name is an error of this call only (message in pbrs_host_load_error); other
+ * parameters are ignored. */
+int pbrs_loaded_scene_filter(const pbrs_loaded_scene*, pbrs_pixel_filter* out);
 
 /* Image output of the reference's front end (src/main.rs:28-53): `write_exr` — f32 RGB, the file a render ends in (:245) —
  * and `write_image` — 8-bit PNG of `gamma_encode().to_u8()` pixels (radiometry/src/color.rs:13-23, :54-66).  `rgb` is

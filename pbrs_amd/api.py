@@ -90,16 +90,57 @@ def _aov_names(aovs):
     return names
 
 
+class PixelFilter(C.Structure):
+    """pbrs_pixel_filter (include/pbrs_gpu.h): kind, radius (x, y), a, b.  The constructors carry pbrt-v3's defaults."""
+    BOX, TRIANGLE, GAUSSIAN, MITCHELL, LANCZOS = range(5)
+    _fields_ = [("kind", C.c_uint32), ("radius", C.c_float * 2), ("a", C.c_float), ("b", C.c_float), ("pad", C.c_uint32)]
+
+    @classmethod
+    def make(cls, kind, rx, ry=None, a=0.0, b=0.0):
+        f = cls()
+        f.kind, f.radius[0], f.radius[1], f.a, f.b = kind, rx, rx if ry is None else ry, a, b
+        return f
+
+    @classmethod
+    def box(cls, rx=0.5, ry=None):
+        return cls.make(cls.BOX, rx, ry)
+
+    @classmethod
+    def triangle(cls, rx=2.0, ry=None):
+        return cls.make(cls.TRIANGLE, rx, ry)
+
+    @classmethod
+    def gaussian(cls, rx=2.0, ry=None, alpha=2.0):
+        return cls.make(cls.GAUSSIAN, rx, ry, alpha)
+
+    @classmethod
+    def mitchell(cls, rx=2.0, ry=None, B=1.0 / 3.0, C=1.0 / 3.0):
+        return cls.make(cls.MITCHELL, rx, ry, B, C)
+
+    @classmethod
+    def lanczos(cls, rx=4.0, ry=None, tau=3.0):
+        return cls.make(cls.LANCZOS, rx, ry, tau)
+
+    def as_tuple(self):
+        return (int(self.kind), float(self.radius[0]), float(self.radius[1]), float(self.a), float(self.b))
+
+    def __repr__(self):
+        names = ("box", "triangle", "gaussian", "mitchell", "lanczos")
+        k = names[self.kind] if self.kind < len(names) else self.kind
+        return f"PixelFilter({k}, radius=({self.radius[0]}, {self.radius[1]}), a={self.a}, b={self.b})"
+
+
 HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
 NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "exp": 6, "ln": 7, "hypot": 8, "div": 9,
                "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "box_quotient": 15}
 
 GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_stream", "pbrs_set_pass_overlap", "pbrs_upload_scene", "pbrs_render_tile",
                "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
-               "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device"]
+               "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
+               "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
-                "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error",
+                "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
                 "pbrs_host_write_exr", "pbrs_host_write_png", "pbrs_host_io_error"]
 
 _host = None
@@ -131,6 +172,7 @@ def host_lib():
         L.pbrs_loaded_scene_spec.restype = C.POINTER(SceneSpec)
         L.pbrs_loaded_scene_spec.argtypes = [C.c_void_p]
         L.pbrs_loaded_scene_free.argtypes = [C.c_void_p]
+        L.pbrs_loaded_scene_filter.argtypes = [C.c_void_p, C.c_void_p]
         L.pbrs_host_load_error.restype = C.c_char_p
         L.pbrs_host_write_exr.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.pbrs_host_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -165,6 +207,8 @@ def gpu_lib():
         L.pbrs_render_sample_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.pbrs_render_tile_aovs.argtypes = [C.c_void_p] * 6
         L.pbrs_render_tile_aovs_device.argtypes = [C.c_void_p] * 6
+        L.pbrs_render_tile_filtered.argtypes = [C.c_void_p] * 6
+        L.pbrs_render_tile_filtered_device.argtypes = [C.c_void_p] * 6
         _gpu = L
     return _gpu
 
@@ -186,6 +230,14 @@ class LoadedScene:
 
     def build(self):
         return self.spec
+
+    def pixel_filter(self):
+        """The file's `Filter` as a PixelFilter (pbrs_loaded_scene_filter: parse_filter's defaults; none: box 0.5)."""
+        f = PixelFilter()
+        rc = host_lib().pbrs_loaded_scene_filter(self._h, C.byref(f))
+        if rc != 0:
+            raise PbrsError(f"pbrs_loaded_scene_filter failed ({rc}): {host_lib().pbrs_host_load_error().decode()}")
+        return f
 
     def close(self):
         if getattr(self, "_h", None):
@@ -349,6 +401,24 @@ class Context:
             setattr(bufs, n, ptr)
         self._check(self._L.pbrs_render_tile_aovs_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
                                                          C.addressof(bufs), None), "pbrs_render_tile_aovs_device")
+
+    def render_filtered(self, pixel_filter, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0, counters=False, timing=False,
+                        integrator="path"):
+        """render() through a pixel reconstruction filter (PixelFilter; include/pbrs_gpu.h, pbrs_render_tile_filtered) -> (h, w, 3) f32
+        radiance, stats dict.  The tile traces a halo of floor(r + 0.5) pixels around it (stats["samples"] counts it)."""
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, None, integrator)
+        out = np.empty((p.h, p.w, 3), dtype=np.float32)
+        st = Stats()
+        self._check(self._L.pbrs_render_tile_filtered(self._h, C.addressof(self.scene.camera), C.addressof(p), C.byref(pixel_filter),
+                                                      out.ctypes.data, C.addressof(st)), "pbrs_render_tile_filtered")
+        return out, st.as_dict()
+
+    def render_filtered_device(self, rgb_device_ptr, pixel_filter, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0,
+                               counters=False, timing=False, integrator="path"):
+        """render_filtered() into caller-owned device memory; asynchronous like render_device: valid after `collect_stats()`."""
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, None, integrator)
+        self._check(self._L.pbrs_render_tile_filtered_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.byref(pixel_filter),
+                                                             C.c_void_p(rgb_device_ptr), None), "pbrs_render_tile_filtered_device")
 
     def collect_stats(self):
         st = Stats()

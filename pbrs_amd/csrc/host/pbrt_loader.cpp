@@ -771,7 +771,10 @@ struct pbrs_loaded_scene {
     std::vector<std::unique_ptr<RawImage>> images;
     std::vector<pbrs_fourier_table_spec> fourier_tables;
     std::vector<std::unique_ptr<RawBsdf>> bsdf_data;
-    std::string filter;  // parsed, not used by this path
+    // `Filter` (loader.rs:822-855): the name and the parameters parse_filter reads, NaN where the file gives none
+    std::string filter;
+    float filter_xwidth = pn_nan(), filter_ywidth = pn_nan(), filter_alpha = pn_nan(), filter_B = pn_nan(), filter_C = pn_nan(),
+          filter_tau = pn_nan();
 };
 
 namespace {
@@ -1271,7 +1274,22 @@ struct Loader {
         if (!(have_fov && have_w && have_h)) fail("the scene needs Camera \"perspective\" and Film x/yresolution");
         for (Option& o : options) {
             if (o.kind == Option::Transform && o.xf.kind != Xform::LookAt) world = affine_mul(world, parse_transform(o.xf));
-            else if (o.kind == Option::Filter) out.filter = o.impl;
+            else if (o.kind == Option::Filter) {
+                out.filter = o.impl;
+                auto num = [&](const char* name, float* v) {
+                    std::string key;
+                    Arg a;
+                    if (!o.params.extract_substr(name, &key, &a)) return;
+                    if (a.kind == Arg::Num) *v = a.x;
+                    else if (a.kind == Arg::Nums && !a.v.empty()) *v = a.v[0];
+                };
+                num("xwidth", &out.filter_xwidth);
+                num("ywidth", &out.filter_ywidth);
+                num("alpha", &out.filter_alpha);
+                num("B", &out.filter_B);
+                num("C", &out.filter_C);
+                num("tau", &out.filter_tau);
+            }
         }
         pbrs_camera_spec& cam = out.spec.camera;
         cam.width = (uint32_t)w;
@@ -1334,5 +1352,26 @@ int pbrs_host_load_pbrt(const char* path, pbrs_loaded_scene** out) {
 }
 const pbrs_scene_spec* pbrs_loaded_scene_spec(const pbrs_loaded_scene* s) { return &s->spec; }
 void pbrs_loaded_scene_free(pbrs_loaded_scene* s) { delete s; }
+
+int pbrs_loaded_scene_filter(const pbrs_loaded_scene* s, pbrs_pixel_filter* out) {  // parse_filter, loader.rs:822-855
+    if (!s || !out) return PBRS_E_INVALID;
+    const std::string& name = s->filter.empty() ? std::string("box") : s->filter;  // Scene's default, loader.rs:73-74
+    pbrs_pixel_filter f{};
+    auto or_default = [](float v, float d) { return pn_isnan(v) ? d : v; };
+    const float r = name == "box" ? 0.5f : name == "sinc" ? 4.0f : 2.0f;
+    if (name == "box") f.kind = PBRS_FILTER_BOX;
+    else if (name == "triangle") f.kind = PBRS_FILTER_TRIANGLE;  // pbrt-v3 (the reference's parse_filter panics on it)
+    else if (name == "gaussian") f.kind = PBRS_FILTER_GAUSSIAN, f.a = or_default(s->filter_alpha, 2.0f);
+    else if (name == "mitchell") f.kind = PBRS_FILTER_MITCHELL, f.a = or_default(s->filter_B, 1.0f / 3.0f), f.b = or_default(s->filter_C, 1.0f / 3.0f);
+    else if (name == "sinc") f.kind = PBRS_FILTER_LANCZOS, f.a = or_default(s->filter_tau, 3.0f);
+    else {
+        g_load_error = "unsupported pixel filter \"" + name + "\" (box, triangle, gaussian, mitchell, sinc)";
+        return PBRS_E_INVALID;
+    }
+    f.radius[0] = or_default(s->filter_xwidth, r);
+    f.radius[1] = or_default(s->filter_ywidth, r);
+    *out = f;
+    return PBRS_OK;
+}
 
 }  // extern "C"

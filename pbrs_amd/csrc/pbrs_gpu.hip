@@ -23,6 +23,7 @@
 #include "../../include/pbrs_gpu.h"
 #include "device/kernels.h"
 #include "device/aov.h"
+#include "device/film.h"
 
 namespace {
 
@@ -232,6 +233,9 @@ struct pbrs_ctx {
     size_t cap_aov_pixels = 0, cap_aov_out_pixels = 0;
     float* aov_state = nullptr;  // PBRS_AOV_STATE_WORDS * cap_aov_pixels, planar
     void* aov_out = nullptr;     // kAovOutWords * cap_aov_out_pixels: the seven buffers of pbrs_aov_buffers, one after the other
+    // filtered film (pbrs_render_tile_filtered*, device/film.h): S.rgb and W of every tile pixel, planar
+    size_t cap_filter_pixels = 0;
+    float* filter_sum = nullptr;  // 4 * cap_filter_pixels
 };
 
 namespace {
@@ -379,6 +383,24 @@ int ensure_aov(pbrs_ctx* c, size_t n_pixels, bool staging) {
     int rc = grow(reinterpret_cast<void**>(&c->aov_state), c->cap_aov_pixels, PBRS_AOV_STATE_WORDS * sizeof(float), "the AOV state");
     if (rc || !staging) return rc;
     return grow(&c->aov_out, c->cap_aov_out_pixels, kAovOutWords * sizeof(uint32_t), "the AOV buffers");
+}
+
+// The filtered film's sums for n_pixels tile pixels; a failure leaves the context without them, usable for every other call.
+int ensure_filter(pbrs_ctx* c, size_t n_pixels) {
+    if (n_pixels <= c->cap_filter_pixels) return PBRS_OK;
+    c->cap_filter_pixels = 0;
+    if (c->filter_sum) (void)hipFree(c->filter_sum);
+    c->filter_sum = nullptr;
+    const size_t total = 4 * n_pixels * sizeof(float);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->filter_sum), total);
+    if (e != hipSuccess) {
+        c->filter_sum = nullptr;
+        c->error = std::string("hipMalloc of the filter sums (") + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
+        (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
+        return PBRS_E_DEVICE;
+    }
+    c->cap_filter_pixels = n_pixels;
+    return PBRS_OK;
 }
 
 void free_aov(pbrs_ctx* c) {
@@ -731,7 +753,9 @@ void poll_split_probe(pbrs_ctx* c) {
 // `handoff`: the pass moves to the late stream at bounce pbrs_ctx::overlap_from (at the latest for its k_accumulate: the late stream runs
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
 // `aov`: the AOV state k_aov folds this pass's first hits into (null: no AOVs).
-int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false, float* aov = nullptr) {
+// `filt`: a filtered render (rc is its traced region): k_filter_accumulate folds the pass into pbrs_ctx::filter_sum instead of k_accumulate.
+int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false, float* aov = nullptr,
+             const FilterConst* filt = nullptr) {
     pbrs_ctx::PassSet& set = c->pass_set[c->cur_set];
     // the set's memory is free once the pass that used it last has accumulated (two passes back, on the late stream)
     if (handoff && set.in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, set.accumulated, 0));
@@ -845,7 +869,11 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         hipLaunchKernelGGL(k_sum_bounce_counts, dim3(1), dim3(64), 0, c->stream, act, ns, N, n_bounces, c->bounce_acc);
     if (handoff && c->stream != c->second_stream) HIPCHK(c, to_late_stream());
     if (tm.begin(4)) return fail(c, PBRS_E_DEVICE, "event record failed");
-    hipLaunchKernelGGL(k_accumulate, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, c->sum, P, kc, rc.chunk_pixels, rc.w, rc.tiles8_per_row, c->nonfinite);
+    if (filt)
+        hipLaunchKernelGGL(k_filter_accumulate, dim3((filt->w + PBRS_FILTER_CELL - 1) / PBRS_FILTER_CELL, (filt->h + PBRS_FILTER_CELL - 1) / PBRS_FILTER_CELL),
+                           dim3(kBlock), filter_lds_bytes(filt->hx, filt->hy), c->stream, c->st, c->filter_sum, rc, *filt, kc, c->nonfinite);
+    else
+        hipLaunchKernelGGL(k_accumulate, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, c->sum, P, kc, rc.chunk_pixels, rc.w, rc.tiles8_per_row, c->nonfinite);
     tm.end();
     if (handoff) {
         HIPCHK(c, hipEventRecord(set.accumulated, c->stream));
@@ -856,7 +884,10 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
 }
 
 // `aovs` (device pointers; null or all-null: none): the first-hit AOVs too, from the state ensure_aov allocated.
-int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device, const pbrs_aov_buffers* aovs = nullptr) {
+// `filt`: a filtered render; `p` is then its traced region (check_filter) and rgb_device receives the tile's filt->w x filt->h pixels,
+// from the sums ensure_filter allocated.
+int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device, const pbrs_aov_buffers* aovs = nullptr,
+                  const FilterConst* filt = nullptr) {
     HIPCHK(c, hipSetDevice(c->device));  // before check_params: the automatic pass size reads THIS device's free memory
     int rcode = check_params(c, cam, p);
     if (rcode) return rcode;
@@ -877,7 +908,8 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (stats) HIPCHK(c, hipMemsetAsync(c->bounce_acc, 0, 2 * PBRS_STATS_MAX_BOUNCES * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->nonfinite, 0, sizeof(unsigned long long), c->stream));
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[0], c->stream));
-    HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
+    if (filt) HIPCHK(c, hipMemsetAsync(c->filter_sum, 0, 4 * (size_t)filt->w * filt->h * sizeof(float), c->stream));
+    else HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
     float* aov = any_aov(aovs) ? c->aov_state : nullptr;
     if (aov) HIPCHK(c, hipMemsetAsync(aov, 0, PBRS_AOV_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     uint32_t passes = 0;
@@ -898,7 +930,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     for (uint32_t first = 0; first < spp; first += K) {
         uint32_t kc = spp - first < K ? spp - first : K;
         if (two) use_pass_set(c, (int)(passes & 1u));  // (also: back to the main stream)
-        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov);
+        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov, filt);
         if (rcode) {
             use_pass_set(c, 0);
             return rcode;
@@ -910,7 +942,12 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
         use_pass_set(c, 0);
         HIPCHK(c, hipStreamWaitEvent(c->main_stream, last, 0));  // the late stream has run every pass's accumulation, in order
     }
-    hipLaunchKernelGGL(k_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->sum, rgb_device, P, 1.0f / (float)spp);
+    if (filt) {
+        const uint32_t PT = filt->w * filt->h;
+        hipLaunchKernelGGL(k_filter_finalize, dim3((PT + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->filter_sum, rgb_device, PT);
+    } else {
+        hipLaunchKernelGGL(k_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->sum, rgb_device, P, 1.0f / (float)spp);
+    }
     if (aov)
         hipLaunchKernelGGL(k_aov_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, aov, c->S.inst, P, rc.w, rc.tiles8_per_row,
                            1.0f / (float)spp, *aovs);
@@ -1072,6 +1109,7 @@ void pbrs_destroy(pbrs_ctx* c) {
     free_scene(c);
     free_work(c);  // (leaves pass set 0 in use)
     free_aov(c);
+    if (c->filter_sum) (void)hipFree(c->filter_sum);
     if (c->counters) (void)hipFree(c->counters);
     if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
     for (int k = 0; k < 2; ++k)
@@ -1544,6 +1582,71 @@ int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render
         for (int k = 0; k < 7; ++k)
             if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], src[k], words[k] * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
+    return collect(c, stats_out);
+}
+
+// The checks of the filtered entry points beyond render_common's; fills the kernel's constants and `region`, the tile plus its
+// halo clipped to the film: the params render_common traces (check_params, the pass size and ensure_work all see the region).
+static int check_filter(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, FilterConst& fc,
+                 pbrs_render_params& region) {
+    int rc = check_params(c, cam, p);
+    if (rc) return rc;
+    if (!f) return fail(c, PBRS_E_INVALID, "null pixel filter");
+    if (p->band_count > 1) return fail(c, PBRS_E_INVALID, "a filtered render takes a rectangular tile, not interleaved row bands");
+    if (p->integrator >= PBRS_INTEGRATOR_MATERIALS) return fail(c, PBRS_E_INVALID, "the visualisers bypass the film: no pixel filter");
+    if (f->kind > PBRS_FILTER_LANCZOS) return fail(c, PBRS_E_INVALID, "unknown pixel filter kind");
+    for (int a = 0; a < 2; ++a)
+        if (!pn_isfinite(f->radius[a]) || !(f->radius[a] > 0.0f)) return fail(c, PBRS_E_INVALID, "a pixel filter radius must be finite and > 0");
+    const uint32_t n_params = f->kind == PBRS_FILTER_MITCHELL ? 2u : (f->kind == PBRS_FILTER_GAUSSIAN || f->kind == PBRS_FILTER_LANCZOS) ? 1u : 0u;
+    if ((n_params > 0 && !pn_isfinite(f->a)) || (n_params > 1 && !pn_isfinite(f->b)))
+        return fail(c, PBRS_E_INVALID, "non-finite pixel filter parameter");
+    if (f->radius[0] > PBRS_FILTER_MAX_RADIUS || f->radius[1] > PBRS_FILTER_MAX_RADIUS)
+        return fail(c, PBRS_E_LIMIT, "pixel filter radius above 4 (the halo's LDS budget)");
+    fc = FilterConst{};
+    fc.kind = f->kind;
+    fc.rx = f->radius[0], fc.ry = f->radius[1], fc.a = f->a, fc.b = f->b;
+    fc.hx = pf_halo(fc.rx), fc.hy = pf_halo(fc.ry);
+    fc.x0 = p->x0, fc.y0 = p->y0, fc.w = p->w, fc.h = p->h;
+    region = *p;
+    region.x0 = p->x0 > fc.hx ? p->x0 - fc.hx : 0u;
+    region.y0 = p->y0 > fc.hy ? p->y0 - fc.hy : 0u;
+    region.w = std::min(p->x0 + p->w + fc.hx, cam->width) - region.x0;
+    region.h = std::min(p->y0 + p->h + fc.hy, cam->height) - region.y0;
+    rc = check_params(c, cam, &region);
+    if (rc) return rc;
+    return ensure_filter(c, (size_t)p->w * p->h);  // before render_common's pass size reads the free memory
+}
+
+int pbrs_render_tile_filtered_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f,
+                                     float* rgb_out_device, pbrs_stats* stats_out) {
+    if (!c) return PBRS_E_INVALID;
+    if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
+    HIPCHK(c, hipSetDevice(c->device));
+    FilterConst fc;
+    pbrs_render_params region;
+    int rc = check_filter(c, cam, p, f, fc, region);
+    if (rc) return rc;
+    rc = render_common(c, cam, &region, rgb_out_device, nullptr, &fc);
+    if (rc) return rc;
+    if (stats_out) return collect(c, stats_out);
+    return PBRS_OK;
+}
+
+int pbrs_render_tile_filtered(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, float* rgb_out_host,
+                              pbrs_stats* stats_out) {
+    if (!c) return PBRS_E_INVALID;
+    if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
+    HIPCHK(c, hipSetDevice(c->device));
+    FilterConst fc;
+    pbrs_render_params region;
+    int rc = check_filter(c, cam, p, f, fc, region);
+    if (rc) return rc;
+    const size_t PR = (size_t)region.w * region.h;  // >= the tile's pixels: rgb_dev holds the tile
+    rc = ensure_work(c, PR * auto_samples_per_pass(c, &region), PR);
+    if (rc) return rc;
+    rc = render_common(c, cam, &region, c->rgb_dev, nullptr, &fc);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * (size_t)p->w * p->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return collect(c, stats_out);
 }
 

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
-<out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits)."""
+<out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
+--pixel-filter: reconstructs the image with the file's `Filter` (include/pbrs_gpu.h, pbrs_render_tile_filtered) instead of the plain
+per-pixel mean; the AOVs stay per-pixel means (a separate render of the same samples)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pbrs_amd
 
 aovs = "--aovs" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--aovs"]
+filtered = "--pixel-filter" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter")]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -19,7 +22,13 @@ ctx = pbrs_amd.Context(0)
 ctx.upload(pbrs_amd.HostScene(ls))
 if integrator in ("materials", "normals"):  # --visualize-materials / --visualize-normals (src/main.rs:180-185): one ray per pixel
     msaa = 1
-if aovs:
+if filtered:
+    pf = ls.pixel_filter()
+    img, st = ctx.render_filtered(pf, msaa, msaa, depth, 1, integrator=integrator, timing=True)
+    print(f"pixel filter: {pf}")
+    if aovs:
+        _, buf, _ = ctx.render_aovs(msaa, msaa, depth, 1, aovs=("albedo", "normal", "depth"), integrator=integrator)
+elif aovs:
     img, buf, st = ctx.render_aovs(msaa, msaa, depth, 1, aovs=("albedo", "normal", "depth"), integrator=integrator, timing=True)
 else:
     img, st = ctx.render(msaa, msaa, depth, 1, integrator=integrator, timing=True)
