@@ -421,6 +421,62 @@ int pbrs_render_tile_filtered(pbrs_ctx*, const pbrs_camera*, const pbrs_render_p
 int pbrs_render_tile_filtered_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, const pbrs_pixel_filter*,
                                      float* rgb_out_device, pbrs_stats* stats_out);
 
+/* Denoiser: the edge-avoiding a-trous wavelet filter of Dammertz, Sewtz, Hanika and Lensch (HPG 2010) over a finished image, guided by
+ * the first-hit AOVs above.  An image operation: it needs a context (device, stream) and no uploaded scene.  All arithmetic is f32
+ * without fused multiply-add, in the order written; pn_* is include/pbrs_numeric.h; p, q are pixels of the w x h image, c = r, g, b.
+ *   Demodulation.  With PBRS_DENOISE_DEMODULATE: d.c = albedo(p).c > albedo_floor ? albedo(p).c : 1.0f (a miss, an emitter, a black
+ *     lobe and a NaN albedo give 1) and c_0(p).c = rgb(p).c / d.c.  Without the flag c_0 = rgb and d = 1.
+ *   Iteration k = 0 .. iterations-1, tap spacing s = 1 << k, gives c_{k+1} from c_k.  For pixel p, from S = (+0, +0, +0), W = +0:
+ *     for dy = -2 .. 2 (outer), for dx = -2 .. 2 (inner): q = p + s * (dx, dy).  q outside the image is skipped; q with a channel of
+ *     c_k(q) that is not finite (pn_isfinite) is skipped.  Otherwise
+ *       spline   hw = K[|dx|] * K[|dy|], K = {0.375f, 0.25f, 0.0625f} (the B3 spline; every product is exact in f32)
+ *       colour   e.c = c_k(q).c - c_k(p).c, d2 = (e.r * e.r + e.g * e.g) + e.b * e.b, wc = pn_exp(-d2 * ic_k) with
+ *                sc_k = sigma_color * pn_exp2i(-k), ic_k = 1.0f / (sc_k * sc_k): the colour sigma halves every iteration
+ *       normal   guides.normal != NULL: the same d2 on normal(q) - normal(p), wn = pn_exp(-d2 * (1.0f / (sigma_normal * sigma_normal)));
+ *                NULL: wn = 1.0f
+ *       depth    guides.depth != NULL, zp = depth(p), zq = depth(q) (+inf where no sample hit): both infinite (pn_isinf): wd = 1.0f;
+ *                exactly one infinite: wd = +0; otherwise r = ((zq - zp) / zp) / (float)s and
+ *                wd = pn_exp(-(r * r) * (1.0f / (sigma_depth * sigma_depth))) — a relative slope per pixel of tap distance, so a
+ *                slanted plane does not stop the filter at large s.  NULL: wd = 1.0f
+ *       wgt = ((hw * wc) * wn) * wd; with PBRS_DENOISE_ID_STOP, instance(q) != instance(p) makes wgt = +0 whatever the stops gave.
+ *     A tap whose wgt is NaN (wgt != wgt: a non-finite guide value, or zp == 0) is skipped.  Otherwise S.c = S.c + wgt * c_k(q).c per
+ *     channel, then W = W + wgt.  The centre tap weighs 0.140625f, so W > 0 whenever the guides at p are finite.
+ *     c_{k+1}(p).c = S.c * (1.0f / W).  If W == 0 (only a non-finite guide at p itself does that), or if a channel of c_k(p) is
+ *     not finite, c_{k+1}(p) = c_k(p): the pixel passes through, a NaN stays visible as in the plain image and, by the tap rule,
+ *     contaminates no neighbour.
+ *   Result.  out(p).c = c_N(p).c * d.c with PBRS_DENOISE_DEMODULATE, c_N(p).c without.
+ * A result pixel depends on 2 * (2^iterations - 1) pixels of surround per side, so the calls take whole images, not tiles.
+ * Guides are the layouts pbrs_aov_buffers writes (albedo, normal: 3 x f32 per pixel; depth: f32; instance: u32); any pointer may be
+ * NULL: that stop is off.  Pointers are host memory for pbrs_denoise (which synchronises before it returns), device memory for
+ * pbrs_denoise_device, which runs on the context's stream (pbrs_set_stream honoured) and does not wait on the device: queued after
+ * pbrs_render_tile_aovs_device on the same context it needs no synchronisation in between, and its output is valid when that
+ * render's would be (pbrs_collect_stats, or the stream's order).  rgb_out may equal rgb_in.
+ * Memory: the first call allocates 52 B of scratch per pixel (two ping-pong colour planes {c.rgb, finite flag} and a guide plane
+ * {normal.xyz, depth} of 16 B each, the instance ids 4 B; pbrs_denoise another 44 B per pixel of staging), a larger image grows it,
+ * pbrs_destroy frees it; a context that never denoises allocates nothing.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, rgb_in, rgb_out or guides; w or h 0; iterations 0 or above
+ * PBRS_DENOISE_MAX_ITERATIONS; a sigma that is not finite or not > 0; an albedo_floor that is not finite or < 0; unknown flag bits;
+ * PBRS_DENOISE_DEMODULATE without guides.albedo; PBRS_DENOISE_ID_STOP without guides.instance.  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_DENOISE_MAX_ITERATIONS 6
+#define PBRS_DENOISE_DEMODULATE 1u /* filter rgb / albedo, multiply back afterwards */
+#define PBRS_DENOISE_ID_STOP 2u    /* a tap on another instance id has weight 0      */
+typedef struct pbrs_denoise_params {
+    uint32_t w, h;       /* image size; every buffer is w*h pixels, row-major */
+    uint32_t iterations; /* 1 .. PBRS_DENOISE_MAX_ITERATIONS: iteration k uses tap spacing 1 << k */
+    uint32_t flags;      /* PBRS_DENOISE_* */
+    float sigma_color, sigma_normal, sigma_depth; /* finite and > 0 */
+    float albedo_floor;                           /* finite and >= 0 */
+} pbrs_denoise_params;                            /* 32 B */
+typedef struct pbrs_denoise_guides {
+    const float* albedo;
+    const float* normal;
+    const float* depth;
+    const uint32_t* instance;
+} pbrs_denoise_guides;
+int pbrs_denoise(pbrs_ctx*, const pbrs_denoise_params*, const float* rgb_in_host, const pbrs_denoise_guides* guides_host, float* rgb_out_host);
+int pbrs_denoise_device(pbrs_ctx*, const pbrs_denoise_params*, const float* rgb_in_device, const pbrs_denoise_guides* guides_device,
+                        float* rgb_out_device);
+
 /* ---- parity-harness entry points (the reference's own functions, batched) -------------------------- */
 typedef struct pbrs_hit_record {
     float t;

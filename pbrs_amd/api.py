@@ -130,6 +130,41 @@ class PixelFilter(C.Structure):
         return f"PixelFilter({k}, radius=({self.radius[0]}, {self.radius[1]}), a={self.a}, b={self.b})"
 
 
+class DenoiseParams(C.Structure):
+    """pbrs_denoise_params (include/pbrs_gpu.h): image size, iterations, flags, the three sigmas and the albedo floor.  `make` carries
+    the defaults ("Denoiser": chosen from the measured error ratios)."""
+    DEMODULATE, ID_STOP = 1, 2
+    MAX_ITERATIONS = 6
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
+
+    @classmethod
+    def make(cls, w, h, iterations=5, sigma_color=16.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
+             id_stop=False):
+        p = cls()
+        p.w, p.h, p.iterations = w, h, iterations
+        p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
+        p.sigma_color, p.sigma_normal, p.sigma_depth, p.albedo_floor = sigma_color, sigma_normal, sigma_depth, albedo_floor
+        return p
+
+    @classmethod
+    def for_guides(cls, w, h, albedo=False, instance=False, **params):
+        """The defaults for the guides at hand: demodulate when there is an albedo, stop at instance edges when there are ids."""
+        params.setdefault("demodulate", bool(albedo))
+        params.setdefault("id_stop", bool(instance))
+        return cls.make(w, h, **params)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DenoiseGuides(C.Structure):
+    """pbrs_denoise_guides: the AOV layouts, NULL = that stop is off."""
+    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance")]
+
+
+DENOISE_GUIDES = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "instance": (1, np.uint32)}
+
 HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
 NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "exp": 6, "ln": 7, "hypot": 8, "div": 9,
                "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "box_quotient": 15}
@@ -137,7 +172,7 @@ NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "
 GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_stream", "pbrs_set_pass_overlap", "pbrs_upload_scene", "pbrs_render_tile",
                "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
                "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
-               "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device"]
+               "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -209,8 +244,27 @@ def gpu_lib():
         L.pbrs_render_tile_aovs_device.argtypes = [C.c_void_p] * 6
         L.pbrs_render_tile_filtered.argtypes = [C.c_void_p] * 6
         L.pbrs_render_tile_filtered_device.argtypes = [C.c_void_p] * 6
+        L.pbrs_denoise.argtypes = [C.c_void_p] * 5
+        L.pbrs_denoise_device.argtypes = [C.c_void_p] * 5
         _gpu = L
     return _gpu
+
+
+_hip = None
+
+
+def hip_runtime():
+    """The HIP runtime libpbrs_gpu.so is linked against (already loaded with it), for the device buffers of Context.render_denoised."""
+    global _hip
+    if _hip is None:
+        gpu_lib()
+        path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
+        L = C.CDLL(path)
+        L.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.hipFree.argtypes = [C.c_void_p]
+        _hip = L
+    return _hip
 
 
 INTEGRATORS = {"path": 0, "direct": 1, "materials": 2, "normals": 3}  # PBRS_INTEGRATOR_*
@@ -419,6 +473,80 @@ class Context:
         p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, None, integrator)
         self._check(self._L.pbrs_render_tile_filtered_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.byref(pixel_filter),
                                                              C.c_void_p(rgb_device_ptr), None), "pbrs_render_tile_filtered_device")
+
+    def denoise(self, rgb, albedo=None, normal=None, depth=None, instance=None, **params):
+        """The edge-avoiding a-trous denoiser (include/pbrs_gpu.h, pbrs_denoise) over an (h, w, 3) f32 image and the guides given
+        (arrays as render_aovs returns them; None = that stop is off) -> (h, w, 3) f32.  params: DenoiseParams.make's keywords; by
+        default the image is demodulated when there is an albedo and taps stop at instance edges when there are ids."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        h, w, _ = rgb.shape
+        given = {"albedo": albedo, "normal": normal, "depth": depth, "instance": instance}
+        p = DenoiseParams.for_guides(w, h, albedo is not None, instance is not None, **params)
+        g, keep = DenoiseGuides(), []
+        for n, a in given.items():
+            if a is None:
+                continue
+            ch, dt = DENOISE_GUIDES[n]
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != ((h, w, ch) if ch > 1 else (h, w)):
+                raise ValueError(f"{n} guide of shape {a.shape} beside an image of {rgb.shape}")
+            keep.append(a)
+            setattr(g, n, a.ctypes.data)
+        out = np.empty_like(rgb)
+        self._check(self._L.pbrs_denoise(self._h, C.addressof(p), rgb.ctypes.data, C.addressof(g), out.ctypes.data), "pbrs_denoise")
+        return out
+
+    def denoise_device(self, rgb_in_device_ptr, rgb_out_device_ptr, w, h, guide_device_ptrs=None, **params):
+        """denoise() on caller-owned device memory: `guide_device_ptrs` = {name: pointer} of albedo / normal / depth / instance.  Runs on
+        the context's stream behind whatever was queued there (a render_aovs_device needs no synchronisation in between) and does not
+        wait: valid after `collect_stats()`.  The output pointer may be the input's."""
+        ptrs = dict(guide_device_ptrs or {})
+        unknown = [n for n in ptrs if n not in DENOISE_GUIDES]
+        if unknown:
+            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
+        p = DenoiseParams.for_guides(w, h, bool(ptrs.get("albedo")), bool(ptrs.get("instance")), **params)
+        g = DenoiseGuides()
+        for n, ptr in ptrs.items():
+            setattr(g, n, ptr)
+        self._check(self._L.pbrs_denoise_device(self._h, C.addressof(p), C.c_void_p(rgb_in_device_ptr), C.addressof(g),
+                                                C.c_void_p(rgb_out_device_ptr)), "pbrs_denoise_device")
+
+    def render_denoised(self, strata_x, strata_y, depth, seed, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                        integrator="path", keep_noisy=False, **params):
+        """The whole frame rendered with its guides and denoised in device memory (render_aovs_device, then denoise_device on the same
+        stream, no synchronisation in between), copied back once -> (h, w, 3) f32 denoised radiance, stats dict; with keep_noisy the
+        plain image comes too: (denoised, noisy, stats)."""
+        unknown = [n for n in guides if n not in DENOISE_GUIDES]
+        if unknown:
+            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
+        w, h = self.scene.width, self.scene.height
+        hip = hip_runtime()
+        n_rgb = 3 * w * h * 4
+        sizes = {"rgb": n_rgb, "out": n_rgb, **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
+        dev = {}
+        try:
+            for n, nbytes in sizes.items():
+                ptr = C.c_void_p()
+                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
+                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_denoised failed")
+                dev[n] = ptr
+            gp = {n: dev[n].value for n in guides}
+            self.render_aovs_device(dev["rgb"].value, gp, strata_x, strata_y, depth, seed, samples_per_pass=samples_per_pass,
+                                    integrator=integrator)
+            self.denoise_device(dev["rgb"].value, dev["out"].value, w, h, gp, **params)
+            stats = self.collect_stats()  # waits for the stream
+            out = np.empty((h, w, 3), dtype=np.float32)
+            if hip.hipMemcpy(out.ctypes.data, dev["out"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
+                raise PbrsError("hipMemcpy of the denoised image failed")
+            if not keep_noisy:
+                return out, stats
+            noisy = np.empty_like(out)
+            if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
+                raise PbrsError("hipMemcpy of the plain image failed")
+            return out, noisy, stats
+        finally:
+            for ptr in dev.values():
+                hip.hipFree(ptr)
 
     def collect_stats(self):
         st = Stats()

@@ -24,6 +24,7 @@
 #include "device/kernels.h"
 #include "device/aov.h"
 #include "device/film.h"
+#include "device/denoise.h"
 
 namespace {
 
@@ -236,6 +237,11 @@ struct pbrs_ctx {
     // filtered film (pbrs_render_tile_filtered*, device/film.h): S.rgb and W of every tile pixel, planar
     size_t cap_filter_pixels = 0;
     float* filter_sum = nullptr;  // 4 * cap_filter_pixels
+    // denoiser (pbrs_denoise*, device/denoise.h), allocated by the first call: two ping-pong colour planes, the guide plane and the
+    // instance ids (16 + 16 + 16 + 4 B per pixel, one allocation), and the host variant's staging (rgb, albedo, normal, depth, instance)
+    size_t cap_denoise_pixels = 0, cap_denoise_stage_pixels = 0;
+    void* denoise_mem = nullptr;
+    void* denoise_stage = nullptr;  // kDenoiseStageWords * cap_denoise_stage_pixels
 };
 
 namespace {
@@ -401,6 +407,33 @@ int ensure_filter(pbrs_ctx* c, size_t n_pixels) {
     }
     c->cap_filter_pixels = n_pixels;
     return PBRS_OK;
+}
+
+constexpr size_t kDenoiseBytesPerPixel = 3 * sizeof(float4) + sizeof(uint32_t);
+constexpr size_t kDenoiseStageWords = 3 + 3 + 3 + 1 + 1;  // rgb, albedo, normal, depth, instance
+
+// The denoiser's scratch (and, with `staging`, the host variant's buffers) for n_pixels: grown like the AOV state; a failure leaves the
+// context without it, usable for every other call.
+int ensure_denoise(pbrs_ctx* c, size_t n_pixels, bool staging) {
+    auto grow = [&](void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) -> int {
+        if (n_pixels <= cap) return PBRS_OK;
+        cap = 0;
+        if (*ptr) (void)hipFree(*ptr);
+        *ptr = nullptr;
+        const size_t total = n_pixels * bytes_per_pixel;
+        hipError_t e = hipMalloc(ptr, total);
+        if (e != hipSuccess) {
+            *ptr = nullptr;
+            c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
+            (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
+            return PBRS_E_DEVICE;
+        }
+        cap = n_pixels;
+        return PBRS_OK;
+    };
+    int rc = grow(&c->denoise_mem, c->cap_denoise_pixels, kDenoiseBytesPerPixel, "the denoiser's scratch");
+    if (rc || !staging) return rc;
+    return grow(&c->denoise_stage, c->cap_denoise_stage_pixels, kDenoiseStageWords * sizeof(float), "the denoiser's staging");
 }
 
 void free_aov(pbrs_ctx* c) {
@@ -1110,6 +1143,8 @@ void pbrs_destroy(pbrs_ctx* c) {
     free_work(c);  // (leaves pass set 0 in use)
     free_aov(c);
     if (c->filter_sum) (void)hipFree(c->filter_sum);
+    if (c->denoise_mem) (void)hipFree(c->denoise_mem);
+    if (c->denoise_stage) (void)hipFree(c->denoise_stage);
     if (c->counters) (void)hipFree(c->counters);
     if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
     for (int k = 0; k < 2; ++k)
@@ -1648,6 +1683,102 @@ int pbrs_render_tile_filtered(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_re
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * (size_t)p->w * p->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return collect(c, stats_out);
+}
+
+// ---- denoiser (include/pbrs_gpu.h, device/denoise.h) ----
+static_assert(sizeof(pbrs_denoise_params) == 32, "pbrs_denoise_params is 32 B");
+
+namespace {
+
+using DenoiseKernel = void (*)(const float4*, const float4*, const uint32_t*, float4*, DenoiseConst);
+// [id stop][iteration]
+constexpr DenoiseKernel kDenoiseAtrous[2][PBRS_DENOISE_MAX_ITERATIONS] = {
+    {k_denoise_atrous<0, false>, k_denoise_atrous<1, false>, k_denoise_atrous<2, false>, k_denoise_atrous<3, false>, k_denoise_atrous<4, false>,
+     k_denoise_atrous<5, false>},
+    {k_denoise_atrous<0, true>, k_denoise_atrous<1, true>, k_denoise_atrous<2, true>, k_denoise_atrous<3, true>, k_denoise_atrous<4, true>,
+     k_denoise_atrous<5, true>}};
+
+int check_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in, const pbrs_denoise_guides* g, const float* rgb_out) {
+    if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
+    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty image");
+    if (p->iterations == 0 || p->iterations > PBRS_DENOISE_MAX_ITERATIONS) return fail(c, PBRS_E_INVALID, "denoise iterations must be 1 .. 6");
+    const float sigma[3] = {p->sigma_color, p->sigma_normal, p->sigma_depth};
+    for (float s : sigma)
+        if (!pn_isfinite(s) || !(s > 0.0f)) return fail(c, PBRS_E_INVALID, "a denoise sigma must be finite and > 0");
+    if (!pn_isfinite(p->albedo_floor) || !(p->albedo_floor >= 0.0f)) return fail(c, PBRS_E_INVALID, "the albedo floor must be finite and >= 0");
+    if (p->flags & ~(PBRS_DENOISE_DEMODULATE | PBRS_DENOISE_ID_STOP)) return fail(c, PBRS_E_INVALID, "unknown denoise flag bits");
+    if ((p->flags & PBRS_DENOISE_DEMODULATE) && !g->albedo) return fail(c, PBRS_E_INVALID, "PBRS_DENOISE_DEMODULATE without an albedo guide");
+    if ((p->flags & PBRS_DENOISE_ID_STOP) && !g->instance) return fail(c, PBRS_E_INVALID, "PBRS_DENOISE_ID_STOP without an instance guide");
+    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The launches of one denoise on the context's stream (arguments checked, scratch there): pack, the iterations ping-pong, unpack.
+int denoise_launch(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in, const pbrs_denoise_guides* g, float* rgb_out) {
+    const uint32_t P = p->w * p->h;
+    float4* plane[2] = {static_cast<float4*>(c->denoise_mem), static_cast<float4*>(c->denoise_mem) + c->cap_denoise_pixels};
+    float4* guide = plane[1] + c->cap_denoise_pixels;
+    uint32_t* ids = reinterpret_cast<uint32_t*>(guide + c->cap_denoise_pixels);
+    const uint32_t demod = p->flags & PBRS_DENOISE_DEMODULATE;
+    const bool id_stop = (p->flags & PBRS_DENOISE_ID_STOP) != 0;
+    pbrs_denoise_guides packed = *g;
+    if (!id_stop) packed.instance = nullptr;
+    const dim3 lin((P + kBlock - 1) / kBlock), cells((p->w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p->h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
+    hipLaunchKernelGGL(k_denoise_pack, lin, dim3(kBlock), 0, c->stream, rgb_in, packed, P, demod, p->albedo_floor, plane[0], guide, ids);
+    DenoiseConst k{};
+    k.w = p->w, k.h = p->h;
+    k.in = 1.0f / (p->sigma_normal * p->sigma_normal);
+    k.id = 1.0f / (p->sigma_depth * p->sigma_depth);
+    for (uint32_t it = 0; it < p->iterations; ++it) {
+        const float sc = p->sigma_color * pn_exp2i(-(int)it);
+        k.ic = 1.0f / (sc * sc);
+        const DenoiseKernel fn = kDenoiseAtrous[id_stop ? 1 : 0][it];
+        hipLaunchKernelGGL(fn, cells, dim3(kBlock), 0, c->stream, plane[it & 1u], guide, ids, plane[(it + 1u) & 1u], k);
+    }
+    hipLaunchKernelGGL(k_denoise_unpack, lin, dim3(kBlock), 0, c->stream, plane[p->iterations & 1u], g->albedo, P, demod, p->albedo_floor, rgb_out);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_denoise_device(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_device, const pbrs_denoise_guides* guides_device,
+                        float* rgb_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_denoise(c, p, rgb_in_device, guides_device, rgb_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_denoise(c, (size_t)p->w * p->h, false);
+    if (rc) return rc;
+    return denoise_launch(c, p, rgb_in_device, guides_device, rgb_out_device);
+}
+
+int pbrs_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_host, const pbrs_denoise_guides* guides_host, float* rgb_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_denoise(c, p, rgb_in_host, guides_host, rgb_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)p->w * p->h;
+    rc = ensure_denoise(c, P, true);
+    if (rc) return rc;
+    // device staging: rgb (in and out), then the given guides
+    float* f = static_cast<float*>(c->denoise_stage);
+    float* rgb = f;
+    pbrs_denoise_guides dev{};
+    dev.albedo = guides_host->albedo ? f + 3 * P : nullptr;
+    dev.normal = guides_host->normal ? f + 6 * P : nullptr;
+    dev.depth = guides_host->depth ? f + 9 * P : nullptr;
+    dev.instance = guides_host->instance ? reinterpret_cast<const uint32_t*>(f + 10 * P) : nullptr;
+    const void* src[5] = {rgb_in_host, guides_host->albedo, guides_host->normal, guides_host->depth, guides_host->instance};
+    const void* dst[5] = {rgb, dev.albedo, dev.normal, dev.depth, dev.instance};
+    const size_t words[5] = {3, 3, 3, 1, 1};
+    for (int k = 0; k < 5; ++k)
+        if (src[k]) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(dst[k]), src[k], words[k] * P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = denoise_launch(c, p, rgb, &dev, rgb);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {
