@@ -505,6 +505,81 @@ int pbrs_numeric_eval(pbrs_ctx*, uint32_t fn, uint32_t n, const float* x, const 
 /* Per-sample radiance of one sample index for a tile (before the sum over samples), for bisecting. */
 int pbrs_render_sample_radiance(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, uint32_t sample_index, float* rgb_out_host);
 
+/* ---- the variance AOV and the variance-guided denoiser ----------------------------------------------- */
+/* In both: f32 without fused multiply-add, in the order written; pn_* is include/pbrs_numeric.h;
+ * lum(c) = (0.21267127f * c.r + 0.71515972f * c.g) + 0.07216883f * c.b.
+ *
+ * Variance AOV.  pbrs_render_tile_aovs[_device] plus `variance`: w*h f32, the tile / band packing of rgb_out; NULL = exactly
+ * pbrs_render_tile_aovs[_device].  The image and the seven AOVs are the bits of that call.  For a pixel, L_i the radiance of its
+ * sample index i (what pbrs_render_sample_radiance exports):
+ *   from m1 = +0, m2 = +0, n = 0; for i = 0 .. spp-1 in order: y = lum(L_i); if pn_isfinite(y): m1 = m1 + y, m2 = m2 + y * y, n = n + 1
+ *   n < 2: variance = +inf ("unknown": the denoiser's luminance stop stays open)
+ *   else:  mean = m1 * (1.0f / (float)n); v = m2 * (1.0f / (float)n) - mean * mean; v = v < 0 ? +0 : v;
+ *          variance = v * (1.0f / (float)(n - 1))
+ * — the variance of the pixel's mean luminance.  The one-pass form cancels for a nearly constant pixel; that is part of the definition
+ * (the clamp catches the negative results).  The sample index is the only loop, so the result does not depend on the passes.
+ * Refused like pbrs_render_tile_aovs (a requested variance counts as a requested buffer).  The context keeps 12 B of moment state per
+ * pixel (m1, m2, n; the host variant 4 B per pixel of staging), allocated by the first call that asks for the variance; the kernel that
+ * folds a pass runs beside k_accumulate and its time counts in pbrs_stats::ms_accumulate. */
+int pbrs_render_tile_aovs_var(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                              float* variance_host, pbrs_stats* stats_out);
+int pbrs_render_tile_aovs_var_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_device,
+                                     const pbrs_aov_buffers* aovs_device, float* variance_device, pbrs_stats* stats_out);
+
+/* Variance-guided denoiser: pbrs_denoise with the colour stop replaced by the luminance stop of SVGF's spatial filter (Schied et al.,
+ * HPG 2017): luminance differences are measured in units of the pixel's own standard deviation, and the variance is filtered along
+ * with the colour, so the stop tightens by itself from one iteration to the next and no sigma depends on the units of the scene.
+ * Everything pbrs_denoise's text says holds unless restated here; v_k(p) is the variance carried beside c_k(p), in [+0, +inf] with
+ * +inf = "unknown".
+ *   Pack.  d and c_0 as pbrs_denoise.  vin = variance(p), +inf if it is NaN or < 0.  With PBRS_DENOISE_DEMODULATE: ld = lum(d),
+ *     v_0(p) = vin / (ld * ld), +inf if that is NaN (0 / 0, inf / inf); without the flag v_0 = vin.
+ *   Rule for every k: where a channel of c_k(p) is not finite, v_k(p) = +inf; a v_k that comes out NaN is +inf.
+ *   Iteration k = 0 .. iterations-1, tap spacing s = 1 << k.  For pixel p:
+ *     Prefiltered variance, always at spacing 1: from A = +0, B = +0, for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), n = p + (dx, dy)
+ *       inside the image with pn_isfinite(v_k(n)): A = A + G * v_k(n), then B = B + G, G = 0.25f (dx = dy = 0), 0.125f (one of them 0),
+ *       0.0625f.  vbar = B == 0 ? +inf : A * (1.0f / B); sd = sigma_luminance * pn_sqrt(vbar).
+ *     Taps: the 25 taps, their order, the skip rules, hw, wn, wd and the id stop of pbrs_denoise; instead of wc,
+ *       dl = pn_abs(lum(c_k(q)) - lum(c_k(p))) and
+ *       pn_isinf(sd): wl = 1.0f;  else sd == 0: wl = dl == 0 ? 1.0f : +0 (a pixel known exactly, such as an emitter seen directly, is
+ *       not blurred);  else wl = pn_exp(-(dl / sd)).
+ *       wgt = ((hw * wl) * wn) * wd, then the id stop and the NaN rule as before.
+ *     Fold: S.c = S.c + wgt * c_k(q).c per channel, W = W + wgt, then ww = wgt * wgt and, unless ww == 0 (a closed tap must not turn an
+ *       unknown neighbour into 0 * inf), V = V + ww * v_k(q), from V = +0.  An infinite v_k(q) behind an open tap makes V infinite:
+ *       "unknown" spreads, and the next iteration's stop at p stays open.
+ *     Result: iw = 1.0f / W; c_{k+1}(p).c = S.c * iw; v_{k+1}(p) = V * (iw * iw).  The pass-through cases of pbrs_denoise (W == 0, a
+ *       non-finite channel of c_k(p)) keep v as well: v_{k+1}(p) = v_k(p).
+ *     No sigma halves per iteration: the variance shrinks instead (v_{k+1} <= the largest v_k under the taps).
+ *   Result.  out as pbrs_denoise.  variance_out (NULL = not wanted; may equal guides.variance): v_N(p) * (ld * ld) with
+ *     PBRS_DENOISE_DEMODULATE, v_N(p) without.
+ * Scale invariance.  For an integer j, denoising (rgb * 2^j, variance * 4^j) gives out * 2^j and variance_out * 4^j bit for bit, as
+ * long as no product or sum above that depends on the scale (rgb / d, lum, G * v, sd, wgt * c, ww * v, S * iw, V * (iw * iw), c * d, ...)
+ * overflows or is a nonzero value below the smallest normal f32 at either scale: every weight is a function of quotients dl / sd and of
+ * the guides, which do not move.  (A stop that is nearly closed, wgt around 1e-38, puts wgt * c among the denormals, where the claim
+ * ends.)
+ * Memory: the first call allocates 52 B of scratch per pixel of its own (two ping-pong planes {c.rgb, v}, a guide plane {normal.xyz,
+ * depth}, the ids; pbrs_denoise_var another 52 B per pixel of staging), grown and freed like pbrs_denoise's; a context that never calls it
+ * allocates nothing.  Host / device pointers, the stream and the ordering after pbrs_render_tile_aovs_var_device: as pbrs_denoise[_device].
+ * Refused with PBRS_E_INVALID (the context stays usable): what pbrs_denoise refuses (sigma_luminance in place of sigma_color), and a NULL
+ * guides.variance.  w * h above 2^28: PBRS_E_LIMIT. */
+typedef struct pbrs_denoise_var_params {
+    uint32_t w, h;       /* image size; every buffer is w*h pixels, row-major */
+    uint32_t iterations; /* 1 .. PBRS_DENOISE_MAX_ITERATIONS */
+    uint32_t flags;      /* PBRS_DENOISE_DEMODULATE, PBRS_DENOISE_ID_STOP */
+    float sigma_luminance, sigma_normal, sigma_depth; /* finite and > 0; sigma_luminance counts standard deviations (SVGF: 4) */
+    float albedo_floor;                               /* finite and >= 0 */
+} pbrs_denoise_var_params;                            /* 32 B */
+typedef struct pbrs_denoise_var_guides {
+    const float* albedo;
+    const float* normal;
+    const float* depth;
+    const uint32_t* instance;
+    const float* variance; /* required: f32 per pixel, as pbrs_render_tile_aovs_var writes it */
+} pbrs_denoise_var_guides;
+int pbrs_denoise_var(pbrs_ctx*, const pbrs_denoise_var_params*, const float* rgb_in_host, const pbrs_denoise_var_guides* guides_host,
+                     float* rgb_out_host, float* variance_out_host);
+int pbrs_denoise_var_device(pbrs_ctx*, const pbrs_denoise_var_params*, const float* rgb_in_device, const pbrs_denoise_var_guides* guides_device,
+                            float* rgb_out_device, float* variance_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,11 +82,14 @@ AOVS = {"albedo": (3, np.float32), "normal": (3, np.float32), "coverage": (1, np
 AOV_NAMES = ("albedo", "normal", "depth", "instance", "material", "prim", "coverage")
 
 
+VARIANCE = "variance"  # the variance AOV (pbrs_render_tile_aovs_var): (h, w) f32, a pointer of its own beside pbrs_aov_buffers
+
+
 def _aov_names(aovs):
     names = tuple(aovs)
-    unknown = [n for n in names if n not in AOVS]
+    unknown = [n for n in names if n not in AOVS and n != VARIANCE]
     if unknown:
-        raise ValueError(f"unknown AOV name(s) {unknown}; known: {sorted(AOVS)}")
+        raise ValueError(f"unknown AOV name(s) {unknown}; known: {sorted(AOVS) + [VARIANCE]}")
     return names
 
 
@@ -163,6 +166,39 @@ class DenoiseGuides(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance")]
 
 
+class DenoiseVarParams(C.Structure):
+    """pbrs_denoise_var_params (include/pbrs_gpu.h): DenoiseParams with sigma_luminance, a count of standard deviations (SVGF's 4),
+    in the place of sigma_color."""
+    DEMODULATE, ID_STOP = DenoiseParams.DEMODULATE, DenoiseParams.ID_STOP
+    MAX_ITERATIONS = DenoiseParams.MAX_ITERATIONS
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_luminance", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
+
+    @classmethod
+    def make(cls, w, h, iterations=5, sigma_luminance=4.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
+             id_stop=False):
+        p = cls()
+        p.w, p.h, p.iterations = w, h, iterations
+        p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
+        p.sigma_luminance, p.sigma_normal, p.sigma_depth, p.albedo_floor = sigma_luminance, sigma_normal, sigma_depth, albedo_floor
+        return p
+
+    @classmethod
+    def for_guides(cls, w, h, albedo=False, instance=False, **params):
+        """The defaults for the guides at hand, as DenoiseParams.for_guides."""
+        params.setdefault("demodulate", bool(albedo))
+        params.setdefault("id_stop", bool(instance))
+        return cls.make(w, h, **params)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DenoiseVarGuides(C.Structure):
+    """pbrs_denoise_var_guides: the four guides of DenoiseGuides and the variance, which is required."""
+    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance", "variance")]
+
+
 DENOISE_GUIDES = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "instance": (1, np.uint32)}
 
 HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
@@ -172,7 +208,8 @@ NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "
 GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_stream", "pbrs_set_pass_overlap", "pbrs_upload_scene", "pbrs_render_tile",
                "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
                "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
-               "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device"]
+               "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device",
+               "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -246,6 +283,10 @@ def gpu_lib():
         L.pbrs_render_tile_filtered_device.argtypes = [C.c_void_p] * 6
         L.pbrs_denoise.argtypes = [C.c_void_p] * 5
         L.pbrs_denoise_device.argtypes = [C.c_void_p] * 5
+        L.pbrs_render_tile_aovs_var.argtypes = [C.c_void_p] * 7
+        L.pbrs_render_tile_aovs_var_device.argtypes = [C.c_void_p] * 7
+        L.pbrs_denoise_var.argtypes = [C.c_void_p] * 6
+        L.pbrs_denoise_var_device.argtypes = [C.c_void_p] * 6
         _gpu = L
     return _gpu
 
@@ -430,18 +471,26 @@ class Context:
     def render_aovs(self, strata_x, strata_y, depth, seed, aovs=AOV_NAMES, tile=None, samples_per_pass=0, counters=False,
                     timing=False, bands=None, integrator="path"):
         """render() plus first-hit AOVs of the same camera samples (include/pbrs_gpu.h, pbrs_aov_buffers) -> (rgb, {name: array},
-        stats).  albedo / normal: (h, w, 3) f32; coverage / depth: (h, w) f32; instance / material / prim: (h, w) u32."""
+        stats).  albedo / normal: (h, w, 3) f32; coverage / depth: (h, w) f32; instance / material / prim: (h, w) u32.  The name
+        "variance" (not in the default) adds the variance of the pixel's mean luminance, (h, w) f32, +inf where fewer than two samples
+        are finite (pbrs_render_tile_aovs_var)."""
         names = _aov_names(aovs)
         p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
         out = np.empty((p.h, p.w, 3), dtype=np.float32)
         bufs, arrays = AovBuffers(), {}
         for n in names:
-            ch, dt = AOVS[n]
+            ch, dt = AOVS.get(n, (1, np.float32))
             arrays[n] = np.empty((p.h, p.w, ch) if ch > 1 else (p.h, p.w), dtype=dt)
-            setattr(bufs, n, arrays[n].ctypes.data)
+            if n != VARIANCE:
+                setattr(bufs, n, arrays[n].ctypes.data)
         st = Stats()
-        self._check(self._L.pbrs_render_tile_aovs(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
-                                                  C.addressof(st)), "pbrs_render_tile_aovs")
+        if VARIANCE in names:
+            self._check(self._L.pbrs_render_tile_aovs_var(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data,
+                                                          C.addressof(bufs), arrays[VARIANCE].ctypes.data, C.addressof(st)),
+                        "pbrs_render_tile_aovs_var")
+        else:
+            self._check(self._L.pbrs_render_tile_aovs(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data,
+                                                      C.addressof(bufs), C.addressof(st)), "pbrs_render_tile_aovs")
         return out, arrays, st.as_dict()
 
     def render_aovs_device(self, rgb_device_ptr, aov_device_ptrs, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0,
@@ -449,12 +498,30 @@ class Context:
         """render_device() plus first-hit AOVs into caller-owned device memory: `aov_device_ptrs` = {name: pointer} (e.g.
         tensor.data_ptr(); sizes as render_aovs returns them).  Asynchronous like render_device: valid after `collect_stats()`."""
         _aov_names(aov_device_ptrs)
+        if VARIANCE in aov_device_ptrs:
+            ptrs = dict(aov_device_ptrs)
+            return self.render_aovs_var_device(rgb_device_ptr, ptrs, ptrs.pop(VARIANCE), strata_x, strata_y, depth, seed, tile,
+                                               samples_per_pass, counters, timing, bands, integrator)
         p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
         bufs = AovBuffers()
         for n, ptr in aov_device_ptrs.items():
             setattr(bufs, n, ptr)
         self._check(self._L.pbrs_render_tile_aovs_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
                                                          C.addressof(bufs), None), "pbrs_render_tile_aovs_device")
+
+    def render_aovs_var_device(self, rgb_device_ptr, aov_device_ptrs, variance_device_ptr, strata_x, strata_y, depth, seed, tile=None,
+                               samples_per_pass=0, counters=False, timing=False, bands=None, integrator="path"):
+        """render_aovs_device() plus the variance AOV into `variance_device_ptr` (w * h f32; pbrs_render_tile_aovs_var_device)."""
+        unknown = [n for n in aov_device_ptrs if n not in AOVS]
+        if unknown:
+            raise ValueError(f"unknown AOV name(s) {unknown}; known: {sorted(AOVS)}")
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
+        bufs = AovBuffers()
+        for n, ptr in aov_device_ptrs.items():
+            setattr(bufs, n, ptr)
+        self._check(self._L.pbrs_render_tile_aovs_var_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
+                                                             C.addressof(bufs), C.c_void_p(variance_device_ptr), None),
+                    "pbrs_render_tile_aovs_var_device")
 
     def render_filtered(self, pixel_filter, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0, counters=False, timing=False,
                         integrator="path"):
@@ -534,6 +601,83 @@ class Context:
             self.render_aovs_device(dev["rgb"].value, gp, strata_x, strata_y, depth, seed, samples_per_pass=samples_per_pass,
                                     integrator=integrator)
             self.denoise_device(dev["rgb"].value, dev["out"].value, w, h, gp, **params)
+            stats = self.collect_stats()  # waits for the stream
+            out = np.empty((h, w, 3), dtype=np.float32)
+            if hip.hipMemcpy(out.ctypes.data, dev["out"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
+                raise PbrsError("hipMemcpy of the denoised image failed")
+            if not keep_noisy:
+                return out, stats
+            noisy = np.empty_like(out)
+            if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
+                raise PbrsError("hipMemcpy of the plain image failed")
+            return out, noisy, stats
+        finally:
+            for ptr in dev.values():
+                hip.hipFree(ptr)
+
+    def denoise_var(self, rgb, variance, albedo=None, normal=None, depth=None, instance=None, return_variance=False, **params):
+        """The variance-guided a-trous denoiser (include/pbrs_gpu.h, pbrs_denoise_var) over an (h, w, 3) f32 image, its (h, w) f32
+        variance (render_aovs(..., aovs=(..., "variance"))) and the guides given -> (h, w, 3) f32; with return_variance also the
+        filtered variance: (denoised, variance_out).  params: DenoiseVarParams.make's keywords, flags by default as denoise()."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        h, w, _ = rgb.shape
+        given = {"albedo": albedo, "normal": normal, "depth": depth, "instance": instance, VARIANCE: variance}
+        p = DenoiseVarParams.for_guides(w, h, albedo is not None, instance is not None, **params)
+        g, keep = DenoiseVarGuides(), []
+        for n, a in given.items():
+            if a is None:
+                continue
+            ch, dt = DENOISE_GUIDES.get(n, (1, np.float32))
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != ((h, w, ch) if ch > 1 else (h, w)):
+                raise ValueError(f"{n} guide of shape {a.shape} beside an image of {rgb.shape}")
+            keep.append(a)
+            setattr(g, n, a.ctypes.data)
+        out = np.empty_like(rgb)
+        vout = np.empty((h, w), dtype=np.float32) if return_variance else None
+        self._check(self._L.pbrs_denoise_var(self._h, C.addressof(p), rgb.ctypes.data, C.addressof(g), out.ctypes.data,
+                                             vout.ctypes.data if return_variance else None), "pbrs_denoise_var")
+        return (out, vout) if return_variance else out
+
+    def denoise_var_device(self, rgb_in_device_ptr, rgb_out_device_ptr, w, h, variance_device_ptr, guide_device_ptrs=None,
+                           variance_out_device_ptr=None, **params):
+        """denoise_var() on caller-owned device memory, asynchronous on the context's stream like denoise_device.  The output pointers
+        may be the inputs'."""
+        ptrs = dict(guide_device_ptrs or {})
+        unknown = [n for n in ptrs if n not in DENOISE_GUIDES]
+        if unknown:
+            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
+        p = DenoiseVarParams.for_guides(w, h, bool(ptrs.get("albedo")), bool(ptrs.get("instance")), **params)
+        g = DenoiseVarGuides()
+        for n, ptr in ptrs.items():
+            setattr(g, n, ptr)
+        g.variance = variance_device_ptr
+        self._check(self._L.pbrs_denoise_var_device(self._h, C.addressof(p), C.c_void_p(rgb_in_device_ptr), C.addressof(g),
+                                                    C.c_void_p(rgb_out_device_ptr), C.c_void_p(variance_out_device_ptr)),
+                    "pbrs_denoise_var_device")
+
+    def render_denoised_var(self, strata_x, strata_y, depth, seed, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                            integrator="path", keep_noisy=False, **params):
+        """render_denoised() through the variance AOV and the variance-guided denoiser (render_aovs_var_device, then denoise_var_device
+        on the same stream, no synchronisation in between), copied back once -> (denoised, stats) or (denoised, noisy, stats)."""
+        unknown = [n for n in guides if n not in DENOISE_GUIDES]
+        if unknown:
+            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
+        w, h = self.scene.width, self.scene.height
+        hip = hip_runtime()
+        n_rgb = 3 * w * h * 4
+        sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
+        dev = {}
+        try:
+            for n, nbytes in sizes.items():
+                ptr = C.c_void_p()
+                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
+                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_denoised_var failed")
+                dev[n] = ptr
+            gp = {n: dev[n].value for n in guides}
+            self.render_aovs_var_device(dev["rgb"].value, gp, dev[VARIANCE].value, strata_x, strata_y, depth, seed,
+                                        samples_per_pass=samples_per_pass, integrator=integrator)
+            self.denoise_var_device(dev["rgb"].value, dev["out"].value, w, h, dev[VARIANCE].value, gp, **params)
             stats = self.collect_stats()  # waits for the stream
             out = np.empty((h, w, 3), dtype=np.float32)
             if hip.hipMemcpy(out.ctypes.data, dev["out"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost

@@ -25,6 +25,8 @@
 #include "device/aov.h"
 #include "device/film.h"
 #include "device/denoise.h"
+#include "device/denoise_var.h"
+#include "device/moments.h"
 
 namespace {
 
@@ -242,6 +244,15 @@ struct pbrs_ctx {
     size_t cap_denoise_pixels = 0, cap_denoise_stage_pixels = 0;
     void* denoise_mem = nullptr;
     void* denoise_stage = nullptr;  // kDenoiseStageWords * cap_denoise_stage_pixels
+    // variance AOV (pbrs_render_tile_aovs_var*, device/moments.h): the per-pixel moments k_moments folds every pass into, and the host
+    // variant's staging for the finished buffer
+    size_t cap_moment_pixels = 0, cap_variance_out_pixels = 0;
+    float* moment_state = nullptr;  // PBRS_MOMENT_STATE_WORDS * cap_moment_pixels, planar
+    float* variance_out = nullptr;  // cap_variance_out_pixels
+    // variance-guided denoiser (pbrs_denoise_var*, device/denoise_var.h): scratch and staging of its own, laid out like the plain one's
+    size_t cap_denoise_var_pixels = 0, cap_denoise_var_stage_pixels = 0;
+    void* denoise_var_mem = nullptr;
+    void* denoise_var_stage = nullptr;  // kDenoiseVarStageWords * cap_denoise_var_stage_pixels
 };
 
 namespace {
@@ -367,25 +378,29 @@ int ensure_work(pbrs_ctx* c, size_t n_slots, size_t n_pixels) {
     return PBRS_OK;
 }
 
+// A per-pixel buffer of a feature that allocates on first use, grown (not copied) to n_pixels: a failure leaves the context without
+// it (cap = 0), usable for every other call.
+int grow_pixels(pbrs_ctx* c, size_t n_pixels, void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) {
+    if (n_pixels <= cap) return PBRS_OK;
+    cap = 0;
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    const size_t total = n_pixels * bytes_per_pixel;
+    hipError_t e = hipMalloc(ptr, total);
+    if (e != hipSuccess) {
+        *ptr = nullptr;
+        c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
+        (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
+        return PBRS_E_DEVICE;
+    }
+    cap = n_pixels;
+    return PBRS_OK;
+}
+
 // The AOV state (and, with `staging`, the host variant's output buffers) for n_pixels, as ensure_work allocates: a failure leaves
 // the context without them (cap_aov_* = 0), usable for every other call.
 int ensure_aov(pbrs_ctx* c, size_t n_pixels, bool staging) {
-    auto grow = [&](void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) -> int {
-        if (n_pixels <= cap) return PBRS_OK;
-        cap = 0;
-        if (*ptr) (void)hipFree(*ptr);
-        *ptr = nullptr;
-        const size_t total = n_pixels * bytes_per_pixel;
-        hipError_t e = hipMalloc(ptr, total);
-        if (e != hipSuccess) {
-            *ptr = nullptr;
-            c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
-            (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
-            return PBRS_E_DEVICE;
-        }
-        cap = n_pixels;
-        return PBRS_OK;
-    };
+    auto grow = [&](void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) { return grow_pixels(c, n_pixels, ptr, cap, bytes_per_pixel, what); };
     int rc = grow(reinterpret_cast<void**>(&c->aov_state), c->cap_aov_pixels, PBRS_AOV_STATE_WORDS * sizeof(float), "the AOV state");
     if (rc || !staging) return rc;
     return grow(&c->aov_out, c->cap_aov_out_pixels, kAovOutWords * sizeof(uint32_t), "the AOV buffers");
@@ -415,25 +430,27 @@ constexpr size_t kDenoiseStageWords = 3 + 3 + 3 + 1 + 1;  // rgb, albedo, normal
 // The denoiser's scratch (and, with `staging`, the host variant's buffers) for n_pixels: grown like the AOV state; a failure leaves the
 // context without it, usable for every other call.
 int ensure_denoise(pbrs_ctx* c, size_t n_pixels, bool staging) {
-    auto grow = [&](void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) -> int {
-        if (n_pixels <= cap) return PBRS_OK;
-        cap = 0;
-        if (*ptr) (void)hipFree(*ptr);
-        *ptr = nullptr;
-        const size_t total = n_pixels * bytes_per_pixel;
-        hipError_t e = hipMalloc(ptr, total);
-        if (e != hipSuccess) {
-            *ptr = nullptr;
-            c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
-            (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
-            return PBRS_E_DEVICE;
-        }
-        cap = n_pixels;
-        return PBRS_OK;
-    };
-    int rc = grow(&c->denoise_mem, c->cap_denoise_pixels, kDenoiseBytesPerPixel, "the denoiser's scratch");
+    int rc = grow_pixels(c, n_pixels, &c->denoise_mem, c->cap_denoise_pixels, kDenoiseBytesPerPixel, "the denoiser's scratch");
     if (rc || !staging) return rc;
-    return grow(&c->denoise_stage, c->cap_denoise_stage_pixels, kDenoiseStageWords * sizeof(float), "the denoiser's staging");
+    return grow_pixels(c, n_pixels, &c->denoise_stage, c->cap_denoise_stage_pixels, kDenoiseStageWords * sizeof(float), "the denoiser's staging");
+}
+
+constexpr size_t kDenoiseVarStageWords = 3 + 3 + 3 + 1 + 1 + 1 + 1;  // rgb, albedo, normal, depth, instance, variance, variance_out
+
+// The same for the variance-guided denoiser, which keeps scratch of its own (the planes have the plain one's size).
+int ensure_denoise_var(pbrs_ctx* c, size_t n_pixels, bool staging) {
+    int rc = grow_pixels(c, n_pixels, &c->denoise_var_mem, c->cap_denoise_var_pixels, kDenoiseBytesPerPixel, "the variance-guided denoiser's scratch");
+    if (rc || !staging) return rc;
+    return grow_pixels(c, n_pixels, &c->denoise_var_stage, c->cap_denoise_var_stage_pixels, kDenoiseVarStageWords * sizeof(float),
+                       "the variance-guided denoiser's staging");
+}
+
+// The moment state of the variance AOV (and, with `staging`, the host variant's output buffer) for n_pixels.
+int ensure_moments(pbrs_ctx* c, size_t n_pixels, bool staging) {
+    int rc = grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->moment_state), c->cap_moment_pixels, PBRS_MOMENT_STATE_WORDS * sizeof(float),
+                         "the variance AOV's moments");
+    if (rc || !staging) return rc;
+    return grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->variance_out), c->cap_variance_out_pixels, sizeof(float), "the variance buffer");
 }
 
 void free_aov(pbrs_ctx* c) {
@@ -787,8 +804,9 @@ void poll_split_probe(pbrs_ctx* c) {
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
 // `aov`: the AOV state k_aov folds this pass's first hits into (null: no AOVs).
 // `filt`: a filtered render (rc is its traced region): k_filter_accumulate folds the pass into pbrs_ctx::filter_sum instead of k_accumulate.
+// `moments`: the moment state of the variance AOV k_moments folds this pass's radiances into (null: no variance).
 int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false, float* aov = nullptr,
-             const FilterConst* filt = nullptr) {
+             const FilterConst* filt = nullptr, float* moments = nullptr) {
     pbrs_ctx::PassSet& set = c->pass_set[c->cur_set];
     // the set's memory is free once the pass that used it last has accumulated (two passes back, on the late stream)
     if (handoff && set.in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, set.accumulated, 0));
@@ -907,6 +925,8 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
                            dim3(kBlock), filter_lds_bytes(filt->hx, filt->hy), c->stream, c->st, c->filter_sum, rc, *filt, kc, c->nonfinite);
     else
         hipLaunchKernelGGL(k_accumulate, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, c->sum, P, kc, rc.chunk_pixels, rc.w, rc.tiles8_per_row, c->nonfinite);
+    // the variance AOV: the same radiances, on the stream that runs the passes' accumulations in pass order
+    if (moments) hipLaunchKernelGGL(k_moments, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, moments, P, kc, rc.chunk_pixels);
     tm.end();
     if (handoff) {
         HIPCHK(c, hipEventRecord(set.accumulated, c->stream));
@@ -919,8 +939,9 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
 // `aovs` (device pointers; null or all-null: none): the first-hit AOVs too, from the state ensure_aov allocated.
 // `filt`: a filtered render; `p` is then its traced region (check_filter) and rgb_device receives the tile's filt->w x filt->h pixels,
 // from the sums ensure_filter allocated.
+// `variance` (device pointer; null: none): the variance AOV too, from the state ensure_moments allocated.
 int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device, const pbrs_aov_buffers* aovs = nullptr,
-                  const FilterConst* filt = nullptr) {
+                  const FilterConst* filt = nullptr, float* variance = nullptr) {
     HIPCHK(c, hipSetDevice(c->device));  // before check_params: the automatic pass size reads THIS device's free memory
     int rcode = check_params(c, cam, p);
     if (rcode) return rcode;
@@ -945,6 +966,8 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     else HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
     float* aov = any_aov(aovs) ? c->aov_state : nullptr;
     if (aov) HIPCHK(c, hipMemsetAsync(aov, 0, PBRS_AOV_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
+    float* moments = variance ? c->moment_state : nullptr;
+    if (moments) HIPCHK(c, hipMemsetAsync(moments, 0, PBRS_MOMENT_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     uint32_t passes = 0;
     // Where the render has more than one pass, passes alternate between the two pass sets and hand their late bounces to the second
     // stream: those are near-empty launches that end with the latency of their longest walks (C4: 47 ms per frame in kernels that leave
@@ -963,7 +986,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     for (uint32_t first = 0; first < spp; first += K) {
         uint32_t kc = spp - first < K ? spp - first : K;
         if (two) use_pass_set(c, (int)(passes & 1u));  // (also: back to the main stream)
-        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov, filt);
+        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov, filt, moments);
         if (rcode) {
             use_pass_set(c, 0);
             return rcode;
@@ -984,6 +1007,8 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (aov)
         hipLaunchKernelGGL(k_aov_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, aov, c->S.inst, P, rc.w, rc.tiles8_per_row,
                            1.0f / (float)spp, *aovs);
+    if (moments)
+        hipLaunchKernelGGL(k_moments_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, moments, P, rc.w, rc.tiles8_per_row, variance);
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending.passes = passes;
@@ -1145,6 +1170,10 @@ void pbrs_destroy(pbrs_ctx* c) {
     if (c->filter_sum) (void)hipFree(c->filter_sum);
     if (c->denoise_mem) (void)hipFree(c->denoise_mem);
     if (c->denoise_stage) (void)hipFree(c->denoise_stage);
+    if (c->moment_state) (void)hipFree(c->moment_state);
+    if (c->variance_out) (void)hipFree(c->variance_out);
+    if (c->denoise_var_mem) (void)hipFree(c->denoise_var_mem);
+    if (c->denoise_var_stage) (void)hipFree(c->denoise_var_stage);
     if (c->counters) (void)hipFree(c->counters);
     if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
     for (int k = 0; k < 2; ++k)
@@ -1560,38 +1589,47 @@ int pbrs_render_tile(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
 }
 
 // The checks of the AOV entry points beyond render_common's: a render that traces no camera ray has no first hits to report.
-int check_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_aov_buffers* aovs) {
+// `variance`: the variance AOV is requested too (pbrs_render_tile_aovs_var*).
+int check_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_aov_buffers* aovs, bool variance = false) {
     int rc = check_params(c, cam, p);
-    if (rc || !any_aov(aovs)) return rc;
+    if (rc || !(any_aov(aovs) || variance)) return rc;
     if (p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0)
         return fail(c, PBRS_E_INVALID, "AOVs requested from a render that traces no camera ray (max_depth 0)");
     // before render_common's pass size reads the free memory
-    return ensure_aov(c, (size_t)p->w * p->h, false);
+    if (any_aov(aovs)) rc = ensure_aov(c, (size_t)p->w * p->h, false);
+    if (!rc && variance) rc = ensure_moments(c, (size_t)p->w * p->h, false);
+    return rc;
 }
 
-int pbrs_render_tile_aovs_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, const pbrs_aov_buffers* aovs_device,
-                                 pbrs_stats* stats_out) {
+int pbrs_render_tile_aovs_var_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
+                                     const pbrs_aov_buffers* aovs_device, float* variance_device, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_aovs(c, cam, p, aovs_device);
+    int rc = check_aovs(c, cam, p, aovs_device, variance_device != nullptr);
     if (rc) return rc;
-    rc = render_common(c, cam, p, rgb_out_device, aovs_device);
+    rc = render_common(c, cam, p, rgb_out_device, aovs_device, nullptr, variance_device);
     if (rc) return rc;
     if (stats_out) return collect(c, stats_out);
     return PBRS_OK;
 }
 
-int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
-                          pbrs_stats* stats_out) {
+int pbrs_render_tile_aovs_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, const pbrs_aov_buffers* aovs_device,
+                                 pbrs_stats* stats_out) {
+    return pbrs_render_tile_aovs_var_device(c, cam, p, rgb_out_device, aovs_device, nullptr, stats_out);
+}
+
+int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                              float* variance_host, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_aovs(c, cam, p, aovs_host);
+    int rc = check_aovs(c, cam, p, aovs_host, variance_host != nullptr);
     if (rc) return rc;
     const size_t P = (size_t)p->w * p->h;
     const bool want = any_aov(aovs_host);
     if (want) rc = ensure_aov(c, P, true);
+    if (!rc && variance_host) rc = ensure_moments(c, P, true);
     if (rc) return rc;
     rc = ensure_work(c, P * auto_samples_per_pass(c, p), P);
     if (rc) return rc;
@@ -1607,9 +1645,10 @@ int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render
         dev.material = aovs_host->material ? reinterpret_cast<uint32_t*>(f + 9 * P) : nullptr;
         dev.prim = aovs_host->prim ? reinterpret_cast<uint32_t*>(f + 10 * P) : nullptr;
     }
-    rc = render_common(c, cam, p, c->rgb_dev, want ? &dev : nullptr);
+    rc = render_common(c, cam, p, c->rgb_dev, want ? &dev : nullptr, nullptr, variance_host ? c->variance_out : nullptr);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (variance_host) HIPCHK(c, hipMemcpyAsync(variance_host, c->variance_out, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (want) {
         const void* src[7] = {dev.albedo, dev.normal, dev.coverage, dev.depth, dev.instance, dev.material, dev.prim};
         void* dst[7] = {aovs_host->albedo, aovs_host->normal, aovs_host->coverage, aovs_host->depth, aovs_host->instance, aovs_host->material, aovs_host->prim};
@@ -1618,6 +1657,11 @@ int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render
             if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], src[k], words[k] * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     return collect(c, stats_out);
+}
+
+int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                          pbrs_stats* stats_out) {
+    return pbrs_render_tile_aovs_var(c, cam, p, rgb_out_host, aovs_host, nullptr, stats_out);
 }
 
 // The checks of the filtered entry points beyond render_common's; fills the kernel's constants and `region`, the tile plus its
@@ -1777,6 +1821,100 @@ int pbrs_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_
     rc = denoise_launch(c, p, rgb, &dev, rgb);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
+}
+
+// ---- variance-guided denoiser (include/pbrs_gpu.h, device/denoise_var.h) ----
+static_assert(sizeof(pbrs_denoise_var_params) == 32, "pbrs_denoise_var_params is 32 B");
+
+namespace {
+
+using DenoiseVarKernel = void (*)(const float4*, const float4*, const uint32_t*, float4*, DenoiseVarConst);
+// [id stop][iteration]
+constexpr DenoiseVarKernel kDenoiseVarAtrous[2][PBRS_DENOISE_MAX_ITERATIONS] = {
+    {k_denoise_var_atrous<0, false>, k_denoise_var_atrous<1, false>, k_denoise_var_atrous<2, false>, k_denoise_var_atrous<3, false>,
+     k_denoise_var_atrous<4, false>, k_denoise_var_atrous<5, false>},
+    {k_denoise_var_atrous<0, true>, k_denoise_var_atrous<1, true>, k_denoise_var_atrous<2, true>, k_denoise_var_atrous<3, true>,
+     k_denoise_var_atrous<4, true>, k_denoise_var_atrous<5, true>}};
+
+int check_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, const float* rgb_out) {
+    if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
+    if (!g->variance) return fail(c, PBRS_E_INVALID, "the variance-guided denoiser needs guides.variance");
+    // the rest is the plain denoiser's list, sigma_luminance in the place of sigma_color
+    const pbrs_denoise_params q{p->w, p->h, p->iterations, p->flags, p->sigma_luminance, p->sigma_normal, p->sigma_depth, p->albedo_floor};
+    const pbrs_denoise_guides gq{g->albedo, g->normal, g->depth, g->instance};
+    return check_denoise(c, &q, rgb_in, &gq, rgb_out);
+}
+
+// The launches of one variance-guided denoise on the context's stream (arguments checked, scratch there).
+int denoise_var_launch(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, float* rgb_out,
+                       float* variance_out) {
+    const uint32_t P = p->w * p->h;
+    const size_t cap = c->cap_denoise_var_pixels;
+    float4* plane[2] = {static_cast<float4*>(c->denoise_var_mem), static_cast<float4*>(c->denoise_var_mem) + cap};
+    float4* guide = plane[1] + cap;
+    uint32_t* ids = reinterpret_cast<uint32_t*>(guide + cap);
+    const uint32_t demod = p->flags & PBRS_DENOISE_DEMODULATE;
+    const bool id_stop = (p->flags & PBRS_DENOISE_ID_STOP) != 0;
+    pbrs_denoise_var_guides packed = *g;
+    if (!id_stop) packed.instance = nullptr;
+    const dim3 lin((P + kBlock - 1) / kBlock), cells((p->w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p->h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
+    hipLaunchKernelGGL(k_denoise_var_pack, lin, dim3(kBlock), 0, c->stream, rgb_in, packed, P, demod, p->albedo_floor, plane[0], guide, ids);
+    DenoiseVarConst k{};
+    k.w = p->w, k.h = p->h;
+    k.sl = p->sigma_luminance;
+    k.in = 1.0f / (p->sigma_normal * p->sigma_normal);
+    k.id = 1.0f / (p->sigma_depth * p->sigma_depth);
+    for (uint32_t it = 0; it < p->iterations; ++it)
+        hipLaunchKernelGGL(kDenoiseVarAtrous[id_stop ? 1 : 0][it], cells, dim3(kBlock), 0, c->stream, plane[it & 1u], guide, ids, plane[(it + 1u) & 1u], k);
+    hipLaunchKernelGGL(k_denoise_var_unpack, lin, dim3(kBlock), 0, c->stream, plane[p->iterations & 1u], g->albedo, P, demod, p->albedo_floor, rgb_out,
+                       variance_out);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_denoise_var_device(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in_device, const pbrs_denoise_var_guides* guides_device,
+                            float* rgb_out_device, float* variance_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_denoise_var(c, p, rgb_in_device, guides_device, rgb_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_denoise_var(c, (size_t)p->w * p->h, false);
+    if (rc) return rc;
+    return denoise_var_launch(c, p, rgb_in_device, guides_device, rgb_out_device, variance_out_device);
+}
+
+int pbrs_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in_host, const pbrs_denoise_var_guides* guides_host,
+                     float* rgb_out_host, float* variance_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_denoise_var(c, p, rgb_in_host, guides_host, rgb_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)p->w * p->h;
+    rc = ensure_denoise_var(c, P, true);
+    if (rc) return rc;
+    // device staging: rgb (in and out), the given guides, the variance in and out
+    float* f = static_cast<float*>(c->denoise_var_stage);
+    float* rgb = f;
+    float* vout = variance_out_host ? f + 12 * P : nullptr;
+    pbrs_denoise_var_guides dev{};
+    dev.albedo = guides_host->albedo ? f + 3 * P : nullptr;
+    dev.normal = guides_host->normal ? f + 6 * P : nullptr;
+    dev.depth = guides_host->depth ? f + 9 * P : nullptr;
+    dev.instance = guides_host->instance ? reinterpret_cast<const uint32_t*>(f + 10 * P) : nullptr;
+    dev.variance = f + 11 * P;
+    const void* src[6] = {rgb_in_host, guides_host->albedo, guides_host->normal, guides_host->depth, guides_host->instance, guides_host->variance};
+    const void* dst[6] = {rgb, dev.albedo, dev.normal, dev.depth, dev.instance, dev.variance};
+    const size_t words[6] = {3, 3, 3, 1, 1, 1};
+    for (int k = 0; k < 6; ++k)
+        if (src[k]) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(dst[k]), src[k], words[k] * P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = denoise_var_launch(c, p, rgb, &dev, rgb, vout);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (vout) HIPCHK(c, hipMemcpyAsync(variance_out_host, vout, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -7,7 +7,11 @@
 per-pixel mean; the AOVs stay per-pixel means (a separate render of the same samples).
 --denoise: also writes <out>.denoised.<ext>, the image through the edge-avoiding a-trous denoiser (include/pbrs_gpu.h, pbrs_denoise)
 guided by the albedo, normal, depth and instance AOVs of the same samples; --denoise-iterations (default 5) and --denoise-sigma
-(colour, normal, depth) override Context.denoise's defaults."""
+(colour, normal, depth) override Context.denoise's defaults.
+--denoise-var: also writes <out>.denoised_var.<ext>, the image through the variance-guided denoiser (include/pbrs_gpu.h,
+pbrs_denoise_var) with the variance AOV of the same samples: no sigma depends on the units of the scene.  --denoise-sigma-luminance
+(default 4, in standard deviations) overrides Context.denoise_var's default; --denoise-iterations and the normal and depth sigmas of
+--denoise-sigma apply to it too."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -16,17 +20,21 @@ import pbrs_amd
 aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
 denoise = "--denoise" in sys.argv
-denoise_params = {}
-for flag in ("--denoise-iterations", "--denoise-sigma"):
+denoise_var = "--denoise-var" in sys.argv
+denoise_params, denoise_var_params = {}, {}
+for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
         del sys.argv[k:k + 2]
         if flag == "--denoise-iterations":
-            denoise_params["iterations"] = int(value)
+            denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
+        elif flag == "--denoise-sigma-luminance":
+            denoise_var_params["sigma_luminance"] = float(value)
         else:
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
-sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise")]
+            denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var")]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -36,22 +44,26 @@ ctx = pbrs_amd.Context(0)
 ctx.upload(pbrs_amd.HostScene(ls))
 if integrator in ("materials", "normals"):  # --visualize-materials / --visualize-normals (src/main.rs:180-185): one ray per pixel
     msaa = 1
-want = ("albedo", "normal", "depth") + (("instance",) if denoise else ())
+guides = ("albedo", "normal", "depth") + (("instance",) if denoise or denoise_var else ())
+want = guides + (("variance",) if denoise_var else ())
 if filtered:
     pf = ls.pixel_filter()
     img, st = ctx.render_filtered(pf, msaa, msaa, depth, 1, integrator=integrator, timing=True)
     print(f"pixel filter: {pf}")
-    if aovs or denoise:
+    if aovs or denoise or denoise_var:
         _, buf, _ = ctx.render_aovs(msaa, msaa, depth, 1, aovs=want, integrator=integrator)
-elif aovs or denoise:
+elif aovs or denoise or denoise_var:
     img, buf, st = ctx.render_aovs(msaa, msaa, depth, 1, aovs=want, integrator=integrator, timing=True)
 else:
     img, st = ctx.render(msaa, msaa, depth, 1, integrator=integrator, timing=True)
 pbrs_amd.write_image(out, img)
 stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
 if denoise:
-    pbrs_amd.write_image(f"{stem}.denoised{ext}", ctx.denoise(img, **{n: buf[n] for n in want}, **denoise_params))
+    pbrs_amd.write_image(f"{stem}.denoised{ext}", ctx.denoise(img, **{n: buf[n] for n in guides}, **denoise_params))
     print(f"-> {stem}.denoised{ext}")
+if denoise_var:
+    pbrs_amd.write_image(f"{stem}.denoised_var{ext}", ctx.denoise_var(img, buf["variance"], **{n: buf[n] for n in guides}, **denoise_var_params))
+    print(f"-> {stem}.denoised_var{ext}")
 if aovs:
     for name in ("albedo", "normal", "depth"):
         a = buf[name] if buf[name].ndim == 3 else np.repeat(buf[name][:, :, None], 3, axis=2)
