@@ -133,21 +133,19 @@ class PixelFilter(C.Structure):
         return f"PixelFilter({k}, radius=({self.radius[0]}, {self.radius[1]}), a={self.a}, b={self.b})"
 
 
-class DenoiseParams(C.Structure):
-    """pbrs_denoise_params (include/pbrs_gpu.h): image size, iterations, flags, the three sigmas and the albedo floor.  `make` carries
-    the defaults (DESIGN.md §4, "Denoiser": chosen from the measured error ratios)."""
+class _DenoiseParamsMixin:
+    """What DenoiseParams and DenoiseVarParams share: the flag bits, the defaults that follow the guides, as_dict."""
     DEMODULATE, ID_STOP = 1, 2
     MAX_ITERATIONS = 6
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float),
-                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
 
     @classmethod
-    def make(cls, w, h, iterations=5, sigma_color=16.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
-             id_stop=False):
+    def _make(cls, w, h, iterations, sigmas, albedo_floor, demodulate, id_stop):
         p = cls()
         p.w, p.h, p.iterations = w, h, iterations
         p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
-        p.sigma_color, p.sigma_normal, p.sigma_depth, p.albedo_floor = sigma_color, sigma_normal, sigma_depth, albedo_floor
+        for (n, _), v in zip(cls._fields_[4:7], sigmas):
+            setattr(p, n, v)
+        p.albedo_floor = albedo_floor
         return p
 
     @classmethod
@@ -161,37 +159,33 @@ class DenoiseParams(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DenoiseParams(_DenoiseParamsMixin, C.Structure):
+    """pbrs_denoise_params (include/pbrs_gpu.h): image size, iterations, flags, the three sigmas and the albedo floor.  `make` carries
+    the defaults (DESIGN.md §4, "Denoiser": chosen from the measured error ratios)."""
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
+
+    @classmethod
+    def make(cls, w, h, iterations=5, sigma_color=16.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
+             id_stop=False):
+        return cls._make(w, h, iterations, (sigma_color, sigma_normal, sigma_depth), albedo_floor, demodulate, id_stop)
+
+
 class DenoiseGuides(C.Structure):
     """pbrs_denoise_guides: the AOV layouts, NULL = that stop is off."""
     _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance")]
 
 
-class DenoiseVarParams(C.Structure):
+class DenoiseVarParams(_DenoiseParamsMixin, C.Structure):
     """pbrs_denoise_var_params (include/pbrs_gpu.h): DenoiseParams with sigma_luminance, a count of standard deviations (SVGF's 4),
     in the place of sigma_color."""
-    DEMODULATE, ID_STOP = DenoiseParams.DEMODULATE, DenoiseParams.ID_STOP
-    MAX_ITERATIONS = DenoiseParams.MAX_ITERATIONS
     _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_luminance", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
 
     @classmethod
     def make(cls, w, h, iterations=5, sigma_luminance=4.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
              id_stop=False):
-        p = cls()
-        p.w, p.h, p.iterations = w, h, iterations
-        p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
-        p.sigma_luminance, p.sigma_normal, p.sigma_depth, p.albedo_floor = sigma_luminance, sigma_normal, sigma_depth, albedo_floor
-        return p
-
-    @classmethod
-    def for_guides(cls, w, h, albedo=False, instance=False, **params):
-        """The defaults for the guides at hand, as DenoiseParams.for_guides."""
-        params.setdefault("demodulate", bool(albedo))
-        params.setdefault("id_stop", bool(instance))
-        return cls.make(w, h, **params)
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
+        return cls._make(w, h, iterations, (sigma_luminance, sigma_normal, sigma_depth), albedo_floor, demodulate, id_stop)
 
 
 class DenoiseVarGuides(C.Structure):
@@ -541,24 +535,44 @@ class Context:
         self._check(self._L.pbrs_render_tile_filtered_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.byref(pixel_filter),
                                                              C.c_void_p(rgb_device_ptr), None), "pbrs_render_tile_filtered_device")
 
+    @staticmethod
+    def _denoise_guide_names(names):
+        unknown = [n for n in names if n not in DENOISE_GUIDES]
+        if unknown:
+            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
+
+    @staticmethod
+    def _host_guides(g, rgb, given):
+        """Fills the guides struct `g` from the arrays of `given` that are there, checked against the image; returns the arrays to keep."""
+        h, w, _ = rgb.shape
+        keep = []
+        for n, a in given.items():
+            if a is None:
+                continue
+            ch, dt = DENOISE_GUIDES.get(n, (1, np.float32))  # (the variance)
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != ((h, w, ch) if ch > 1 else (h, w)):
+                raise ValueError(f"{n} guide of shape {a.shape} beside an image of {rgb.shape}")
+            keep.append(a)
+            setattr(g, n, a.ctypes.data)
+        return keep
+
+    def _device_guides(self, g, guide_device_ptrs):
+        ptrs = dict(guide_device_ptrs or {})
+        self._denoise_guide_names(ptrs)
+        for n, ptr in ptrs.items():
+            setattr(g, n, ptr)
+        return ptrs
+
     def denoise(self, rgb, albedo=None, normal=None, depth=None, instance=None, **params):
         """The edge-avoiding a-trous denoiser (include/pbrs_gpu.h, pbrs_denoise) over an (h, w, 3) f32 image and the guides given
         (arrays as render_aovs returns them; None = that stop is off) -> (h, w, 3) f32.  params: DenoiseParams.make's keywords; by
         default the image is demodulated when there is an albedo and taps stop at instance edges when there are ids."""
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
         h, w, _ = rgb.shape
-        given = {"albedo": albedo, "normal": normal, "depth": depth, "instance": instance}
         p = DenoiseParams.for_guides(w, h, albedo is not None, instance is not None, **params)
-        g, keep = DenoiseGuides(), []
-        for n, a in given.items():
-            if a is None:
-                continue
-            ch, dt = DENOISE_GUIDES[n]
-            a = np.ascontiguousarray(a, dtype=dt)
-            if a.shape != ((h, w, ch) if ch > 1 else (h, w)):
-                raise ValueError(f"{n} guide of shape {a.shape} beside an image of {rgb.shape}")
-            keep.append(a)
-            setattr(g, n, a.ctypes.data)
+        g = DenoiseGuides()
+        keep = self._host_guides(g, rgb, {"albedo": albedo, "normal": normal, "depth": depth, "instance": instance})  # noqa: F841
         out = np.empty_like(rgb)
         self._check(self._L.pbrs_denoise(self._h, C.addressof(p), rgb.ctypes.data, C.addressof(g), out.ctypes.data), "pbrs_denoise")
         return out
@@ -567,40 +581,37 @@ class Context:
         """denoise() on caller-owned device memory: `guide_device_ptrs` = {name: pointer} of albedo / normal / depth / instance.  Runs on
         the context's stream behind whatever was queued there (a render_aovs_device needs no synchronisation in between) and does not
         wait: valid after `collect_stats()`.  The output pointer may be the input's."""
-        ptrs = dict(guide_device_ptrs or {})
-        unknown = [n for n in ptrs if n not in DENOISE_GUIDES]
-        if unknown:
-            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
-        p = DenoiseParams.for_guides(w, h, bool(ptrs.get("albedo")), bool(ptrs.get("instance")), **params)
         g = DenoiseGuides()
-        for n, ptr in ptrs.items():
-            setattr(g, n, ptr)
+        ptrs = self._device_guides(g, guide_device_ptrs)
+        p = DenoiseParams.for_guides(w, h, bool(ptrs.get("albedo")), bool(ptrs.get("instance")), **params)
         self._check(self._L.pbrs_denoise_device(self._h, C.addressof(p), C.c_void_p(rgb_in_device_ptr), C.addressof(g),
                                                 C.c_void_p(rgb_out_device_ptr)), "pbrs_denoise_device")
 
-    def render_denoised(self, strata_x, strata_y, depth, seed, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                        integrator="path", keep_noisy=False, **params):
-        """The whole frame rendered with its guides and denoised in device memory (render_aovs_device, then denoise_device on the same
-        stream, no synchronisation in between), copied back once -> (h, w, 3) f32 denoised radiance, stats dict; with keep_noisy the
-        plain image comes too: (denoised, noisy, stats)."""
-        unknown = [n for n in guides if n not in DENOISE_GUIDES]
-        if unknown:
-            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
+    def _render_denoised(self, name, with_variance, strata_x, strata_y, depth, seed, guides, samples_per_pass, integrator, keep_noisy, params):
+        """render_denoised / render_denoised_var: the frame's device buffers (with_variance: and the variance's), the render with its
+        guides, the denoise behind it on the same stream, one copy back."""
+        self._denoise_guide_names(guides)
         w, h = self.scene.width, self.scene.height
         hip = hip_runtime()
         n_rgb = 3 * w * h * 4
-        sizes = {"rgb": n_rgb, "out": n_rgb, **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
+        sizes = {"rgb": n_rgb, "out": n_rgb, **({VARIANCE: w * h * 4} if with_variance else {}),
+                 **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
         dev = {}
         try:
             for n, nbytes in sizes.items():
                 ptr = C.c_void_p()
                 if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_denoised failed")
+                    raise PbrsError(f"hipMalloc of {nbytes} bytes for {name} failed")
                 dev[n] = ptr
             gp = {n: dev[n].value for n in guides}
-            self.render_aovs_device(dev["rgb"].value, gp, strata_x, strata_y, depth, seed, samples_per_pass=samples_per_pass,
-                                    integrator=integrator)
-            self.denoise_device(dev["rgb"].value, dev["out"].value, w, h, gp, **params)
+            if with_variance:
+                self.render_aovs_var_device(dev["rgb"].value, gp, dev[VARIANCE].value, strata_x, strata_y, depth, seed,
+                                            samples_per_pass=samples_per_pass, integrator=integrator)
+                self.denoise_var_device(dev["rgb"].value, dev["out"].value, w, h, dev[VARIANCE].value, gp, **params)
+            else:
+                self.render_aovs_device(dev["rgb"].value, gp, strata_x, strata_y, depth, seed, samples_per_pass=samples_per_pass,
+                                        integrator=integrator)
+                self.denoise_device(dev["rgb"].value, dev["out"].value, w, h, gp, **params)
             stats = self.collect_stats()  # waits for the stream
             out = np.empty((h, w, 3), dtype=np.float32)
             if hip.hipMemcpy(out.ctypes.data, dev["out"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
@@ -615,24 +626,24 @@ class Context:
             for ptr in dev.values():
                 hip.hipFree(ptr)
 
+    def render_denoised(self, strata_x, strata_y, depth, seed, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                        integrator="path", keep_noisy=False, **params):
+        """The whole frame rendered with its guides and denoised in device memory (render_aovs_device, then denoise_device on the same
+        stream, no synchronisation in between), copied back once -> (h, w, 3) f32 denoised radiance, stats dict; with keep_noisy the
+        plain image comes too: (denoised, noisy, stats)."""
+        return self._render_denoised("render_denoised", False, strata_x, strata_y, depth, seed, guides, samples_per_pass, integrator,
+                                     keep_noisy, params)
+
     def denoise_var(self, rgb, variance, albedo=None, normal=None, depth=None, instance=None, return_variance=False, **params):
         """The variance-guided a-trous denoiser (include/pbrs_gpu.h, pbrs_denoise_var) over an (h, w, 3) f32 image, its (h, w) f32
         variance (render_aovs(..., aovs=(..., "variance"))) and the guides given -> (h, w, 3) f32; with return_variance also the
         filtered variance: (denoised, variance_out).  params: DenoiseVarParams.make's keywords, flags by default as denoise()."""
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
         h, w, _ = rgb.shape
-        given = {"albedo": albedo, "normal": normal, "depth": depth, "instance": instance, VARIANCE: variance}
         p = DenoiseVarParams.for_guides(w, h, albedo is not None, instance is not None, **params)
-        g, keep = DenoiseVarGuides(), []
-        for n, a in given.items():
-            if a is None:
-                continue
-            ch, dt = DENOISE_GUIDES.get(n, (1, np.float32))
-            a = np.ascontiguousarray(a, dtype=dt)
-            if a.shape != ((h, w, ch) if ch > 1 else (h, w)):
-                raise ValueError(f"{n} guide of shape {a.shape} beside an image of {rgb.shape}")
-            keep.append(a)
-            setattr(g, n, a.ctypes.data)
+        g = DenoiseVarGuides()
+        keep = self._host_guides(g, rgb, {"albedo": albedo, "normal": normal, "depth": depth, "instance": instance,  # noqa: F841
+                                          VARIANCE: variance})
         out = np.empty_like(rgb)
         vout = np.empty((h, w), dtype=np.float32) if return_variance else None
         self._check(self._L.pbrs_denoise_var(self._h, C.addressof(p), rgb.ctypes.data, C.addressof(g), out.ctypes.data,
@@ -643,14 +654,9 @@ class Context:
                            variance_out_device_ptr=None, **params):
         """denoise_var() on caller-owned device memory, asynchronous on the context's stream like denoise_device.  The output pointers
         may be the inputs'."""
-        ptrs = dict(guide_device_ptrs or {})
-        unknown = [n for n in ptrs if n not in DENOISE_GUIDES]
-        if unknown:
-            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
-        p = DenoiseVarParams.for_guides(w, h, bool(ptrs.get("albedo")), bool(ptrs.get("instance")), **params)
         g = DenoiseVarGuides()
-        for n, ptr in ptrs.items():
-            setattr(g, n, ptr)
+        ptrs = self._device_guides(g, guide_device_ptrs)
+        p = DenoiseVarParams.for_guides(w, h, bool(ptrs.get("albedo")), bool(ptrs.get("instance")), **params)
         g.variance = variance_device_ptr
         self._check(self._L.pbrs_denoise_var_device(self._h, C.addressof(p), C.c_void_p(rgb_in_device_ptr), C.addressof(g),
                                                     C.c_void_p(rgb_out_device_ptr), C.c_void_p(variance_out_device_ptr)),
@@ -660,37 +666,8 @@ class Context:
                             integrator="path", keep_noisy=False, **params):
         """render_denoised() through the variance AOV and the variance-guided denoiser (render_aovs_var_device, then denoise_var_device
         on the same stream, no synchronisation in between), copied back once -> (denoised, stats) or (denoised, noisy, stats)."""
-        unknown = [n for n in guides if n not in DENOISE_GUIDES]
-        if unknown:
-            raise ValueError(f"unknown denoise guide(s) {unknown}; known: {sorted(DENOISE_GUIDES)}")
-        w, h = self.scene.width, self.scene.height
-        hip = hip_runtime()
-        n_rgb = 3 * w * h * 4
-        sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
-        dev = {}
-        try:
-            for n, nbytes in sizes.items():
-                ptr = C.c_void_p()
-                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_denoised_var failed")
-                dev[n] = ptr
-            gp = {n: dev[n].value for n in guides}
-            self.render_aovs_var_device(dev["rgb"].value, gp, dev[VARIANCE].value, strata_x, strata_y, depth, seed,
-                                        samples_per_pass=samples_per_pass, integrator=integrator)
-            self.denoise_var_device(dev["rgb"].value, dev["out"].value, w, h, dev[VARIANCE].value, gp, **params)
-            stats = self.collect_stats()  # waits for the stream
-            out = np.empty((h, w, 3), dtype=np.float32)
-            if hip.hipMemcpy(out.ctypes.data, dev["out"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
-                raise PbrsError("hipMemcpy of the denoised image failed")
-            if not keep_noisy:
-                return out, stats
-            noisy = np.empty_like(out)
-            if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
-                raise PbrsError("hipMemcpy of the plain image failed")
-            return out, noisy, stats
-        finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+        return self._render_denoised("render_denoised_var", True, strata_x, strata_y, depth, seed, guides, samples_per_pass, integrator,
+                                     keep_noisy, params)
 
     def collect_stats(self):
         st = Stats()

@@ -25,7 +25,6 @@
 #include "device/aov.h"
 #include "device/film.h"
 #include "device/denoise.h"
-#include "device/denoise_var.h"
 #include "device/moments.h"
 
 namespace {
@@ -160,6 +159,15 @@ struct KernelPlan {
 
 }  // namespace
 
+// A denoiser's device memory, allocated by its first call: two ping-pong colour planes, the guide plane and the instance ids (16 + 16 + 16 +
+// 4 B per pixel, one allocation), and the host variant's staging (rgb, albedo, normal, depth, instance; variance-guided: and the variance
+// in and out).
+struct DenoiseScratch {
+    size_t cap_pixels = 0, cap_stage_pixels = 0;
+    void* mem = nullptr;
+    void* stage = nullptr;  // kDenoiseStageWords * cap_stage_pixels
+};
+
 struct pbrs_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -239,20 +247,14 @@ struct pbrs_ctx {
     // filtered film (pbrs_render_tile_filtered*, device/film.h): S.rgb and W of every tile pixel, planar
     size_t cap_filter_pixels = 0;
     float* filter_sum = nullptr;  // 4 * cap_filter_pixels
-    // denoiser (pbrs_denoise*, device/denoise.h), allocated by the first call: two ping-pong colour planes, the guide plane and the
-    // instance ids (16 + 16 + 16 + 4 B per pixel, one allocation), and the host variant's staging (rgb, albedo, normal, depth, instance)
-    size_t cap_denoise_pixels = 0, cap_denoise_stage_pixels = 0;
-    void* denoise_mem = nullptr;
-    void* denoise_stage = nullptr;  // kDenoiseStageWords * cap_denoise_stage_pixels
+    // denoisers (pbrs_denoise*, pbrs_denoise_var*, device/denoise.h): each keeps scratch and staging of its own, [0] the plain filter's, [1]
+    // the variance-guided one's
+    DenoiseScratch denoise[2];
     // variance AOV (pbrs_render_tile_aovs_var*, device/moments.h): the per-pixel moments k_moments folds every pass into, and the host
     // variant's staging for the finished buffer
     size_t cap_moment_pixels = 0, cap_variance_out_pixels = 0;
     float* moment_state = nullptr;  // PBRS_MOMENT_STATE_WORDS * cap_moment_pixels, planar
     float* variance_out = nullptr;  // cap_variance_out_pixels
-    // variance-guided denoiser (pbrs_denoise_var*, device/denoise_var.h): scratch and staging of its own, laid out like the plain one's
-    size_t cap_denoise_var_pixels = 0, cap_denoise_var_stage_pixels = 0;
-    void* denoise_var_mem = nullptr;
-    void* denoise_var_stage = nullptr;  // kDenoiseVarStageWords * cap_denoise_var_stage_pixels
 };
 
 namespace {
@@ -408,41 +410,22 @@ int ensure_aov(pbrs_ctx* c, size_t n_pixels, bool staging) {
 
 // The filtered film's sums for n_pixels tile pixels; a failure leaves the context without them, usable for every other call.
 int ensure_filter(pbrs_ctx* c, size_t n_pixels) {
-    if (n_pixels <= c->cap_filter_pixels) return PBRS_OK;
-    c->cap_filter_pixels = 0;
-    if (c->filter_sum) (void)hipFree(c->filter_sum);
-    c->filter_sum = nullptr;
-    const size_t total = 4 * n_pixels * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->filter_sum), total);
-    if (e != hipSuccess) {
-        c->filter_sum = nullptr;
-        c->error = std::string("hipMalloc of the filter sums (") + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
-        (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
-        return PBRS_E_DEVICE;
-    }
-    c->cap_filter_pixels = n_pixels;
-    return PBRS_OK;
+    return grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->filter_sum), c->cap_filter_pixels, 4 * sizeof(float), "the filter sums");
 }
 
 constexpr size_t kDenoiseBytesPerPixel = 3 * sizeof(float4) + sizeof(uint32_t);
-constexpr size_t kDenoiseStageWords = 3 + 3 + 3 + 1 + 1;  // rgb, albedo, normal, depth, instance
+// rgb, albedo, normal, depth, instance; variance-guided: and variance, variance_out
+constexpr size_t kDenoiseStageWords[2] = {3 + 3 + 3 + 1 + 1, 3 + 3 + 3 + 1 + 1 + 1 + 1};
 
-// The denoiser's scratch (and, with `staging`, the host variant's buffers) for n_pixels: grown like the AOV state; a failure leaves the
-// context without it, usable for every other call.
-int ensure_denoise(pbrs_ctx* c, size_t n_pixels, bool staging) {
-    int rc = grow_pixels(c, n_pixels, &c->denoise_mem, c->cap_denoise_pixels, kDenoiseBytesPerPixel, "the denoiser's scratch");
+// A denoiser's scratch (and, with `staging`, the host variant's buffers) for n_pixels: grown like the AOV state; a failure leaves the
+// context without it, usable for every other call.  The variance-guided denoiser keeps scratch of its own (the planes have the plain
+// one's size).
+int ensure_denoise(pbrs_ctx* c, bool var, size_t n_pixels, bool staging) {
+    DenoiseScratch& d = c->denoise[var];
+    int rc = grow_pixels(c, n_pixels, &d.mem, d.cap_pixels, kDenoiseBytesPerPixel, var ? "the variance-guided denoiser's scratch" : "the denoiser's scratch");
     if (rc || !staging) return rc;
-    return grow_pixels(c, n_pixels, &c->denoise_stage, c->cap_denoise_stage_pixels, kDenoiseStageWords * sizeof(float), "the denoiser's staging");
-}
-
-constexpr size_t kDenoiseVarStageWords = 3 + 3 + 3 + 1 + 1 + 1 + 1;  // rgb, albedo, normal, depth, instance, variance, variance_out
-
-// The same for the variance-guided denoiser, which keeps scratch of its own (the planes have the plain one's size).
-int ensure_denoise_var(pbrs_ctx* c, size_t n_pixels, bool staging) {
-    int rc = grow_pixels(c, n_pixels, &c->denoise_var_mem, c->cap_denoise_var_pixels, kDenoiseBytesPerPixel, "the variance-guided denoiser's scratch");
-    if (rc || !staging) return rc;
-    return grow_pixels(c, n_pixels, &c->denoise_var_stage, c->cap_denoise_var_stage_pixels, kDenoiseVarStageWords * sizeof(float),
-                       "the variance-guided denoiser's staging");
+    return grow_pixels(c, n_pixels, &d.stage, d.cap_stage_pixels, kDenoiseStageWords[var] * sizeof(float),
+                       var ? "the variance-guided denoiser's staging" : "the denoiser's staging");
 }
 
 // The moment state of the variance AOV (and, with `staging`, the host variant's output buffer) for n_pixels.
@@ -1168,12 +1151,12 @@ void pbrs_destroy(pbrs_ctx* c) {
     free_work(c);  // (leaves pass set 0 in use)
     free_aov(c);
     if (c->filter_sum) (void)hipFree(c->filter_sum);
-    if (c->denoise_mem) (void)hipFree(c->denoise_mem);
-    if (c->denoise_stage) (void)hipFree(c->denoise_stage);
+    for (DenoiseScratch& d : c->denoise) {
+        if (d.mem) (void)hipFree(d.mem);
+        if (d.stage) (void)hipFree(d.stage);
+    }
     if (c->moment_state) (void)hipFree(c->moment_state);
     if (c->variance_out) (void)hipFree(c->variance_out);
-    if (c->denoise_var_mem) (void)hipFree(c->denoise_var_mem);
-    if (c->denoise_var_stage) (void)hipFree(c->denoise_var_stage);
     if (c->counters) (void)hipFree(c->counters);
     if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
     for (int k = 0; k < 2; ++k)
@@ -1729,18 +1712,20 @@ int pbrs_render_tile_filtered(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_re
     return collect(c, stats_out);
 }
 
-// ---- denoiser (include/pbrs_gpu.h, device/denoise.h) ----
+// ---- denoisers (include/pbrs_gpu.h, device/denoise.h) ----
 static_assert(sizeof(pbrs_denoise_params) == 32, "pbrs_denoise_params is 32 B");
+static_assert(sizeof(pbrs_denoise_var_params) == 32, "pbrs_denoise_var_params is 32 B");
 
 namespace {
 
 using DenoiseKernel = void (*)(const float4*, const float4*, const uint32_t*, float4*, DenoiseConst);
-// [id stop][iteration]
-constexpr DenoiseKernel kDenoiseAtrous[2][PBRS_DENOISE_MAX_ITERATIONS] = {
-    {k_denoise_atrous<0, false>, k_denoise_atrous<1, false>, k_denoise_atrous<2, false>, k_denoise_atrous<3, false>, k_denoise_atrous<4, false>,
-     k_denoise_atrous<5, false>},
-    {k_denoise_atrous<0, true>, k_denoise_atrous<1, true>, k_denoise_atrous<2, true>, k_denoise_atrous<3, true>, k_denoise_atrous<4, true>,
-     k_denoise_atrous<5, true>}};
+#define PBRS_DENOISE_ROW(IDS, VAR)                                                                                             \
+    {k_denoise_atrous<0, IDS, VAR>, k_denoise_atrous<1, IDS, VAR>, k_denoise_atrous<2, IDS, VAR>, k_denoise_atrous<3, IDS, VAR>, \
+     k_denoise_atrous<4, IDS, VAR>, k_denoise_atrous<5, IDS, VAR>}
+// [variance-guided][id stop][iteration]
+constexpr DenoiseKernel kDenoiseAtrous[2][2][PBRS_DENOISE_MAX_ITERATIONS] = {{PBRS_DENOISE_ROW(false, false), PBRS_DENOISE_ROW(true, false)},
+                                                                             {PBRS_DENOISE_ROW(false, true), PBRS_DENOISE_ROW(true, true)}};
+#undef PBRS_DENOISE_ROW
 
 int check_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in, const pbrs_denoise_guides* g, const float* rgb_out) {
     if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
@@ -1757,30 +1742,81 @@ int check_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in
     return PBRS_OK;
 }
 
+// The variance-guided denoiser's parameters and guides as the plain one's: sigma_luminance in the place of sigma_color (the two
+// parameter structs have one layout), the variance left out.
+pbrs_denoise_params plain_params(const pbrs_denoise_var_params& p) {
+    return {p.w, p.h, p.iterations, p.flags, p.sigma_luminance, p.sigma_normal, p.sigma_depth, p.albedo_floor};
+}
+
+int check_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, const float* rgb_out) {
+    if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
+    if (!g->variance) return fail(c, PBRS_E_INVALID, "the variance-guided denoiser needs guides.variance");
+    // the rest is the plain denoiser's list
+    const pbrs_denoise_params q = plain_params(*p);
+    const pbrs_denoise_guides gq{g->albedo, g->normal, g->depth, g->instance};
+    return check_denoise(c, &q, rgb_in, &gq, rgb_out);
+}
+
 // The launches of one denoise on the context's stream (arguments checked, scratch there): pack, the iterations ping-pong, unpack.
-int denoise_launch(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in, const pbrs_denoise_guides* g, float* rgb_out) {
-    const uint32_t P = p->w * p->h;
-    float4* plane[2] = {static_cast<float4*>(c->denoise_mem), static_cast<float4*>(c->denoise_mem) + c->cap_denoise_pixels};
-    float4* guide = plane[1] + c->cap_denoise_pixels;
-    uint32_t* ids = reinterpret_cast<uint32_t*>(guide + c->cap_denoise_pixels);
-    const uint32_t demod = p->flags & PBRS_DENOISE_DEMODULATE;
-    const bool id_stop = (p->flags & PBRS_DENOISE_ID_STOP) != 0;
-    pbrs_denoise_guides packed = *g;
+// g.variance chooses the filter: given, the variance-guided one, whose first sigma is sigma_luminance.
+int denoise_launch(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_in, const DenoiseGuides& g, float* rgb_out, float* variance_out) {
+    const bool var = g.variance != nullptr;
+    const uint32_t P = p.w * p.h;
+    const size_t cap = c->denoise[var].cap_pixels;
+    float4* plane[2] = {static_cast<float4*>(c->denoise[var].mem), static_cast<float4*>(c->denoise[var].mem) + cap};
+    float4* guide = plane[1] + cap;
+    uint32_t* ids = reinterpret_cast<uint32_t*>(guide + cap);
+    const uint32_t demod = p.flags & PBRS_DENOISE_DEMODULATE;
+    const bool id_stop = (p.flags & PBRS_DENOISE_ID_STOP) != 0;
+    DenoiseGuides packed = g;
     if (!id_stop) packed.instance = nullptr;
-    const dim3 lin((P + kBlock - 1) / kBlock), cells((p->w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p->h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
-    hipLaunchKernelGGL(k_denoise_pack, lin, dim3(kBlock), 0, c->stream, rgb_in, packed, P, demod, p->albedo_floor, plane[0], guide, ids);
+    const dim3 lin((P + kBlock - 1) / kBlock), cells((p.w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p.h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
+    hipLaunchKernelGGL(k_denoise_pack, lin, dim3(kBlock), 0, c->stream, rgb_in, packed, P, demod, p.albedo_floor, plane[0], guide, ids);
     DenoiseConst k{};
-    k.w = p->w, k.h = p->h;
-    k.in = 1.0f / (p->sigma_normal * p->sigma_normal);
-    k.id = 1.0f / (p->sigma_depth * p->sigma_depth);
-    for (uint32_t it = 0; it < p->iterations; ++it) {
-        const float sc = p->sigma_color * pn_exp2i(-(int)it);
-        k.ic = 1.0f / (sc * sc);
-        const DenoiseKernel fn = kDenoiseAtrous[id_stop ? 1 : 0][it];
-        hipLaunchKernelGGL(fn, cells, dim3(kBlock), 0, c->stream, plane[it & 1u], guide, ids, plane[(it + 1u) & 1u], k);
+    k.w = p.w, k.h = p.h;
+    k.c1 = p.sigma_color;  // variance-guided: sigma_luminance, the same at every iteration
+    k.in = 1.0f / (p.sigma_normal * p.sigma_normal);
+    k.id = 1.0f / (p.sigma_depth * p.sigma_depth);
+    for (uint32_t it = 0; it < p.iterations; ++it) {
+        if (!var) {
+            const float sc = p.sigma_color * pn_exp2i(-(int)it);
+            k.c1 = 1.0f / (sc * sc);
+        }
+        hipLaunchKernelGGL(kDenoiseAtrous[var][id_stop][it], cells, dim3(kBlock), 0, c->stream, plane[it & 1u], guide, ids, plane[(it + 1u) & 1u], k);
     }
-    hipLaunchKernelGGL(k_denoise_unpack, lin, dim3(kBlock), 0, c->stream, plane[p->iterations & 1u], g->albedo, P, demod, p->albedo_floor, rgb_out);
+    hipLaunchKernelGGL(k_denoise_unpack, lin, dim3(kBlock), 0, c->stream, plane[p.iterations & 1u], g.albedo, P, demod, p.albedo_floor, rgb_out,
+                       variance_out);
     HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+// The host variants: the image and the given guides go through the denoiser's device staging (rgb in and out, the guides, variance-guided:
+// the variance in and out), and the call waits for the result.
+int denoise_staged(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_in_host, const DenoiseGuides& host, float* rgb_out_host,
+                   float* variance_out_host) {
+    const bool var = host.variance != nullptr;
+    const size_t P = (size_t)p.w * p.h;
+    int rc = ensure_denoise(c, var, P, true);
+    if (rc) return rc;
+    float* f = static_cast<float*>(c->denoise[var].stage);
+    float* rgb = f;
+    float* vout = variance_out_host ? f + 12 * P : nullptr;
+    DenoiseGuides dev{};
+    dev.albedo = host.albedo ? f + 3 * P : nullptr;
+    dev.normal = host.normal ? f + 6 * P : nullptr;
+    dev.depth = host.depth ? f + 9 * P : nullptr;
+    dev.instance = host.instance ? reinterpret_cast<const uint32_t*>(f + 10 * P) : nullptr;
+    dev.variance = var ? f + 11 * P : nullptr;
+    const void* src[6] = {rgb_in_host, host.albedo, host.normal, host.depth, host.instance, host.variance};
+    const void* dst[6] = {rgb, dev.albedo, dev.normal, dev.depth, dev.instance, dev.variance};
+    const size_t words[6] = {3, 3, 3, 1, 1, 1};
+    for (int k = 0; k < 6; ++k)
+        if (src[k]) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(dst[k]), src[k], words[k] * P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = denoise_launch(c, p, rgb, dev, rgb, vout);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (vout) HIPCHK(c, hipMemcpyAsync(variance_out_host, vout, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
 
@@ -1792,9 +1828,10 @@ int pbrs_denoise_device(pbrs_ctx* c, const pbrs_denoise_params* p, const float* 
     int rc = check_denoise(c, p, rgb_in_device, guides_device, rgb_out_device);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = ensure_denoise(c, (size_t)p->w * p->h, false);
+    rc = ensure_denoise(c, false, (size_t)p->w * p->h, false);
     if (rc) return rc;
-    return denoise_launch(c, p, rgb_in_device, guides_device, rgb_out_device);
+    const pbrs_denoise_guides& g = *guides_device;
+    return denoise_launch(c, *p, rgb_in_device, {g.albedo, g.normal, g.depth, g.instance, nullptr}, rgb_out_device, nullptr);
 }
 
 int pbrs_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_host, const pbrs_denoise_guides* guides_host, float* rgb_out_host) {
@@ -1802,79 +1839,9 @@ int pbrs_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_
     int rc = check_denoise(c, p, rgb_in_host, guides_host, rgb_out_host);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t P = (size_t)p->w * p->h;
-    rc = ensure_denoise(c, P, true);
-    if (rc) return rc;
-    // device staging: rgb (in and out), then the given guides
-    float* f = static_cast<float*>(c->denoise_stage);
-    float* rgb = f;
-    pbrs_denoise_guides dev{};
-    dev.albedo = guides_host->albedo ? f + 3 * P : nullptr;
-    dev.normal = guides_host->normal ? f + 6 * P : nullptr;
-    dev.depth = guides_host->depth ? f + 9 * P : nullptr;
-    dev.instance = guides_host->instance ? reinterpret_cast<const uint32_t*>(f + 10 * P) : nullptr;
-    const void* src[5] = {rgb_in_host, guides_host->albedo, guides_host->normal, guides_host->depth, guides_host->instance};
-    const void* dst[5] = {rgb, dev.albedo, dev.normal, dev.depth, dev.instance};
-    const size_t words[5] = {3, 3, 3, 1, 1};
-    for (int k = 0; k < 5; ++k)
-        if (src[k]) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(dst[k]), src[k], words[k] * P * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = denoise_launch(c, p, rgb, &dev, rgb);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    const pbrs_denoise_guides& g = *guides_host;
+    return denoise_staged(c, *p, rgb_in_host, {g.albedo, g.normal, g.depth, g.instance, nullptr}, rgb_out_host, nullptr);
 }
-
-// ---- variance-guided denoiser (include/pbrs_gpu.h, device/denoise_var.h) ----
-static_assert(sizeof(pbrs_denoise_var_params) == 32, "pbrs_denoise_var_params is 32 B");
-
-namespace {
-
-using DenoiseVarKernel = void (*)(const float4*, const float4*, const uint32_t*, float4*, DenoiseVarConst);
-// [id stop][iteration]
-constexpr DenoiseVarKernel kDenoiseVarAtrous[2][PBRS_DENOISE_MAX_ITERATIONS] = {
-    {k_denoise_var_atrous<0, false>, k_denoise_var_atrous<1, false>, k_denoise_var_atrous<2, false>, k_denoise_var_atrous<3, false>,
-     k_denoise_var_atrous<4, false>, k_denoise_var_atrous<5, false>},
-    {k_denoise_var_atrous<0, true>, k_denoise_var_atrous<1, true>, k_denoise_var_atrous<2, true>, k_denoise_var_atrous<3, true>,
-     k_denoise_var_atrous<4, true>, k_denoise_var_atrous<5, true>}};
-
-int check_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, const float* rgb_out) {
-    if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
-    if (!g->variance) return fail(c, PBRS_E_INVALID, "the variance-guided denoiser needs guides.variance");
-    // the rest is the plain denoiser's list, sigma_luminance in the place of sigma_color
-    const pbrs_denoise_params q{p->w, p->h, p->iterations, p->flags, p->sigma_luminance, p->sigma_normal, p->sigma_depth, p->albedo_floor};
-    const pbrs_denoise_guides gq{g->albedo, g->normal, g->depth, g->instance};
-    return check_denoise(c, &q, rgb_in, &gq, rgb_out);
-}
-
-// The launches of one variance-guided denoise on the context's stream (arguments checked, scratch there).
-int denoise_var_launch(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, float* rgb_out,
-                       float* variance_out) {
-    const uint32_t P = p->w * p->h;
-    const size_t cap = c->cap_denoise_var_pixels;
-    float4* plane[2] = {static_cast<float4*>(c->denoise_var_mem), static_cast<float4*>(c->denoise_var_mem) + cap};
-    float4* guide = plane[1] + cap;
-    uint32_t* ids = reinterpret_cast<uint32_t*>(guide + cap);
-    const uint32_t demod = p->flags & PBRS_DENOISE_DEMODULATE;
-    const bool id_stop = (p->flags & PBRS_DENOISE_ID_STOP) != 0;
-    pbrs_denoise_var_guides packed = *g;
-    if (!id_stop) packed.instance = nullptr;
-    const dim3 lin((P + kBlock - 1) / kBlock), cells((p->w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p->h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
-    hipLaunchKernelGGL(k_denoise_var_pack, lin, dim3(kBlock), 0, c->stream, rgb_in, packed, P, demod, p->albedo_floor, plane[0], guide, ids);
-    DenoiseVarConst k{};
-    k.w = p->w, k.h = p->h;
-    k.sl = p->sigma_luminance;
-    k.in = 1.0f / (p->sigma_normal * p->sigma_normal);
-    k.id = 1.0f / (p->sigma_depth * p->sigma_depth);
-    for (uint32_t it = 0; it < p->iterations; ++it)
-        hipLaunchKernelGGL(kDenoiseVarAtrous[id_stop ? 1 : 0][it], cells, dim3(kBlock), 0, c->stream, plane[it & 1u], guide, ids, plane[(it + 1u) & 1u], k);
-    hipLaunchKernelGGL(k_denoise_var_unpack, lin, dim3(kBlock), 0, c->stream, plane[p->iterations & 1u], g->albedo, P, demod, p->albedo_floor, rgb_out,
-                       variance_out);
-    HIPCHK(c, hipGetLastError());
-    return PBRS_OK;
-}
-
-}  // namespace
 
 int pbrs_denoise_var_device(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in_device, const pbrs_denoise_var_guides* guides_device,
                             float* rgb_out_device, float* variance_out_device) {
@@ -1882,9 +1849,9 @@ int pbrs_denoise_var_device(pbrs_ctx* c, const pbrs_denoise_var_params* p, const
     int rc = check_denoise_var(c, p, rgb_in_device, guides_device, rgb_out_device);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = ensure_denoise_var(c, (size_t)p->w * p->h, false);
+    rc = ensure_denoise(c, true, (size_t)p->w * p->h, false);
     if (rc) return rc;
-    return denoise_var_launch(c, p, rgb_in_device, guides_device, rgb_out_device, variance_out_device);
+    return denoise_launch(c, plain_params(*p), rgb_in_device, *guides_device, rgb_out_device, variance_out_device);
 }
 
 int pbrs_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in_host, const pbrs_denoise_var_guides* guides_host,
@@ -1893,30 +1860,7 @@ int pbrs_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float*
     int rc = check_denoise_var(c, p, rgb_in_host, guides_host, rgb_out_host);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t P = (size_t)p->w * p->h;
-    rc = ensure_denoise_var(c, P, true);
-    if (rc) return rc;
-    // device staging: rgb (in and out), the given guides, the variance in and out
-    float* f = static_cast<float*>(c->denoise_var_stage);
-    float* rgb = f;
-    float* vout = variance_out_host ? f + 12 * P : nullptr;
-    pbrs_denoise_var_guides dev{};
-    dev.albedo = guides_host->albedo ? f + 3 * P : nullptr;
-    dev.normal = guides_host->normal ? f + 6 * P : nullptr;
-    dev.depth = guides_host->depth ? f + 9 * P : nullptr;
-    dev.instance = guides_host->instance ? reinterpret_cast<const uint32_t*>(f + 10 * P) : nullptr;
-    dev.variance = f + 11 * P;
-    const void* src[6] = {rgb_in_host, guides_host->albedo, guides_host->normal, guides_host->depth, guides_host->instance, guides_host->variance};
-    const void* dst[6] = {rgb, dev.albedo, dev.normal, dev.depth, dev.instance, dev.variance};
-    const size_t words[6] = {3, 3, 3, 1, 1, 1};
-    for (int k = 0; k < 6; ++k)
-        if (src[k]) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(dst[k]), src[k], words[k] * P * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = denoise_var_launch(c, p, rgb, &dev, rgb, vout);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (vout) HIPCHK(c, hipMemcpyAsync(variance_out_host, vout, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    return denoise_staged(c, plain_params(*p), rgb_in_host, *guides_host, rgb_out_host, variance_out_host);
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {

@@ -1,6 +1,7 @@
 """tools/isa_same_kernels.py on two small hand-made device assemblies: a kernel whose local labels are merely renumbered counts as the
 same, one with another instruction or another register budget does not (the comparison behind `same_isa_as_measured`)."""
 import os
+import re
 import subprocess
 import sys
 
@@ -36,3 +37,16 @@ def test_kernels_that_differ_are_named(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_same_kernels.py"), a, b], capture_output=True, text=True, check=True).stdout
     assert "kernels 3: same 1, different 2" in out
     assert "k_two" in out and "k_three" in out and "k_one" not in out.split("\n", 1)[1]
+
+
+def test_a_renamed_kernel_with_the_same_body_and_budget_counts_as_the_same(tmp_path):
+    a, b = str(tmp_path / "a.s"), str(tmp_path / "b.s")
+    asm(a, [("_Z5k_onev", 1, 8), ("_Z5k_oldv", 2, 8), ("_Z6k_gonev", 3, 8), ("_Z6k_lessv", 4, 8)])
+    asm(b, [("_Z5k_onev", 1, 8), ("_Z5k_newv", 2, 8), ("_Z6k_camev", 7, 8), ("_Z6k_morev", 4, 16)])
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_same_kernels.py"), a, b], capture_output=True, text=True, check=True).stdout
+    # k_old -> k_new: same body, same registers.  k_gone / k_came differ in an instruction, k_less / k_more in the register budget.
+    assert "kernels 6: same 2 (1 of them renamed), different 4" in out
+    assert re.search(r"renamed: \S*k_old\S* -> \S*k_new", out)  # (mangled where there is no demangler)
+    assert out.count("renamed:") == 1 and out.count("differs:") == 4
+    for n in ("k_gone", "k_came", "k_less", "k_more"):
+        assert any(n in line and "differs:" in line for line in out.splitlines())

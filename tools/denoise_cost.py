@@ -9,7 +9,6 @@ with this one's, in child processes that alternate, so that the denoise's share 
 plain frame of the two builds compared on one box.  Writes profiles/denoise_cost.json (or --out) and prints it.
     python tools/denoise_cost.py [--config c4] [--runs N] [--parent-tree DIR] [--out PATH]"""
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -31,51 +30,10 @@ sys.path.insert(0, os.path.abspath(args.tree))
 import pbrs_amd  # noqa: E402
 from pbrs_amd import api, scenes  # noqa: E402
 
-# the HIP runtime the library is linked against (already loaded with it); the parent's package has no api.hip_runtime
-pbrs_amd.gpu_lib()
-hip = C.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line))
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-hip.hipEventSynchronize.argtypes = [C.c_void_p]
+from hip_event_timing import Timing  # noqa: E402
 
-
-def check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
-
-
-stream, ev0, ev1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-check(hip.hipStreamCreate(C.byref(stream)), "hipStreamCreate")
-check(hip.hipEventCreate(C.byref(ev0)), "hipEventCreate")
-check(hip.hipEventCreate(C.byref(ev1)), "hipEventCreate")
-ctx = pbrs_amd.Context(0)
-ctx.set_stream(stream.value)
-
-
-def timed(fn):
-    """Milliseconds of what fn queues on the context's stream."""
-    check(hip.hipEventRecord(ev0, stream), "hipEventRecord")
-    fn()
-    check(hip.hipEventRecord(ev1, stream), "hipEventRecord")
-    check(hip.hipEventSynchronize(ev1), "hipEventSynchronize")
-    ms = C.c_float()
-    check(hip.hipEventElapsedTime(C.byref(ms), ev0, ev1), "hipEventElapsedTime")
-    return float(ms.value)
-
-
-def median_of(fn, runs, warmup=1):
-    for _ in range(warmup):
-        timed(fn)
-    ms = [round(timed(fn), 4) for _ in range(runs)]
-    return {"ms": ms, "median_ms": round(statistics.median(ms), 4)}
-
-
-def dev_alloc(nbytes):
-    ptr = C.c_void_p()
-    check(hip.hipMalloc(C.byref(ptr), nbytes), "hipMalloc")
-    return ptr
-
+T = Timing(pbrs_amd, warmup=1)
+ctx, median_of, dev_alloc = T.ctx, T.median_of, T.dev_alloc
 
 sb, cfg = scenes.build_config(args.config)
 W, H = cfg["width"], cfg["height"]

@@ -28,7 +28,8 @@ def kernels(path):
                 cur = None
                 continue
             t = s.strip()
-            if t.startswith((".loc", ".file", ".cfi", ".p2align")):
+            # (a template kernel's descriptor block stands before its .Lfunc_end: the two lines of it that name the kernel are no code)
+            if t.startswith((".loc", ".file", ".cfi", ".p2align", ".amdhsa_kernel ", ".section")):
                 continue
             cur.append(t)
     # resource directives: the .amdhsa_kernel blocks
@@ -64,13 +65,29 @@ a, ra = kernels(sys.argv[1])
 b, rb = kernels(sys.argv[2])
 names = sorted(set(a) | set(b))
 dm = demangle(names)
+short = {n: dm[n].split("(")[0] for n in names}
 same, diff = [], []
 for n in names:
     if n in a and n in b and canon(a[n]) == canon(b[n]) and ra.get(n) == rb.get(n):
         same.append(n)
+    elif n in a and n in b:
+        diff.append(n)
+# a kernel on one side only may be a renamed one: pair the leftovers of the two sides whose body and resource directives are equal (a
+# kernel's body does not name its own symbol), in name order where several are alike
+renamed, left = [], {}
+for n in sorted(set(b) - set(a)):
+    left.setdefault((canon(b[n]), tuple(rb.get(n, ()))), []).append(n)
+for n in sorted(set(a) - set(b)):
+    twins = left.get((canon(a[n]), tuple(ra.get(n, ()))))
+    if twins:
+        renamed.append((n, twins.pop(0)))
     else:
         diff.append(n)
-print(f"kernels {len(names)}: same {len(same)}, different {len(diff)}")
-for n in diff:
+diff += [n for twins in left.values() for n in twins]
+pairs = f" ({len(renamed)} of them renamed)" if renamed else ""
+print(f"kernels {len(same) + len(renamed) + len(diff)}: same {len(same) + len(renamed)}{pairs}, different {len(diff)}")
+for old, new in renamed:
+    print("  renamed:", short[old], "->", short[new])
+for n in sorted(diff):
     why = "only in one" if not (n in a and n in b) else f"{len(a[n])} -> {len(b[n])} lines"
-    print("  differs:", dm[n].split("(")[0], f"({why})")
+    print("  differs:", short[n], f"({why})")
