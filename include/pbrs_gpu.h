@@ -580,6 +580,70 @@ int pbrs_denoise_var(pbrs_ctx*, const pbrs_denoise_var_params*, const float* rgb
 int pbrs_denoise_var_device(pbrs_ctx*, const pbrs_denoise_var_params*, const float* rgb_in_device, const pbrs_denoise_var_guides* guides_device,
                             float* rgb_out_device, float* variance_out_device);
 
+/* ---- id mattes ---------------------------------------------------------------------------------------- */
+/* Per pixel the few ids that cover it and how much of the pixel each covers, from the render's own camera samples, so that a matte for
+ * any set of objects can be pulled afterwards with the image's own anti-aliasing (Friedman and Jones, "Fully automatic ID mattes with
+ * support for motion blur and transparency", SIGGRAPH 2015 posters: Cryptomatte).  The ids are the indices the AOVs use; names for them
+ * (a manifest, hashed names) are not part of this interface.
+ *
+ * The key of a hit is its instance, an index into pbrs_scene_desc::instances (PBRS_MATTE_INSTANCE), or instances[instance].material
+ * (PBRS_MATTE_MATERIAL).  The first hit of sample s of a pixel is the one the first-hit AOVs use (pbrs_aov_buffers): the hit record of
+ * `scene.tlas.intersect` on its camera ray (bounce 0); spp = strata_x * strata_y.
+ *   Per pixel a table of `slots` entries (id, count), all empty, and overflow = 0.  For sample index s = 0 .. spp-1 in order: a miss does
+ *   nothing; a hit with key `id`: if an entry holds `id`, its count + 1; else if an entry is empty, the first empty one becomes (id, 1);
+ *   else overflow + 1.  First come, first kept: nothing is ever evicted, so overflow == 0 means the table is exact, and the sample
+ *   index is the only loop, so the result does not depend on the passes.
+ *   Ranks: the used entries sorted by count, descending; equal counts: the lower id first.  Output, the tile / band packing of rgb_out:
+ *     ids       u32, w * h * slots, pixel-major ([pixel][rank]); an unused rank: 0xffffffff
+ *     coverage  f32, the same shape: (float)count * (1.0f / spp), the expression of the coverage AOV; an unused rank: +0
+ *     residual  f32, w * h: (float)overflow * (1.0f / spp); may be NULL (not wanted)
+ *   In integers, for every pixel: the sum of the counts + overflow == n_hit of the coverage AOV.
+ * pbrs_render_tile_matte[_device]: pbrs_render_tile_aovs_var[_device] (`aovs` and `variance` may be NULL) that also fills the matte; a
+ * NULL `matte` is exactly that call (`params` is then not read), and the image, the seven AOVs and the variance are the bits of that
+ * call.  Pointers are host memory for pbrs_render_tile_matte, device memory for pbrs_render_tile_matte_device, which is asynchronous like
+ * pbrs_render_tile_device: valid after pbrs_collect_stats.  Any integrator.  The matte kernels' time counts in pbrs_stats::ms_total
+ * only.  The context keeps 8 * slots + 4 B of matte state per pixel (and, for the host variant, as many bytes of staging), allocated by
+ * the first call that asks for a matte.  Not offered through the filtered film.
+ * Refused with PBRS_E_INVALID (the context stays usable), beside what pbrs_render_tile_aovs_var refuses: PBRS_INTEGRATOR_PATH / _DIRECT
+ * with max_depth == 0 (no camera ray is traced); NULL params beside a matte; slots 0 or above PBRS_MATTE_MAX_SLOTS; an unknown key; NULL
+ * ids or coverage. */
+#define PBRS_MATTE_INSTANCE 0u
+#define PBRS_MATTE_MATERIAL 1u
+#define PBRS_MATTE_MAX_SLOTS 8u
+typedef struct pbrs_matte_params {
+    uint32_t key;   /* PBRS_MATTE_INSTANCE or PBRS_MATTE_MATERIAL */
+    uint32_t slots; /* 1 .. PBRS_MATTE_MAX_SLOTS: entries kept (and ranks written) per pixel */
+} pbrs_matte_params; /* 8 B */
+typedef struct pbrs_matte_buffers {
+    uint32_t* ids;   /* w * h * slots */
+    float* coverage; /* w * h * slots */
+    float* residual; /* w * h; may be NULL */
+} pbrs_matte_buffers;
+int pbrs_render_tile_matte(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                           float* variance_host, const pbrs_matte_params* params, const pbrs_matte_buffers* matte_host, pbrs_stats* stats_out);
+int pbrs_render_tile_matte_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_device,
+                                  const pbrs_aov_buffers* aovs_device, float* variance_device, const pbrs_matte_params* params,
+                                  const pbrs_matte_buffers* matte_device, pbrs_stats* stats_out);
+
+/* The mask of a set of ids, pulled from the layers above.  An image operation like pbrs_denoise: it needs a context (device, stream)
+ * and no uploaded scene.  `ids` and `coverage` are w * h * slots as pbrs_render_tile_matte writes them; `select` is n_select ids in
+ * strictly ascending order (NULL allowed when n_select == 0).  For every pixel, from m = +0, for rank r = 0 .. slots-1 in order: where
+ * ids[r] is one of the selected ids, m = m + coverage[r].  mask_out: f32, w * h.
+ * ids, coverage and mask_out are host memory for pbrs_matte_mask (which synchronises before it returns), device memory for
+ * pbrs_matte_mask_device, which runs on the context's stream (pbrs_set_stream honoured): queued after pbrs_render_tile_matte_device on
+ * the same context it needs no synchronisation in between, and its output is valid when that render's would be.  `select` is host
+ * memory in both (a parameter, like the structs: the call checks and copies it before it returns).
+ * Memory: the first call allocates PBRS_MATTE_MAX_SELECT * 4 B for the selection; pbrs_matte_mask another 8 * slots + 4 B per pixel of
+ * staging, shared with pbrs_render_tile_matte's.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL ids, coverage or mask_out; w or h 0; slots 0 or above
+ * PBRS_MATTE_MAX_SLOTS; n_select above PBRS_MATTE_MAX_SELECT (the selection is staged in LDS: 16 KB); NULL select with n_select > 0; a
+ * selection that is not strictly ascending.  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_MATTE_MAX_SELECT 4096u
+int pbrs_matte_mask(pbrs_ctx*, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_host, const float* coverage_host,
+                    const uint32_t* select, uint32_t n_select, float* mask_out_host);
+int pbrs_matte_mask_device(pbrs_ctx*, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_device, const float* coverage_device,
+                           const uint32_t* select, uint32_t n_select, float* mask_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,39 @@ class DenoiseVarGuides(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance", "variance")]
 
 
+class MatteParams(C.Structure):
+    """pbrs_matte_params (include/pbrs_gpu.h): what a hit is keyed by and how many (id, count) entries a pixel keeps."""
+    INSTANCE, MATERIAL = 0, 1
+    KEYS = {"instance": INSTANCE, "material": MATERIAL}
+    MAX_SLOTS = 8
+    MAX_SELECT = 4096
+    _fields_ = [("key", C.c_uint32), ("slots", C.c_uint32)]
+
+    @classmethod
+    def make(cls, key="instance", slots=6):
+        if key not in cls.KEYS:
+            raise ValueError(f"unknown matte key {key!r}; known: {sorted(cls.KEYS)}")
+        p = cls()
+        p.key, p.slots = cls.KEYS[key], slots
+        return p
+
+
+class MatteBuffers(C.Structure):
+    """pbrs_matte_buffers: ids and coverage, (h, w, slots) u32 / f32, ranked per pixel; residual (h, w) f32, NULL = not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ("ids", "coverage", "residual")]
+
+
+MATTE_LAYERS = ("ids", "coverage", "residual")
+
+
+def _matte_select(select):
+    """The selected ids as pbrs_matte_mask wants them: u32, strictly ascending (sorted and deduplicated here)."""
+    sel = np.unique(np.asarray(select, dtype=np.int64).reshape(-1))
+    if sel.size and (sel[0] < 0 or sel[-1] > 0xFFFFFFFF):
+        raise ValueError("a selected id is not a u32")
+    return np.ascontiguousarray(sel, dtype=np.uint32)
+
+
 DENOISE_GUIDES = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "instance": (1, np.uint32)}
 
 HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
@@ -203,7 +236,8 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
                "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
                "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device",
-               "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device"]
+               "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device",
+               "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -281,6 +315,10 @@ def gpu_lib():
         L.pbrs_render_tile_aovs_var_device.argtypes = [C.c_void_p] * 7
         L.pbrs_denoise_var.argtypes = [C.c_void_p] * 6
         L.pbrs_denoise_var_device.argtypes = [C.c_void_p] * 6
+        L.pbrs_render_tile_matte.argtypes = [C.c_void_p] * 9
+        L.pbrs_render_tile_matte_device.argtypes = [C.c_void_p] * 9
+        L.pbrs_matte_mask.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.pbrs_matte_mask_device.argtypes = L.pbrs_matte_mask.argtypes
         _gpu = L
     return _gpu
 
@@ -516,6 +554,77 @@ class Context:
         self._check(self._L.pbrs_render_tile_aovs_var_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
                                                              C.addressof(bufs), C.c_void_p(variance_device_ptr), None),
                     "pbrs_render_tile_aovs_var_device")
+
+    def render_matte(self, strata_x, strata_y, depth, seed, key="instance", slots=6, aovs=(), tile=None, samples_per_pass=0, counters=False,
+                     timing=False, bands=None, integrator="path"):
+        """render_aovs() plus the id matte of the same camera samples (include/pbrs_gpu.h, pbrs_render_tile_matte) -> (rgb, matte, aovs,
+        stats).  matte = {"ids": (h, w, slots) u32, "coverage": (h, w, slots) f32, "residual": (h, w) f32}: per pixel the ids ranked by the
+        share of the pixel's samples each covers (an unused rank: 0xffffffff, +0), and the share of the hits the table had no entry for.
+        key: "instance" or "material"; aovs: names as render_aovs takes them ("variance" included)."""
+        names = _aov_names(aovs)
+        mp = MatteParams.make(key, slots)
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
+        out = np.empty((p.h, p.w, 3), dtype=np.float32)
+        bufs, arrays = AovBuffers(), {}
+        for n in names:
+            ch, dt = AOVS.get(n, (1, np.float32))
+            arrays[n] = np.empty((p.h, p.w, ch) if ch > 1 else (p.h, p.w), dtype=dt)
+            if n != VARIANCE:
+                setattr(bufs, n, arrays[n].ctypes.data)
+        layers = max(int(slots), 0)  # (a refused `slots` still reaches the library: it is the one that refuses)
+        matte = {"ids": np.empty((p.h, p.w, layers), dtype=np.uint32), "coverage": np.empty((p.h, p.w, layers), dtype=np.float32),
+                 "residual": np.empty((p.h, p.w), dtype=np.float32)}
+        mb = MatteBuffers()
+        for n in MATTE_LAYERS:
+            setattr(mb, n, matte[n].ctypes.data)
+        st = Stats()
+        self._check(self._L.pbrs_render_tile_matte(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
+                                                   arrays[VARIANCE].ctypes.data if VARIANCE in names else None, C.addressof(mp), C.addressof(mb),
+                                                   C.addressof(st)), "pbrs_render_tile_matte")
+        return out, matte, arrays, st.as_dict()
+
+    def render_matte_device(self, rgb_device_ptr, matte_device_ptrs, strata_x, strata_y, depth, seed, key="instance", slots=6,
+                            aov_device_ptrs=None, tile=None, samples_per_pass=0, counters=False, timing=False, bands=None, integrator="path"):
+        """render_matte() into caller-owned device memory: `matte_device_ptrs` = {"ids", "coverage"[, "residual"]: pointer}, `aov_device_ptrs`
+        as render_aovs_device takes them ("variance" included).  Asynchronous like render_device: valid after `collect_stats()`."""
+        unknown = [n for n in matte_device_ptrs if n not in MATTE_LAYERS]
+        if unknown:
+            raise ValueError(f"unknown matte layer(s) {unknown}; known: {list(MATTE_LAYERS)}")
+        ptrs = dict(aov_device_ptrs or {})
+        _aov_names(ptrs)
+        variance = ptrs.pop(VARIANCE, None)
+        mp = MatteParams.make(key, slots)
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
+        bufs, mb = AovBuffers(), MatteBuffers()
+        for n, ptr in ptrs.items():
+            setattr(bufs, n, ptr)
+        for n, ptr in matte_device_ptrs.items():
+            setattr(mb, n, ptr)
+        self._check(self._L.pbrs_render_tile_matte_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
+                                                          C.addressof(bufs), C.c_void_p(variance), C.addressof(mp), C.addressof(mb), None),
+                    "pbrs_render_tile_matte_device")
+
+    def matte_mask(self, ids, coverage, select):
+        """The mask of the ids in `select` (any order, duplicates allowed: sorted here) from the layers render_matte returns -> (h, w) f32:
+        per pixel the coverages of the selected ids, summed in rank order (include/pbrs_gpu.h, pbrs_matte_mask)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        coverage = np.ascontiguousarray(coverage, dtype=np.float32)
+        if ids.ndim != 3 or ids.shape != coverage.shape:
+            raise ValueError(f"ids of shape {ids.shape} beside a coverage of {coverage.shape}; both are (h, w, slots)")
+        h, w, slots = ids.shape
+        sel = _matte_select(select)
+        out = np.empty((h, w), dtype=np.float32)
+        self._check(self._L.pbrs_matte_mask(self._h, w, h, slots, ids.ctypes.data, coverage.ctypes.data, sel.ctypes.data if sel.size else None,
+                                            sel.size, out.ctypes.data), "pbrs_matte_mask")
+        return out
+
+    def matte_mask_device(self, ids_device_ptr, coverage_device_ptr, mask_device_ptr, w, h, slots, select):
+        """matte_mask() on caller-owned device memory.  Runs on the context's stream behind whatever was queued there (a
+        render_matte_device needs no synchronisation in between) and does not wait: valid after `collect_stats()`."""
+        sel = _matte_select(select)
+        self._check(self._L.pbrs_matte_mask_device(self._h, w, h, slots, C.c_void_p(ids_device_ptr), C.c_void_p(coverage_device_ptr),
+                                                   sel.ctypes.data if sel.size else None, sel.size, C.c_void_p(mask_device_ptr)),
+                    "pbrs_matte_mask_device")
 
     def render_filtered(self, pixel_filter, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0, counters=False, timing=False,
                         integrator="path"):

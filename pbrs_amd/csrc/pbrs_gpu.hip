@@ -26,6 +26,7 @@
 #include "device/film.h"
 #include "device/denoise.h"
 #include "device/moments.h"
+#include "device/matte.h"
 
 namespace {
 
@@ -255,6 +256,13 @@ struct pbrs_ctx {
     size_t cap_moment_pixels = 0, cap_variance_out_pixels = 0;
     float* moment_state = nullptr;  // PBRS_MOMENT_STATE_WORDS * cap_moment_pixels, planar
     float* variance_out = nullptr;  // cap_variance_out_pixels
+    // id mattes (pbrs_render_tile_matte*, pbrs_matte_mask*, device/matte.h): the per-pixel tables k_matte folds every pass into, the host
+    // variants' staging (ids, coverage, then residual or the mask) and the selection of pbrs_matte_mask*; capacities in words, since
+    // the words per pixel follow `slots`
+    size_t cap_matte_words = 0, cap_matte_out_words = 0, cap_matte_select = 0;
+    uint32_t* matte_state = nullptr;   // PBRS_MATTE_STATE_WORDS(slots) * pixels, planar
+    uint32_t* matte_out = nullptr;     // (2 * slots + 1) * pixels
+    uint32_t* matte_select = nullptr;  // PBRS_MATTE_MAX_SELECT
 };
 
 namespace {
@@ -434,6 +442,14 @@ int ensure_moments(pbrs_ctx* c, size_t n_pixels, bool staging) {
                          "the variance AOV's moments");
     if (rc || !staging) return rc;
     return grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->variance_out), c->cap_variance_out_pixels, sizeof(float), "the variance buffer");
+}
+
+// The matte state (and, with `staging`, the host variants' buffers) for n_pixels at `slots` entries per pixel.
+int ensure_matte(pbrs_ctx* c, size_t n_pixels, uint32_t slots, bool state, bool staging) {
+    const size_t words = n_pixels * PBRS_MATTE_STATE_WORDS(slots);
+    int rc = state ? grow_pixels(c, words, reinterpret_cast<void**>(&c->matte_state), c->cap_matte_words, sizeof(uint32_t), "the matte state") : PBRS_OK;
+    if (rc || !staging) return rc;
+    return grow_pixels(c, words, reinterpret_cast<void**>(&c->matte_out), c->cap_matte_out_words, sizeof(uint32_t), "the matte buffers");
 }
 
 void free_aov(pbrs_ctx* c) {
@@ -782,14 +798,25 @@ void poll_split_probe(pbrs_ctx* c) {
     c->split_decision = (c->split_host[0] * 100ull <= c->split_host[1] * PBRS_SPLIT_KEEP_PERCENT) ? 1 : 2;
 }
 
+// The matte kernels by `slots` (device/matte.h): the table is a register array, so its size is a template argument.
+struct MatteKernels {
+    void (*fold)(const pbrs_instance*, PathState, uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
+    void (*finalize)(const uint32_t*, uint32_t, uint32_t, uint32_t, float, uint32_t*, float*, float*);
+};
+#define PBRS_MATTE_KERNELS(N) {k_matte<N>, k_matte_finalize<N>}
+constexpr MatteKernels kMatte[PBRS_MATTE_MAX_SLOTS] = {PBRS_MATTE_KERNELS(1), PBRS_MATTE_KERNELS(2), PBRS_MATTE_KERNELS(3), PBRS_MATTE_KERNELS(4),
+                                                       PBRS_MATTE_KERNELS(5), PBRS_MATTE_KERNELS(6), PBRS_MATTE_KERNELS(7), PBRS_MATTE_KERNELS(8)};
+#undef PBRS_MATTE_KERNELS
+
 // One pass: kc sample indices starting at `first` for every pixel of the tile.
 // `handoff`: the pass moves to the late stream at bounce pbrs_ctx::overlap_from (at the latest for its k_accumulate: the late stream runs
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
 // `aov`: the AOV state k_aov folds this pass's first hits into (null: no AOVs).
 // `filt`: a filtered render (rc is its traced region): k_filter_accumulate folds the pass into pbrs_ctx::filter_sum instead of k_accumulate.
 // `moments`: the moment state of the variance AOV k_moments folds this pass's radiances into (null: no variance).
+// `matte`: the matte tables k_matte folds this pass's first hits into (null: no matte).
 int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false, float* aov = nullptr,
-             const FilterConst* filt = nullptr, float* moments = nullptr) {
+             const FilterConst* filt = nullptr, float* moments = nullptr, const pbrs_matte_params* matte = nullptr) {
     pbrs_ctx::PassSet& set = c->pass_set[c->cur_set];
     // the set's memory is free once the pass that used it last has accumulated (two passes back, on the late stream)
     if (handoff && set.in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, set.accumulated, 0));
@@ -855,6 +882,10 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         // (render_common joins the late stream before k_aov_finalize).
         if (b == 0 && aov)
             hipLaunchKernelGGL(k_aov, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, c->st, aov, P, kc, rc.chunk_pixels, qsplit);
+        // id mattes: the same hit records, the same place and stream for the same reasons
+        if (b == 0 && matte)
+            hipLaunchKernelGGL(kMatte[matte->slots - 1u].fold, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S.inst, c->st, c->matte_state, P, kc,
+                               rc.chunk_pixels, qsplit, matte->key);
         if (tm.begin(2)) return fail(c, PBRS_E_DEVICE, "event record failed");
         // the queue in the order the plan asks for; a queue k_extend split: class-major over its two classes, class 1 = the kept paths, last
         const IntegratorPlan::Order order = qsplit ? IntegratorPlan::CLASS_MAJOR : ip.order;
@@ -923,8 +954,10 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
 // `filt`: a filtered render; `p` is then its traced region (check_filter) and rgb_device receives the tile's filt->w x filt->h pixels,
 // from the sums ensure_filter allocated.
 // `variance` (device pointer; null: none): the variance AOV too, from the state ensure_moments allocated.
+// `matte`, `matte_out` (device pointers; null: none): the id matte too (arguments checked by check_matte), from the state ensure_matte allocated.
 int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device, const pbrs_aov_buffers* aovs = nullptr,
-                  const FilterConst* filt = nullptr, float* variance = nullptr) {
+                  const FilterConst* filt = nullptr, float* variance = nullptr, const pbrs_matte_params* matte = nullptr,
+                  const pbrs_matte_buffers* matte_out = nullptr) {
     HIPCHK(c, hipSetDevice(c->device));  // before check_params: the automatic pass size reads THIS device's free memory
     int rcode = check_params(c, cam, p);
     if (rcode) return rcode;
@@ -951,6 +984,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (aov) HIPCHK(c, hipMemsetAsync(aov, 0, PBRS_AOV_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     float* moments = variance ? c->moment_state : nullptr;
     if (moments) HIPCHK(c, hipMemsetAsync(moments, 0, PBRS_MOMENT_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
+    if (matte) HIPCHK(c, hipMemsetAsync(c->matte_state, 0, PBRS_MATTE_STATE_WORDS(matte->slots) * (size_t)P * sizeof(uint32_t), c->stream));
     uint32_t passes = 0;
     // Where the render has more than one pass, passes alternate between the two pass sets and hand their late bounces to the second
     // stream: those are near-empty launches that end with the latency of their longest walks (C4: 47 ms per frame in kernels that leave
@@ -969,7 +1003,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     for (uint32_t first = 0; first < spp; first += K) {
         uint32_t kc = spp - first < K ? spp - first : K;
         if (two) use_pass_set(c, (int)(passes & 1u));  // (also: back to the main stream)
-        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov, filt, moments);
+        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov, filt, moments, matte);
         if (rcode) {
             use_pass_set(c, 0);
             return rcode;
@@ -992,6 +1026,9 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
                            1.0f / (float)spp, *aovs);
     if (moments)
         hipLaunchKernelGGL(k_moments_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, moments, P, rc.w, rc.tiles8_per_row, variance);
+    if (matte)
+        hipLaunchKernelGGL(kMatte[matte->slots - 1u].finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->matte_state, P, rc.w,
+                           rc.tiles8_per_row, 1.0f / (float)spp, matte_out->ids, matte_out->coverage, matte_out->residual);
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending.passes = passes;
@@ -1157,6 +1194,9 @@ void pbrs_destroy(pbrs_ctx* c) {
     }
     if (c->moment_state) (void)hipFree(c->moment_state);
     if (c->variance_out) (void)hipFree(c->variance_out);
+    if (c->matte_state) (void)hipFree(c->matte_state);
+    if (c->matte_out) (void)hipFree(c->matte_out);
+    if (c->matte_select) (void)hipFree(c->matte_select);
     if (c->counters) (void)hipFree(c->counters);
     if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
     for (int k = 0; k < 2; ++k)
@@ -1584,17 +1624,36 @@ int check_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p,
     return rc;
 }
 
-int pbrs_render_tile_aovs_var_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
-                                     const pbrs_aov_buffers* aovs_device, float* variance_device, pbrs_stats* stats_out) {
+// The checks of the matte entry points beyond check_aovs's (a matte is requested), and its state (`staging`: and the host variant's buffers).
+int check_matte(pbrs_ctx* c, const pbrs_render_params* p, const pbrs_matte_params* mp, const pbrs_matte_buffers* m, bool staging) {
+    if (!mp) return fail(c, PBRS_E_INVALID, "a matte without pbrs_matte_params");
+    if (mp->key != PBRS_MATTE_INSTANCE && mp->key != PBRS_MATTE_MATERIAL) return fail(c, PBRS_E_INVALID, "unknown matte key");
+    if (mp->slots == 0 || mp->slots > PBRS_MATTE_MAX_SLOTS) return fail(c, PBRS_E_INVALID, "matte slots must be 1 .. 8");
+    if (!m->ids || !m->coverage) return fail(c, PBRS_E_INVALID, "a matte needs ids and coverage");
+    if (p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0)
+        return fail(c, PBRS_E_INVALID, "a matte requested from a render that traces no camera ray (max_depth 0)");
+    // before render_common's pass size reads the free memory
+    return ensure_matte(c, (size_t)p->w * p->h, mp->slots, true, staging);
+}
+
+int pbrs_render_tile_matte_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
+                                  const pbrs_aov_buffers* aovs_device, float* variance_device, const pbrs_matte_params* params,
+                                  const pbrs_matte_buffers* matte_device, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->device));
     int rc = check_aovs(c, cam, p, aovs_device, variance_device != nullptr);
+    if (!rc && matte_device) rc = check_matte(c, p, params, matte_device, false);
     if (rc) return rc;
-    rc = render_common(c, cam, p, rgb_out_device, aovs_device, nullptr, variance_device);
+    rc = render_common(c, cam, p, rgb_out_device, aovs_device, nullptr, variance_device, matte_device ? params : nullptr, matte_device);
     if (rc) return rc;
     if (stats_out) return collect(c, stats_out);
     return PBRS_OK;
+}
+
+int pbrs_render_tile_aovs_var_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
+                                     const pbrs_aov_buffers* aovs_device, float* variance_device, pbrs_stats* stats_out) {
+    return pbrs_render_tile_matte_device(c, cam, p, rgb_out_device, aovs_device, variance_device, nullptr, nullptr, stats_out);
 }
 
 int pbrs_render_tile_aovs_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, const pbrs_aov_buffers* aovs_device,
@@ -1602,12 +1661,13 @@ int pbrs_render_tile_aovs_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs
     return pbrs_render_tile_aovs_var_device(c, cam, p, rgb_out_device, aovs_device, nullptr, stats_out);
 }
 
-int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
-                              float* variance_host, pbrs_stats* stats_out) {
+int pbrs_render_tile_matte(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                           float* variance_host, const pbrs_matte_params* params, const pbrs_matte_buffers* matte_host, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
     HIPCHK(c, hipSetDevice(c->device));
     int rc = check_aovs(c, cam, p, aovs_host, variance_host != nullptr);
+    if (!rc && matte_host) rc = check_matte(c, p, params, matte_host, true);
     if (rc) return rc;
     const size_t P = (size_t)p->w * p->h;
     const bool want = any_aov(aovs_host);
@@ -1628,7 +1688,16 @@ int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_re
         dev.material = aovs_host->material ? reinterpret_cast<uint32_t*>(f + 9 * P) : nullptr;
         dev.prim = aovs_host->prim ? reinterpret_cast<uint32_t*>(f + 10 * P) : nullptr;
     }
-    rc = render_common(c, cam, p, c->rgb_dev, want ? &dev : nullptr, nullptr, variance_host ? c->variance_out : nullptr);
+    // the matte's staging: ids, coverage, residual
+    pbrs_matte_buffers mdev{};
+    const size_t MS = matte_host ? P * params->slots : 0;
+    if (matte_host) {
+        mdev.ids = c->matte_out;
+        mdev.coverage = reinterpret_cast<float*>(c->matte_out + MS);
+        mdev.residual = matte_host->residual ? reinterpret_cast<float*>(c->matte_out + 2 * MS) : nullptr;
+    }
+    rc = render_common(c, cam, p, c->rgb_dev, want ? &dev : nullptr, nullptr, variance_host ? c->variance_out : nullptr, matte_host ? params : nullptr,
+                       matte_host ? &mdev : nullptr);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (variance_host) HIPCHK(c, hipMemcpyAsync(variance_host, c->variance_out, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1639,7 +1708,17 @@ int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_re
         for (int k = 0; k < 7; ++k)
             if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], src[k], words[k] * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
+    if (matte_host) {
+        HIPCHK(c, hipMemcpyAsync(matte_host->ids, mdev.ids, MS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(matte_host->coverage, mdev.coverage, MS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (mdev.residual) HIPCHK(c, hipMemcpyAsync(matte_host->residual, mdev.residual, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
     return collect(c, stats_out);
+}
+
+int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                              float* variance_host, pbrs_stats* stats_out) {
+    return pbrs_render_tile_matte(c, cam, p, rgb_out_host, aovs_host, variance_host, nullptr, nullptr, stats_out);
 }
 
 int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
@@ -1861,6 +1940,68 @@ int pbrs_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float*
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return denoise_staged(c, plain_params(*p), rgb_in_host, *guides_host, rgb_out_host, variance_out_host);
+}
+
+// ---- id mattes: the mask of a selection (include/pbrs_gpu.h, device/matte.h) ----
+static_assert(sizeof(pbrs_matte_params) == 8, "pbrs_matte_params is 8 B");
+
+namespace {
+
+int check_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids, const float* coverage, const uint32_t* select, uint32_t n_select,
+                     const float* mask_out) {
+    if (!ids || !coverage || !mask_out) return fail(c, PBRS_E_INVALID, "null matte layers or mask");
+    if (w == 0 || h == 0) return fail(c, PBRS_E_INVALID, "empty image");
+    if (slots == 0 || slots > PBRS_MATTE_MAX_SLOTS) return fail(c, PBRS_E_INVALID, "matte slots must be 1 .. 8");
+    if (n_select > PBRS_MATTE_MAX_SELECT) return fail(c, PBRS_E_INVALID, "more than PBRS_MATTE_MAX_SELECT selected ids");
+    if (n_select && !select) return fail(c, PBRS_E_INVALID, "null selection");
+    for (uint32_t i = 1; i < n_select; ++i)
+        if (select[i - 1] >= select[i]) return fail(c, PBRS_E_INVALID, "the selected ids must be strictly ascending");
+    if ((uint64_t)w * h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The selection to the device and the kernel, on the context's stream (arguments checked).
+int matte_mask_launch(pbrs_ctx* c, uint32_t P, uint32_t slots, const uint32_t* ids, const float* coverage, const uint32_t* select, uint32_t n_select, float* mask) {
+    int rc = grow_pixels(c, PBRS_MATTE_MAX_SELECT, reinterpret_cast<void**>(&c->matte_select), c->cap_matte_select, sizeof(uint32_t), "the matte selection");
+    if (rc) return rc;
+    // from the caller's memory: the runtime has taken the bytes when the call returns, and the copy runs in the stream's order
+    if (n_select) HIPCHK(c, hipMemcpyAsync(c->matte_select, select, n_select * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_matte_mask, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), n_select * sizeof(uint32_t), c->stream, ids, coverage, c->matte_select, n_select,
+                       P, slots, mask);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_matte_mask_device(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_device, const float* coverage_device,
+                           const uint32_t* select, uint32_t n_select, float* mask_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_matte_mask(c, w, h, slots, ids_device, coverage_device, select, n_select, mask_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return matte_mask_launch(c, w * h, slots, ids_device, coverage_device, select, n_select, mask_out_device);
+}
+
+int pbrs_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_host, const float* coverage_host,
+                    const uint32_t* select, uint32_t n_select, float* mask_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_matte_mask(c, w, h, slots, ids_host, coverage_host, select, n_select, mask_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)w * h, MS = P * slots;
+    rc = ensure_matte(c, P, slots, false, true);
+    if (rc) return rc;
+    uint32_t* ids = c->matte_out;
+    float* coverage = reinterpret_cast<float*>(c->matte_out + MS);
+    float* mask = reinterpret_cast<float*>(c->matte_out + 2 * MS);
+    HIPCHK(c, hipMemcpyAsync(ids, ids_host, MS * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(coverage, coverage_host, MS * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = matte_mask_launch(c, (uint32_t)P, slots, ids, coverage, select, n_select, mask);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(mask_out_host, mask, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -11,7 +11,11 @@ guided by the albedo, normal, depth and instance AOVs of the same samples; --den
 --denoise-var: also writes <out>.denoised_var.<ext>, the image through the variance-guided denoiser (include/pbrs_gpu.h,
 pbrs_denoise_var) with the variance AOV of the same samples: no sigma depends on the units of the scene.  --denoise-sigma-luminance
 (default 4, in standard deviations) overrides Context.denoise_var's default; --denoise-iterations and the normal and depth sigmas of
---denoise-sigma apply to it too."""
+--denoise-sigma apply to it too.
+--matte instance|material: also writes <out>.matte.npz, the id matte of the same samples (include/pbrs_gpu.h, pbrs_render_tile_matte):
+`ids` (h, w, slots) u32, `coverage` (h, w, slots) f32, `residual` (h, w) f32 — per pixel the ids ranked by the share of the pixel each
+covers (an .npz because the EXR writer holds RGB f32 only and cannot hold ids).  --matte-slots (default 6, at most 8) is the number of
+ids kept per pixel.  --matte-select i,j,...: also writes <out>.mask.png, the anti-aliased mask of those ids (pbrs_matte_mask)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,13 +26,20 @@ filtered = "--pixel-filter" in sys.argv
 denoise = "--denoise" in sys.argv
 denoise_var = "--denoise-var" in sys.argv
 denoise_params, denoise_var_params = {}, {}
-for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance"):
+matte_key, matte_slots, matte_select = None, 6, None
+for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
         del sys.argv[k:k + 2]
         if flag == "--denoise-iterations":
             denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
+        elif flag == "--matte":
+            matte_key = value
+        elif flag == "--matte-slots":
+            matte_slots = int(value)
+        elif flag == "--matte-select":
+            matte_select = [int(v) for v in value.split(",") if v]
         elif flag == "--denoise-sigma-luminance":
             denoise_var_params["sigma_luminance"] = float(value)
         else:
@@ -52,6 +63,11 @@ if filtered:
     print(f"pixel filter: {pf}")
     if aovs or denoise or denoise_var:
         _, buf, _ = ctx.render_aovs(msaa, msaa, depth, 1, aovs=want, integrator=integrator)
+    if matte_key:  # like the AOVs: per-pixel, from a separate render of the same samples
+        matte = ctx.render_matte(msaa, msaa, depth, 1, key=matte_key, slots=matte_slots, integrator=integrator)[1]
+elif matte_key:
+    img, matte, buf, st = ctx.render_matte(msaa, msaa, depth, 1, key=matte_key, slots=matte_slots, aovs=want if aovs or denoise or denoise_var else (),
+                                           integrator=integrator, timing=True)
 elif aovs or denoise or denoise_var:
     img, buf, st = ctx.render_aovs(msaa, msaa, depth, 1, aovs=want, integrator=integrator, timing=True)
 else:
@@ -69,4 +85,11 @@ if aovs:
         a = buf[name] if buf[name].ndim == 3 else np.repeat(buf[name][:, :, None], 3, axis=2)
         pbrs_amd.write_image(f"{stem}.{name}.exr", a)
         print(f"-> {stem}.{name}.exr")
+if matte_key:
+    np.savez(f"{stem}.matte.npz", **matte)
+    print(f"-> {stem}.matte.npz ({matte_key} ids, {matte_slots} per pixel; {int((matte['residual'] > 0).sum())} pixels hold more)")
+    if matte_select is not None:
+        m = ctx.matte_mask(matte["ids"], matte["coverage"], matte_select)
+        pbrs_amd.write_image(f"{stem}.mask.png", np.repeat(m[:, :, None], 3, axis=2))
+        print(f"-> {stem}.mask.png")
 print(f"{img.shape[1]}x{img.shape[0]} at {msaa * msaa} spp in {st['ms_total']:.1f} ms -> {out}")
