@@ -500,6 +500,44 @@ class Context:
         self._check(self._L.pbrs_render_tile_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr), None),
                     "pbrs_render_tile_device")
 
+    @staticmethod
+    def _aov_arrays(names, p):
+        """The host arrays of the AOVs named ("variance" among them) for the tile of `p`, and the AovBuffers that points at them."""
+        bufs, arrays = AovBuffers(), {}
+        for n in names:
+            ch, dt = AOVS.get(n, (1, np.float32))
+            arrays[n] = np.empty((p.h, p.w, ch) if ch > 1 else (p.h, p.w), dtype=dt)
+            if n != VARIANCE:
+                setattr(bufs, n, arrays[n].ctypes.data)
+        return bufs, arrays
+
+    @staticmethod
+    def _aov_device(aov_device_ptrs):
+        """{name: device pointer} -> the AovBuffers of the first-hit AOVs and the pointer of "variance" (None: not asked for)."""
+        ptrs = dict(aov_device_ptrs or {})
+        _aov_names(ptrs)
+        variance = ptrs.pop(VARIANCE, None)
+        bufs = AovBuffers()
+        for n, ptr in ptrs.items():
+            setattr(bufs, n, ptr)
+        return bufs, variance
+
+    def _render_host(self, p, names, mp=None, mb=None):
+        """A host render of `p` with the AOVs named and, with `mp` and `mb`, a matte -> (rgb, {name: array}, stats).  One entry point
+        serves all of them: the library forwards the AOV ones to it."""
+        out = np.empty((p.h, p.w, 3), dtype=np.float32)
+        bufs, arrays = self._aov_arrays(names, p)
+        st = Stats()
+        self._check(self._L.pbrs_render_tile_matte(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
+                                                   arrays[VARIANCE].ctypes.data if VARIANCE in names else None, C.addressof(mp) if mp else None,
+                                                   C.addressof(mb) if mb else None, C.addressof(st)), "pbrs_render_tile_matte")
+        return out, arrays, st.as_dict()
+
+    def _render_device(self, p, rgb_device_ptr, bufs, variance, mp=None, mb=None):
+        self._check(self._L.pbrs_render_tile_matte_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
+                                                          C.addressof(bufs), C.c_void_p(variance), C.addressof(mp) if mp else None,
+                                                          C.addressof(mb) if mb else None, None), "pbrs_render_tile_matte_device")
+
     def render_aovs(self, strata_x, strata_y, depth, seed, aovs=AOV_NAMES, tile=None, samples_per_pass=0, counters=False,
                     timing=False, bands=None, integrator="path"):
         """render() plus first-hit AOVs of the same camera samples (include/pbrs_gpu.h, pbrs_aov_buffers) -> (rgb, {name: array},
@@ -507,39 +545,15 @@ class Context:
         "variance" (not in the default) adds the variance of the pixel's mean luminance, (h, w) f32, +inf where fewer than two samples
         are finite (pbrs_render_tile_aovs_var)."""
         names = _aov_names(aovs)
-        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
-        out = np.empty((p.h, p.w, 3), dtype=np.float32)
-        bufs, arrays = AovBuffers(), {}
-        for n in names:
-            ch, dt = AOVS.get(n, (1, np.float32))
-            arrays[n] = np.empty((p.h, p.w, ch) if ch > 1 else (p.h, p.w), dtype=dt)
-            if n != VARIANCE:
-                setattr(bufs, n, arrays[n].ctypes.data)
-        st = Stats()
-        if VARIANCE in names:
-            self._check(self._L.pbrs_render_tile_aovs_var(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data,
-                                                          C.addressof(bufs), arrays[VARIANCE].ctypes.data, C.addressof(st)),
-                        "pbrs_render_tile_aovs_var")
-        else:
-            self._check(self._L.pbrs_render_tile_aovs(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data,
-                                                      C.addressof(bufs), C.addressof(st)), "pbrs_render_tile_aovs")
-        return out, arrays, st.as_dict()
+        return self._render_host(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator), names)
 
     def render_aovs_device(self, rgb_device_ptr, aov_device_ptrs, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0,
                            counters=False, timing=False, bands=None, integrator="path"):
         """render_device() plus first-hit AOVs into caller-owned device memory: `aov_device_ptrs` = {name: pointer} (e.g.
         tensor.data_ptr(); sizes as render_aovs returns them).  Asynchronous like render_device: valid after `collect_stats()`."""
-        _aov_names(aov_device_ptrs)
-        if VARIANCE in aov_device_ptrs:
-            ptrs = dict(aov_device_ptrs)
-            return self.render_aovs_var_device(rgb_device_ptr, ptrs, ptrs.pop(VARIANCE), strata_x, strata_y, depth, seed, tile,
-                                               samples_per_pass, counters, timing, bands, integrator)
-        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
-        bufs = AovBuffers()
-        for n, ptr in aov_device_ptrs.items():
-            setattr(bufs, n, ptr)
-        self._check(self._L.pbrs_render_tile_aovs_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
-                                                         C.addressof(bufs), None), "pbrs_render_tile_aovs_device")
+        bufs, variance = self._aov_device(aov_device_ptrs)
+        self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator),
+                            rgb_device_ptr, bufs, variance)
 
     def render_aovs_var_device(self, rgb_device_ptr, aov_device_ptrs, variance_device_ptr, strata_x, strata_y, depth, seed, tile=None,
                                samples_per_pass=0, counters=False, timing=False, bands=None, integrator="path"):
@@ -547,13 +561,9 @@ class Context:
         unknown = [n for n in aov_device_ptrs if n not in AOVS]
         if unknown:
             raise ValueError(f"unknown AOV name(s) {unknown}; known: {sorted(AOVS)}")
-        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
-        bufs = AovBuffers()
-        for n, ptr in aov_device_ptrs.items():
-            setattr(bufs, n, ptr)
-        self._check(self._L.pbrs_render_tile_aovs_var_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
-                                                             C.addressof(bufs), C.c_void_p(variance_device_ptr), None),
-                    "pbrs_render_tile_aovs_var_device")
+        bufs, _ = self._aov_device(aov_device_ptrs)
+        self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator),
+                            rgb_device_ptr, bufs, variance_device_ptr)
 
     def render_matte(self, strata_x, strata_y, depth, seed, key="instance", slots=6, aovs=(), tile=None, samples_per_pass=0, counters=False,
                      timing=False, bands=None, integrator="path"):
@@ -564,24 +574,14 @@ class Context:
         names = _aov_names(aovs)
         mp = MatteParams.make(key, slots)
         p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
-        out = np.empty((p.h, p.w, 3), dtype=np.float32)
-        bufs, arrays = AovBuffers(), {}
-        for n in names:
-            ch, dt = AOVS.get(n, (1, np.float32))
-            arrays[n] = np.empty((p.h, p.w, ch) if ch > 1 else (p.h, p.w), dtype=dt)
-            if n != VARIANCE:
-                setattr(bufs, n, arrays[n].ctypes.data)
         layers = max(int(slots), 0)  # (a refused `slots` still reaches the library: it is the one that refuses)
         matte = {"ids": np.empty((p.h, p.w, layers), dtype=np.uint32), "coverage": np.empty((p.h, p.w, layers), dtype=np.float32),
                  "residual": np.empty((p.h, p.w), dtype=np.float32)}
         mb = MatteBuffers()
         for n in MATTE_LAYERS:
             setattr(mb, n, matte[n].ctypes.data)
-        st = Stats()
-        self._check(self._L.pbrs_render_tile_matte(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
-                                                   arrays[VARIANCE].ctypes.data if VARIANCE in names else None, C.addressof(mp), C.addressof(mb),
-                                                   C.addressof(st)), "pbrs_render_tile_matte")
-        return out, matte, arrays, st.as_dict()
+        out, arrays, stats = self._render_host(p, names, mp, mb)
+        return out, matte, arrays, stats
 
     def render_matte_device(self, rgb_device_ptr, matte_device_ptrs, strata_x, strata_y, depth, seed, key="instance", slots=6,
                             aov_device_ptrs=None, tile=None, samples_per_pass=0, counters=False, timing=False, bands=None, integrator="path"):
@@ -590,19 +590,12 @@ class Context:
         unknown = [n for n in matte_device_ptrs if n not in MATTE_LAYERS]
         if unknown:
             raise ValueError(f"unknown matte layer(s) {unknown}; known: {list(MATTE_LAYERS)}")
-        ptrs = dict(aov_device_ptrs or {})
-        _aov_names(ptrs)
-        variance = ptrs.pop(VARIANCE, None)
-        mp = MatteParams.make(key, slots)
-        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
-        bufs, mb = AovBuffers(), MatteBuffers()
-        for n, ptr in ptrs.items():
-            setattr(bufs, n, ptr)
+        bufs, variance = self._aov_device(aov_device_ptrs)
+        mp, mb = MatteParams.make(key, slots), MatteBuffers()
         for n, ptr in matte_device_ptrs.items():
             setattr(mb, n, ptr)
-        self._check(self._L.pbrs_render_tile_matte_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
-                                                          C.addressof(bufs), C.c_void_p(variance), C.addressof(mp), C.addressof(mb), None),
-                    "pbrs_render_tile_matte_device")
+        self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator),
+                            rgb_device_ptr, bufs, variance, mp, mb)
 
     def matte_mask(self, ids, coverage, select):
         """The mask of the ids in `select` (any order, duplicates allowed: sorted here) from the layers render_matte returns -> (h, w) f32:

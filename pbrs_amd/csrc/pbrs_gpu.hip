@@ -43,7 +43,6 @@ constexpr uint32_t kSlowGrid = 64;
 constexpr uint32_t kStreamGridCap = 4096;  // blocks of k_nee_resolve, whose work is counted on the device (kernels.h)
 constexpr uint32_t kPersistentBlocks = PBRS_PERSISTENT_BLOCKS;  // 256 CUs x up to 6 resident 256-thread blocks (VGPR/LDS permitting)
 constexpr size_t kLdsBytesPerCU = 160 * 1024;
-constexpr uint32_t kAovOutWords = 3 + 3 + 1 + 1 + 1 + 1 + 1;  // pbrs_aov_buffers: albedo, normal, coverage, depth, instance, material, prim
 
 struct StageEvent {
     int stage;  // 0 raygen, 1 extend, 2 shade, 3 shadow, 4 accumulate
@@ -158,16 +157,37 @@ struct KernelPlan {
     IntegratorPlan integ[PBRS_INTEGRATOR_NORMALS + 1];
 };
 
-}  // namespace
-
-// A denoiser's device memory, allocated by its first call: two ping-pong colour planes, the guide plane and the instance ids (16 + 16 + 16 +
-// 4 B per pixel, one allocation), and the host variant's staging (rgb, albedo, normal, depth, instance; variance-guided: and the variance
-// in and out).
-struct DenoiseScratch {
-    size_t cap_pixels = 0, cap_stage_pixels = 0;
-    void* mem = nullptr;
-    void* stage = nullptr;  // kDenoiseStageWords * cap_stage_pixels
+// A device buffer of a feature that allocates on first use.  `grow` makes it hold at least `bytes`, grown (not copied): a failure leaves
+// the context without it (cap_bytes = 0), usable for every other call.
+struct DeviceBuffer {
+    void* p = nullptr;
+    size_t cap_bytes = 0;
+    int grow(pbrs_ctx* c, size_t bytes, const char* what);
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
 };
+// Every first-use buffer of a context (pbrs_ctx::buf).  pbrs_destroy frees the whole array: a new buffer is a new name here and nothing else.
+enum BufferId {
+    // first-hit AOVs (pbrs_render_tile_aovs*, device/aov.h): the per-pixel running state k_aov folds every pass into (PBRS_AOV_STATE_WORDS per
+    // pixel, planar), and the host variant's staging for the finished buffers (the seven of pbrs_aov_buffers, one after the other)
+    BUF_AOV_STATE, BUF_AOV_OUT,
+    // filtered film (pbrs_render_tile_filtered*, device/film.h): S.rgb and W of every tile pixel, planar
+    BUF_FILTER_SUM,
+    // denoisers (pbrs_denoise*, pbrs_denoise_var*, device/denoise.h): two ping-pong colour planes, the guide plane and the instance ids (16 +
+    // 16 + 16 + 4 B per pixel, one allocation), and the host variant's staging (denoise_staged).  Each denoiser keeps scratch and staging
+    // of its own: + 0 the plain filter's, + 1 the variance-guided one's
+    BUF_DENOISE, BUF_DENOISE_VAR, BUF_DENOISE_STAGE, BUF_DENOISE_VAR_STAGE,
+    // variance AOV (pbrs_render_tile_aovs_var*, device/moments.h): the per-pixel moments k_moments folds every pass into
+    // (PBRS_MOMENT_STATE_WORDS per pixel, planar), and the host variant's staging for the finished buffer
+    BUF_MOMENT_STATE, BUF_VARIANCE_OUT,
+    // id mattes (pbrs_render_tile_matte*, pbrs_matte_mask*, device/matte.h): the per-pixel tables k_matte folds every pass into
+    // (PBRS_MATTE_STATE_WORDS(slots) per pixel, planar), the host variants' staging (ids, coverage, then residual or the mask) and the
+    // selection of pbrs_matte_mask* (PBRS_MATTE_MAX_SELECT ids)
+    BUF_MATTE_STATE, BUF_MATTE_OUT, BUF_MATTE_SELECT,
+    N_BUFFERS
+};
+
+}  // namespace
 
 struct pbrs_ctx {
     int device = 0;
@@ -184,14 +204,14 @@ struct pbrs_ctx {
     // Two sets of per-pass working memory (path state, queues, counters) and two streams.  Consecutive passes of a render alternate
     // between the sets; a pass runs its bounces below overlap_from on the main stream and the rest — near-empty launches that end with
     // the latency of their longest walks — on a second, high-priority stream, beside the full kernels of the next pass's first bounces
-    // (render_common, run_pass).  The fields below (state_mem .. counters) are the view of the set in use; use_pass_set swaps them.
+    // (render_common, run_pass).  cur_set names the set in use (cur(c)); pass set 0 is the one in use between calls.
     struct PassSet {
-        void* state_mem = nullptr;
+        void* state_mem = nullptr;    // every per-path array of PathState, carved out of one allocation
         size_t cap_slots = 0;
         PathState st{};
-        uint32_t* neeq = nullptr;
-        uint32_t* slow = nullptr;
-        uint32_t* counters = nullptr;
+        uint32_t* neeq = nullptr;     // cap_slots: slots of the paths whose estimate waits for two shadow rays
+        uint32_t* slow = nullptr;     // 2 * cap_slots: queue positions the wide-walk k_shadow handed to the binary-walk kernel
+        uint32_t* counters = nullptr; // kCounterWords: act, ns (u64), extend work heads, shadow work heads
         hipEvent_t accumulated = nullptr;  // the set's last k_accumulate has run (late stream): the set's memory is free for its next pass
         hipEvent_t late = nullptr;         // the set's pass has run its bounces below pbrs_ctx::overlap_from (main stream): the late stream takes over
         bool in_flight = false;            // `accumulated` has been recorded at least once
@@ -207,11 +227,7 @@ struct pbrs_ctx {
     // every bounce overlapped: -2.6 %, profiles/r04l_ab_pass_overlap_streams_by_pass.log).
     uint32_t overlap_from = 2;
     // working set
-    size_t cap_slots = 0, cap_pixels = 0;
-    void* state_mem = nullptr;    // every per-path array of PathState, carved out of one allocation
-    PathState st{};
-    uint32_t* neeq = nullptr;     // cap_slots: slots of the paths whose estimate waits for two shadow rays
-    uint32_t* counters = nullptr; // kCounterWords: act, ns (u64), extend work heads, shadow work heads
+    size_t cap_pixels = 0;
     float* sum = nullptr;         // 3 * cap_pixels, planar
     float* rgb_dev = nullptr;     // 3 * cap_pixels, row-major (for the host-output variant)
     GlobalCounters* gcnt = nullptr;  // [0] extend, [1] shadow
@@ -236,33 +252,10 @@ struct pbrs_ctx {
     unsigned long long* split_host = nullptr;  // pinned: (paths kept, paths in all) of the probed pass
     hipEvent_t split_ev = nullptr;
     bool split_probe_in_flight = false;
-    uint32_t* slow = nullptr;      // 2 * cap_slots: queue positions the wide-walk k_shadow handed to the binary-walk kernel
     bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
     uint64_t pending_closest = 0;
     pbrs_intersect_info last_intersect{};  // which walks the last pbrs_intersect_rays went through
-    // first-hit AOVs (pbrs_render_tile_aovs*, device/aov.h): the per-pixel running state k_aov folds every pass into, and the host variant's
-    // staging for the finished buffers
-    size_t cap_aov_pixels = 0, cap_aov_out_pixels = 0;
-    float* aov_state = nullptr;  // PBRS_AOV_STATE_WORDS * cap_aov_pixels, planar
-    void* aov_out = nullptr;     // kAovOutWords * cap_aov_out_pixels: the seven buffers of pbrs_aov_buffers, one after the other
-    // filtered film (pbrs_render_tile_filtered*, device/film.h): S.rgb and W of every tile pixel, planar
-    size_t cap_filter_pixels = 0;
-    float* filter_sum = nullptr;  // 4 * cap_filter_pixels
-    // denoisers (pbrs_denoise*, pbrs_denoise_var*, device/denoise.h): each keeps scratch and staging of its own, [0] the plain filter's, [1]
-    // the variance-guided one's
-    DenoiseScratch denoise[2];
-    // variance AOV (pbrs_render_tile_aovs_var*, device/moments.h): the per-pixel moments k_moments folds every pass into, and the host
-    // variant's staging for the finished buffer
-    size_t cap_moment_pixels = 0, cap_variance_out_pixels = 0;
-    float* moment_state = nullptr;  // PBRS_MOMENT_STATE_WORDS * cap_moment_pixels, planar
-    float* variance_out = nullptr;  // cap_variance_out_pixels
-    // id mattes (pbrs_render_tile_matte*, pbrs_matte_mask*, device/matte.h): the per-pixel tables k_matte folds every pass into, the host
-    // variants' staging (ids, coverage, then residual or the mask) and the selection of pbrs_matte_mask*; capacities in words, since
-    // the words per pixel follow `slots`
-    size_t cap_matte_words = 0, cap_matte_out_words = 0, cap_matte_select = 0;
-    uint32_t* matte_state = nullptr;   // PBRS_MATTE_STATE_WORDS(slots) * pixels, planar
-    uint32_t* matte_out = nullptr;     // (2 * slots + 1) * pixels
-    uint32_t* matte_select = nullptr;  // PBRS_MATTE_MAX_SELECT
+    DeviceBuffer buf[N_BUFFERS];  // the features' first-use buffers (BufferId)
 };
 
 namespace {
@@ -300,29 +293,27 @@ void free_scene(pbrs_ctx* c) {
     c->has_scene = false;
 }
 
-// The per-pass working memory in use (pbrs_ctx::pass_set): stores the context's view into the set it came from and loads set k,
-// whose stream becomes the context's.
+// The per-pass working memory in use (pbrs_ctx::pass_set).
+pbrs_ctx::PassSet& cur(pbrs_ctx* c) { return c->pass_set[c->cur_set]; }
+
+// Set k becomes the one in use; its stream, the main one, becomes the context's.
 void use_pass_set(pbrs_ctx* c, int k) {
-    pbrs_ctx::PassSet& o = c->pass_set[c->cur_set];
-    o.state_mem = c->state_mem; o.cap_slots = c->cap_slots; o.st = c->st; o.neeq = c->neeq; o.slow = c->slow; o.counters = c->counters;
     c->cur_set = k;
-    const pbrs_ctx::PassSet& n = c->pass_set[k];
-    c->state_mem = n.state_mem; c->cap_slots = n.cap_slots; c->st = n.st; c->neeq = n.neeq; c->slow = n.slow; c->counters = n.counters;
     c->stream = c->main_stream;
 }
 
-void free_work(pbrs_ctx* c) {
+void free_paths(pbrs_ctx::PassSet& set) {
     // capacities first: whatever happens below, no later call may take the old pointers for valid
-    for (int k = 0; k < 2; ++k) {
-        use_pass_set(c, k);
-        c->cap_slots = 0;
-        c->st = PathState{};
-        if (c->state_mem) (void)hipFree(c->state_mem);
-        c->state_mem = nullptr;
-        c->neeq = nullptr;
-        c->slow = nullptr;
-    }
-    use_pass_set(c, 0);
+    set.cap_slots = 0;
+    set.st = PathState{};
+    set.neeq = nullptr;
+    set.slow = nullptr;
+    if (set.state_mem) (void)hipFree(set.state_mem);
+    set.state_mem = nullptr;
+}
+
+void free_work(pbrs_ctx* c) {
+    for (pbrs_ctx::PassSet& set : c->pass_set) free_paths(set);
     c->cap_pixels = 0;
     if (c->sum) (void)hipFree(c->sum);
     if (c->rgb_dev) (void)hipFree(c->rgb_dev);
@@ -330,17 +321,13 @@ void free_work(pbrs_ctx* c) {
     c->rgb_dev = nullptr;
 }
 
+// The path state of `set` for n_slots paths, and the context's per-pixel sums for n_pixels.
 // Carves the per-path arrays of PathState out of one allocation; every array starts 256-byte aligned.  The new
 // capacities are published only after every allocation has succeeded: a failure leaves the context without a working
 // set (cap_* = 0, PathState cleared), never with pointers into freed memory.
-int ensure_work(pbrs_ctx* c, size_t n_slots, size_t n_pixels) {
-    if (n_slots > c->cap_slots) {
-        c->cap_slots = 0;
-        c->st = PathState{};
-        c->neeq = nullptr;
-        c->slow = nullptr;
-        if (c->state_mem) (void)hipFree(c->state_mem);
-        c->state_mem = nullptr;
+int ensure_work(pbrs_ctx* c, pbrs_ctx::PassSet& set, size_t n_slots, size_t n_pixels) {
+    if (n_slots > set.cap_slots) {
+        free_paths(set);
         auto align = [](size_t b) { return (b + 255) / 256 * 256; };
         const size_t v16 = align(n_slots * sizeof(float4));
         // q[2][3], hit, L, nee[3]: one float4 per path each; sr[3]: two per path; occ: two bytes; nee queue: one word
@@ -348,32 +335,33 @@ int ensure_work(pbrs_ctx* c, size_t n_slots, size_t n_pixels) {
         const size_t sort_bytes = align(n_tiles * PBRS_MAX_CLASSES * sizeof(uint32_t)) + align((PBRS_MAX_CLASSES + 1) * sizeof(uint2));
         const size_t total = (6 + 1 + 1 + 3) * v16 + 3 * 2 * v16 + align(2 * n_slots) + align(n_slots * sizeof(uint32_t)) + align(n_slots * sizeof(uint32_t)) +
                              sort_bytes + align(n_slots) + align(2 * n_slots * sizeof(uint32_t));
-        hipError_t e = hipMalloc(&c->state_mem, total);
+        void* mem = nullptr;
+        hipError_t e = hipMalloc(&mem, total);
         if (e != hipSuccess) {
-            c->state_mem = nullptr;
             c->error = std::string("hipMalloc of the path state (") + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
             (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
             return PBRS_E_DEVICE;
         }
-        char* p = static_cast<char*>(c->state_mem);
+        set.state_mem = mem;
+        char* p = static_cast<char*>(mem);
         auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
         PathState s{};
-        for (int set = 0; set < 2; ++set)
-            for (int k = 0; k < 3; ++k) s.q[set][k] = reinterpret_cast<float4*>(take(v16));
+        for (int half = 0; half < 2; ++half)
+            for (int k = 0; k < 3; ++k) s.q[half][k] = reinterpret_cast<float4*>(take(v16));
         s.hit = reinterpret_cast<float4*>(take(v16));
         s.L = reinterpret_cast<float4*>(take(v16));
         for (int k = 0; k < 3; ++k) s.nee[k] = reinterpret_cast<float4*>(take(v16));
         for (int k = 0; k < 3; ++k) s.sr[k] = reinterpret_cast<float4*>(take(2 * v16));
         s.occ[0] = reinterpret_cast<uint8_t*>(take(align(2 * n_slots)));
         s.occ[1] = s.occ[0] + n_slots;
-        c->neeq = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
+        set.neeq = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
         s.perm = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
         s.cls = reinterpret_cast<uint8_t*>(take(align(n_slots)));
-        c->slow = reinterpret_cast<uint32_t*>(take(align(2 * n_slots * sizeof(uint32_t))));
+        set.slow = reinterpret_cast<uint32_t*>(take(align(2 * n_slots * sizeof(uint32_t))));
         s.tile_hist = reinterpret_cast<uint32_t*>(take(align(n_tiles * PBRS_MAX_CLASSES * sizeof(uint32_t))));
         s.class_range = reinterpret_cast<uint2*>(take(align((PBRS_MAX_CLASSES + 1) * sizeof(uint2))));
-        c->st = s;
-        c->cap_slots = n_slots;
+        set.st = s;
+        set.cap_slots = n_slots;
     }
     if (n_pixels > c->cap_pixels) {
         c->cap_pixels = 0;
@@ -388,81 +376,79 @@ int ensure_work(pbrs_ctx* c, size_t n_slots, size_t n_pixels) {
     return PBRS_OK;
 }
 
-// A per-pixel buffer of a feature that allocates on first use, grown (not copied) to n_pixels: a failure leaves the context without
-// it (cap = 0), usable for every other call.
-int grow_pixels(pbrs_ctx* c, size_t n_pixels, void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) {
-    if (n_pixels <= cap) return PBRS_OK;
-    cap = 0;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    const size_t total = n_pixels * bytes_per_pixel;
-    hipError_t e = hipMalloc(ptr, total);
+int DeviceBuffer::grow(pbrs_ctx* c, size_t bytes, const char* what) {
+    if (bytes <= cap_bytes) return PBRS_OK;
+    cap_bytes = 0;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
-        *ptr = nullptr;
-        c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
+        p = nullptr;
+        c->error = std::string("hipMalloc of ") + what + " (" + std::to_string(bytes >> 20) + " MiB): " + hipGetErrorString(e);
         (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
         return PBRS_E_DEVICE;
     }
-    cap = n_pixels;
+    cap_bytes = bytes;
     return PBRS_OK;
 }
 
-// The AOV state (and, with `staging`, the host variant's output buffers) for n_pixels, as ensure_work allocates: a failure leaves
-// the context without them (cap_aov_* = 0), usable for every other call.
-int ensure_aov(pbrs_ctx* c, size_t n_pixels, bool staging) {
-    auto grow = [&](void** ptr, size_t& cap, size_t bytes_per_pixel, const char* what) { return grow_pixels(c, n_pixels, ptr, cap, bytes_per_pixel, what); };
-    int rc = grow(reinterpret_cast<void**>(&c->aov_state), c->cap_aov_pixels, PBRS_AOV_STATE_WORDS * sizeof(float), "the AOV state");
-    if (rc || !staging) return rc;
-    return grow(&c->aov_out, c->cap_aov_out_pixels, kAovOutWords * sizeof(uint32_t), "the AOV buffers");
+// One buffer of a host variant's device staging: the caller's host pointer (null: not given, or not wanted), its words per pixel, and
+// where `stage` put it on the device (null with the host pointer).
+struct Staged {
+    const void* host;
+    size_t words;
+    void* dev = nullptr;
+    template <class T>
+    T* as() const { return static_cast<T*>(dev); }
+};
+
+// Lays the n buffers of `s` out in `buf`, one after the other in the order of `s`, for P pixels.  `buf` is grown to hold all n, given or
+// not: neither its size nor where a buffer sits depends on which ones a call asks for.  The allocation, the device pointers and
+// (copy_staged) the copies all follow from the words per pixel in `s`.
+int stage(pbrs_ctx* c, DeviceBuffer& buf, const char* what, Staged* s, size_t n, size_t P) {
+    size_t words = 0;
+    for (size_t k = 0; k < n; ++k) words += s[k].words;
+    int rc = buf.grow(c, words * P * sizeof(uint32_t), what);
+    if (rc) return rc;
+    uint32_t* at = buf.as<uint32_t>();
+    for (size_t k = 0; k < n; ++k) {
+        s[k].dev = s[k].host ? at : nullptr;
+        at += s[k].words * P;
+    }
+    return PBRS_OK;
 }
 
-// The filtered film's sums for n_pixels tile pixels; a failure leaves the context without them, usable for every other call.
-int ensure_filter(pbrs_ctx* c, size_t n_pixels) {
-    return grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->filter_sum), c->cap_filter_pixels, 4 * sizeof(float), "the filter sums");
+// The given buffers of `s` to the device (hipMemcpyHostToDevice) or back to the host, on the context's stream.
+int copy_staged(pbrs_ctx* c, const Staged* s, size_t n, size_t P, hipMemcpyKind kind) {
+    for (size_t k = 0; k < n; ++k) {
+        if (!s[k].host) continue;
+        void* host = const_cast<void*>(s[k].host);
+        const bool up = kind == hipMemcpyHostToDevice;
+        HIPCHK(c, hipMemcpyAsync(up ? s[k].dev : host, up ? host : s[k].dev, s[k].words * P * sizeof(uint32_t), kind, c->stream));
+    }
+    return PBRS_OK;
 }
 
 constexpr size_t kDenoiseBytesPerPixel = 3 * sizeof(float4) + sizeof(uint32_t);
-// rgb, albedo, normal, depth, instance; variance-guided: and variance, variance_out
-constexpr size_t kDenoiseStageWords[2] = {3 + 3 + 3 + 1 + 1, 3 + 3 + 3 + 1 + 1 + 1 + 1};
 
-// A denoiser's scratch (and, with `staging`, the host variant's buffers) for n_pixels: grown like the AOV state; a failure leaves the
-// context without it, usable for every other call.  The variance-guided denoiser keeps scratch of its own (the planes have the plain
-// one's size).
-int ensure_denoise(pbrs_ctx* c, bool var, size_t n_pixels, bool staging) {
-    DenoiseScratch& d = c->denoise[var];
-    int rc = grow_pixels(c, n_pixels, &d.mem, d.cap_pixels, kDenoiseBytesPerPixel, var ? "the variance-guided denoiser's scratch" : "the denoiser's scratch");
-    if (rc || !staging) return rc;
-    return grow_pixels(c, n_pixels, &d.stage, d.cap_stage_pixels, kDenoiseStageWords[var] * sizeof(float),
-                       var ? "the variance-guided denoiser's staging" : "the denoiser's staging");
-}
+// What a render produces beside its statistics, as render_common and run_pass see it: device pointers.  Each feature's state lives in
+// the context (pbrs_ctx::buf), allocated by `render` before the pass size is computed.
+struct RenderTargets {
+    float* rgb = nullptr;      // the image: w x h of the params; a filtered render: the tile's filt->w x filt->h pixels
+    pbrs_aov_buffers aovs{};   // the first-hit AOVs wanted (all null: none), from the state in BUF_AOV_STATE
+    float* variance = nullptr; // the variance AOV (null: none), from the moments in BUF_MOMENT_STATE
+    // the id matte (want_matte; arguments checked by check_targets), from the tables in BUF_MATTE_STATE
+    bool want_matte = false;
+    const pbrs_matte_params* matte = nullptr;
+    pbrs_matte_buffers matte_out{};
+    // a filtered render: the params are then its traced region (check_filter) and the pass is folded into BUF_FILTER_SUM
+    const FilterConst* filt = nullptr;
 
-// The moment state of the variance AOV (and, with `staging`, the host variant's output buffer) for n_pixels.
-int ensure_moments(pbrs_ctx* c, size_t n_pixels, bool staging) {
-    int rc = grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->moment_state), c->cap_moment_pixels, PBRS_MOMENT_STATE_WORDS * sizeof(float),
-                         "the variance AOV's moments");
-    if (rc || !staging) return rc;
-    return grow_pixels(c, n_pixels, reinterpret_cast<void**>(&c->variance_out), c->cap_variance_out_pixels, sizeof(float), "the variance buffer");
-}
-
-// The matte state (and, with `staging`, the host variants' buffers) for n_pixels at `slots` entries per pixel.
-int ensure_matte(pbrs_ctx* c, size_t n_pixels, uint32_t slots, bool state, bool staging) {
-    const size_t words = n_pixels * PBRS_MATTE_STATE_WORDS(slots);
-    int rc = state ? grow_pixels(c, words, reinterpret_cast<void**>(&c->matte_state), c->cap_matte_words, sizeof(uint32_t), "the matte state") : PBRS_OK;
-    if (rc || !staging) return rc;
-    return grow_pixels(c, words, reinterpret_cast<void**>(&c->matte_out), c->cap_matte_out_words, sizeof(uint32_t), "the matte buffers");
-}
-
-void free_aov(pbrs_ctx* c) {
-    if (c->aov_state) (void)hipFree(c->aov_state);
-    if (c->aov_out) (void)hipFree(c->aov_out);
-    c->aov_state = nullptr;
-    c->aov_out = nullptr;
-    c->cap_aov_pixels = c->cap_aov_out_pixels = 0;
-}
-
-bool any_aov(const pbrs_aov_buffers* a) {
-    return a && (a->albedo || a->normal || a->coverage || a->depth || a->instance || a->material || a->prim);
-}
+    bool want_aovs() const {
+        const pbrs_aov_buffers& a = aovs;
+        return a.albedo || a.normal || a.coverage || a.depth || a.instance || a.material || a.prim;
+    }
+};
 
 uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p);
 
@@ -486,8 +472,15 @@ int check_params(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* 
     if (p->integrator == PBRS_INTEGRATOR_NORMALS && !c->has_vis_records)
         return fail(c, PBRS_E_INVALID, "the scene's materials carry no pbrs_material::vis_bxdf records");
     if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "tile above 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The samples per pass of a render of `p` (checked by check_params), from the memory that is free on the current device NOW: whatever the
+// call allocates beside the path state comes first.
+int pass_size(pbrs_ctx* c, const pbrs_render_params* p, uint32_t& K) {
+    K = auto_samples_per_pass(c, p);
     // records keep two flag bits next to the slot index, and 16-byte records are addressed with 32-bit element indices
-    if ((uint64_t)p->w * p->h * auto_samples_per_pass(c, p) >= (1ull << 28)) return fail(c, PBRS_E_LIMIT, "tile x samples_per_pass above 2^28 paths");
+    if ((uint64_t)p->w * p->h * K >= (1ull << 28)) return fail(c, PBRS_E_LIMIT, "tile x samples_per_pass above 2^28 paths");
     return PBRS_OK;
 }
 
@@ -587,7 +580,7 @@ uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p) {
             const uint64_t per_path = PBRS_STATE_BYTES_PER_PATH;  // path, hit, radiance, shadow-ray and nee records
             // what this context already holds for paths counts as available: the answer must not change between calls
             // (... in both of its pass sets: a set may take a quarter of the memory, the two of them half)
-            const uint64_t held = (uint64_t)c->cap_slots + (uint64_t)c->pass_set[c->cur_set ^ 1].cap_slots;
+            const uint64_t held = (uint64_t)c->pass_set[0].cap_slots + (uint64_t)c->pass_set[1].cap_slots;
             const uint64_t fit = ((uint64_t)free_b + held * per_path) / 4 / per_path;
             if (fit < target) target = fit < (4ull << 20) ? (4ull << 20) : fit;
         }
@@ -808,16 +801,22 @@ constexpr MatteKernels kMatte[PBRS_MATTE_MAX_SLOTS] = {PBRS_MATTE_KERNELS(1), PB
                                                        PBRS_MATTE_KERNELS(5), PBRS_MATTE_KERNELS(6), PBRS_MATTE_KERNELS(7), PBRS_MATTE_KERNELS(8)};
 #undef PBRS_MATTE_KERNELS
 
+// The bounces a pass runs: one k_extend, k_shade and k_shadow stage each.
+uint32_t bounce_count(const RenderConst& rc) {
+    // the direct-lighting integrator is at most two rays deep whatever `depth` says (directlighting.rs:15-17, :36, :49)
+    if (rc.integrator == PBRS_INTEGRATOR_DIRECT) return rc.max_depth ? 2u : 0u;
+    if (rc.integrator >= PBRS_INTEGRATOR_MATERIALS) return 1u;  // the visualisers: one cast, no lights
+    return rc.max_depth;
+}
+
 // One pass: kc sample indices starting at `first` for every pixel of the tile.
 // `handoff`: the pass moves to the late stream at bounce pbrs_ctx::overlap_from (at the latest for its k_accumulate: the late stream runs
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
-// `aov`: the AOV state k_aov folds this pass's first hits into (null: no AOVs).
-// `filt`: a filtered render (rc is its traced region): k_filter_accumulate folds the pass into pbrs_ctx::filter_sum instead of k_accumulate.
-// `moments`: the moment state of the variance AOV k_moments folds this pass's radiances into (null: no variance).
-// `matte`: the matte tables k_matte folds this pass's first hits into (null: no matte).
-int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff = false, float* aov = nullptr,
-             const FilterConst* filt = nullptr, float* moments = nullptr, const pbrs_matte_params* matte = nullptr) {
-    pbrs_ctx::PassSet& set = c->pass_set[c->cur_set];
+// `t`: what the render produces.  The pass folds its first hits into the AOV state (k_aov) and the matte tables (k_matte) and its
+// radiances into the moments of the variance AOV (k_moments), each where asked for; a filtered render (rc is its traced region) folds
+// the pass into the filter sums (k_filter_accumulate) instead of k_accumulate.
+int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff, const RenderTargets& t) {
+    pbrs_ctx::PassSet& set = cur(c);
     // the set's memory is free once the pass that used it last has accumulated (two passes back, on the late stream)
     if (handoff && set.in_flight) HIPCHK(c, hipStreamWaitEvent(c->stream, set.accumulated, 0));
     auto to_late_stream = [&]() -> hipError_t {
@@ -834,15 +833,15 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     // persistent traversal kernels: enough blocks to fill the chip, each pulls work until the queue is empty
     const uint32_t pgrid = grid < kPersistentBlocks ? grid : kPersistentBlocks;
     const uint32_t stride = kMaxDepth + 2;
-    uint32_t* act = c->counters;                 // act[b]: paths entering bounce b (b >= 1)
+    uint32_t* act = set.counters;               // act[b]: paths entering bounce b (b >= 1)
     // ns[b]: one 64-bit word per bounce: low half = paths whose light estimate waits for visibility, high half = shadow rays
-    unsigned long long* ns = reinterpret_cast<unsigned long long*>(c->counters + stride);
-    uint32_t* slows = c->counters + 3 * stride;  // k_shadow's slow-list length per bounce
+    unsigned long long* ns = reinterpret_cast<unsigned long long*>(set.counters + stride);
+    uint32_t* slows = set.counters + 3 * stride;  // k_shadow's slow-list length per bounce
     // work-fetch heads of k_extend / k_shadow: kHeadWords words per bounce (one head per queue segment, kernels.h)
-    uint32_t* xhead = c->counters + 4 * stride;
+    uint32_t* xhead = set.counters + 4 * stride;
     uint32_t* shead = xhead + stride * kHeadWords;
     uint32_t* shead2 = shead + stride * kHeadWords;  // the binary-walk launch over k_shadow's slow list
-    uint32_t* neeq = c->neeq;
+    uint32_t* neeq = set.neeq;
     const KernelPlan& plan = c->plan;
     const IntegratorPlan& ip = plan.integ[rc.integrator];
     const StageKernel<extend_fn_t>& xk = plan.extend[stats];
@@ -851,15 +850,12 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     // alone, and the instrumented variant, which carries every feature, must then walk the tree like the timed one
     DevScene xS = c->S;
     if (!(xS.features & PBRS_FEAT_FLAT_TLAS)) xS.n_flat = 0u;
-    HIPCHK(c, hipMemsetAsync(c->counters, 0, kCounterWords * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(set.counters, 0, kCounterWords * sizeof(uint32_t), c->stream));
     if (tm.begin(0)) return fail(c, PBRS_E_DEVICE, "event record failed");
-    hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, c->stream, c->st, rc);
+    hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, c->stream, set.st, rc);
     tm.end();
     poll_split_probe(c);
-    // the direct-lighting integrator is at most two rays deep whatever `depth` says (directlighting.rs:15-17, :36, :49)
-    const uint32_t n_bounces = rc.integrator == PBRS_INTEGRATOR_DIRECT      ? (rc.max_depth ? 2u : 0u)
-                               : rc.integrator >= PBRS_INTEGRATOR_MATERIALS ? 1u  // the visualisers: one cast, no lights
-                                                                            : rc.max_depth;
+    const uint32_t n_bounces = bounce_count(rc);
     // this pass counts what k_extend's queue split keeps (the first path-integrator pass of an uploaded one-class scene)
     const bool probe_split = c->split_decision == 0 && !c->split_probe_in_flight && rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && n_bounces > 0;
     for (uint32_t b = 0; b < n_bounces; ++b) {
@@ -871,7 +867,7 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         // the path integrator on a scene with one shading class (no class sort): k_extend splits its queue into the hits k_shade
         // shades, the paths that only end (emitter hits, misses that see the environment) and the misses nothing happens to
         const uint32_t qsplit = (rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && c->split_decision != 2) ? (1u | (b == 0 ? 2u : 0u)) : 0u;
-        hipLaunchKernelGGL(xk.fn, dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, c->st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr, nullptr,
+        hipLaunchKernelGGL(xk.fn, dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, set.st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr, nullptr,
                            nullptr, qsplit);
         c->pending.kernel_features_extend = xk.features;
         tm.end();
@@ -880,44 +876,45 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         // passes, so their k_aov launches must run in pass order on one stream: bounce 0 runs on the main stream for every pass unless
         // overlap_from is 0 (a developer override), and then on the late stream for every pass — one stream either way, in pass order
         // (render_common joins the late stream before k_aov_finalize).
-        if (b == 0 && aov)
-            hipLaunchKernelGGL(k_aov, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, c->st, aov, P, kc, rc.chunk_pixels, qsplit);
+        if (b == 0 && t.want_aovs())
+            hipLaunchKernelGGL(k_aov, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, set.st, c->buf[BUF_AOV_STATE].as<float>(), P, kc,
+                               rc.chunk_pixels, qsplit);
         // id mattes: the same hit records, the same place and stream for the same reasons
-        if (b == 0 && matte)
-            hipLaunchKernelGGL(kMatte[matte->slots - 1u].fold, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S.inst, c->st, c->matte_state, P, kc,
-                               rc.chunk_pixels, qsplit, matte->key);
+        if (b == 0 && t.want_matte)
+            hipLaunchKernelGGL(kMatte[t.matte->slots - 1u].fold, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S.inst, set.st,
+                               c->buf[BUF_MATTE_STATE].as<uint32_t>(), P, kc, rc.chunk_pixels, qsplit, t.matte->key);
         if (tm.begin(2)) return fail(c, PBRS_E_DEVICE, "event record failed");
         // the queue in the order the plan asks for; a queue k_extend split: class-major over its two classes, class 1 = the kept paths, last
         const IntegratorPlan::Order order = qsplit ? IntegratorPlan::CLASS_MAJOR : ip.order;
         const uint32_t n_tiles = (N + PBRS_SORT_TILE - 1) / PBRS_SORT_TILE;
         if (order == IntegratorPlan::CLASS_MAJOR) {
-            if (qsplit) hipLaunchKernelGGL(k_class_count<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
-            else hipLaunchKernelGGL(k_class_count<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
-            hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, c->st, cnt_in, N, qsplit ? 1u : ip.last_class,
+            if (qsplit) hipLaunchKernelGGL(k_class_count<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
+            else hipLaunchKernelGGL(k_class_count<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
+            hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, set.st, cnt_in, N, qsplit ? 1u : ip.last_class,
                                (qsplit && probe_split) ? c->bounce_acc + 2 * PBRS_STATS_MAX_BOUNCES : nullptr);
-            if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
-            else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
+            if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
+            else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
         } else if (order == IntegratorPlan::CLASS_SORT) {
-            hipLaunchKernelGGL(k_class_sort, dim3(n_tiles), dim3(kBlock), 0, c->stream, c->st, cnt_in, N);
+            hipLaunchKernelGGL(k_class_sort, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
         }
         const uint32_t sorted = order != IntegratorPlan::NO_ORDER ? 1u : 0u;
         for (uint32_t k = 0; k < ip.n_shade; ++k) {
             const ShadeLaunch& l = ip.shade[k];
             // one class range of a class-major queue; a split queue: the kept paths
-            const uint2* range = l.range ? c->st.class_range + l.range : qsplit ? c->st.class_range + 1 : nullptr;
-            hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), l.lds, c->stream, c->S, c->st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b, sorted, range);
+            const uint2* range = l.range ? set.st.class_range + l.range : qsplit ? set.st.class_range + 1 : nullptr;
+            hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), l.lds, c->stream, c->S, set.st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b, sorted, range);
         }
         tm.end();
         if (tm.begin(3)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        hipLaunchKernelGGL(sk.fn, dim3(pgrid), dim3(kBlock), sk.lds, c->stream, c->S, c->st, reinterpret_cast<const uint32_t*>(ns + b), shead + b * kHeadWords, c->gcnt + 1,
-                           nullptr, c->slow, slows + b);
+        hipLaunchKernelGGL(sk.fn, dim3(pgrid), dim3(kBlock), sk.lds, c->stream, c->S, set.st, reinterpret_cast<const uint32_t*>(ns + b), shead + b * kHeadWords, c->gcnt + 1,
+                           nullptr, set.slow, slows + b);
         c->pending.kernel_features_shadow = sk.features;
         if (plan.wide_shadow && !stats) {  // what the wide walks refused (rays outside the guarded range of the division-free box test, overlong stacks)
             const StageKernel<shadow_fn_t>& slow = plan.shadow_slow;
-            hipLaunchKernelGGL(slow.fn, dim3(pgrid < kSlowGrid ? pgrid : kSlowGrid), dim3(kBlock), slow.lds, c->stream, c->S, c->st, slows + b, shead2 + b * kHeadWords,
-                               c->gcnt + 1, c->slow, nullptr, nullptr);
+            hipLaunchKernelGGL(slow.fn, dim3(pgrid < kSlowGrid ? pgrid : kSlowGrid), dim3(kBlock), slow.lds, c->stream, c->S, set.st, slows + b, shead2 + b * kHeadWords,
+                               c->gcnt + 1, set.slow, nullptr, nullptr);
         }
-        hipLaunchKernelGGL(k_nee_resolve, dim3(sgrid), dim3(kBlock), 0, c->stream, c->st, neeq, reinterpret_cast<const uint32_t*>(ns + b));
+        hipLaunchKernelGGL(k_nee_resolve, dim3(sgrid), dim3(kBlock), 0, c->stream, set.st, neeq, reinterpret_cast<const uint32_t*>(ns + b));
         tm.end();
     }
     if (probe_split) {
@@ -934,13 +931,14 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         hipLaunchKernelGGL(k_sum_bounce_counts, dim3(1), dim3(64), 0, c->stream, act, ns, N, n_bounces, c->bounce_acc);
     if (handoff && c->stream != c->second_stream) HIPCHK(c, to_late_stream());
     if (tm.begin(4)) return fail(c, PBRS_E_DEVICE, "event record failed");
-    if (filt)
+    if (const FilterConst* filt = t.filt)
         hipLaunchKernelGGL(k_filter_accumulate, dim3((filt->w + PBRS_FILTER_CELL - 1) / PBRS_FILTER_CELL, (filt->h + PBRS_FILTER_CELL - 1) / PBRS_FILTER_CELL),
-                           dim3(kBlock), filter_lds_bytes(filt->hx, filt->hy), c->stream, c->st, c->filter_sum, rc, *filt, kc, c->nonfinite);
+                           dim3(kBlock), filter_lds_bytes(filt->hx, filt->hy), c->stream, set.st, c->buf[BUF_FILTER_SUM].as<float>(), rc, *filt, kc, c->nonfinite);
     else
-        hipLaunchKernelGGL(k_accumulate, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, c->sum, P, kc, rc.chunk_pixels, rc.w, rc.tiles8_per_row, c->nonfinite);
+        hipLaunchKernelGGL(k_accumulate, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, set.st, c->sum, P, kc, rc.chunk_pixels, rc.w, rc.tiles8_per_row, c->nonfinite);
     // the variance AOV: the same radiances, on the stream that runs the passes' accumulations in pass order
-    if (moments) hipLaunchKernelGGL(k_moments, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, moments, P, kc, rc.chunk_pixels);
+    if (t.variance)
+        hipLaunchKernelGGL(k_moments, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, set.st, c->buf[BUF_MOMENT_STATE].as<float>(), P, kc, rc.chunk_pixels);
     tm.end();
     if (handoff) {
         HIPCHK(c, hipEventRecord(set.accumulated, c->stream));
@@ -950,22 +948,15 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     return PBRS_OK;
 }
 
-// `aovs` (device pointers; null or all-null: none): the first-hit AOVs too, from the state ensure_aov allocated.
-// `filt`: a filtered render; `p` is then its traced region (check_filter) and rgb_device receives the tile's filt->w x filt->h pixels,
-// from the sums ensure_filter allocated.
-// `variance` (device pointer; null: none): the variance AOV too, from the state ensure_moments allocated.
-// `matte`, `matte_out` (device pointers; null: none): the id matte too (arguments checked by check_matte), from the state ensure_matte allocated.
-int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_device, const pbrs_aov_buffers* aovs = nullptr,
-                  const FilterConst* filt = nullptr, float* variance = nullptr, const pbrs_matte_params* matte = nullptr,
-                  const pbrs_matte_buffers* matte_out = nullptr) {
-    HIPCHK(c, hipSetDevice(c->device));  // before check_params: the automatic pass size reads THIS device's free memory
-    int rcode = check_params(c, cam, p);
-    if (rcode) return rcode;
+// Queues a render of `p` (checked; K its samples per pass, the working set and the targets' state there) into `t` on the context's stream.
+int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, uint32_t K, const RenderTargets& t) {
     const uint32_t P = p->w * p->h;
     const uint32_t spp = p->strata_x * p->strata_y;
-    const uint32_t K = auto_samples_per_pass(c, p);
-    rcode = ensure_work(c, (size_t)P * K, P);
-    if (rcode) return rcode;
+    const FilterConst* filt = t.filt;
+    float* aov = t.want_aovs() ? c->buf[BUF_AOV_STATE].as<float>() : nullptr;
+    float* moments = t.variance ? c->buf[BUF_MOMENT_STATE].as<float>() : nullptr;
+    uint32_t* matte = t.want_matte ? c->buf[BUF_MATTE_STATE].as<uint32_t>() : nullptr;
+    float* filter_sum = c->buf[BUF_FILTER_SUM].as<float>();
     RenderConst rc = make_const(c, cam, p);
     const bool stats = p->collect_counters != 0;
     Timer tm{c, p->time_stages != 0};
@@ -978,32 +969,25 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (stats) HIPCHK(c, hipMemsetAsync(c->bounce_acc, 0, 2 * PBRS_STATS_MAX_BOUNCES * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->nonfinite, 0, sizeof(unsigned long long), c->stream));
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[0], c->stream));
-    if (filt) HIPCHK(c, hipMemsetAsync(c->filter_sum, 0, 4 * (size_t)filt->w * filt->h * sizeof(float), c->stream));
+    if (filt) HIPCHK(c, hipMemsetAsync(filter_sum, 0, 4 * (size_t)filt->w * filt->h * sizeof(float), c->stream));
     else HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
-    float* aov = any_aov(aovs) ? c->aov_state : nullptr;
     if (aov) HIPCHK(c, hipMemsetAsync(aov, 0, PBRS_AOV_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
-    float* moments = variance ? c->moment_state : nullptr;
     if (moments) HIPCHK(c, hipMemsetAsync(moments, 0, PBRS_MOMENT_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
-    if (matte) HIPCHK(c, hipMemsetAsync(c->matte_state, 0, PBRS_MATTE_STATE_WORDS(matte->slots) * (size_t)P * sizeof(uint32_t), c->stream));
+    if (matte) HIPCHK(c, hipMemsetAsync(matte, 0, PBRS_MATTE_STATE_WORDS(t.matte->slots) * (size_t)P * sizeof(uint32_t), c->stream));
     uint32_t passes = 0;
     // Where the render has more than one pass, passes alternate between the two pass sets and hand their late bounces to the second
     // stream: those are near-empty launches that end with the latency of their longest walks (C4: 47 ms per frame in kernels that leave
     // most of the chip idle, profiles/r04k_trace_gaps_c4.log) — the next pass's first bounces, queued behind the hand-over on the main
     // stream, fill it.  The instrumented render keeps one stream (its counters are per pass).
     bool two = c->overlap_passes && !stats && spp > K;
-    if (two) {
-        use_pass_set(c, 1);
-        rcode = ensure_work(c, (size_t)P * K, P);
-        use_pass_set(c, 0);
-        if (rcode) {  // no memory for the second set (a device shared with other processes): every pass on the main stream, as before
-            two = false;
-            c->error.clear();
-        }
+    if (two && ensure_work(c, c->pass_set[1], (size_t)P * K, P)) {
+        two = false;  // no memory for the second set (a device shared with other processes): every pass on the main stream, as before
+        c->error.clear();
     }
     for (uint32_t first = 0; first < spp; first += K) {
         uint32_t kc = spp - first < K ? spp - first : K;
         if (two) use_pass_set(c, (int)(passes & 1u));  // (also: back to the main stream)
-        rcode = run_pass(c, rc, first, kc, stats, tm, two, aov, filt, moments, matte);
+        const int rcode = run_pass(c, rc, first, kc, stats, tm, two, t);
         if (rcode) {
             use_pass_set(c, 0);
             return rcode;
@@ -1011,29 +995,28 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
         ++passes;
     }
     if (two) {
-        const hipEvent_t last = c->pass_set[c->cur_set].accumulated;
+        const hipEvent_t last = cur(c).accumulated;
         use_pass_set(c, 0);
         HIPCHK(c, hipStreamWaitEvent(c->main_stream, last, 0));  // the late stream has run every pass's accumulation, in order
     }
     if (filt) {
         const uint32_t PT = filt->w * filt->h;
-        hipLaunchKernelGGL(k_filter_finalize, dim3((PT + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->filter_sum, rgb_device, PT);
+        hipLaunchKernelGGL(k_filter_finalize, dim3((PT + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, filter_sum, t.rgb, PT);
     } else {
-        hipLaunchKernelGGL(k_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->sum, rgb_device, P, 1.0f / (float)spp);
+        hipLaunchKernelGGL(k_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->sum, t.rgb, P, 1.0f / (float)spp);
     }
     if (aov)
         hipLaunchKernelGGL(k_aov_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, aov, c->S.inst, P, rc.w, rc.tiles8_per_row,
-                           1.0f / (float)spp, *aovs);
+                           1.0f / (float)spp, t.aovs);
     if (moments)
-        hipLaunchKernelGGL(k_moments_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, moments, P, rc.w, rc.tiles8_per_row, variance);
+        hipLaunchKernelGGL(k_moments_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, moments, P, rc.w, rc.tiles8_per_row, t.variance);
     if (matte)
-        hipLaunchKernelGGL(kMatte[matte->slots - 1u].finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->matte_state, P, rc.w,
-                           rc.tiles8_per_row, 1.0f / (float)spp, matte_out->ids, matte_out->coverage, matte_out->residual);
+        hipLaunchKernelGGL(kMatte[t.matte->slots - 1u].finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, matte, P, rc.w,
+                           rc.tiles8_per_row, 1.0f / (float)spp, t.matte_out.ids, t.matte_out.coverage, t.matte_out.residual);
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending.passes = passes;
-    c->pending.launches_extend = c->pending.launches_shade = c->pending.launches_shadow =
-        passes * (p->integrator == PBRS_INTEGRATOR_DIRECT ? (p->max_depth ? 2u : 0u) : p->integrator >= PBRS_INTEGRATOR_MATERIALS ? 1u : p->max_depth);
+    c->pending.launches_extend = c->pending.launches_shade = c->pending.launches_shadow = passes * bounce_count(rc);
     return PBRS_OK;
 }
 
@@ -1096,6 +1079,118 @@ int configure_kernels(pbrs_ctx* c) {
     for (const void* k : traversal_kernels) HIPCHK(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
     if (c->device < 64) g_kernel_cfg_done[c->device] = true;
     return PBRS_OK;
+}
+
+// The checks of what a render is to produce, beyond check_params's.
+int check_targets(pbrs_ctx* c, const pbrs_render_params* p, const RenderTargets& t) {
+    // a render that traces no camera ray has no first hits to report
+    const bool no_camera_ray = p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0;
+    if ((t.want_aovs() || t.variance) && no_camera_ray)
+        return fail(c, PBRS_E_INVALID, "AOVs requested from a render that traces no camera ray (max_depth 0)");
+    if (!t.want_matte) return PBRS_OK;
+    const pbrs_matte_params* mp = t.matte;
+    if (!mp) return fail(c, PBRS_E_INVALID, "a matte without pbrs_matte_params");
+    if (mp->key != PBRS_MATTE_INSTANCE && mp->key != PBRS_MATTE_MATERIAL) return fail(c, PBRS_E_INVALID, "unknown matte key");
+    if (mp->slots == 0 || mp->slots > PBRS_MATTE_MAX_SLOTS) return fail(c, PBRS_E_INVALID, "matte slots must be 1 .. 8");
+    if (!t.matte_out.ids || !t.matte_out.coverage) return fail(c, PBRS_E_INVALID, "a matte needs ids and coverage");
+    if (no_camera_ray) return fail(c, PBRS_E_INVALID, "a matte requested from a render that traces no camera ray (max_depth 0)");
+    return PBRS_OK;
+}
+
+// The checks of a filtered render beyond check_params's; fills the kernel's constants and `region`, the tile plus its halo clipped to
+// the film: the params the render traces (the pass size and ensure_work see the region).
+int check_filter(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, FilterConst& fc, pbrs_render_params& region) {
+    if (p->band_count > 1) return fail(c, PBRS_E_INVALID, "a filtered render takes a rectangular tile, not interleaved row bands");
+    if (p->integrator >= PBRS_INTEGRATOR_MATERIALS) return fail(c, PBRS_E_INVALID, "the visualisers bypass the film: no pixel filter");
+    if (f->kind > PBRS_FILTER_LANCZOS) return fail(c, PBRS_E_INVALID, "unknown pixel filter kind");
+    for (int a = 0; a < 2; ++a)
+        if (!pn_isfinite(f->radius[a]) || !(f->radius[a] > 0.0f)) return fail(c, PBRS_E_INVALID, "a pixel filter radius must be finite and > 0");
+    const uint32_t n_params = f->kind == PBRS_FILTER_MITCHELL ? 2u : (f->kind == PBRS_FILTER_GAUSSIAN || f->kind == PBRS_FILTER_LANCZOS) ? 1u : 0u;
+    if ((n_params > 0 && !pn_isfinite(f->a)) || (n_params > 1 && !pn_isfinite(f->b)))
+        return fail(c, PBRS_E_INVALID, "non-finite pixel filter parameter");
+    if (f->radius[0] > PBRS_FILTER_MAX_RADIUS || f->radius[1] > PBRS_FILTER_MAX_RADIUS)
+        return fail(c, PBRS_E_LIMIT, "pixel filter radius above 4 (the halo's LDS budget)");
+    fc = FilterConst{};
+    fc.kind = f->kind;
+    fc.rx = f->radius[0], fc.ry = f->radius[1], fc.a = f->a, fc.b = f->b;
+    fc.hx = pf_halo(fc.rx), fc.hy = pf_halo(fc.ry);
+    fc.x0 = p->x0, fc.y0 = p->y0, fc.w = p->w, fc.h = p->h;
+    region = *p;
+    region.x0 = p->x0 > fc.hx ? p->x0 - fc.hx : 0u;
+    region.y0 = p->y0 > fc.hy ? p->y0 - fc.hy : 0u;
+    region.w = std::min(p->x0 + p->w + fc.hx, cam->width) - region.x0;
+    region.h = std::min(p->y0 + p->h + fc.hy, cam->height) - region.y0;
+    return check_params(c, cam, &region);
+}
+
+// Every render entry point, after its own argument checks.  `filter`: null, or a filtered render of the tile `p`.  `t`: what the caller
+// wants, in device memory, or with `host` in host memory: the render then goes through the context's staging, is copied back and waited
+// for.  A device render is only queued; it waits (collect) where the caller asks for the statistics.
+int render(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* filter, RenderTargets t, bool host, pbrs_stats* stats_out) {
+    HIPCHK(c, hipSetDevice(c->device));  // first: the buffers below and the pass size, which reads the free memory, are THIS device's
+    FilterConst fc;
+    pbrs_render_params region;
+    int rc = check_params(c, cam, p);
+    if (rc) return rc;
+    const size_t PT = (size_t)p->w * p->h;  // the tile's pixels
+    if (filter) {
+        if ((rc = check_filter(c, cam, p, filter, fc, region))) return rc;
+        t.filt = &fc;
+        p = &region;
+    }
+    if ((rc = check_targets(c, p, t))) return rc;
+    const size_t P = (size_t)p->w * p->h;  // the pixels traced: a filtered render's region, else the tile
+    // Each feature's state and, for a host render, the staging of what it writes: before the pass size reads the free memory.  The staging
+    // layouts are these tables: one buffer after the other, in the order of pbrs_aov_buffers and pbrs_matte_buffers.
+    const pbrs_aov_buffers& a = t.aovs;
+    Staged aovs[] = {{a.albedo, 3}, {a.normal, 3}, {a.coverage, 1}, {a.depth, 1}, {a.instance, 1}, {a.material, 1}, {a.prim, 1}};
+    Staged variance[] = {{t.variance, 1}};
+    const size_t slots = t.want_matte ? t.matte->slots : 0;
+    Staged matte[] = {{t.matte_out.ids, slots}, {t.matte_out.coverage, slots}, {t.matte_out.residual, 1}};
+    float* const rgb_host = t.rgb;
+    if (t.filt) rc = c->buf[BUF_FILTER_SUM].grow(c, 4 * PT * sizeof(float), "the filter sums");
+    if (t.want_aovs()) {
+        if (!rc) rc = c->buf[BUF_AOV_STATE].grow(c, PBRS_AOV_STATE_WORDS * P * sizeof(float), "the AOV state");
+        if (!rc && host) rc = stage(c, c->buf[BUF_AOV_OUT], "the AOV buffers", aovs, std::size(aovs), P);
+    }
+    if (t.variance) {
+        if (!rc) rc = c->buf[BUF_MOMENT_STATE].grow(c, PBRS_MOMENT_STATE_WORDS * P * sizeof(float), "the variance AOV's moments");
+        if (!rc && host) rc = stage(c, c->buf[BUF_VARIANCE_OUT], "the variance buffer", variance, std::size(variance), P);
+    }
+    if (t.want_matte) {
+        if (!rc) rc = c->buf[BUF_MATTE_STATE].grow(c, PBRS_MATTE_STATE_WORDS(slots) * P * sizeof(uint32_t), "the matte state");
+        if (!rc && host) rc = stage(c, c->buf[BUF_MATTE_OUT], "the matte buffers", matte, std::size(matte), P);
+    }
+    uint32_t K = 0;
+    if (!rc) rc = pass_size(c, p, K);
+    if (!rc) rc = ensure_work(c, cur(c), P * K, P);
+    if (rc) return rc;
+    if (host) {
+        t.rgb = c->rgb_dev;  // P pixels: a filtered render's tile fits
+        t.aovs = {aovs[0].as<float>(), aovs[1].as<float>(), aovs[2].as<float>(), aovs[3].as<float>(), aovs[4].as<uint32_t>(), aovs[5].as<uint32_t>(), aovs[6].as<uint32_t>()};
+        t.variance = variance[0].as<float>();
+        t.matte_out = {matte[0].as<uint32_t>(), matte[1].as<float>(), matte[2].as<float>()};
+    }
+    rc = render_common(c, cam, p, K, t);
+    if (rc) return rc;
+    if (!host) return stats_out ? collect(c, stats_out) : PBRS_OK;
+    HIPCHK(c, hipMemcpyAsync(rgb_host, t.rgb, 3 * PT * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = copy_staged(c, variance, std::size(variance), P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, aovs, std::size(aovs), P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, matte, std::size(matte), P, hipMemcpyDeviceToHost))) return rc;
+    return collect(c, stats_out);
+}
+
+// The targets of the AOV and matte entry points: the buffers given (null: none).  A matte is wanted where its buffers are given.
+RenderTargets make_targets(float* rgb, const pbrs_aov_buffers* aovs, float* variance, const pbrs_matte_params* params, const pbrs_matte_buffers* matte) {
+    RenderTargets t;
+    t.rgb = rgb;
+    if (aovs) t.aovs = *aovs;
+    t.variance = variance;
+    t.want_matte = matte != nullptr;
+    t.matte = params;
+    if (matte) t.matte_out = *matte;
+    return t;
 }
 
 }  // namespace
@@ -1161,9 +1256,8 @@ int pbrs_create(int device_ordinal, pbrs_ctx** out) {
         ok = hipEventCreate(&ev) == hipSuccess;
         if (ok) c->total_ev.push_back(ev);
     }
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->pass_set[1].counters), kCounterWords * sizeof(uint32_t)) == hipSuccess &&
-         hipMalloc(reinterpret_cast<void**>(&c->counters), kCounterWords * sizeof(uint32_t)) == hipSuccess &&
-         hipMalloc(reinterpret_cast<void**>(&c->gcnt), 2 * sizeof(GlobalCounters)) == hipSuccess &&
+    for (pbrs_ctx::PassSet& set : c->pass_set) ok = ok && hipMalloc(reinterpret_cast<void**>(&set.counters), kCounterWords * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->gcnt), 2 * sizeof(GlobalCounters)) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&c->nonfinite), sizeof(unsigned long long)) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&c->bounce_acc), (2 * PBRS_STATS_MAX_BOUNCES + 2) * sizeof(unsigned long long)) == hipSuccess &&
          hipMemset(c->bounce_acc, 0, (2 * PBRS_STATS_MAX_BOUNCES + 2) * sizeof(unsigned long long)) == hipSuccess &&
@@ -1185,20 +1279,11 @@ void pbrs_destroy(pbrs_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->second_stream) (void)hipStreamSynchronize(c->second_stream);
     free_scene(c);
-    free_work(c);  // (leaves pass set 0 in use)
-    free_aov(c);
-    if (c->filter_sum) (void)hipFree(c->filter_sum);
-    for (DenoiseScratch& d : c->denoise) {
-        if (d.mem) (void)hipFree(d.mem);
-        if (d.stage) (void)hipFree(d.stage);
-    }
-    if (c->moment_state) (void)hipFree(c->moment_state);
-    if (c->variance_out) (void)hipFree(c->variance_out);
-    if (c->matte_state) (void)hipFree(c->matte_state);
-    if (c->matte_out) (void)hipFree(c->matte_out);
-    if (c->matte_select) (void)hipFree(c->matte_select);
-    if (c->counters) (void)hipFree(c->counters);
-    if (c->pass_set[1].counters) (void)hipFree(c->pass_set[1].counters);
+    free_work(c);
+    for (DeviceBuffer& b : c->buf)
+        if (b.p) (void)hipFree(b.p);
+    for (pbrs_ctx::PassSet& set : c->pass_set)
+        if (set.counters) (void)hipFree(set.counters);
     for (int k = 0; k < 2; ++k)
         if (c->pass_set[k].accumulated) (void)hipEventDestroy(c->pass_set[k].accumulated);
     for (int k = 0; k < 2; ++k)
@@ -1588,67 +1673,12 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     return PBRS_OK;
 }
 
-int pbrs_render_tile_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, pbrs_stats* stats_out) {
-    if (!c) return PBRS_E_INVALID;
-    if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
-    int rc = render_common(c, cam, p, rgb_out_device);
-    if (rc) return rc;
-    if (stats_out) return collect(c, stats_out);
-    return PBRS_OK;
-}
-
-int pbrs_render_tile(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, pbrs_stats* stats_out) {
-    if (!c) return PBRS_E_INVALID;
-    if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_params(c, cam, p);
-    if (rc) return rc;
-    rc = ensure_work(c, (size_t)p->w * p->h * auto_samples_per_pass(c, p), (size_t)p->w * p->h);
-    if (rc) return rc;
-    rc = render_common(c, cam, p, c->rgb_dev);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * (size_t)p->w * p->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return collect(c, stats_out);
-}
-
-// The checks of the AOV entry points beyond render_common's: a render that traces no camera ray has no first hits to report.
-// `variance`: the variance AOV is requested too (pbrs_render_tile_aovs_var*).
-int check_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_aov_buffers* aovs, bool variance = false) {
-    int rc = check_params(c, cam, p);
-    if (rc || !(any_aov(aovs) || variance)) return rc;
-    if (p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0)
-        return fail(c, PBRS_E_INVALID, "AOVs requested from a render that traces no camera ray (max_depth 0)");
-    // before render_common's pass size reads the free memory
-    if (any_aov(aovs)) rc = ensure_aov(c, (size_t)p->w * p->h, false);
-    if (!rc && variance) rc = ensure_moments(c, (size_t)p->w * p->h, false);
-    return rc;
-}
-
-// The checks of the matte entry points beyond check_aovs's (a matte is requested), and its state (`staging`: and the host variant's buffers).
-int check_matte(pbrs_ctx* c, const pbrs_render_params* p, const pbrs_matte_params* mp, const pbrs_matte_buffers* m, bool staging) {
-    if (!mp) return fail(c, PBRS_E_INVALID, "a matte without pbrs_matte_params");
-    if (mp->key != PBRS_MATTE_INSTANCE && mp->key != PBRS_MATTE_MATERIAL) return fail(c, PBRS_E_INVALID, "unknown matte key");
-    if (mp->slots == 0 || mp->slots > PBRS_MATTE_MAX_SLOTS) return fail(c, PBRS_E_INVALID, "matte slots must be 1 .. 8");
-    if (!m->ids || !m->coverage) return fail(c, PBRS_E_INVALID, "a matte needs ids and coverage");
-    if (p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0)
-        return fail(c, PBRS_E_INVALID, "a matte requested from a render that traces no camera ray (max_depth 0)");
-    // before render_common's pass size reads the free memory
-    return ensure_matte(c, (size_t)p->w * p->h, mp->slots, true, staging);
-}
-
 int pbrs_render_tile_matte_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
                                   const pbrs_aov_buffers* aovs_device, float* variance_device, const pbrs_matte_params* params,
                                   const pbrs_matte_buffers* matte_device, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_aovs(c, cam, p, aovs_device, variance_device != nullptr);
-    if (!rc && matte_device) rc = check_matte(c, p, params, matte_device, false);
-    if (rc) return rc;
-    rc = render_common(c, cam, p, rgb_out_device, aovs_device, nullptr, variance_device, matte_device ? params : nullptr, matte_device);
-    if (rc) return rc;
-    if (stats_out) return collect(c, stats_out);
-    return PBRS_OK;
+    return render(c, cam, p, nullptr, make_targets(rgb_out_device, aovs_device, variance_device, params, matte_device), false, stats_out);
 }
 
 int pbrs_render_tile_aovs_var_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
@@ -1658,62 +1688,18 @@ int pbrs_render_tile_aovs_var_device(pbrs_ctx* c, const pbrs_camera* cam, const 
 
 int pbrs_render_tile_aovs_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, const pbrs_aov_buffers* aovs_device,
                                  pbrs_stats* stats_out) {
-    return pbrs_render_tile_aovs_var_device(c, cam, p, rgb_out_device, aovs_device, nullptr, stats_out);
+    return pbrs_render_tile_matte_device(c, cam, p, rgb_out_device, aovs_device, nullptr, nullptr, nullptr, stats_out);
+}
+
+int pbrs_render_tile_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device, pbrs_stats* stats_out) {
+    return pbrs_render_tile_matte_device(c, cam, p, rgb_out_device, nullptr, nullptr, nullptr, nullptr, stats_out);
 }
 
 int pbrs_render_tile_matte(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
                            float* variance_host, const pbrs_matte_params* params, const pbrs_matte_buffers* matte_host, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_aovs(c, cam, p, aovs_host, variance_host != nullptr);
-    if (!rc && matte_host) rc = check_matte(c, p, params, matte_host, true);
-    if (rc) return rc;
-    const size_t P = (size_t)p->w * p->h;
-    const bool want = any_aov(aovs_host);
-    if (want) rc = ensure_aov(c, P, true);
-    if (!rc && variance_host) rc = ensure_moments(c, P, true);
-    if (rc) return rc;
-    rc = ensure_work(c, P * auto_samples_per_pass(c, p), P);
-    if (rc) return rc;
-    // device staging of the requested buffers, in the order of pbrs_aov_buffers
-    pbrs_aov_buffers dev{};
-    float* f = static_cast<float*>(c->aov_out);
-    if (want) {
-        dev.albedo = aovs_host->albedo ? f : nullptr;
-        dev.normal = aovs_host->normal ? f + 3 * P : nullptr;
-        dev.coverage = aovs_host->coverage ? f + 6 * P : nullptr;
-        dev.depth = aovs_host->depth ? f + 7 * P : nullptr;
-        dev.instance = aovs_host->instance ? reinterpret_cast<uint32_t*>(f + 8 * P) : nullptr;
-        dev.material = aovs_host->material ? reinterpret_cast<uint32_t*>(f + 9 * P) : nullptr;
-        dev.prim = aovs_host->prim ? reinterpret_cast<uint32_t*>(f + 10 * P) : nullptr;
-    }
-    // the matte's staging: ids, coverage, residual
-    pbrs_matte_buffers mdev{};
-    const size_t MS = matte_host ? P * params->slots : 0;
-    if (matte_host) {
-        mdev.ids = c->matte_out;
-        mdev.coverage = reinterpret_cast<float*>(c->matte_out + MS);
-        mdev.residual = matte_host->residual ? reinterpret_cast<float*>(c->matte_out + 2 * MS) : nullptr;
-    }
-    rc = render_common(c, cam, p, c->rgb_dev, want ? &dev : nullptr, nullptr, variance_host ? c->variance_out : nullptr, matte_host ? params : nullptr,
-                       matte_host ? &mdev : nullptr);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (variance_host) HIPCHK(c, hipMemcpyAsync(variance_host, c->variance_out, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (want) {
-        const void* src[7] = {dev.albedo, dev.normal, dev.coverage, dev.depth, dev.instance, dev.material, dev.prim};
-        void* dst[7] = {aovs_host->albedo, aovs_host->normal, aovs_host->coverage, aovs_host->depth, aovs_host->instance, aovs_host->material, aovs_host->prim};
-        const size_t words[7] = {3, 3, 1, 1, 1, 1, 1};
-        for (int k = 0; k < 7; ++k)
-            if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], src[k], words[k] * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (matte_host) {
-        HIPCHK(c, hipMemcpyAsync(matte_host->ids, mdev.ids, MS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(matte_host->coverage, mdev.coverage, MS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (mdev.residual) HIPCHK(c, hipMemcpyAsync(matte_host->residual, mdev.residual, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    }
-    return collect(c, stats_out);
+    return render(c, cam, p, nullptr, make_targets(rgb_out_host, aovs_host, variance_host, params, matte_host), true, stats_out);
 }
 
 int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
@@ -1723,72 +1709,27 @@ int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_re
 
 int pbrs_render_tile_aovs(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
                           pbrs_stats* stats_out) {
-    return pbrs_render_tile_aovs_var(c, cam, p, rgb_out_host, aovs_host, nullptr, stats_out);
+    return pbrs_render_tile_matte(c, cam, p, rgb_out_host, aovs_host, nullptr, nullptr, nullptr, stats_out);
 }
 
-// The checks of the filtered entry points beyond render_common's; fills the kernel's constants and `region`, the tile plus its
-// halo clipped to the film: the params render_common traces (check_params, the pass size and ensure_work all see the region).
-static int check_filter(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, FilterConst& fc,
-                 pbrs_render_params& region) {
-    int rc = check_params(c, cam, p);
-    if (rc) return rc;
-    if (!f) return fail(c, PBRS_E_INVALID, "null pixel filter");
-    if (p->band_count > 1) return fail(c, PBRS_E_INVALID, "a filtered render takes a rectangular tile, not interleaved row bands");
-    if (p->integrator >= PBRS_INTEGRATOR_MATERIALS) return fail(c, PBRS_E_INVALID, "the visualisers bypass the film: no pixel filter");
-    if (f->kind > PBRS_FILTER_LANCZOS) return fail(c, PBRS_E_INVALID, "unknown pixel filter kind");
-    for (int a = 0; a < 2; ++a)
-        if (!pn_isfinite(f->radius[a]) || !(f->radius[a] > 0.0f)) return fail(c, PBRS_E_INVALID, "a pixel filter radius must be finite and > 0");
-    const uint32_t n_params = f->kind == PBRS_FILTER_MITCHELL ? 2u : (f->kind == PBRS_FILTER_GAUSSIAN || f->kind == PBRS_FILTER_LANCZOS) ? 1u : 0u;
-    if ((n_params > 0 && !pn_isfinite(f->a)) || (n_params > 1 && !pn_isfinite(f->b)))
-        return fail(c, PBRS_E_INVALID, "non-finite pixel filter parameter");
-    if (f->radius[0] > PBRS_FILTER_MAX_RADIUS || f->radius[1] > PBRS_FILTER_MAX_RADIUS)
-        return fail(c, PBRS_E_LIMIT, "pixel filter radius above 4 (the halo's LDS budget)");
-    fc = FilterConst{};
-    fc.kind = f->kind;
-    fc.rx = f->radius[0], fc.ry = f->radius[1], fc.a = f->a, fc.b = f->b;
-    fc.hx = pf_halo(fc.rx), fc.hy = pf_halo(fc.ry);
-    fc.x0 = p->x0, fc.y0 = p->y0, fc.w = p->w, fc.h = p->h;
-    region = *p;
-    region.x0 = p->x0 > fc.hx ? p->x0 - fc.hx : 0u;
-    region.y0 = p->y0 > fc.hy ? p->y0 - fc.hy : 0u;
-    region.w = std::min(p->x0 + p->w + fc.hx, cam->width) - region.x0;
-    region.h = std::min(p->y0 + p->h + fc.hy, cam->height) - region.y0;
-    rc = check_params(c, cam, &region);
-    if (rc) return rc;
-    return ensure_filter(c, (size_t)p->w * p->h);  // before render_common's pass size reads the free memory
+int pbrs_render_tile(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, pbrs_stats* stats_out) {
+    return pbrs_render_tile_matte(c, cam, p, rgb_out_host, nullptr, nullptr, nullptr, nullptr, stats_out);
 }
 
 int pbrs_render_tile_filtered_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f,
                                      float* rgb_out_device, pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->device));
-    FilterConst fc;
-    pbrs_render_params region;
-    int rc = check_filter(c, cam, p, f, fc, region);
-    if (rc) return rc;
-    rc = render_common(c, cam, &region, rgb_out_device, nullptr, &fc);
-    if (rc) return rc;
-    if (stats_out) return collect(c, stats_out);
-    return PBRS_OK;
+    if (!f) return fail(c, PBRS_E_INVALID, "null pixel filter");
+    return render(c, cam, p, f, make_targets(rgb_out_device, nullptr, nullptr, nullptr, nullptr), false, stats_out);
 }
 
 int pbrs_render_tile_filtered(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, float* rgb_out_host,
                               pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
-    HIPCHK(c, hipSetDevice(c->device));
-    FilterConst fc;
-    pbrs_render_params region;
-    int rc = check_filter(c, cam, p, f, fc, region);
-    if (rc) return rc;
-    const size_t PR = (size_t)region.w * region.h;  // >= the tile's pixels: rgb_dev holds the tile
-    rc = ensure_work(c, PR * auto_samples_per_pass(c, &region), PR);
-    if (rc) return rc;
-    rc = render_common(c, cam, &region, c->rgb_dev, nullptr, &fc);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * (size_t)p->w * p->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return collect(c, stats_out);
+    if (!f) return fail(c, PBRS_E_INVALID, "null pixel filter");
+    return render(c, cam, p, f, make_targets(rgb_out_host, nullptr, nullptr, nullptr, nullptr), true, stats_out);
 }
 
 // ---- denoisers (include/pbrs_gpu.h, device/denoise.h) ----
@@ -1841,8 +1782,9 @@ int check_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float
 int denoise_launch(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_in, const DenoiseGuides& g, float* rgb_out, float* variance_out) {
     const bool var = g.variance != nullptr;
     const uint32_t P = p.w * p.h;
-    const size_t cap = c->denoise[var].cap_pixels;
-    float4* plane[2] = {static_cast<float4*>(c->denoise[var].mem), static_cast<float4*>(c->denoise[var].mem) + cap};
+    const DeviceBuffer& scratch = c->buf[BUF_DENOISE + var];
+    const size_t cap = scratch.cap_bytes / kDenoiseBytesPerPixel;
+    float4* plane[2] = {scratch.as<float4>(), scratch.as<float4>() + cap};
     float4* guide = plane[1] + cap;
     uint32_t* ids = reinterpret_cast<uint32_t*>(guide + cap);
     const uint32_t demod = p.flags & PBRS_DENOISE_DEMODULATE;
@@ -1869,32 +1811,29 @@ int denoise_launch(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_i
     return PBRS_OK;
 }
 
+// A denoiser's scratch for P pixels.  The variance-guided denoiser keeps scratch of its own (the planes have the plain one's size).
+int grow_denoise(pbrs_ctx* c, bool var, size_t P) {
+    return c->buf[BUF_DENOISE + var].grow(c, P * kDenoiseBytesPerPixel, var ? "the variance-guided denoiser's scratch" : "the denoiser's scratch");
+}
+
 // The host variants: the image and the given guides go through the denoiser's device staging (rgb in and out, the guides, variance-guided:
 // the variance in and out), and the call waits for the result.
 int denoise_staged(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_in_host, const DenoiseGuides& host, float* rgb_out_host,
                    float* variance_out_host) {
     const bool var = host.variance != nullptr;
     const size_t P = (size_t)p.w * p.h;
-    int rc = ensure_denoise(c, var, P, true);
+    int rc = grow_denoise(c, var, P);
     if (rc) return rc;
-    float* f = static_cast<float*>(c->denoise[var].stage);
-    float* rgb = f;
-    float* vout = variance_out_host ? f + 12 * P : nullptr;
-    DenoiseGuides dev{};
-    dev.albedo = host.albedo ? f + 3 * P : nullptr;
-    dev.normal = host.normal ? f + 6 * P : nullptr;
-    dev.depth = host.depth ? f + 9 * P : nullptr;
-    dev.instance = host.instance ? reinterpret_cast<const uint32_t*>(f + 10 * P) : nullptr;
-    dev.variance = var ? f + 11 * P : nullptr;
-    const void* src[6] = {rgb_in_host, host.albedo, host.normal, host.depth, host.instance, host.variance};
-    const void* dst[6] = {rgb, dev.albedo, dev.normal, dev.depth, dev.instance, dev.variance};
-    const size_t words[6] = {3, 3, 3, 1, 1, 1};
-    for (int k = 0; k < 6; ++k)
-        if (src[k]) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(dst[k]), src[k], words[k] * P * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = denoise_launch(c, p, rgb, dev, rgb, vout);
+    // the plain denoiser's staging ends with the instance ids
+    Staged s[7] = {{rgb_in_host, 3}, {host.albedo, 3}, {host.normal, 3}, {host.depth, 1}, {host.instance, 1}, {host.variance, 1}, {variance_out_host, 1}};
+    rc = stage(c, c->buf[BUF_DENOISE_STAGE + var], var ? "the variance-guided denoiser's staging" : "the denoiser's staging", s, var ? 7 : 5, P);
+    if (!rc) rc = copy_staged(c, s, 6, P, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    float* rgb = s[0].as<float>();
+    rc = denoise_launch(c, p, rgb, {s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>(), s[5].as<float>()}, rgb, s[6].as<float>());
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (vout) HIPCHK(c, hipMemcpyAsync(variance_out_host, vout, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = copy_staged(c, s + 6, 1, P, hipMemcpyDeviceToHost))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
@@ -1907,7 +1846,7 @@ int pbrs_denoise_device(pbrs_ctx* c, const pbrs_denoise_params* p, const float* 
     int rc = check_denoise(c, p, rgb_in_device, guides_device, rgb_out_device);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = ensure_denoise(c, false, (size_t)p->w * p->h, false);
+    rc = grow_denoise(c, false, (size_t)p->w * p->h);
     if (rc) return rc;
     const pbrs_denoise_guides& g = *guides_device;
     return denoise_launch(c, *p, rgb_in_device, {g.albedo, g.normal, g.depth, g.instance, nullptr}, rgb_out_device, nullptr);
@@ -1928,7 +1867,7 @@ int pbrs_denoise_var_device(pbrs_ctx* c, const pbrs_denoise_var_params* p, const
     int rc = check_denoise_var(c, p, rgb_in_device, guides_device, rgb_out_device);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = ensure_denoise(c, true, (size_t)p->w * p->h, false);
+    rc = grow_denoise(c, true, (size_t)p->w * p->h);
     if (rc) return rc;
     return denoise_launch(c, plain_params(*p), rgb_in_device, *guides_device, rgb_out_device, variance_out_device);
 }
@@ -1962,11 +1901,12 @@ int check_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const 
 
 // The selection to the device and the kernel, on the context's stream (arguments checked).
 int matte_mask_launch(pbrs_ctx* c, uint32_t P, uint32_t slots, const uint32_t* ids, const float* coverage, const uint32_t* select, uint32_t n_select, float* mask) {
-    int rc = grow_pixels(c, PBRS_MATTE_MAX_SELECT, reinterpret_cast<void**>(&c->matte_select), c->cap_matte_select, sizeof(uint32_t), "the matte selection");
+    DeviceBuffer& sel = c->buf[BUF_MATTE_SELECT];
+    int rc = sel.grow(c, PBRS_MATTE_MAX_SELECT * sizeof(uint32_t), "the matte selection");
     if (rc) return rc;
     // from the caller's memory: the runtime has taken the bytes when the call returns, and the copy runs in the stream's order
-    if (n_select) HIPCHK(c, hipMemcpyAsync(c->matte_select, select, n_select * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_matte_mask, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), n_select * sizeof(uint32_t), c->stream, ids, coverage, c->matte_select, n_select,
+    if (n_select) HIPCHK(c, hipMemcpyAsync(sel.p, select, n_select * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_matte_mask, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), n_select * sizeof(uint32_t), c->stream, ids, coverage, sel.as<uint32_t>(), n_select,
                        P, slots, mask);
     HIPCHK(c, hipGetLastError());
     return PBRS_OK;
@@ -1989,17 +1929,13 @@ int pbrs_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const u
     int rc = check_matte_mask(c, w, h, slots, ids_host, coverage_host, select, n_select, mask_out_host);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t P = (size_t)w * h, MS = P * slots;
-    rc = ensure_matte(c, P, slots, false, true);
+    const size_t P = (size_t)w * h;
+    Staged s[3] = {{ids_host, slots}, {coverage_host, slots}, {mask_out_host, 1}};  // the staging of a matte render, the mask in the residual's place
+    rc = stage(c, c->buf[BUF_MATTE_OUT], "the matte buffers", s, 3, P);
+    if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
+    if (!rc) rc = matte_mask_launch(c, (uint32_t)P, slots, s[0].as<uint32_t>(), s[1].as<float>(), select, n_select, s[2].as<float>());
+    if (!rc) rc = copy_staged(c, s + 2, 1, P, hipMemcpyDeviceToHost);
     if (rc) return rc;
-    uint32_t* ids = c->matte_out;
-    float* coverage = reinterpret_cast<float*>(c->matte_out + MS);
-    float* mask = reinterpret_cast<float*>(c->matte_out + 2 * MS);
-    HIPCHK(c, hipMemcpyAsync(ids, ids_host, MS * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(coverage, coverage_host, MS * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = matte_mask_launch(c, (uint32_t)P, slots, ids, coverage, select, n_select, mask);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(mask_out_host, mask, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
@@ -2089,18 +2025,20 @@ int pbrs_camera_rays(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
     if (rc) return rc;
     if (!origins_out || !dirs_out) return fail(c, PBRS_E_INVALID, "null output");
     const uint32_t P = p->w * p->h;
-    rc = ensure_work(c, P, P);
+    uint32_t K;
+    if ((rc = pass_size(c, p, K))) return rc;  // (the render's limit; one sample index here)
+    rc = ensure_work(c, cur(c), P, P);
     if (rc) return rc;
     RenderConst k = make_const(c, cam, p);
     k.tiles8_per_row = 0u;  // one sample index, exported by pixel: slot = pixel
     k.pass_first_sample = sample_index;
     k.n_slots = P;
-    hipLaunchKernelGGL(k_raygen, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, k);
+    hipLaunchKernelGGL(k_raygen, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, k);
     float *d_o = nullptr, *d_d = nullptr;
     auto cleanup = [&]() { (void)hipFree(d_o); (void)hipFree(d_d); };
     TRY(hipMalloc(reinterpret_cast<void**>(&d_o), (size_t)P * 12));
     TRY(hipMalloc(reinterpret_cast<void**>(&d_d), (size_t)P * 12));
-    hipLaunchKernelGGL(k_export_rays, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, P, d_o, d_d);
+    hipLaunchKernelGGL(k_export_rays, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, P, d_o, d_d);
     TRY(hipGetLastError());
     TRY(hipMemcpyAsync(origins_out, d_o, (size_t)P * 12, hipMemcpyDeviceToHost, c->stream));
     TRY(hipMemcpyAsync(dirs_out, d_d, (size_t)P * 12, hipMemcpyDeviceToHost, c->stream));
@@ -2138,15 +2076,17 @@ int pbrs_render_sample_radiance(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_
     if (rc) return rc;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
     const uint32_t P = p->w * p->h;
-    rc = ensure_work(c, P, P);
+    uint32_t K;
+    if ((rc = pass_size(c, p, K))) return rc;  // (the render's limit; one sample index here)
+    rc = ensure_work(c, cur(c), P, P);
     if (rc) return rc;
     RenderConst k = make_const(c, cam, p);
     k.tiles8_per_row = 0u;  // one sample index, exported by pixel: slot = pixel
     Timer tm{c, false};
     HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
-    rc = run_pass(c, k, sample_index, 1, false, tm);
+    rc = run_pass(c, k, sample_index, 1, false, tm, false, RenderTargets{});
     if (rc) return rc;
-    hipLaunchKernelGGL(k_export_radiance, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->st, P, c->rgb_dev);
+    hipLaunchKernelGGL(k_export_radiance, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, P, c->rgb_dev);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(rgb_out_host, c->rgb_dev, 3 * (size_t)P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
