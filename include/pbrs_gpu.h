@@ -502,6 +502,9 @@ int pbrs_camera_rays(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, u
                      float* dirs_out);
 /* include/pbrs_numeric.h evaluated on the device (fn ids as oracle_numeric_eval). */
 int pbrs_numeric_eval(pbrs_ctx*, uint32_t fn, uint32_t n, const float* x, const float* y, float* out);
+/* Its functions of more than two operands (include/pbrs_numeric_probe.h: pn_probe_eval_k): `ops` is an n x k matrix of 32-bit
+ * words, row-major, k <= 16; out[i] is the result word of row i. */
+int pbrs_numeric_eval_k(pbrs_ctx*, uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out);
 /* Per-sample radiance of one sample index for a tile (before the sum over samples), for bisecting. */
 int pbrs_render_sample_radiance(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, uint32_t sample_index, float* rgb_out_host);
 

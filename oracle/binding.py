@@ -61,6 +61,7 @@ def lib():
         L.oracle_intersect_rays.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
         L.oracle_camera_rays.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_uint64, C.c_void_p, C.c_void_p]
         L.oracle_numeric_eval.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_numeric_eval_k.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.oracle_rng_stream.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.oracle_temperature_to_color.argtypes = [C.c_float, C.c_void_p]
         L.oracle_spd_to_color.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -73,7 +74,11 @@ def lib():
 
 
 NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "exp": 6, "ln": 7, "hypot": 8, "div": 9,
-               "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14}
+               "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "trunc": 16, "f32_to_i32": 17, "ldexp": 18, "max": 19,
+               "min": 20, "signum": 21, "weak_recip": 22, "sincos64_sin_hi": 23, "sincos64_sin_lo": 24, "sincos64_cos_hi": 25,
+               "sincos64_cos_lo": 26, "rng_u32": 27, "rng_f32": 28}
+# include/pbrs_numeric_probe.h: ids from 16 on return raw 32-bit words (view the result as uint32 where it is no f32)
+NUMERIC_K_FNS = {"mul_add": 0, "clamp": 1, "slab_filter": 2, "rng_init_lo": 3, "rng_init_hi": 4, "rng_stream_u32": 5, "rng_stream_f32": 6}
 
 
 def numeric_eval(fn, x, y=None):
@@ -84,6 +89,16 @@ def numeric_eval(fn, x, y=None):
         y = np.ascontiguousarray(y, dtype=np.float32)
         yp = y.ctypes.data
     rc = lib().oracle_numeric_eval(NUMERIC_FNS[fn], x.size, x.ctypes.data, yp, out.ctypes.data)
+    assert rc == 0
+    return out
+
+
+def numeric_eval_k(fn, ops):
+    """A function of more than two operands on the rows of `ops` (n x k, 32-bit words: float32 or uint32) -> n uint32 words."""
+    ops = np.ascontiguousarray(ops)
+    assert ops.ndim == 2 and ops.dtype.itemsize == 4
+    out = np.empty(len(ops), dtype=np.uint32)
+    rc = lib().oracle_numeric_eval_k(NUMERIC_K_FNS[fn], ops.shape[0], ops.shape[1], ops.ctypes.data, out.ctypes.data)
     assert rc == 0
     return out
 

@@ -69,6 +69,8 @@ int oracle_camera_rays(const oracle_scene*, uint32_t x0, uint32_t y0, uint32_t w
 int oracle_texture_value(const pbrs_texture_spec* tex, uint32_t n, const float* uv, const float* pos, float* rgb_out);
 int oracle_env_eval(const oracle_scene*, uint32_t n, const float* dirs, float* rgb_out);
 int oracle_numeric_eval(uint32_t fn, uint32_t n, const float* x, const float* y, float* out);
+/* functions of more than two operands (include/pbrs_numeric_probe.h): n x k words, row-major -> n words */
+int oracle_numeric_eval_k(uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out);
 /* radiometry/src/spectrum.rs: temperature_to_color(kelvin) (:38-55) and sampled_spectrum_to_color over n (lambda, value) samples
  * (:57-70).  Return the number of panic sites reached. */
 int oracle_temperature_to_color(float kelvin, float* rgb_out);

@@ -18,6 +18,7 @@
 
 #include "oracle_api.h"
 #include "ref_scene.h"
+#include "../include/pbrs_numeric_probe.h"
 
 namespace ref {
 
@@ -707,9 +708,21 @@ int oracle_numeric_eval(uint32_t fn, uint32_t n, const float* x, const float* y,
             case 12: r = pn_powi(a, (int)b); break;
             case 13: r = pn_fract(a); break;
             case 14: r = pn_floor(a); break;
-            default: return -1;
+            default:
+                if (fn < PN_PROBE_FIRST || fn > PN_PROBE_LAST) return -1;
+                r = pn_from_bits(pn_probe_eval(fn, a, b));  // raw words
         }
-        out[i] = r;
+        const uint32_t word = pn_bits(r);
+        __builtin_memcpy(out + i, &word, 4);
+    }
+    return 0;
+}
+int oracle_numeric_eval_k(uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out) {
+    if (fn > PN_PROBE_K_LAST || k > PN_PROBE_MAX_K || k < pn_probe_k_operands(fn)) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t w[PN_PROBE_MAX_K] = {0};
+        for (uint32_t j = 0; j < k; ++j) w[j] = ops[(size_t)i * k + j];
+        out[i] = pn_probe_eval_k(fn, w);
     }
     return 0;
 }

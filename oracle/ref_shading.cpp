@@ -531,12 +531,12 @@ void BSDF::sample(Vec3 wo_world, float u, float v, Color* f, Vec3* wi_out, Prob*
 static Color c3(const float* p) { return Color{p[0], p[1], p[2]}; }
 // ---- texture/src/lib.rs ------------------------------------------------------------------------------------
 float Texture::noise(Point3 p) const {  // :97-137
-    auto split = [](float f, int* i, float* u) {
+    auto split = [](float f, uint32_t* i, float* u) {
         float fl = pn_floor(f);
-        *i = (int)fl;  // `f.floor() as i32`
+        *i = (uint32_t)pn_f32_to_i32(fl);  // `f.floor() as i32`: saturating; unsigned, so that `i + di` wraps as the release build does
         *u = f - fl;
     };
-    int i, j, k;
+    uint32_t i, j, k;
     float u, v, w;
     split(p.x * freq, &i, &u);
     split(p.y * freq, &j, &v);
@@ -548,7 +548,7 @@ float Texture::noise(Point3 p) const {  // :97-137
     for (int di = 0; di < 2; ++di)
         for (int dj = 0; dj < 2; ++dj)
             for (int dk = 0; dk < 2; ++dk) {
-                uint32_t index = perm_x[(size_t)((i + di) & 255)] ^ perm_y[(size_t)((j + dj) & 255)] ^ perm_z[(size_t)((k + dk) & 255)];
+                uint32_t index = perm_x[(size_t)((i + (uint32_t)di) & 255u)] ^ perm_y[(size_t)((j + (uint32_t)dj) & 255u)] ^ perm_z[(size_t)((k + (uint32_t)dk) & 255u)];
                 c[di][dj][dk] = rand_vec[index];
             }
     float accum = 0.0f;

@@ -230,11 +230,15 @@ DENOISE_GUIDES = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth":
 
 HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
 NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "exp": 6, "ln": 7, "hypot": 8, "div": 9,
-               "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "box_quotient": 15}
+               "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "box_quotient": 15, "trunc": 16, "f32_to_i32": 17, "ldexp": 18, "max": 19,
+               "min": 20, "signum": 21, "weak_recip": 22, "sincos64_sin_hi": 23, "sincos64_sin_lo": 24, "sincos64_cos_hi": 25,
+               "sincos64_cos_lo": 26, "rng_u32": 27, "rng_f32": 28}
+# include/pbrs_numeric_probe.h: ids from 16 on return raw 32-bit words (view the result as uint32 where it is no f32)
+NUMERIC_K_FNS = {"mul_add": 0, "clamp": 1, "slab_filter": 2, "rng_init_lo": 3, "rng_init_hi": 4, "rng_stream_u32": 5, "rng_stream_f32": 6}
 
 GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_stream", "pbrs_set_pass_overlap", "pbrs_upload_scene", "pbrs_render_tile",
                "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
-               "pbrs_numeric_eval", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
+               "pbrs_numeric_eval", "pbrs_numeric_eval_k", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
                "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device",
                "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device",
                "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device"]
@@ -304,6 +308,7 @@ def gpu_lib():
         L.pbrs_last_intersect_info.argtypes = [C.c_void_p, C.c_void_p]
         L.pbrs_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.pbrs_numeric_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbrs_numeric_eval_k.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.pbrs_render_sample_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.pbrs_render_tile_aovs.argtypes = [C.c_void_p] * 6
         L.pbrs_render_tile_aovs_device.argtypes = [C.c_void_p] * 6
@@ -817,4 +822,13 @@ class Context:
             y = np.ascontiguousarray(y, dtype=np.float32)
             yp = y.ctypes.data
         self._check(self._L.pbrs_numeric_eval(self._h, NUMERIC_FNS[fn], x.size, x.ctypes.data, yp, out.ctypes.data), "pbrs_numeric_eval")
+        return out
+
+    def numeric_eval_k(self, fn, ops):
+        """A function of more than two operands on the rows of `ops` (n x k, 32-bit words: float32 or uint32) -> n uint32 words."""
+        ops = np.ascontiguousarray(ops)
+        assert ops.ndim == 2 and ops.dtype.itemsize == 4
+        out = np.empty(len(ops), dtype=np.uint32)
+        self._check(self._L.pbrs_numeric_eval_k(self._h, NUMERIC_K_FNS[fn], ops.shape[0], ops.shape[1], ops.ctypes.data, out.ctypes.data),
+                    "pbrs_numeric_eval_k")
         return out

@@ -17,6 +17,7 @@
 #include "lights.h"
 #include "textures.h"
 #include "traverse.h"
+#include "../../../include/pbrs_numeric_probe.h"
 
 struct PathState {
     // Path records by queue position i, structure-of-float4-arrays, ping-pong by bounce parity (k_shade reads set b & 1
@@ -1356,9 +1357,17 @@ __global__ void __launch_bounds__(256) k_numeric_eval(uint32_t fn, uint32_t n, c
         case 13: r = pn_fract(a); break;
         case 14: r = pn_floor(a); break;
         case 15: r = qdiv(-a, b, -(1.0f / b)); break;  // the box test's quotient (traverse.h): must equal a / b in its guarded range
-        default: break;
+        default: r = pn_from_bits(pn_probe_eval(fn, a, b)); break;  // ids 16 on: include/pbrs_numeric_probe.h (raw words)
     }
-    out[i] = r;
+    reinterpret_cast<uint32_t*>(out)[i] = pn_bits(r);
+}
+// functions of more than two operands: row i of the n x k operand matrix (words) -> one word
+__global__ void __launch_bounds__(256) k_numeric_eval_k(uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[PN_PROBE_MAX_K];
+    for (uint32_t j = 0; j < PN_PROBE_MAX_K; ++j) w[j] = j < k ? ops[(size_t)i * k + j] : 0u;
+    out[i] = pn_probe_eval_k(fn, w);
 }
 
 __global__ void __launch_bounds__(256) k_export_rays(PathState st, uint32_t n, float* origins, float* dirs) {

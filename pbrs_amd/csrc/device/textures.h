@@ -7,7 +7,9 @@
 PD float perlin_noise(const DevScene& S, const pbrs_texture& t, f3 p) {
     const float fx = p.x * t.freq, fy = p.y * t.freq, fz = p.z * t.freq;
     const float flx = pn_floor(fx), fly = pn_floor(fy), flz = pn_floor(fz);
-    const int i = (int)flx, j = (int)fly, k = (int)flz;  // `f.floor() as i32` (saturating; in range for any scene scale in use)
+    // `f.floor() as i32` saturates (turbulance scales p by up to 64: |p| freq reaches 2^31 at scene coordinates near 1e7), and the
+    // `i + di` behind it wraps as the reference's release build does: unsigned lattice indices
+    const uint32_t i = (uint32_t)pn_f32_to_i32(flx), j = (uint32_t)pn_f32_to_i32(fly), k = (uint32_t)pn_f32_to_i32(flz);
     float u = fx - flx, v = fy - fly, w = fz - flz;
     u = u * u * (3.0f - 2.0f * u);
     v = v * v * (3.0f - 2.0f * v);
@@ -22,7 +24,7 @@ PD float perlin_noise(const DevScene& S, const pbrs_texture& t, f3 p) {
         for (int dj = 0; dj < 2; ++dj)
 #pragma unroll
             for (int dk = 0; dk < 2; ++dk) {
-                const uint32_t index = perm_x[(i + di) & 255] ^ perm_y[(j + dj) & 255] ^ perm_z[(k + dk) & 255];
+                const uint32_t index = perm_x[(i + (uint32_t)di) & 255u] ^ perm_y[(j + (uint32_t)dj) & 255u] ^ perm_z[(k + (uint32_t)dk) & 255u];
                 const f3 c = ld3(rand_vec + 3u * index);
                 const f3 weight_v = mk3(u - (float)di, v - (float)dj, w - (float)dk);
                 const float dot_product = dot(c, weight_v);

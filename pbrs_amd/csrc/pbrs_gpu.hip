@@ -2050,7 +2050,7 @@ int pbrs_camera_rays(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
 int pbrs_numeric_eval(pbrs_ctx* c, uint32_t fn, uint32_t n, const float* x, const float* y, float* out) {
     if (!c) return PBRS_E_INVALID;
     if (n == 0) return PBRS_OK;
-    if (!x || !out || fn > 15) return fail(c, PBRS_E_INVALID, "bad numeric_eval arguments");
+    if (!x || !out || fn > PN_PROBE_LAST) return fail(c, PBRS_E_INVALID, "bad numeric_eval arguments");
     HIPCHK(c, hipSetDevice(c->device));
     float *d_x = nullptr, *d_y = nullptr, *d_r = nullptr;
     auto cleanup = [&]() { (void)hipFree(d_x); (void)hipFree(d_y); (void)hipFree(d_r); };
@@ -2062,6 +2062,25 @@ int pbrs_numeric_eval(pbrs_ctx* c, uint32_t fn, uint32_t n, const float* x, cons
         TRY(hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     }
     hipLaunchKernelGGL(k_numeric_eval, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, fn, n, d_x, d_y, d_r);
+    TRY(hipGetLastError());
+    TRY(hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    TRY(hipStreamSynchronize(c->stream));
+    cleanup();
+    return PBRS_OK;
+}
+
+int pbrs_numeric_eval_k(pbrs_ctx* c, uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out) {
+    if (!c) return PBRS_E_INVALID;
+    if (n == 0) return PBRS_OK;
+    if (!ops || !out || fn > PN_PROBE_K_LAST || k > PN_PROBE_MAX_K || k < pn_probe_k_operands(fn))
+        return fail(c, PBRS_E_INVALID, "bad numeric_eval_k arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    uint32_t *d_ops = nullptr, *d_r = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_ops); (void)hipFree(d_r); };
+    TRY(hipMalloc(reinterpret_cast<void**>(&d_ops), (size_t)n * k * 4));
+    TRY(hipMalloc(reinterpret_cast<void**>(&d_r), (size_t)n * 4));
+    TRY(hipMemcpyAsync(d_ops, ops, (size_t)n * k * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_numeric_eval_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, fn, n, k, d_ops, d_r);
     TRY(hipGetLastError());
     TRY(hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     TRY(hipStreamSynchronize(c->stream));

@@ -1,9 +1,12 @@
 /* tests/slab_filter_check.c — the conservative box-test filter of include/pbrs_numeric.h against the reference's test
  * (geometry/src/bvh.rs:84-99 with correctly rounded f32 divisions) on random and adversarial boxes and rays inside the guarded
- * range of the division-free test.  Prints: cases, exact passes, filter passes, violations (exact pass without filter pass). */
+ * range of the division-free test.  Prints: cases, exact passes, filter passes, violations (exact pass without filter pass).
+ * usage: slab_filter_check N [unused|dump] [FILE]: with FILE, every case is also written to it as 14 words, the filter's 13
+ * operands in declaration order and its decision (tests/test_gpu_numeric_sweep.py runs the same cases on the device). */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "../include/pbrs_numeric.h"
 
 static uint64_t s = 0x9e3779b97f4a7c15ULL;
@@ -12,6 +15,17 @@ static float uni(void) { return (float)(u32() >> 8) * 5.9604644775390625e-8f; }
 static float range(float a, float b) { return a + (b - a) * uni(); }
 static float mn(float a, float b) { return a < b ? a : b; }
 static float mx(float a, float b) { return a > b ? a : b; }
+static FILE* g_dump;
+static int filter(const float* nr, const float* fr, const float* o, const float* r, float t_max) {
+    const int f = pn_slab_filter(nr[0], nr[1], nr[2], fr[0], fr[1], fr[2], o[0], o[1], o[2], r[0], r[1], r[2], t_max);
+    if (g_dump) {
+        const float ops[13] = {nr[0], nr[1], nr[2], fr[0], fr[1], fr[2], o[0], o[1], o[2], r[0], r[1], r[2], t_max};
+        const uint32_t word = (uint32_t)f;
+        fwrite(ops, 4, 13, g_dump);
+        fwrite(&word, 4, 1, g_dump);
+    }
+    return f;
+}
 static int exact(const float* bmin, const float* bmax, const float* o, const float* d, float t_max) {
     float lo = -INFINITY, hi = INFINITY;
     for (int a = 0; a < 3; ++a) {
@@ -46,14 +60,19 @@ static int unused_slots(long n) {
         }
         const uint32_t k = u32() % 4u;
         const float t_max = k == 0u ? INFINITY : k == 1u ? 0.0f : k == 2u ? 3.4028234663852886e38f : ldexpf(1.0f + uni(), (int)(u32() % 200u) - 100);
-        passes += pn_slab_filter(nr[0], nr[1], nr[2], fr[0], fr[1], fr[2], o[0], o[1], o[2], r[0], r[1], r[2], t_max) ? 1 : 0;
+        passes += filter(nr, fr, o, r, t_max) ? 1 : 0;
     }
     printf("%ld %ld\n", n, passes);
     return passes != 0;
 }
 int main(int argc, char** argv) {
     long n = argc > 1 ? atol(argv[1]) : 1000000;
-    if (argc > 2) return unused_slots(n);
+    if (argc > 3 && !(g_dump = fopen(argv[3], "wb"))) return 2;
+    if (argc > 2 && strcmp(argv[2], "unused") == 0) {
+        const int rc = unused_slots(n);
+        if (g_dump) fclose(g_dump);
+        return rc;
+    }
     long passes = 0, fpasses = 0, bad = 0;
     for (long i = 0; i < n; ++i) {
         float bmin[3], bmax[3], o[3], d[3], t_max;
@@ -90,7 +109,7 @@ int main(int argc, char** argv) {
             fr[a] = d[a] > 0.0f ? bmax[a] : bmin[a];
         }
         int e = exact(bmin, bmax, o, d, t_max);
-        int f = pn_slab_filter(nr[0], nr[1], nr[2], fr[0], fr[1], fr[2], o[0], o[1], o[2], r[0], r[1], r[2], t_max);
+        int f = filter(nr, fr, o, r, t_max);
         passes += e;
         fpasses += f;
         if (e && !f) {
@@ -99,5 +118,6 @@ int main(int argc, char** argv) {
         }
     }
     printf("%ld %ld %ld %ld\n", n, passes, fpasses, bad);
+    if (g_dump) fclose(g_dump);
     return bad != 0;
 }

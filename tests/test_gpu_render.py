@@ -394,6 +394,47 @@ def test_textures_and_environment_lights_match_oracle(gpu_ctx, env, integrator):
     assert np.nanstd(ref) > 0.01
 
 
+def _far_marble_floor():
+    """A strip of Perlin-marble floor at y = 0.37 around x = 4e7: freq 4 times turbulance's 64 puts the lattice coordinate of x
+    past 2^31 in the upper octaves (`f.floor() as i32` saturates) while y and z keep their fractions; |z| < 1500 keeps the
+    marble's sin(freq z + ...) inside pn_sincos's range."""
+    from pbrs_amd.spec import ENV_BLUE_SKY, SceneBuilder, deg
+    sb = SceneBuilder()
+    pl = sb.perlin(4.0, seed=5)
+    sb.instance(scenes.quad_mesh(sb, (2e7, 0.37, -1500.0), (6e7, 0.37, -1500.0), (2e7, 0.37, 1500.0), (6e7, 0.37, 1500.0), (0, 1, 0)), sb.lambertian(pl))
+    sb.env_sky(ENV_BLUE_SKY)
+    sb.set_camera(16, 12, deg(50.0), (4e7, 2000.0, -2500.0), (4e7, 0.37, 0.0))
+    return sb, pl
+
+
+def test_perlin_lattice_index_saturates_like_the_reference(gpu_ctx):
+    """texture/src/lib.rs:99 `f.floor() as i32` saturates out of range and :112 `i + di` wraps in a release build.  x86's
+    conversion gives INT_MIN there and gfx950's saturates, so a plain cast makes the two sides pick different lattice vectors:
+    both go through pn_f32_to_i32."""
+    from oracle.binding import texture_value
+    sb, pl = _far_marble_floor()
+    osc = OracleScene(sb)
+    pos = []
+    for row in range(12):
+        for col in range(16):
+            tr = osc.trace_sample(row, col, 0, 1, 1, 1, 3)
+            if tr.n_bounces and tr.bounce[0].hit:
+                pos.append(list(tr.bounce[0].pos))
+    pos = np.array(pos, dtype=np.float32)
+    assert len(pos) >= 96
+    past = (np.abs(pos.astype(np.float64)) * 4.0 * 64.0 >= 2.0 ** 31).any(axis=1)
+    fractional = (np.modf(pos.astype(np.float64) * 4.0)[0] != 0).any(axis=1)
+    assert (past & fractional).sum() >= len(pos) / 4
+    marble, panics = texture_value(sb.textures[pl], np.zeros((len(pos), 2)), pos)
+    assert panics == 0 and len(np.unique(marble[past & fractional, 0])) > 8
+    gpu_ctx.upload(pbrs_amd.HostScene(sb))
+    for strata in (1, 2):
+        ref, ost = osc.render(strata, strata, 3, 3)
+        img, _ = gpu_ctx.render(strata, strata, 3, 3)
+        assert np.isfinite(ref).all() and np.std(ref) > 0.01
+        assert (bits(img) == bits(ref)).all()
+
+
 def test_tiles_passes_and_bands_do_not_change_the_image(gpu_ctx):
     """The RNG is keyed by film pixel and sample index: any tiling, any samples_per_pass and any GPU count give
     the same bits (the multi-GPU correctness argument)."""
