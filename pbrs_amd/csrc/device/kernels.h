@@ -370,26 +370,22 @@ struct AnySel<0u, STATS, FEAT> {
 // rows (pbrs_upload_scene: C2 / C3, 8 KB) every block copies them in once and the walk's scene view points into the copy: node,
 // triangle, instance and shape fetches become ds_read_b128; what stays on the texture path is a ray's own record (fetched at its
 // start, read again when it leaves an instance) and its result.
+PD uint4* stage_array(uint4* dst, const void* src_, uint32_t n16) {  // one array into the block's LDS, 16 bytes per thread and turn; returns its end
+    const uint4* src = reinterpret_cast<const uint4*>(src_);
+    for (uint32_t i = threadIdx.x; i < n16; i += PBRS_TRAVERSAL_BLOCK) dst[i] = src[i];
+    return dst + n16;
+}
 PD DevScene stage_scene(const DevScene& G, uint32_t* lds_base) {
     DevScene S = G;
     uint4* dst = reinterpret_cast<uint4*>(__builtin_assume_aligned(lds_base + G.lds_off_words, 16));
-    const uint32_t n_nodes = G.lds_nodes * (uint32_t)(sizeof(pbrs_node) / 16), n_tv = G.lds_tris * (uint32_t)(sizeof(pbrs_tri_verts) / 16),
-                   n_inst = G.lds_inst * (uint32_t)(sizeof(pbrs_instance) / 16), n_shapes = G.lds_shapes * (uint32_t)(sizeof(pbrs_shape) / 16);
-    const uint4* src = reinterpret_cast<const uint4*>(G.nodes);
-    for (uint32_t i = threadIdx.x; i < n_nodes; i += PBRS_TRAVERSAL_BLOCK) dst[i] = src[i];
     S.nodes = reinterpret_cast<const pbrs_node*>(dst);
-    dst += n_nodes;
-    src = reinterpret_cast<const uint4*>(G.tv);
-    for (uint32_t i = threadIdx.x; i < n_tv; i += PBRS_TRAVERSAL_BLOCK) dst[i] = src[i];
+    dst = stage_array(dst, G.nodes, G.lds_nodes * (uint32_t)(sizeof(pbrs_node) / 16));
     S.tv = reinterpret_cast<const pbrs_tri_verts*>(dst);
-    dst += n_tv;
-    src = reinterpret_cast<const uint4*>(G.inst);
-    for (uint32_t i = threadIdx.x; i < n_inst; i += PBRS_TRAVERSAL_BLOCK) dst[i] = src[i];
+    dst = stage_array(dst, G.tv, G.lds_tris * (uint32_t)(sizeof(pbrs_tri_verts) / 16));
     S.inst = reinterpret_cast<const pbrs_instance*>(dst);
-    dst += n_inst;
-    src = reinterpret_cast<const uint4*>(G.shapes);
-    for (uint32_t i = threadIdx.x; i < n_shapes; i += PBRS_TRAVERSAL_BLOCK) dst[i] = src[i];
+    dst = stage_array(dst, G.inst, G.lds_inst * (uint32_t)(sizeof(pbrs_instance) / 16));
     S.shapes = reinterpret_cast<const pbrs_shape*>(dst);
+    stage_array(dst, G.shapes, G.lds_shapes * (uint32_t)(sizeof(pbrs_shape) / 16));
     __syncthreads();
     return S;
 }
@@ -400,10 +396,8 @@ static_assert(sizeof(pbrs_node) % 16 == 0 && sizeof(pbrs_tri_verts) % 16 == 0 &&
 PD DevScene stage_top(const DevScene& G, uint32_t* lds_base) {
     DevScene S = G;
     uint4* dst = reinterpret_cast<uint4*>(__builtin_assume_aligned(lds_base + G.lds_off_words, 16));
-    const uint4* src = reinterpret_cast<const uint4*>(G.nodes);
-    const uint32_t n16 = G.lds_nodes * (uint32_t)(sizeof(pbrs_node) / 16);
-    for (uint32_t i = threadIdx.x; i < n16; i += PBRS_TRAVERSAL_BLOCK) dst[i] = src[i];
     S.nodes_top = reinterpret_cast<const pbrs_node*>(dst);
+    stage_array(dst, G.nodes, G.lds_nodes * (uint32_t)(sizeof(pbrs_node) / 16));
     __syncthreads();
     return S;
 }
@@ -522,11 +516,6 @@ PD float power_heuristic2(float f_pdf, float g_pdf) {  // src/directlighting.rs:
 #ifndef PBRS_FOURIER_AK_ROWS
 #define PBRS_FOURIER_AK_ROWS 48u  // terms of a luminance series kept in LDS per lane; longer series are recomputed where they are consumed
 #endif
-PD uint4* stage_array(uint4* dst, const void* src_, uint32_t n16) {
-    const uint4* src = reinterpret_cast<const uint4*>(src_);
-    for (uint32_t i = threadIdx.x; i < n16; i += 256u) dst[i] = src[i];
-    return dst + n16;
-}
 template <uint32_t SPEC>
 PD DevScene stage_shade_scene(const DevScene& G, uint32_t* lds_base) {
     DevScene S = G;

@@ -10,6 +10,12 @@
 // wave's lanes, TriShare), or an instance boundary (ray into / out of the instance's space).  The kernels (kernels.h, PBRS_STEP_WALK) run, each round, whichever steps their lanes are
 // waiting for — lanes in different phases of their walks share the instruction stream — and refill finished lanes.
 //
+// In this file: the box test (RaySpace, qdiv, slab_rs) and the instance boundary (enter_instance, leave_instance); the two ways a wave
+// shares work among its lanes — TriShare (triangle tests) and FlatScan (the leaf boxes of a small TLAS: one scaffold, FlatScan::scan,
+// behind the exact test of the any-hit walks and the f32 filter of the closest-hit walk); the walks ClosestWalk, AnyWalk and, derived
+// from it for four-wide BLAS nodes (wide.h), AnyWalkW, whose leaf step is AnyWalk::share_leaf behind a prologue of its own; and the
+// run-to-completion drivers of the parity harness (tlas_closest, tlas_any, tlas_any_wide).
+//
 // Box test.  geometry/src/bvh.rs:84-99 divides six times per node; IEEE f32 division costs ~11 instructions on gfx950.  With
 // nr = -RN(1 / d) — the correctly rounded reciprocal, once per ray and per instance — the quotient of a numerator n is three
 // instructions on its negation nn = -n:   q0 = RN(nn nr);  e = RN(d q0 + nn), which is exact;  q = RN(e nr + q0),   and q IS
@@ -91,18 +97,6 @@ PD bool slab_rs(const pbrs_node& n, const RaySpace& R, float t_max) {
     float t_low = __builtin_fmaxf(lo_el, 0.0f);
     float t_high = __builtin_fminf(hi_el, t_max);  // minNum: a NaN extent is ignored, as f32::min does
     return t_low <= t_high;
-}
-
-// The same test with an infinite extent, for a ray on the division-free test, returning t_low = max(lo_el, 0) as well: with a
-// finite extent t the reference's test is t_low <= min(hi_el, t), i.e. this result AND t_low <= t — which is how a closest-hit
-// walk re-evaluates a scanned TLAS leaf at its turn without fetching the box again (FlatScan::run_tlow).
-PD bool slab_rs_tlow(const pbrs_node& n, const RaySpace& R, float& t_low) {
-    float t0x = qdiv(R.o.x - n.min[0], R.d.x, R.nr.x), t0y = qdiv(R.o.y - n.min[1], R.d.y, R.nr.y), t0z = qdiv(R.o.z - n.min[2], R.d.z, R.nr.z);
-    float t1x = qdiv(R.o.x - n.max[0], R.d.x, R.nr.x), t1y = qdiv(R.o.y - n.max[1], R.d.y, R.nr.y), t1z = qdiv(R.o.z - n.max[2], R.d.z, R.nr.z);
-    float lo_el = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t0x, t1x), __builtin_fminf(t0y, t1y)), __builtin_fminf(t0z, t1z));
-    float hi_el = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t0x, t1x), __builtin_fmaxf(t0y, t1y)), __builtin_fmaxf(t0z, t1z));
-    t_low = __builtin_fmaxf(lo_el, 0.0f);
-    return t_low <= hi_el;
 }
 #include "wide.h"
 
@@ -236,10 +230,47 @@ struct TriShare {
 struct FlatScan {
     PD static uint32_t pull(uint32_t from, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(from << 2), (int)v); }
     PD static float pull(uint32_t from, float v) { return __uint_as_float(pull(from, __float_as_uint(v))); }
-    // Returns, to each fresh lane, the mask of the leaves whose box its ray R (on the division-free test) passes within
-    // t_max; `tested` counts the box tests this lane ran as a helper.  Every lane of the wave calls this together;
+    // What a helper slot needs of its owner's ray and the box test it runs with it: scan()'s template parameter.  Built once per lane
+    // from the lane's own ray, from(owner) pulls the owner's.
+    struct Exact {  // the reference's test within t_max: an any-hit walk's scan
+        RaySpace O;
+        float t;
+        PD Exact(const RaySpace& R, float t_max) : O(R), t(t_max) {}
+        PD Exact from(uint32_t owner) const {
+            Exact y = *this;
+            y.O.o = mk3(pull(owner, O.o.x), pull(owner, O.o.y), pull(owner, O.o.z));
+            y.O.d = mk3(pull(owner, O.d.x), pull(owner, O.d.y), pull(owner, O.d.z));
+            y.O.nr = mk3(pull(owner, O.nr.x), pull(owner, O.nr.y), pull(owner, O.nr.z));
+            y.O.fast = true;
+            y.t = pull(owner, t);
+            return y;
+        }
+        PD bool test(const pbrs_node& n) const { return slab_rs(n, O, t); }
+    };
+    // A closest-hit walk's scan only FILTERS (an infinite extent; the reference's test of a leaf's box is made when the leaf's turn
+    // comes, ClosestWalk::node_step): the conservative f32 filter of include/pbrs_numeric.h — it passes whenever the exact test
+    // passes, in 57 instead of 120 issue cycles per box — and three pulled reciprocals instead of six pulled halves.
+    struct Filter {
+        f3 o, r;  // r: RN(1 / d), what the filter is proved on
+        PD Filter(const RaySpace& R, float) : o(R.o), r(-R.nr) {}
+        PD Filter from(uint32_t owner) const {
+            Filter y = *this;
+            y.o = mk3(pull(owner, o.x), pull(owner, o.y), pull(owner, o.z));
+            y.r = mk3(pull(owner, r.x), pull(owner, r.y), pull(owner, r.z));
+            return y;
+        }
+        PD bool test(const pbrs_node& n) const {
+            // the planes met first / last on an axis by the sign of the reciprocal (= the direction's)
+            return pn_slab_filter(r.x > 0.0f ? n.min[0] : n.max[0], r.y > 0.0f ? n.min[1] : n.max[1], r.z > 0.0f ? n.min[2] : n.max[2],
+                                  r.x > 0.0f ? n.max[0] : n.min[0], r.y > 0.0f ? n.max[1] : n.min[1], r.z > 0.0f ? n.max[2] : n.min[2], o.x, o.y, o.z,
+                                  r.x, r.y, r.z, pn_inf()) != 0;
+        }
+    };
+    // The scaffold: returns, to each fresh lane, the mask of the leaves whose box passes Ray::test for its ray R (on the division-free
+    // test); `tested` counts the box tests this lane ran as a helper.  Every lane of the wave calls this together;
     // S.n_flat <= PBRS_FLAT_TLAS_MAX_ANYHIT = 32.
-    PD static uint32_t run(const DevScene& S, bool fresh, const RaySpace& R, float t_max, uint32_t& tested) {
+    template <class Ray>
+    PD static uint32_t scan(const DevScene& S, bool fresh, const RaySpace& R, float t_max, uint32_t& tested) {
         const uint64_t m = __ballot(fresh);
         if (m == 0) return 0u;
         const uint32_t lane = threadIdx.x & 63u;
@@ -249,24 +280,19 @@ struct FlatScan {
         // lane r learns which lane holds the r-th fresh ray (the others write to lane 63, which no rank reaches unless all 64 are fresh)
         const uint32_t list = (uint32_t)__builtin_amdgcn_ds_permute((int)((fresh ? rank : 63u) << 2), (int)lane);
         const uint32_t magic = (65536u + H - 1u) / H;  // p / H == p * magic >> 16 for p < 1024
+        const Ray mine_ray(R, t_max);
         uint32_t mine = 0;
         for (uint32_t base = 0; base < total; base += 64u) {
             const uint32_t p = base + lane;
             const bool valid = p < total;
             const uint32_t r = (p * magic) >> 16, h = p - r * H;
-            const uint32_t owner = pull(r, list);
-            RaySpace O;
-            O.o = mk3(pull(owner, R.o.x), pull(owner, R.o.y), pull(owner, R.o.z));
-            O.d = mk3(pull(owner, R.d.x), pull(owner, R.d.y), pull(owner, R.d.z));
-            O.nr = mk3(pull(owner, R.nr.x), pull(owner, R.nr.y), pull(owner, R.nr.z));
-            O.fast = true;
-            const float ot = pull(owner, t_max);
+            const Ray O = mine_ray.from(pull(r, list));
             bool pass0 = false, pass1 = false;
             if (valid) {
-                pass0 = slab_rs(load_node(S.nodes + S.flat_off + h), O, ot);
+                pass0 = O.test(load_node(S.nodes + S.flat_off + h));
                 tested += 1u;
                 if (h + H < S.n_flat) {
-                    pass1 = slab_rs(load_node(S.nodes + S.flat_off + h + H), O, ot);
+                    pass1 = O.test(load_node(S.nodes + S.flat_off + h + H));
                     tested += 1u;
                 }
             }
@@ -280,97 +306,9 @@ struct FlatScan {
         }
         return mine;
     }
-    // The same for a closest-hit walk, whose scan only FILTERS (an infinite extent; the reference's test of a leaf's box is made when
-    // the leaf's turn comes, ClosestWalk::node_step): the conservative f32 filter of include/pbrs_numeric.h — it passes whenever the
-    // exact test passes, in 57 instead of 120 issue cycles per box — and three pulled reciprocals instead of six pulled halves.
-    PD static uint32_t run_filter(const DevScene& S, bool fresh, const RaySpace& R, uint32_t& tested) {
-        const uint64_t m = __ballot(fresh);
-        if (m == 0) return 0u;
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t H = (S.n_flat + 1u) >> 1;
-        const uint32_t total = (uint32_t)__popcll(m) * H;
-        const uint32_t rank = lane_prefix(m);
-        const uint32_t list = (uint32_t)__builtin_amdgcn_ds_permute((int)((fresh ? rank : 63u) << 2), (int)lane);
-        const uint32_t magic = (65536u + H - 1u) / H;
-        const f3 r32 = -R.nr;  // RN(1 / d): what the filter is proved on
-        uint32_t mine = 0;
-        for (uint32_t base = 0; base < total; base += 64u) {
-            const uint32_t p = base + lane;
-            const bool valid = p < total;
-            const uint32_t r = (p * magic) >> 16, h = p - r * H;
-            const uint32_t owner = pull(r, list);
-            const f3 oo = mk3(pull(owner, R.o.x), pull(owner, R.o.y), pull(owner, R.o.z));
-            const f3 rr = mk3(pull(owner, r32.x), pull(owner, r32.y), pull(owner, r32.z));
-            bool pass0 = false, pass1 = false;
-            if (valid) {
-                const pbrs_node n0 = load_node(S.nodes + S.flat_off + h);
-                // the planes met first / last on an axis by the sign of the reciprocal (= the direction's)
-                pass0 = pn_slab_filter(rr.x > 0.0f ? n0.min[0] : n0.max[0], rr.y > 0.0f ? n0.min[1] : n0.max[1], rr.z > 0.0f ? n0.min[2] : n0.max[2],
-                                       rr.x > 0.0f ? n0.max[0] : n0.min[0], rr.y > 0.0f ? n0.max[1] : n0.min[1], rr.z > 0.0f ? n0.max[2] : n0.min[2], oo.x, oo.y,
-                                       oo.z, rr.x, rr.y, rr.z, pn_inf()) != 0;
-                tested += 1u;
-                if (h + H < S.n_flat) {
-                    const pbrs_node n1 = load_node(S.nodes + S.flat_off + h + H);
-                    pass1 = pn_slab_filter(rr.x > 0.0f ? n1.min[0] : n1.max[0], rr.y > 0.0f ? n1.min[1] : n1.max[1], rr.z > 0.0f ? n1.min[2] : n1.max[2],
-                                           rr.x > 0.0f ? n1.max[0] : n1.min[0], rr.y > 0.0f ? n1.max[1] : n1.min[1], rr.z > 0.0f ? n1.max[2] : n1.min[2], oo.x,
-                                           oo.y, oo.z, rr.x, rr.y, rr.z, pn_inf()) != 0;
-                    tested += 1u;
-                }
-            }
-            const uint64_t w0 = __ballot(pass0), w1 = __ballot(pass1);
-            const int sft = (int)(rank * H) - (int)base;
-            if (fresh && sft > -(int)H && sft < 64) {
-                const uint64_t a = sft >= 0 ? w0 >> sft : w0 << -sft, b = sft >= 0 ? w1 >> sft : w1 << -sft;
-                const uint32_t keep = (1u << H) - 1u;
-                mine |= ((uint32_t)a & keep) | (((uint32_t)b & keep) << H);
-            }
-        }
-        return mine;
-    }
+    PD static uint32_t run(const DevScene& S, bool fresh, const RaySpace& R, float t_max, uint32_t& tested) { return scan<Exact>(S, fresh, R, t_max, tested); }
+    PD static uint32_t run_filter(const DevScene& S, bool fresh, const RaySpace& R, uint32_t& tested) { return scan<Filter>(S, fresh, R, pn_inf(), tested); }
 };
-
-// FlatScan::run with an infinite extent that also leaves, for every leaf that passed, the exact entry distance t_low in the
-// owner's column of a block-wide LDS table (tl_block[leaf * 256 + thread of the owner]).
-PD uint32_t flat_scan_tlow(const DevScene& S, bool fresh, const RaySpace& R, float* tl_block) {
-    const uint64_t m = __ballot(fresh);
-    if (m == 0) return 0u;
-    const uint32_t lane = threadIdx.x & 63u, wave_base = threadIdx.x & ~63u;
-    const uint32_t H = (S.n_flat + 1u) >> 1;
-    const uint32_t total = (uint32_t)__popcll(m) * H;
-    const uint32_t rank = lane_prefix(m);
-    const uint32_t list = (uint32_t)__builtin_amdgcn_ds_permute((int)((fresh ? rank : 63u) << 2), (int)lane);
-    const uint32_t magic = (65536u + H - 1u) / H;
-    uint32_t mine = 0;
-    for (uint32_t base = 0; base < total; base += 64u) {
-        const uint32_t p = base + lane;
-        const bool valid = p < total;
-        const uint32_t r = (p * magic) >> 16, h = p - r * H;
-        const uint32_t owner = FlatScan::pull(r, list);
-        RaySpace O;
-        O.o = mk3(FlatScan::pull(owner, R.o.x), FlatScan::pull(owner, R.o.y), FlatScan::pull(owner, R.o.z));
-        O.d = mk3(FlatScan::pull(owner, R.d.x), FlatScan::pull(owner, R.d.y), FlatScan::pull(owner, R.d.z));
-        O.nr = mk3(FlatScan::pull(owner, R.nr.x), FlatScan::pull(owner, R.nr.y), FlatScan::pull(owner, R.nr.z));
-        O.fast = true;
-        bool pass0 = false, pass1 = false;
-        if (valid) {
-            float t_low;
-            pass0 = slab_rs_tlow(load_node(S.nodes + S.flat_off + h), O, t_low);
-            if (pass0) tl_block[h * PBRS_TRAVERSAL_BLOCK + wave_base + owner] = t_low;
-            if (h + H < S.n_flat) {
-                pass1 = slab_rs_tlow(load_node(S.nodes + S.flat_off + h + H), O, t_low);
-                if (pass1) tl_block[(h + H) * PBRS_TRAVERSAL_BLOCK + wave_base + owner] = t_low;
-            }
-        }
-        const uint64_t w0 = __ballot(pass0), w1 = __ballot(pass1);
-        const int sft = (int)(rank * H) - (int)base;
-        if (fresh && sft > -(int)H && sft < 64) {
-            const uint64_t a = sft >= 0 ? w0 >> sft : w0 << -sft, b = sft >= 0 ? w1 >> sft : w1 << -sft;
-            const uint32_t keep = (1u << H) - 1u;
-            mine |= ((uint32_t)a & keep) | (((uint32_t)b & keep) << H);
-        }
-    }
-    return mine;
-}
 
 template <bool STATS, uint32_t FEAT>
 struct ClosestWalk {
@@ -432,11 +370,7 @@ struct ClosestWalk {
     PD void scan_wave(const DevScene& S, Cnt<STATS>& cnt) {
         if (!(FEAT & PBRS_FEAT_FLAT_TLAS) || EXT) return;
         uint32_t tested = 0;
-#ifdef PBRS_EXACT_CLOSEST_SCAN
-        const uint32_t mine = FlatScan::run(S, mode == PBRS_WALK_SCAN, C, pn_inf(), tested);
-#else
         const uint32_t mine = FlatScan::run_filter(S, mode == PBRS_WALK_SCAN, C, tested);
-#endif
         if (STATS) cnt.c.tlas_nodes += tested;
         if (mode == PBRS_WALK_SCAN) {
             cand = mine;
@@ -915,7 +849,9 @@ struct AnyWalk {
     }
     // The held leaves of the whole wave in one execution (TriShare); every lane of the wave calls this together.
     // `intersect_bvh_pred` stops at a leaf's first occluder (blas.rs:478-495): the owner counts its triangles up to that one.
-    PD void leaf_wave(const DevScene& S, Cnt<STATS>& cnt) {
+    // `after_leaf()`: where a lane goes whose leaf is used up without one.
+    template <class AfterLeaf>
+    PD void share_leaf(const DevScene& S, Cnt<STATS>& cnt, AfterLeaf after_leaf) {
         const bool tri_leaf = mode == PBRS_WALK_LEAF;  // analytic shapes never wait here (analytic_visit)
         TriShare sh;
         sh.build(tri_leaf ? leaf_end - leaf_a : 0u);
@@ -942,12 +878,15 @@ struct AnyWalk {
             }
             if (STATS) cnt.c.triangles += tested;
             leaf_a += sh.cnt;
-            mode = leaf_a != leaf_end ? PBRS_WALK_LEAF : sp == blas_base ? PBRS_WALK_XFER : PBRS_WALK_NODE;
+            mode = leaf_a != leaf_end ? PBRS_WALK_LEAF : after_leaf();
             if (occ) {
                 occluded = true;
                 mode = PBRS_WALK_DONE;
             }
         }
+    }
+    PD void leaf_wave(const DevScene& S, Cnt<STATS>& cnt) {
+        share_leaf(S, cnt, [&]() __attribute__((always_inline)) { return sp == blas_base ? PBRS_WALK_XFER : PBRS_WALK_NODE; });
     }
     // Instance::occludes (instance.rs:68-72) for an analytic shape in one go, see ClosestWalk::analytic_visit; an occluder
     // ends the walk (mode DONE, occluded set).
@@ -988,13 +927,13 @@ struct AnyWalk {
 
 // ---- walks over four-wide nodes (device/wide.h) ----------------------------------------------------------------------------
 // For scenes whose TLAS is scanned (PBRS_FEAT_FLAT_TLAS) and rays on the division-free box test.  Same states, same boundary
-// and leaf steps as the binary walks above — they inherit them — but: inside a mesh a node step takes a WIDE node (four boxes
-// through the conservative filter, the survivors pushed in the reference's order, the first one kept in a register); a BLAS leaf
-// that comes up is held UNVERIFIED until the shared leaf step gives it the reference's own box test with the extent of that
-// moment; at the TLAS level a scanned leaf is re-evaluated at its turn from the entry distance the scan left in LDS (t_low <=
-// t_max: the reference's test, slab_rs_tlow) — no box is fetched twice.  A ray that leaves the guarded range (at its start or
-// inside an instance) or whose stack would exceed DevScene::wide_cap takes mode PBRS_WALK_SLOW: the kernel hands it, whole, to
-// the binary-walk kernel (kernels.h).
+// and leaf steps as the binary any-hit walk above — AnyWalkW inherits them, and its leaf step is AnyWalk::share_leaf behind a prologue
+// of its own — but: inside a mesh a node step takes a WIDE node (four boxes through the conservative filter, the survivors pushed near
+// side first, the first one kept in a register), from an empty stack (the TLAS level is the scan's mask alone: any hit, the extent
+// never changes, a leaf that passed the scan is entered without a second test); a BLAS leaf that comes up is held UNVERIFIED until
+// the leaf step gives it the reference's own box test.  A ray that leaves the guarded range (at its start or inside an instance) or
+// whose stack would exceed DevScene::wide_cap takes mode PBRS_WALK_SLOW: the kernel hands it, whole, to the binary-walk kernel
+// (kernels.h).
 #define PBRS_WALK_SLOW 6u
 #define PBRS_LEAF_UNVERIFIED 0xffffffffu
 template <uint32_t FEAT>
@@ -1133,32 +1072,7 @@ struct AnyWalkW : AnyWalk<false, FEAT> {
             if (leaf_end != leaf_a) PBRS_TP(4);
             if (leaf_end == leaf_a) mode = after_leaf();
         }
-        const bool tri_leaf = mode == PBRS_WALK_LEAF;
-        TriShare sh;
-        sh.build(tri_leaf ? leaf_end - leaf_a : 0u);
-        if (sh.has[0] == 0) return;
-        const f3 ho = sh.from_owner(C.o), hd = sh.from_owner(C.d);
-        const float htmax = sh.from_owner(t_max);
-        const uint32_t hti = sh.from_owner(leaf_a) + sh.k();
-        bool hit = false;
-        if (sh.helper()) {
-            PBRS_TP(5);
-            pbrs_tri_verts tv = load_tri(S.tv + hti);
-            hit = mesh_tri_pred(tv, ho, hd, htmax);
-        }
-        const uint64_t hits = __ballot(hit);
-        if (tri_leaf) {
-            bool occ = false;
-#pragma unroll
-            for (uint32_t j = 4u; j-- > 0u;)
-                if (j < sh.cnt && ((hits >> sh.pos(j)) & 1ull)) occ = true;
-            leaf_a += sh.cnt;
-            mode = leaf_a != leaf_end ? PBRS_WALK_LEAF : after_leaf();
-            if (occ) {
-                occluded = true;
-                mode = PBRS_WALK_DONE;
-            }
-        }
+        B::share_leaf(S, cnt, [&]() __attribute__((always_inline)) { return after_leaf(); });
     }
 };
 

@@ -1,4 +1,4 @@
-// device/wide.h — four-wide BVH nodes for the BLAS walk of k_shadow (round 3; the closest-hit walk over them: device/experimental/).
+// device/wide.h — four-wide BVH nodes for the BLAS walk of k_shadow (AnyWalkW, traverse.h; the closest-hit walk over them was retired).
 //
 // What the reference's traversal DEFINES, for a ray on the division-free box test (no NaN quotients, traverse.h), is small:
 //   * closest hit in a mesh (shape/src/blas.rs:422-476): the leaves are taken in the order of the near-first depth-first walk
@@ -99,19 +99,6 @@ PD WideTest wide_test(const pbrs_wnode* nodes, uint32_t wi, const RaySpace& C, c
 struct WideOrder {
     uint32_t r[4], p[4];
 };
-// The reference's order (blas.rs:456-466: the left child first iff `ray.dir[axis] > 0`, at X and at each of its children)
-PD WideOrder wide_order(const WideTest& t, f3 d) {
-    const bool sx = !(comp(d, t.axis_x()) > 0.0f);         // X: its right child's side first
-    const bool sa = !(comp(d, t.axis_left()) > 0.0f);  // within X's left child
-    const bool sb = !(comp(d, t.axis_right()) > 0.0f);  // within X's right child
-    const uint32_t q0 = t.pass & 1u, q1 = (t.pass >> 1) & 1u, q2 = (t.pass >> 2) & 1u, q3 = (t.pass >> 3) & 1u;
-    const uint32_t a0 = sa ? t.child[1] : t.child[0], a1 = sa ? t.child[0] : t.child[1], qa0 = sa ? q1 : q0, qa1 = sa ? q0 : q1;
-    const uint32_t b0 = sb ? t.child[3] : t.child[2], b1 = sb ? t.child[2] : t.child[3], qb0 = sb ? q3 : q2, qb1 = sb ? q2 : q3;
-    WideOrder o;
-    o.r[0] = sx ? b0 : a0, o.r[1] = sx ? b1 : a1, o.r[2] = sx ? a0 : b0, o.r[3] = sx ? a1 : b1;
-    o.p[0] = sx ? qb0 : qa0, o.p[1] = sx ? qb1 : qa1, o.p[2] = sx ? qa0 : qb0, o.p[3] = sx ? qa1 : qb1;
-    return o;
-}
 // Any order gives an any-hit walk the same answer; the side of X the ray enters first goes first (finds an occluder sooner)
 PD WideOrder wide_order_any(const WideTest& t, f3 d) {
     const bool sx = !(comp(d, t.axis_x()) > 0.0f);

@@ -1,11 +1,16 @@
 """Developer tool (CPU): which kernels of two device assemblies of pbrs_gpu.hip are the same instruction for instruction.
 
-usage: python tools/isa_same_kernels.py OLD.s NEW.s        (hipcc <the Makefile's flags> --cuda-device-only -S -o X.s pbrs_gpu.hip)
+usage: python tools/isa_same_kernels.py [--mask-registers] OLD.s NEW.s        (hipcc <the Makefile's flags> --cuda-device-only -S -o X.s pbrs_gpu.hip)
 
 A counter file (profiles/*traffic*.json) is stamped with a hash of ALL kernel sources; a change to one header moves the hash although
 most kernels compile to the same code.  This tool compares every kernel's body (label .. .Lfunc_end, local labels renumbered in order of
 appearance, comments and debug directives dropped) and its resource directives (registers, scratch, LDS) and prints the kernels that
-differ: a counter file may then name the new hash under `same_isa_as_measured` for the kernels this tool finds unchanged."""
+differ: a counter file may then name the new hash under `same_isa_as_measured` for the kernels this tool finds unchanged.
+
+--mask-registers gives the kernels that differ a second comparison with every register number masked (v12, s3, a0, v[4:7] -> v#, s#, a#,
+v[#+3]): the same opcodes in the same order on the same operands' kinds and widths, with equal resource directives — what a source-level
+refactor may leave behind when two values swap their registers.  Those kernels are listed by name and are NOT unchanged for a counter file.
+The exit status is 1 when a kernel is in neither class (without the option: when any kernel differs)."""
 import hashlib
 import re
 import subprocess
@@ -46,12 +51,23 @@ def kernels(path):
     return out, res
 
 
-def canon(body):
+MASK = "--mask-registers" in sys.argv[1:]
+ARGS = [x for x in sys.argv[1:] if x != "--mask-registers"]
+if len(ARGS) != 2:
+    sys.exit(__doc__)
+
+
+def mask(line):
+    line = re.sub(r"\b([vsa])\[(\d+):(\d+)\]", lambda m: "%s[#+%d]" % (m.group(1), int(m.group(3)) - int(m.group(2))), line)
+    return re.sub(r"\b([vsa])\d+\b", r"\1#", line)
+
+
+def canon(body, masked=False):
     ids = {}
 
     def ren(m):
         return ids.setdefault(m.group(0), ".L%d" % len(ids))
-    return hashlib.sha256("\n".join(re.sub(r"\.L[A-Za-z_]*\d+(_\d+)?", ren, l) for l in body).encode()).hexdigest()[:16]
+    return hashlib.sha256("\n".join(re.sub(r"\.L[A-Za-z_]*\d+(_\d+)?", ren, mask(l) if masked else l) for l in body).encode()).hexdigest()[:16]
 
 
 def demangle(names):
@@ -61,8 +77,8 @@ def demangle(names):
         return {n: n for n in names}
 
 
-a, ra = kernels(sys.argv[1])
-b, rb = kernels(sys.argv[2])
+a, ra = kernels(ARGS[0])
+b, rb = kernels(ARGS[1])
 names = sorted(set(a) | set(b))
 dm = demangle(names)
 short = {n: dm[n].split("(")[0] for n in names}
@@ -84,10 +100,16 @@ for n in sorted(set(a) - set(b)):
     else:
         diff.append(n)
 diff += [n for twins in left.values() for n in twins]
+masked = [n for n in diff if MASK and n in a and n in b and canon(a[n], True) == canon(b[n], True) and ra.get(n) == rb.get(n)]
+diff = [n for n in diff if n not in masked]
 pairs = f" ({len(renamed)} of them renamed)" if renamed else ""
-print(f"kernels {len(same) + len(renamed) + len(diff)}: same {len(same) + len(renamed)}{pairs}, different {len(diff)}")
+also = f", same once register numbers are masked {len(masked)}" if MASK else ""
+print(f"kernels {len(same) + len(renamed) + len(masked) + len(diff)}: same {len(same) + len(renamed)}{pairs}{also}, different {len(diff)}")
 for old, new in renamed:
     print("  renamed:", short[old], "->", short[new])
+for n in sorted(masked):
+    print("  same once masked:", dm[n].split("(")[0])
 for n in sorted(diff):
     why = "only in one" if not (n in a and n in b) else f"{len(a[n])} -> {len(b[n])} lines"
     print("  differs:", short[n], f"({why})")
+sys.exit(1 if diff else 0)
