@@ -647,6 +647,62 @@ int pbrs_matte_mask(pbrs_ctx*, uint32_t w, uint32_t h, uint32_t slots, const uin
 int pbrs_matte_mask_device(pbrs_ctx*, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_device, const float* coverage_device,
                            const uint32_t* select, uint32_t n_select, float* mask_out_device);
 
+/* ---- light passes -------------------------------------------------------------------------------------- */
+/* Direct and indirect light beside the image, each with the variance of its pixel mean, from the render's own camera samples: what a
+ * compositor takes as separate layers, and what lets the variance-guided denoiser filter the two apart (SVGF filters direct and indirect
+ * illumination separately: direct light is nearly converged at a few samples per pixel, the noise sits in the indirect light).  All
+ * arithmetic is f32 without fused multiply-add, in the order written; lum is the variance AOV's.
+ *
+ * For camera sample i of a pixel, rendered with PBRS_INTEGRATOR_PATH at max_depth >= 1:
+ *   L_i  its radiance (what pbrs_render_sample_radiance exports).
+ *   D_i  its radiance after the first path vertex: the emission of the surface hit, or the environment a primary miss sees, plus the
+ *        light estimate at the first hit (`radiance` after the first iteration of src/pathintegrator.rs:14-71).  Neither the random
+ *        draws nor Russian roulette depend on `depth`, so D_i is L_i of the same sample rendered at max_depth = 1, bit for bit.
+ *   I_i  = L_i - D_i, per component.  A path that ends at its first vertex gives +0; non-finite values propagate as written
+ *        (inf - inf is NaN).  Emission picked up behind a specular bounce belongs to I_i.
+ * Outputs, the tile / band packing of rgb_out, spp = strata_x * strata_y; every pointer may be NULL (not wanted):
+ *   direct             3 x f32 row-major RGB: (sum_i D_i, i ascending, from +0) * (1.0f / spp)
+ *   indirect           3 x f32: the same over I_i
+ *   direct_variance    f32: the variance AOV's recipe with lum(D_i) in the place of lum(L_i), its skip of non-finite luminances and its
+ *                      +inf below two finite samples included
+ *   indirect_variance  f32: the same with lum(I_i)
+ * The sample index is the only loop, so no output depends on the passes.  direct + indirect equals the image only to rounding, not
+ * bit for bit: the image sums L_i, the layers sum D_i and L_i - D_i, and each of those sums and differences rounds on its own.
+ * pbrs_render_tile_passes[_device]: pbrs_render_tile_matte[_device] (`aovs`, `variance`, `matte` may be NULL) that also fills the light
+ * passes; `passes` NULL or all-NULL is exactly that call, and the image, the AOVs, the variance and the matte are the bits of that call
+ * whatever is asked for here.  Pointers are host memory for pbrs_render_tile_passes, device memory for pbrs_render_tile_passes_device,
+ * which is asynchronous like pbrs_render_tile_device: valid after pbrs_collect_stats.  Row bands are supported.  While passes are
+ * wanted every path of a pass carries 16 B more state (D_i beside L_i; the samples per pass chosen for samples_per_pass = 0 account for
+ * it) and the context keeps 48 B of state per pixel (the host variant 32 B per pixel of staging), allocated by the first call that asks
+ * for a pass; a render that asks for none allocates none of it, launches the kernels it launched before and takes passes of the same
+ * size.  Two kernels per pass (one copies D_i behind bounce 0, one folds the pass beside k_accumulate: its time counts in
+ * pbrs_stats::ms_accumulate; the copy's in ms_total only).  Not offered through the filtered film.
+ * Refused with PBRS_E_INVALID (the context stays usable), beside what pbrs_render_tile_matte refuses, when a pass is wanted: any integrator
+ * but PBRS_INTEGRATOR_PATH (the direct integrator has depth semantics of its own and keeps 1 / mass beside its radiance; the visualisers
+ * bypass the film); max_depth == 0. */
+typedef struct pbrs_pass_buffers {
+    float* direct;            /* w * h * 3 */
+    float* indirect;          /* w * h * 3 */
+    float* direct_variance;   /* w * h */
+    float* indirect_variance; /* w * h */
+} pbrs_pass_buffers;          /* NULL = not wanted */
+int pbrs_render_tile_passes(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                            float* variance_host, const pbrs_matte_params* matte_params, const pbrs_matte_buffers* matte_host,
+                            const pbrs_pass_buffers* passes_host, pbrs_stats* stats_out);
+int pbrs_render_tile_passes_device(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, float* rgb_out_device,
+                                   const pbrs_aov_buffers* aovs_device, float* variance_device, const pbrs_matte_params* matte_params,
+                                   const pbrs_matte_buffers* matte_device, const pbrs_pass_buffers* passes_device, pbrs_stats* stats_out);
+
+/* Puts the two layers back together: rgb_out = direct + indirect per component, w * h * 3 f32 each.  An image operation like
+ * pbrs_denoise: it needs a context (device, stream) and no uploaded scene.  rgb_out may be either input.  Host memory for
+ * pbrs_combine_passes (which synchronises before it returns; it stages through the host render's pass staging), device memory for
+ * pbrs_combine_passes_device, which runs on the context's stream (pbrs_set_stream honoured) and does not wait: queued after
+ * pbrs_render_tile_passes_device or pbrs_denoise_var_device on the same context it needs no synchronisation in between.
+ * Refused with PBRS_E_INVALID: a NULL pointer, w or h 0.  w * h above 2^28: PBRS_E_LIMIT. */
+int pbrs_combine_passes(pbrs_ctx*, uint32_t w, uint32_t h, const float* direct_host, const float* indirect_host, float* rgb_out_host);
+int pbrs_combine_passes_device(pbrs_ctx*, uint32_t w, uint32_t h, const float* direct_device, const float* indirect_device,
+                               float* rgb_out_device);
+
 #ifdef __cplusplus
 }
 #endif

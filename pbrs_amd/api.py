@@ -218,6 +218,25 @@ class MatteBuffers(C.Structure):
 MATTE_LAYERS = ("ids", "coverage", "residual")
 
 
+class PassBuffers(C.Structure):
+    """pbrs_pass_buffers: direct and indirect light, (h, w, 3) f32, and the variance of each one's pixel mean, (h, w) f32; NULL = not
+    wanted (include/pbrs_gpu.h, "light passes")."""
+    _fields_ = [(n, C.c_void_p) for n in ("direct", "indirect", "direct_variance", "indirect_variance")]
+
+
+# name -> channels of each light pass, in the order of pbrs_pass_buffers
+PASSES = ("direct", "indirect", "direct_variance", "indirect_variance")
+PASS_CHANNELS = {"direct": 3, "indirect": 3, "direct_variance": 1, "indirect_variance": 1}
+
+
+def _pass_names(passes):
+    names = tuple(passes)
+    unknown = [n for n in names if n not in PASS_CHANNELS]
+    if unknown:
+        raise ValueError(f"unknown light pass(es) {unknown}; known: {list(PASSES)}")
+    return names
+
+
 def _matte_select(select):
     """The selected ids as pbrs_matte_mask wants them: u32, strictly ascending (sorted and deduplicated here)."""
     sel = np.unique(np.asarray(select, dtype=np.int64).reshape(-1))
@@ -241,7 +260,8 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_numeric_eval", "pbrs_numeric_eval_k", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
                "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device",
                "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device",
-               "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device"]
+               "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device",
+               "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -324,6 +344,10 @@ def gpu_lib():
         L.pbrs_render_tile_matte_device.argtypes = [C.c_void_p] * 9
         L.pbrs_matte_mask.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.pbrs_matte_mask_device.argtypes = L.pbrs_matte_mask.argtypes
+        L.pbrs_render_tile_passes.argtypes = [C.c_void_p] * 10
+        L.pbrs_render_tile_passes_device.argtypes = [C.c_void_p] * 10
+        L.pbrs_combine_passes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbrs_combine_passes_device.argtypes = L.pbrs_combine_passes.argtypes
         _gpu = L
     return _gpu
 
@@ -527,21 +551,23 @@ class Context:
             setattr(bufs, n, ptr)
         return bufs, variance
 
-    def _render_host(self, p, names, mp=None, mb=None):
-        """A host render of `p` with the AOVs named and, with `mp` and `mb`, a matte -> (rgb, {name: array}, stats).  One entry point
-        serves all of them: the library forwards the AOV ones to it."""
+    def _render_host(self, p, names, mp=None, mb=None, pb=None):
+        """A host render of `p` with the AOVs named and, with `mp` and `mb`, a matte, with `pb`, light passes -> (rgb, {name: array},
+        stats).  One entry point serves all of them: the library forwards the AOV and matte ones to it."""
         out = np.empty((p.h, p.w, 3), dtype=np.float32)
         bufs, arrays = self._aov_arrays(names, p)
         st = Stats()
-        self._check(self._L.pbrs_render_tile_matte(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
-                                                   arrays[VARIANCE].ctypes.data if VARIANCE in names else None, C.addressof(mp) if mp else None,
-                                                   C.addressof(mb) if mb else None, C.addressof(st)), "pbrs_render_tile_matte")
+        self._check(self._L.pbrs_render_tile_passes(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
+                                                    arrays[VARIANCE].ctypes.data if VARIANCE in names else None, C.addressof(mp) if mp else None,
+                                                    C.addressof(mb) if mb else None, C.addressof(pb) if pb else None, C.addressof(st)),
+                    "pbrs_render_tile_passes")
         return out, arrays, st.as_dict()
 
-    def _render_device(self, p, rgb_device_ptr, bufs, variance, mp=None, mb=None):
-        self._check(self._L.pbrs_render_tile_matte_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
-                                                          C.addressof(bufs), C.c_void_p(variance), C.addressof(mp) if mp else None,
-                                                          C.addressof(mb) if mb else None, None), "pbrs_render_tile_matte_device")
+    def _render_device(self, p, rgb_device_ptr, bufs, variance, mp=None, mb=None, pb=None):
+        self._check(self._L.pbrs_render_tile_passes_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
+                                                           C.addressof(bufs), C.c_void_p(variance), C.addressof(mp) if mp else None,
+                                                           C.addressof(mb) if mb else None, C.addressof(pb) if pb else None, None),
+                    "pbrs_render_tile_passes_device")
 
     def render_aovs(self, strata_x, strata_y, depth, seed, aovs=AOV_NAMES, tile=None, samples_per_pass=0, counters=False,
                     timing=False, bands=None, integrator="path"):
@@ -601,6 +627,50 @@ class Context:
             setattr(mb, n, ptr)
         self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator),
                             rgb_device_ptr, bufs, variance, mp, mb)
+
+    def render_passes(self, strata_x, strata_y, depth, seed, passes=PASSES, aovs=(), tile=None, samples_per_pass=0, counters=False,
+                      timing=False, bands=None, integrator="path"):
+        """render_aovs() plus the light passes of the same camera samples (include/pbrs_gpu.h, pbrs_render_tile_passes) -> (rgb,
+        {pass: array}, {aov: array}, stats).  "direct" / "indirect": (h, w, 3) f32, the light that reaches the camera after one path
+        vertex and after more; "direct_variance" / "indirect_variance": (h, w) f32, the variance of each one's pixel-mean luminance, +inf
+        where fewer than two samples are finite.  The path integrator at depth >= 1 only."""
+        pnames, names = _pass_names(passes), _aov_names(aovs)
+        p = self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator)
+        layers = {n: np.empty((p.h, p.w, 3) if PASS_CHANNELS[n] > 1 else (p.h, p.w), dtype=np.float32) for n in pnames}
+        pb = PassBuffers()
+        for n in pnames:
+            setattr(pb, n, layers[n].ctypes.data)
+        out, arrays, stats = self._render_host(p, names, pb=pb)
+        return out, layers, arrays, stats
+
+    def render_passes_device(self, rgb_device_ptr, pass_device_ptrs, strata_x, strata_y, depth, seed, aov_device_ptrs=None, tile=None,
+                             samples_per_pass=0, counters=False, timing=False, bands=None, integrator="path"):
+        """render_passes() into caller-owned device memory: `pass_device_ptrs` = {pass: pointer}, `aov_device_ptrs` as render_aovs_device
+        takes them ("variance" included).  Asynchronous like render_device: valid after `collect_stats()`."""
+        _pass_names(pass_device_ptrs)
+        bufs, variance = self._aov_device(aov_device_ptrs)
+        pb = PassBuffers()
+        for n, ptr in pass_device_ptrs.items():
+            setattr(pb, n, ptr)
+        self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator),
+                            rgb_device_ptr, bufs, variance, pb=pb)
+
+    def combine_passes(self, direct, indirect):
+        """direct + indirect per component on the device (include/pbrs_gpu.h, pbrs_combine_passes) -> (h, w, 3) f32."""
+        direct = np.ascontiguousarray(direct, dtype=np.float32)
+        indirect = np.ascontiguousarray(indirect, dtype=np.float32)
+        if direct.ndim != 3 or direct.shape[2] != 3 or direct.shape != indirect.shape:
+            raise ValueError(f"a direct layer of shape {direct.shape} beside an indirect one of {indirect.shape}; both are (h, w, 3)")
+        h, w, _ = direct.shape
+        out = np.empty_like(direct)
+        self._check(self._L.pbrs_combine_passes(self._h, w, h, direct.ctypes.data, indirect.ctypes.data, out.ctypes.data), "pbrs_combine_passes")
+        return out
+
+    def combine_passes_device(self, direct_device_ptr, indirect_device_ptr, rgb_out_device_ptr, w, h):
+        """combine_passes() on caller-owned device memory; the output pointer may be either input's.  Runs on the context's stream behind
+        whatever was queued there and does not wait: valid after `collect_stats()`."""
+        self._check(self._L.pbrs_combine_passes_device(self._h, w, h, C.c_void_p(direct_device_ptr), C.c_void_p(indirect_device_ptr),
+                                                       C.c_void_p(rgb_out_device_ptr)), "pbrs_combine_passes_device")
 
     def matte_mask(self, ids, coverage, select):
         """The mask of the ids in `select` (any order, duplicates allowed: sorted here) from the layers render_matte returns -> (h, w) f32:
@@ -775,6 +845,44 @@ class Context:
         on the same stream, no synchronisation in between), copied back once -> (denoised, stats) or (denoised, noisy, stats)."""
         return self._render_denoised("render_denoised_var", True, strata_x, strata_y, depth, seed, guides, samples_per_pass, integrator,
                                      keep_noisy, params)
+
+    def render_denoised_passes(self, strata_x, strata_y, depth, seed, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                               keep_noisy=False, **params):
+        """The whole frame rendered once with its guides and the four light passes, direct and indirect light each through the
+        variance-guided denoiser with its own variance, the two summed again (render_passes_device, denoise_var_device twice,
+        combine_passes_device: one stream, no synchronisation in between), copied back once -> (denoised, stats) or (denoised, noisy,
+        stats).  params: DenoiseVarParams.make's keywords, for both layers."""
+        self._denoise_guide_names(guides)
+        w, h = self.scene.width, self.scene.height
+        hip = hip_runtime()
+        n_rgb = 3 * w * h * 4
+        sizes = {"rgb": n_rgb, **{n: PASS_CHANNELS[n] * w * h * 4 for n in PASSES}, **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
+        dev = {}
+        try:
+            for n, nbytes in sizes.items():
+                ptr = C.c_void_p()
+                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
+                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_denoised_passes failed")
+                dev[n] = ptr
+            gp = {n: dev[n].value for n in guides}
+            self.render_passes_device(dev["rgb"].value, {n: dev[n].value for n in PASSES}, strata_x, strata_y, depth, seed, aov_device_ptrs=gp,
+                                      samples_per_pass=samples_per_pass)
+            for layer in ("direct", "indirect"):  # each in place
+                self.denoise_var_device(dev[layer].value, dev[layer].value, w, h, dev[layer + "_variance"].value, gp, **params)
+            self.combine_passes_device(dev["direct"].value, dev["indirect"].value, dev["direct"].value, w, h)
+            stats = self.collect_stats()  # waits for the stream
+            out = np.empty((h, w, 3), dtype=np.float32)
+            if hip.hipMemcpy(out.ctypes.data, dev["direct"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
+                raise PbrsError("hipMemcpy of the denoised image failed")
+            if not keep_noisy:
+                return out, stats
+            noisy = np.empty_like(out)
+            if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
+                raise PbrsError("hipMemcpy of the plain image failed")
+            return out, noisy, stats
+        finally:
+            for ptr in dev.values():
+                hip.hipFree(ptr)
 
     def collect_stats(self):
         st = Stats()

@@ -27,6 +27,7 @@
 #include "device/denoise.h"
 #include "device/moments.h"
 #include "device/matte.h"
+#include "device/passes.h"
 
 namespace {
 
@@ -184,6 +185,10 @@ enum BufferId {
     // (PBRS_MATTE_STATE_WORDS(slots) per pixel, planar), the host variants' staging (ids, coverage, then residual or the mask) and the
     // selection of pbrs_matte_mask* (PBRS_MATTE_MAX_SELECT ids)
     BUF_MATTE_STATE, BUF_MATTE_OUT, BUF_MATTE_SELECT,
+    // light passes (pbrs_render_tile_passes*, pbrs_combine_passes, device/passes.h): the per-pixel running state k_pass_fold folds every pass
+    // into (PBRS_PASS_STATE_WORDS per pixel, planar), the host variants' staging (the four of pbrs_pass_buffers, one after the other) and the
+    // D column of each pass set (PassSet::direct: one float4 per path beside its PathState), held only by a context that has rendered passes
+    BUF_PASS_STATE, BUF_PASS_OUT, BUF_PASS_DIRECT, BUF_PASS_DIRECT_SET1,
     N_BUFFERS
 };
 
@@ -212,6 +217,7 @@ struct pbrs_ctx {
         uint32_t* neeq = nullptr;     // cap_slots: slots of the paths whose estimate waits for two shadow rays
         uint32_t* slow = nullptr;     // 2 * cap_slots: queue positions the wide-walk k_shadow handed to the binary-walk kernel
         uint32_t* counters = nullptr; // kCounterWords: act, ns (u64), extend work heads, shadow work heads
+        float4* direct = nullptr;     // light passes: the D column, [slot] = L[slot] as bounce 0 left it (device/passes.h); null unless the render asks for passes
         hipEvent_t accumulated = nullptr;  // the set's last k_accumulate has run (late stream): the set's memory is free for its next pass
         hipEvent_t late = nullptr;         // the set's pass has run its bounces below pbrs_ctx::overlap_from (main stream): the late stream takes over
         bool in_flight = false;            // `accumulated` has been recorded at least once
@@ -392,6 +398,18 @@ int DeviceBuffer::grow(pbrs_ctx* c, size_t bytes, const char* what) {
     return PBRS_OK;
 }
 
+// The D column of pass set k (PassSet::direct) for n_slots paths, or none: a render without light passes leaves the column null and
+// allocates nothing.
+int ensure_direct(pbrs_ctx* c, int k, size_t n_slots, bool wanted) {
+    c->pass_set[k].direct = nullptr;
+    if (!wanted) return PBRS_OK;
+    DeviceBuffer& b = c->buf[BUF_PASS_DIRECT + k];
+    const int rc = b.grow(c, n_slots * sizeof(float4), "the light passes' path column");
+    if (rc) return rc;
+    c->pass_set[k].direct = b.as<float4>();
+    return PBRS_OK;
+}
+
 // One buffer of a host variant's device staging: the caller's host pointer (null: not given, or not wanted), its words per pixel, and
 // where `stage` put it on the device (null with the host pointer).
 struct Staged {
@@ -441,6 +459,7 @@ struct RenderTargets {
     bool want_matte = false;
     const pbrs_matte_params* matte = nullptr;
     pbrs_matte_buffers matte_out{};
+    pbrs_pass_buffers passes{};  // the light passes wanted (all null: none), from the state in BUF_PASS_STATE
     // a filtered render: the params are then its traced region (check_filter) and the pass is folded into BUF_FILTER_SUM
     const FilterConst* filt = nullptr;
 
@@ -448,9 +467,10 @@ struct RenderTargets {
         const pbrs_aov_buffers& a = aovs;
         return a.albedo || a.normal || a.coverage || a.depth || a.instance || a.material || a.prim;
     }
+    bool want_passes() const { return passes.direct || passes.indirect || passes.direct_variance || passes.indirect_variance; }
 };
 
-uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p);
+uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p, bool with_direct);
 
 int check_params(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p) {
     if (!cam || !p) return fail(c, PBRS_E_INVALID, "null camera or params");
@@ -476,9 +496,9 @@ int check_params(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* 
 }
 
 // The samples per pass of a render of `p` (checked by check_params), from the memory that is free on the current device NOW: whatever the
-// call allocates beside the path state comes first.
-int pass_size(pbrs_ctx* c, const pbrs_render_params* p, uint32_t& K) {
-    K = auto_samples_per_pass(c, p);
+// call allocates beside the path state comes first.  `with_direct`: every path carries a record of the D column as well (light passes).
+int pass_size(pbrs_ctx* c, const pbrs_render_params* p, uint32_t& K, bool with_direct = false) {
+    K = auto_samples_per_pass(c, p, with_direct);
     // records keep two flag bits next to the slot index, and 16-byte records are addressed with 32-bit element indices
     if ((uint64_t)p->w * p->h * K >= (1ull << 28)) return fail(c, PBRS_E_LIMIT, "tile x samples_per_pass above 2^28 paths");
     return PBRS_OK;
@@ -565,7 +585,7 @@ RenderConst make_const(const pbrs_ctx* c, const pbrs_camera* cam, const pbrs_ren
     return rc;
 }
 
-uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p) {
+uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p, bool with_direct) {
     uint64_t P = (uint64_t)p->w * p->h, spp = (uint64_t)p->strata_x * p->strata_y;
     uint64_t k = p->samples_per_pass;
     if (k == 0) {
@@ -577,11 +597,13 @@ uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p) {
         uint64_t target = 240ull << 20;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t per_path = PBRS_STATE_BYTES_PER_PATH;  // path, hit, radiance, shadow-ray and nee records
+            // path, hit, radiance, shadow-ray and nee records; a render with light passes: and the D column
+            const uint64_t per_path = PBRS_STATE_BYTES_PER_PATH + (with_direct ? sizeof(float4) : 0u);
             // what this context already holds for paths counts as available: the answer must not change between calls
             // (... in both of its pass sets: a set may take a quarter of the memory, the two of them half)
             const uint64_t held = (uint64_t)c->pass_set[0].cap_slots + (uint64_t)c->pass_set[1].cap_slots;
-            const uint64_t fit = ((uint64_t)free_b + held * per_path) / 4 / per_path;
+            const uint64_t held_direct = with_direct ? c->buf[BUF_PASS_DIRECT].cap_bytes + c->buf[BUF_PASS_DIRECT_SET1].cap_bytes : 0u;
+            const uint64_t fit = ((uint64_t)free_b + held * PBRS_STATE_BYTES_PER_PATH + held_direct) / 4 / per_path;
             if (fit < target) target = fit < (4ull << 20) ? (4ull << 20) : fit;
         }
         k = P >= target ? 1 : target / P;
@@ -812,8 +834,9 @@ uint32_t bounce_count(const RenderConst& rc) {
 // One pass: kc sample indices starting at `first` for every pixel of the tile.
 // `handoff`: the pass moves to the late stream at bounce pbrs_ctx::overlap_from (at the latest for its k_accumulate: the late stream runs
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
-// `t`: what the render produces.  The pass folds its first hits into the AOV state (k_aov) and the matte tables (k_matte) and its
-// radiances into the moments of the variance AOV (k_moments), each where asked for; a filtered render (rc is its traced region) folds
+// `t`: what the render produces.  The pass folds its first hits into the AOV state (k_aov) and the matte tables (k_matte), its
+// radiances into the moments of the variance AOV (k_moments) and, split at the first path vertex (k_pass_direct), into the state of the
+// light passes (k_pass_fold), each where asked for; a filtered render (rc is its traced region) folds
 // the pass into the filter sums (k_filter_accumulate) instead of k_accumulate.
 int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff, const RenderTargets& t) {
     pbrs_ctx::PassSet& set = cur(c);
@@ -916,6 +939,10 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         }
         hipLaunchKernelGGL(k_nee_resolve, dim3(sgrid), dim3(kBlock), 0, c->stream, set.st, neeq, reinterpret_cast<const uint32_t*>(ns + b));
         tm.end();
+        // light passes: L is now the radiance after the first path vertex; kept in the set's D column before bounce 1 adds to L.  On the
+        // stream that ran bounce 0; k_pass_fold reads the column behind the pass's last bounce (the hand-over events order the two).
+        // Outside the stage brackets: counted in ms_total only.
+        if (b == 0 && t.want_passes()) hipLaunchKernelGGL(k_pass_direct, dim3(grid), dim3(kBlock), 0, c->stream, set.st.L, set.direct, N);
     }
     if (probe_split) {
         // the first pass of this scene through the path integrator: how much of its queues did the split keep for k_shade?  The
@@ -939,6 +966,10 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     // the variance AOV: the same radiances, on the stream that runs the passes' accumulations in pass order
     if (t.variance)
         hipLaunchKernelGGL(k_moments, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, set.st, c->buf[BUF_MOMENT_STATE].as<float>(), P, kc, rc.chunk_pixels);
+    // the light passes: L and the D column of the same samples, on the same stream for the same reason
+    if (t.want_passes())
+        hipLaunchKernelGGL(k_pass_fold, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, set.st.L, set.direct,
+                           c->buf[BUF_PASS_STATE].as<float>(), P, kc, rc.chunk_pixels);
     tm.end();
     if (handoff) {
         HIPCHK(c, hipEventRecord(set.accumulated, c->stream));
@@ -956,6 +987,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     float* aov = t.want_aovs() ? c->buf[BUF_AOV_STATE].as<float>() : nullptr;
     float* moments = t.variance ? c->buf[BUF_MOMENT_STATE].as<float>() : nullptr;
     uint32_t* matte = t.want_matte ? c->buf[BUF_MATTE_STATE].as<uint32_t>() : nullptr;
+    float* pass_state = t.want_passes() ? c->buf[BUF_PASS_STATE].as<float>() : nullptr;
     float* filter_sum = c->buf[BUF_FILTER_SUM].as<float>();
     RenderConst rc = make_const(c, cam, p);
     const bool stats = p->collect_counters != 0;
@@ -974,13 +1006,14 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (aov) HIPCHK(c, hipMemsetAsync(aov, 0, PBRS_AOV_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     if (moments) HIPCHK(c, hipMemsetAsync(moments, 0, PBRS_MOMENT_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     if (matte) HIPCHK(c, hipMemsetAsync(matte, 0, PBRS_MATTE_STATE_WORDS(t.matte->slots) * (size_t)P * sizeof(uint32_t), c->stream));
+    if (pass_state) HIPCHK(c, hipMemsetAsync(pass_state, 0, PBRS_PASS_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     uint32_t passes = 0;
     // Where the render has more than one pass, passes alternate between the two pass sets and hand their late bounces to the second
     // stream: those are near-empty launches that end with the latency of their longest walks (C4: 47 ms per frame in kernels that leave
     // most of the chip idle, profiles/r04k_trace_gaps_c4.log) — the next pass's first bounces, queued behind the hand-over on the main
     // stream, fill it.  The instrumented render keeps one stream (its counters are per pass).
     bool two = c->overlap_passes && !stats && spp > K;
-    if (two && ensure_work(c, c->pass_set[1], (size_t)P * K, P)) {
+    if (two && (ensure_work(c, c->pass_set[1], (size_t)P * K, P) || ensure_direct(c, 1, (size_t)P * K, pass_state != nullptr))) {
         two = false;  // no memory for the second set (a device shared with other processes): every pass on the main stream, as before
         c->error.clear();
     }
@@ -1013,6 +1046,9 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (matte)
         hipLaunchKernelGGL(kMatte[t.matte->slots - 1u].finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, matte, P, rc.w,
                            rc.tiles8_per_row, 1.0f / (float)spp, t.matte_out.ids, t.matte_out.coverage, t.matte_out.residual);
+    if (pass_state)
+        hipLaunchKernelGGL(k_pass_finalize, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, pass_state, P, rc.w, rc.tiles8_per_row,
+                           1.0f / (float)spp, t.passes);
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending.passes = passes;
@@ -1087,6 +1123,11 @@ int check_targets(pbrs_ctx* c, const pbrs_render_params* p, const RenderTargets&
     const bool no_camera_ray = p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0;
     if ((t.want_aovs() || t.variance) && no_camera_ray)
         return fail(c, PBRS_E_INVALID, "AOVs requested from a render that traces no camera ray (max_depth 0)");
+    if (t.want_passes()) {
+        if (p->integrator != PBRS_INTEGRATOR_PATH)
+            return fail(c, PBRS_E_INVALID, "light passes need the path integrator (the direct integrator has its own depth semantics, the visualisers bypass the film)");
+        if (p->max_depth == 0) return fail(c, PBRS_E_INVALID, "light passes requested from a render that traces no camera ray (max_depth 0)");
+    }
     if (!t.want_matte) return PBRS_OK;
     const pbrs_matte_params* mp = t.matte;
     if (!mp) return fail(c, PBRS_E_INVALID, "a matte without pbrs_matte_params");
@@ -1141,12 +1182,13 @@ int render(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, con
     if ((rc = check_targets(c, p, t))) return rc;
     const size_t P = (size_t)p->w * p->h;  // the pixels traced: a filtered render's region, else the tile
     // Each feature's state and, for a host render, the staging of what it writes: before the pass size reads the free memory.  The staging
-    // layouts are these tables: one buffer after the other, in the order of pbrs_aov_buffers and pbrs_matte_buffers.
+    // layouts are these tables: one buffer after the other, in the order of pbrs_aov_buffers, pbrs_matte_buffers and pbrs_pass_buffers.
     const pbrs_aov_buffers& a = t.aovs;
     Staged aovs[] = {{a.albedo, 3}, {a.normal, 3}, {a.coverage, 1}, {a.depth, 1}, {a.instance, 1}, {a.material, 1}, {a.prim, 1}};
     Staged variance[] = {{t.variance, 1}};
     const size_t slots = t.want_matte ? t.matte->slots : 0;
     Staged matte[] = {{t.matte_out.ids, slots}, {t.matte_out.coverage, slots}, {t.matte_out.residual, 1}};
+    Staged passes[] = {{t.passes.direct, 3}, {t.passes.indirect, 3}, {t.passes.direct_variance, 1}, {t.passes.indirect_variance, 1}};
     float* const rgb_host = t.rgb;
     if (t.filt) rc = c->buf[BUF_FILTER_SUM].grow(c, 4 * PT * sizeof(float), "the filter sums");
     if (t.want_aovs()) {
@@ -1161,15 +1203,21 @@ int render(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, con
         if (!rc) rc = c->buf[BUF_MATTE_STATE].grow(c, PBRS_MATTE_STATE_WORDS(slots) * P * sizeof(uint32_t), "the matte state");
         if (!rc && host) rc = stage(c, c->buf[BUF_MATTE_OUT], "the matte buffers", matte, std::size(matte), P);
     }
+    if (t.want_passes()) {
+        if (!rc) rc = c->buf[BUF_PASS_STATE].grow(c, PBRS_PASS_STATE_WORDS * P * sizeof(float), "the light passes' state");
+        if (!rc && host) rc = stage(c, c->buf[BUF_PASS_OUT], "the light pass buffers", passes, std::size(passes), P);
+    }
     uint32_t K = 0;
-    if (!rc) rc = pass_size(c, p, K);
+    if (!rc) rc = pass_size(c, p, K, t.want_passes());
     if (!rc) rc = ensure_work(c, cur(c), P * K, P);
+    if (!rc) rc = ensure_direct(c, c->cur_set, P * K, t.want_passes());
     if (rc) return rc;
     if (host) {
         t.rgb = c->rgb_dev;  // P pixels: a filtered render's tile fits
         t.aovs = {aovs[0].as<float>(), aovs[1].as<float>(), aovs[2].as<float>(), aovs[3].as<float>(), aovs[4].as<uint32_t>(), aovs[5].as<uint32_t>(), aovs[6].as<uint32_t>()};
         t.variance = variance[0].as<float>();
         t.matte_out = {matte[0].as<uint32_t>(), matte[1].as<float>(), matte[2].as<float>()};
+        t.passes = {passes[0].as<float>(), passes[1].as<float>(), passes[2].as<float>(), passes[3].as<float>()};
     }
     rc = render_common(c, cam, p, K, t);
     if (rc) return rc;
@@ -1178,11 +1226,13 @@ int render(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, con
     if ((rc = copy_staged(c, variance, std::size(variance), P, hipMemcpyDeviceToHost))) return rc;
     if ((rc = copy_staged(c, aovs, std::size(aovs), P, hipMemcpyDeviceToHost))) return rc;
     if ((rc = copy_staged(c, matte, std::size(matte), P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, passes, std::size(passes), P, hipMemcpyDeviceToHost))) return rc;
     return collect(c, stats_out);
 }
 
-// The targets of the AOV and matte entry points: the buffers given (null: none).  A matte is wanted where its buffers are given.
-RenderTargets make_targets(float* rgb, const pbrs_aov_buffers* aovs, float* variance, const pbrs_matte_params* params, const pbrs_matte_buffers* matte) {
+// The targets of the AOV, matte and light pass entry points: the buffers given (null: none).  A matte is wanted where its buffers are given.
+RenderTargets make_targets(float* rgb, const pbrs_aov_buffers* aovs, float* variance, const pbrs_matte_params* params, const pbrs_matte_buffers* matte,
+                           const pbrs_pass_buffers* passes) {
     RenderTargets t;
     t.rgb = rgb;
     if (aovs) t.aovs = *aovs;
@@ -1190,6 +1240,7 @@ RenderTargets make_targets(float* rgb, const pbrs_aov_buffers* aovs, float* vari
     t.want_matte = matte != nullptr;
     t.matte = params;
     if (matte) t.matte_out = *matte;
+    if (passes) t.passes = *passes;
     return t;
 }
 
@@ -1673,12 +1724,18 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     return PBRS_OK;
 }
 
+int pbrs_render_tile_passes_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
+                                   const pbrs_aov_buffers* aovs_device, float* variance_device, const pbrs_matte_params* params,
+                                   const pbrs_matte_buffers* matte_device, const pbrs_pass_buffers* passes_device, pbrs_stats* stats_out) {
+    if (!c) return PBRS_E_INVALID;
+    if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
+    return render(c, cam, p, nullptr, make_targets(rgb_out_device, aovs_device, variance_device, params, matte_device, passes_device), false, stats_out);
+}
+
 int pbrs_render_tile_matte_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
                                   const pbrs_aov_buffers* aovs_device, float* variance_device, const pbrs_matte_params* params,
                                   const pbrs_matte_buffers* matte_device, pbrs_stats* stats_out) {
-    if (!c) return PBRS_E_INVALID;
-    if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
-    return render(c, cam, p, nullptr, make_targets(rgb_out_device, aovs_device, variance_device, params, matte_device), false, stats_out);
+    return pbrs_render_tile_passes_device(c, cam, p, rgb_out_device, aovs_device, variance_device, params, matte_device, nullptr, stats_out);
 }
 
 int pbrs_render_tile_aovs_var_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_device,
@@ -1695,11 +1752,17 @@ int pbrs_render_tile_device(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_rend
     return pbrs_render_tile_matte_device(c, cam, p, rgb_out_device, nullptr, nullptr, nullptr, nullptr, stats_out);
 }
 
-int pbrs_render_tile_matte(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
-                           float* variance_host, const pbrs_matte_params* params, const pbrs_matte_buffers* matte_host, pbrs_stats* stats_out) {
+int pbrs_render_tile_passes(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                            float* variance_host, const pbrs_matte_params* params, const pbrs_matte_buffers* matte_host, const pbrs_pass_buffers* passes_host,
+                            pbrs_stats* stats_out) {
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
-    return render(c, cam, p, nullptr, make_targets(rgb_out_host, aovs_host, variance_host, params, matte_host), true, stats_out);
+    return render(c, cam, p, nullptr, make_targets(rgb_out_host, aovs_host, variance_host, params, matte_host, passes_host), true, stats_out);
+}
+
+int pbrs_render_tile_matte(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
+                           float* variance_host, const pbrs_matte_params* params, const pbrs_matte_buffers* matte_host, pbrs_stats* stats_out) {
+    return pbrs_render_tile_passes(c, cam, p, rgb_out_host, aovs_host, variance_host, params, matte_host, nullptr, stats_out);
 }
 
 int pbrs_render_tile_aovs_var(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, float* rgb_out_host, const pbrs_aov_buffers* aovs_host,
@@ -1721,7 +1784,7 @@ int pbrs_render_tile_filtered_device(pbrs_ctx* c, const pbrs_camera* cam, const 
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_device) return fail(c, PBRS_E_INVALID, "null output");
     if (!f) return fail(c, PBRS_E_INVALID, "null pixel filter");
-    return render(c, cam, p, f, make_targets(rgb_out_device, nullptr, nullptr, nullptr, nullptr), false, stats_out);
+    return render(c, cam, p, f, make_targets(rgb_out_device, nullptr, nullptr, nullptr, nullptr, nullptr), false, stats_out);
 }
 
 int pbrs_render_tile_filtered(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, float* rgb_out_host,
@@ -1729,7 +1792,7 @@ int pbrs_render_tile_filtered(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_re
     if (!c) return PBRS_E_INVALID;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
     if (!f) return fail(c, PBRS_E_INVALID, "null pixel filter");
-    return render(c, cam, p, f, make_targets(rgb_out_host, nullptr, nullptr, nullptr, nullptr), true, stats_out);
+    return render(c, cam, p, f, make_targets(rgb_out_host, nullptr, nullptr, nullptr, nullptr, nullptr), true, stats_out);
 }
 
 // ---- denoisers (include/pbrs_gpu.h, device/denoise.h) ----
@@ -1935,6 +1998,52 @@ int pbrs_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const u
     if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
     if (!rc) rc = matte_mask_launch(c, (uint32_t)P, slots, s[0].as<uint32_t>(), s[1].as<float>(), select, n_select, s[2].as<float>());
     if (!rc) rc = copy_staged(c, s + 2, 1, P, hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
+}
+
+namespace {
+
+int check_combine(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct, const float* indirect, const float* rgb_out) {
+    if (!direct || !indirect || !rgb_out) return fail(c, PBRS_E_INVALID, "null light passes or output");
+    if (w == 0 || h == 0) return fail(c, PBRS_E_INVALID, "empty image");
+    if ((uint64_t)w * h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The add over the 3 * P words of an image, on the context's stream (arguments checked).
+int combine_launch(pbrs_ctx* c, size_t P, const float* direct, const float* indirect, float* rgb_out) {
+    const uint32_t n = (uint32_t)(3 * P);
+    const uint32_t grid = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_combine_passes, dim3(grid < kStreamGridCap ? grid : kStreamGridCap), dim3(kBlock), 0, c->stream, direct, indirect, rgb_out, n);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_combine_passes_device(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct_device, const float* indirect_device, float* rgb_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_combine(c, w, h, direct_device, indirect_device, rgb_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return combine_launch(c, (size_t)w * h, direct_device, indirect_device, rgb_out_device);
+}
+
+int pbrs_combine_passes(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct_host, const float* indirect_host, float* rgb_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_combine(c, w, h, direct_host, indirect_host, rgb_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)w * h;
+    // the staging of a render with passes; the sum lands in the direct layer's place
+    Staged s[4] = {{direct_host, 3}, {indirect_host, 3}, {nullptr, 1}, {nullptr, 1}};
+    rc = stage(c, c->buf[BUF_PASS_OUT], "the light pass buffers", s, 4, P);
+    if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
+    if (!rc) rc = combine_launch(c, P, s[0].as<float>(), s[1].as<float>(), s[0].as<float>());
+    Staged out{rgb_out_host, 3, s[0].dev};
+    if (!rc) rc = copy_staged(c, &out, 1, P, hipMemcpyDeviceToHost);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -15,7 +15,11 @@ pbrs_denoise_var) with the variance AOV of the same samples: no sigma depends on
 --matte instance|material: also writes <out>.matte.npz, the id matte of the same samples (include/pbrs_gpu.h, pbrs_render_tile_matte):
 `ids` (h, w, slots) u32, `coverage` (h, w, slots) f32, `residual` (h, w) f32 — per pixel the ids ranked by the share of the pixel each
 covers (an .npz because the EXR writer holds RGB f32 only and cannot hold ids).  --matte-slots (default 6, at most 8) is the number of
-ids kept per pixel.  --matte-select i,j,...: also writes <out>.mask.png, the anti-aliased mask of those ids (pbrs_matte_mask)."""
+ids kept per pixel.  --matte-select i,j,...: also writes <out>.mask.png, the anti-aliased mask of those ids (pbrs_matte_mask).
+--passes: also writes <out>.direct.exr and <out>.indirect.exr, the light of the same samples that reaches the camera after one path
+vertex and after more (include/pbrs_gpu.h, pbrs_render_tile_passes; the path integrator only).
+--denoise-passes: also writes <out>.denoised_passes.<ext>: direct and indirect light each through the variance-guided denoiser with its
+own variance, summed again (pbrs_combine_passes); --denoise-var's parameters apply."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -25,6 +29,8 @@ aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
 denoise = "--denoise" in sys.argv
 denoise_var = "--denoise-var" in sys.argv
+passes = "--passes" in sys.argv
+denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
@@ -45,7 +51,7 @@ for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminan
         else:
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
             denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
-sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var")]
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes")]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -55,23 +61,29 @@ ctx = pbrs_amd.Context(0)
 ctx.upload(pbrs_amd.HostScene(ls))
 if integrator in ("materials", "normals"):  # --visualize-materials / --visualize-normals (src/main.rs:180-185): one ray per pixel
     msaa = 1
-guides = ("albedo", "normal", "depth") + (("instance",) if denoise or denoise_var else ())
+guides = ("albedo", "normal", "depth") + (("instance",) if denoise or denoise_var or denoise_passes else ())
 want = guides + (("variance",) if denoise_var else ())
+want_buf = aovs or denoise or denoise_var or denoise_passes
+want_layers = pbrs_amd.api.PASSES if denoise_passes else ("direct", "indirect") if passes else ()
 if filtered:
     pf = ls.pixel_filter()
     img, st = ctx.render_filtered(pf, msaa, msaa, depth, 1, integrator=integrator, timing=True)
     print(f"pixel filter: {pf}")
-    if aovs or denoise or denoise_var:
+    if want_buf:
         _, buf, _ = ctx.render_aovs(msaa, msaa, depth, 1, aovs=want, integrator=integrator)
     if matte_key:  # like the AOVs: per-pixel, from a separate render of the same samples
         matte = ctx.render_matte(msaa, msaa, depth, 1, key=matte_key, slots=matte_slots, integrator=integrator)[1]
 elif matte_key:
-    img, matte, buf, st = ctx.render_matte(msaa, msaa, depth, 1, key=matte_key, slots=matte_slots, aovs=want if aovs or denoise or denoise_var else (),
+    img, matte, buf, st = ctx.render_matte(msaa, msaa, depth, 1, key=matte_key, slots=matte_slots, aovs=want if want_buf else (),
                                            integrator=integrator, timing=True)
-elif aovs or denoise or denoise_var:
+elif want_layers:
+    img, layers, buf, st = ctx.render_passes(msaa, msaa, depth, 1, passes=want_layers, aovs=want if want_buf else (), integrator=integrator, timing=True)
+elif want_buf:
     img, buf, st = ctx.render_aovs(msaa, msaa, depth, 1, aovs=want, integrator=integrator, timing=True)
 else:
     img, st = ctx.render(msaa, msaa, depth, 1, integrator=integrator, timing=True)
+if want_layers and (filtered or matte_key):  # like the AOVs beside a filtered image: from a separate render of the same samples
+    layers = ctx.render_passes(msaa, msaa, depth, 1, passes=want_layers, integrator=integrator)[1]
 pbrs_amd.write_image(out, img)
 stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
 if denoise:
@@ -80,6 +92,14 @@ if denoise:
 if denoise_var:
     pbrs_amd.write_image(f"{stem}.denoised_var{ext}", ctx.denoise_var(img, buf["variance"], **{n: buf[n] for n in guides}, **denoise_var_params))
     print(f"-> {stem}.denoised_var{ext}")
+if passes:
+    for name in ("direct", "indirect"):
+        pbrs_amd.write_image(f"{stem}.{name}.exr", layers[name])
+        print(f"-> {stem}.{name}.exr")
+if denoise_passes:
+    clean = [ctx.denoise_var(layers[n], layers[n + "_variance"], **{g: buf[g] for g in guides}, **denoise_var_params) for n in ("direct", "indirect")]
+    pbrs_amd.write_image(f"{stem}.denoised_passes{ext}", ctx.combine_passes(*clean))
+    print(f"-> {stem}.denoised_passes{ext}")
 if aovs:
     for name in ("albedo", "normal", "depth"):
         a = buf[name] if buf[name].ndim == 3 else np.repeat(buf[name][:, :, None], 3, axis=2)
