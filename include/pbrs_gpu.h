@@ -703,6 +703,87 @@ int pbrs_combine_passes(pbrs_ctx*, uint32_t w, uint32_t h, const float* direct_h
 int pbrs_combine_passes_device(pbrs_ctx*, uint32_t w, uint32_t h, const float* direct_device, const float* indirect_device,
                                float* rgb_out_device);
 
+/* ---- temporal accumulation ------------------------------------------------------------------------------ */
+/* The temporal half of SVGF (Schied et al., HPG 2017): the previous frame's accumulated colour, luminance moments and history length
+ * are reprojected to this frame through the two cameras and the depth AOV, tested against the previous frame's guides, and blended
+ * with this frame's image; the variance of the accumulated pixel comes from the moments once the history is long enough.  Only the
+ * camera moves (instances have no motion here), and a miss pixel (depth +inf) gets no history.  An image operation like pbrs_denoise:
+ * it needs a context (device, stream) and no uploaded scene.  All arithmetic is f32 without fused multiply-add, in the order written;
+ * pn_* is include/pbrs_numeric.h; lum is the variance AOV's; dot(p, q) = (p.x * q.x + p.y * q.y) + p.z * q.z;
+ * cross(p, q) = (p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x); d2 is pbrs_denoise's squared distance.
+ * center, c, a, b are `cam`'s, the primed ones `cam_prev`'s.  For pixel p = (px, py), cur = rgb(p), y = lum(cur):
+ *   A. Non-finite pixel.  A channel of cur is not finite (pn_isfinite): rgb_out = cur, moments_out = (+0, +0), length_out = +0,
+ *      variance_out = +inf.  The NaN stays visible in this frame; length 0 carries nothing into the next one (rule B skips it).
+ *   B. Reprojection, with history_in != NULL and z = depth(p) finite and > 0.
+ *      x = (float)px + 0.5f, yc = (float)py + 0.5f; dir = (c + a * x) + b * yc per component (the camera ray through the pixel's
+ *      centre); P = center + dir * z (the depth AOV is the ray parameter of that direction, not normalised: the surface point).
+ *      e = P - center'; nu = cross(b', c'), nv = cross(c', a'), nw = cross(a', b'), D = dot(a', nu) (Cramer's rule for
+ *      e = wq * (c' + a' * xq + b' * yq)).  wq = dot(e, nw) / D: the depth the previous frame would have recorded; rejected unless
+ *      pn_isfinite(wq) && wq > 0.  xq = (dot(e, nu) / D) / wq, yq = (dot(e, nv) / D) / wq; fx = xq - 0.5f, fy = yq - 0.5f; rejected
+ *      unless fx > -1.0f && fx < (float)w && fy > -1.0f && fy < (float)h (a NaN rejects; the casts below stay in range).
+ *      ix = pn_f32_to_i32(pn_floor(fx)), tx = fx - pn_floor(fx); iy, ty likewise.  Taps j = 0, 1 (outer), i = 0, 1 (inner):
+ *      q = (ix + i, iy + j), bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty).  A tap counts only if q is inside the image, bw > 0,
+ *      length_in(q) > 0 (a NaN fails), every channel of rgb_in(q) and both moments are finite, zq = depth'(q) is finite and
+ *      pn_abs(zq - wq) <= depth_tolerance * wq, with both normals given d2(normal'(q) - normal(p)) <= normal_tolerance *
+ *      normal_tolerance, and with PBRS_TEMPORAL_ID_TEST instance'(q) == instance(p).  For each counted tap, from +0:
+ *      S.c = S.c + bw * rgb_in(q).c, A1 = A1 + bw * m1(q), A2 = A2 + bw * m2(q), N = N + bw * length_in(q), W = W + bw.
+ *      W == 0 or a rejected pixel: no history.  Otherwise iw = 1.0f / W, H = S * iw, h1 = A1 * iw, h2 = A2 * iw, n = N * iw.
+ *   C. Blend.  No history: rgb_out = cur, moments_out = (y, y * y), length_out = 1.0f.  With history:
+ *      n1 = pn_min(n + 1.0f, max_history), al = 1.0f / n1; rgb_out.c = H.c + al * (cur.c - H.c); m1 = h1 + al * (y - h1),
+ *      m2 = h2 + al * (y * y - h2); length_out = n1: the running mean up to max_history frames, an exponential average after that.
+ *   D. Variance of the accumulated pixel's luminance.  length_out >= min_temporal: v = m2 - m1 * m1; v = v < 0 ? +0 : v; a NaN becomes
+ *      +inf; variance_out = v * (1.0f / length_out).  Otherwise vin = +inf where frame.variance is NULL, NaN or < 0, else variance(p),
+ *      and variance_out = vin * (1.0f / length_out); +inf keeps its meaning of "unknown", as in pbrs_denoise_var.
+ * Scale rule.  For an integer j, inputs times 2^j (rgb, rgb_in, m1; m2 and the variance times 4^j) give rgb_out times 2^j, the moments
+ * times (2^j, 4^j), variance_out times 4^j and the same lengths, bit for bit, with pbrs_denoise_var's proviso: no product or sum that
+ * depends on the scale overflows or is a nonzero value below the smallest normal f32 at either scale.
+ * Layouts: frame and prev as pbrs_aov_buffers writes them (rgb, normal: 3 x f32 per pixel; variance, depth: f32; instance: u32); a history
+ * is rgb 3, moments 2 (m1, m2), length 1 f32 per pixel.  history_in == NULL is the first frame of a sequence; cam_prev and prev may then
+ * be NULL and are not read.  variance_out may be NULL.  The caller keeps this frame's depth, normal and instance as the next call's
+ * `prev`.  Pointers inside the structs are host memory for pbrs_temporal_accumulate (which stages 108 B per pixel on first use and
+ * synchronises before it returns), device memory for pbrs_temporal_accumulate_device, which needs no scratch, runs on the context's
+ * stream (pbrs_set_stream honoured) and does not wait: queued behind pbrs_render_tile_passes_device and ahead of
+ * pbrs_denoise_var_device on the same context it needs no synchronisation in between.  A context that never calls it allocates nothing.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, cam, frame, frame->rgb, frame->depth, history_out or one of its
+ * planes; history_in with a NULL plane or with cam_prev, prev or prev->depth NULL; a normal or an instance given for only one of the two
+ * frames; PBRS_TEMPORAL_ID_TEST without frame->instance; unknown flag bits; w or h 0; a camera whose size is not w x h; max_history not
+ * finite or < 1; a tolerance not finite or not > 0; min_temporal not finite or < 2; a plane of history_out equal to the matching plane of
+ * history_in (the kernel gathers: it cannot run in place).  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_TEMPORAL_ID_TEST 1u
+typedef struct pbrs_temporal_params {
+    uint32_t w, h;           /* whole images; both cameras must have width == w, height == h */
+    uint32_t flags;          /* PBRS_TEMPORAL_ID_TEST */
+    float max_history;       /* finite, >= 1: the history length saturates here (SVGF's alpha 0.2 is 5) */
+    float depth_tolerance;   /* finite, > 0: relative */
+    float normal_tolerance;  /* finite, > 0 */
+    float min_temporal;      /* finite, >= 2: from this length on the variance comes from the temporal moments (SVGF: 4) */
+    uint32_t pad;
+} pbrs_temporal_params;      /* 32 B */
+typedef struct pbrs_temporal_frame { /* this frame, layouts of pbrs_aov_buffers */
+    const float* rgb;         /* required: the image or one light-pass layer */
+    const float* variance;    /* nullable: the variance AOV of rgb */
+    const float* depth;       /* required */
+    const float* normal;      /* nullable */
+    const uint32_t* instance; /* nullable; required with PBRS_TEMPORAL_ID_TEST */
+} pbrs_temporal_frame;
+typedef struct pbrs_temporal_guides { /* the previous frame's */
+    const float* depth;
+    const float* normal;
+    const uint32_t* instance;
+} pbrs_temporal_guides;
+typedef struct pbrs_temporal_history {
+    float* rgb;     /* w * h * 3 */
+    float* moments; /* w * h * 2 */
+    float* length;  /* w * h */
+} pbrs_temporal_history;
+int pbrs_temporal_accumulate(pbrs_ctx*, const pbrs_temporal_params*, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                             const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
+                             const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host, float* variance_out_host);
+int pbrs_temporal_accumulate_device(pbrs_ctx*, const pbrs_temporal_params*, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                    const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
+                                    const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
+                                    float* variance_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,56 @@ def _pass_names(passes):
     return names
 
 
+class TemporalParams(C.Structure):
+    """pbrs_temporal_params (include/pbrs_gpu.h, "temporal accumulation"): image size, flags, where the history length saturates, the
+    two reprojection tolerances and the length from which the variance comes from the temporal moments."""
+    ID_TEST = 1
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("max_history", C.c_float), ("depth_tolerance", C.c_float),
+                ("normal_tolerance", C.c_float), ("min_temporal", C.c_float), ("pad", C.c_uint32)]
+
+    @classmethod
+    def make(cls, w, h, max_history=32.0, depth_tolerance=0.05, normal_tolerance=0.3, min_temporal=4.0, id_test=False):
+        p = cls()
+        p.w, p.h, p.flags = w, h, cls.ID_TEST if id_test else 0
+        p.max_history, p.depth_tolerance, p.normal_tolerance, p.min_temporal = max_history, depth_tolerance, normal_tolerance, min_temporal
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TemporalFrame(C.Structure):
+    """pbrs_temporal_frame: this frame's image, its variance AOV and its guides; rgb and depth are required."""
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "variance", "depth", "normal", "instance")]
+
+
+class TemporalGuides(C.Structure):
+    """pbrs_temporal_guides: the previous frame's depth, normal and instance."""
+    _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]
+
+
+class TemporalHistory(C.Structure):
+    """pbrs_temporal_history: accumulated colour (h, w, 3), luminance moments (h, w, 2) and history length (h, w), all f32."""
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "moments", "length")]
+
+
+# name -> (channels, dtype) of the planes of each struct above
+TEMPORAL_FRAME = {"rgb": (3, np.float32), "variance": (1, np.float32), "depth": (1, np.float32), "normal": (3, np.float32),
+                  "instance": (1, np.uint32)}
+TEMPORAL_GUIDES = {n: TEMPORAL_FRAME[n] for n in ("depth", "normal", "instance")}
+TEMPORAL_HISTORY = {"rgb": (3, np.float32), "moments": (2, np.float32), "length": (1, np.float32)}
+
+
+def _temporal_struct(cls, layout, ptrs, what):
+    """The ctypes struct `cls` from {name: pointer} (None entries: NULL)."""
+    s = cls()
+    for n, ptr in dict(ptrs).items():
+        if n not in layout:
+            raise ValueError(f"unknown {what} plane {n!r}; known: {list(layout)}")
+        setattr(s, n, ptr)
+    return s
+
+
 def _matte_select(select):
     """The selected ids as pbrs_matte_mask wants them: u32, strictly ascending (sorted and deduplicated here)."""
     sel = np.unique(np.asarray(select, dtype=np.int64).reshape(-1))
@@ -261,7 +311,8 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device",
                "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device",
                "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device",
-               "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device"]
+               "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device",
+               "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -348,6 +399,8 @@ def gpu_lib():
         L.pbrs_render_tile_passes_device.argtypes = [C.c_void_p] * 10
         L.pbrs_combine_passes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pbrs_combine_passes_device.argtypes = L.pbrs_combine_passes.argtypes
+        L.pbrs_temporal_accumulate.argtypes = [C.c_void_p] * 9
+        L.pbrs_temporal_accumulate_device.argtypes = [C.c_void_p] * 9
         _gpu = L
     return _gpu
 
@@ -367,6 +420,24 @@ def hip_runtime():
         L.hipFree.argtypes = [C.c_void_p]
         _hip = L
     return _hip
+
+
+def orbited(camera, about, axis, degrees):
+    """`camera` (a Camera) turned by `degrees` about the line through the point `about` along `axis`: a frame of a turntable or of an
+    orbit about the look-at point -> a new Camera of the same film."""
+    k = np.asarray(axis, dtype=np.float64)
+    k = k / np.linalg.norm(k)
+    t = np.radians(degrees)
+
+    def rot(v):
+        return v * np.cos(t) + np.cross(k, v) * np.sin(t) + k * np.dot(k, v) * (1.0 - np.cos(t))
+    about = np.asarray(about, dtype=np.float64)
+    out = Camera()
+    out.width, out.height = camera.width, camera.height
+    out.center[:] = [float(v) for v in about + rot(np.array(list(camera.center), dtype=np.float64) - about)]
+    for n in ("c", "a", "b"):
+        getattr(out, n)[:] = [float(v) for v in rot(np.array(list(getattr(camera, n)), dtype=np.float64))]
+    return out
 
 
 INTEGRATORS = {"path": 0, "direct": 1, "materials": 2, "normals": 3}  # PBRS_INTEGRATOR_*
@@ -551,32 +622,35 @@ class Context:
             setattr(bufs, n, ptr)
         return bufs, variance
 
-    def _render_host(self, p, names, mp=None, mb=None, pb=None):
+    def _render_host(self, p, names, mp=None, mb=None, pb=None, camera=None):
         """A host render of `p` with the AOVs named and, with `mp` and `mb`, a matte, with `pb`, light passes -> (rgb, {name: array},
         stats).  One entry point serves all of them: the library forwards the AOV and matte ones to it."""
         out = np.empty((p.h, p.w, 3), dtype=np.float32)
         bufs, arrays = self._aov_arrays(names, p)
         st = Stats()
-        self._check(self._L.pbrs_render_tile_passes(self._h, C.addressof(self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
+        self._check(self._L.pbrs_render_tile_passes(self._h, C.addressof(camera or self.scene.camera), C.addressof(p), out.ctypes.data, C.addressof(bufs),
                                                     arrays[VARIANCE].ctypes.data if VARIANCE in names else None, C.addressof(mp) if mp else None,
                                                     C.addressof(mb) if mb else None, C.addressof(pb) if pb else None, C.addressof(st)),
                     "pbrs_render_tile_passes")
         return out, arrays, st.as_dict()
 
-    def _render_device(self, p, rgb_device_ptr, bufs, variance, mp=None, mb=None, pb=None):
-        self._check(self._L.pbrs_render_tile_passes_device(self._h, C.addressof(self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
+    def _render_device(self, p, rgb_device_ptr, bufs, variance, mp=None, mb=None, pb=None, camera=None):
+        """`camera`: a Camera in the place of the scene's own (render_temporal's moving camera)."""
+        self._check(self._L.pbrs_render_tile_passes_device(self._h, C.addressof(camera or self.scene.camera), C.addressof(p), C.c_void_p(rgb_device_ptr),
                                                            C.addressof(bufs), C.c_void_p(variance), C.addressof(mp) if mp else None,
                                                            C.addressof(mb) if mb else None, C.addressof(pb) if pb else None, None),
                     "pbrs_render_tile_passes_device")
 
     def render_aovs(self, strata_x, strata_y, depth, seed, aovs=AOV_NAMES, tile=None, samples_per_pass=0, counters=False,
-                    timing=False, bands=None, integrator="path"):
+                    timing=False, bands=None, integrator="path", camera=None):
         """render() plus first-hit AOVs of the same camera samples (include/pbrs_gpu.h, pbrs_aov_buffers) -> (rgb, {name: array},
         stats).  albedo / normal: (h, w, 3) f32; coverage / depth: (h, w) f32; instance / material / prim: (h, w) u32.  The name
         "variance" (not in the default) adds the variance of the pixel's mean luminance, (h, w) f32, +inf where fewer than two samples
-        are finite (pbrs_render_tile_aovs_var)."""
+        are finite (pbrs_render_tile_aovs_var).  `camera`: a Camera of the film's size in the place of the scene's own (a frame of a
+        camera move, as render_temporal renders it)."""
         names = _aov_names(aovs)
-        return self._render_host(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator), names)
+        return self._render_host(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass, counters, timing, bands, integrator), names,
+                                 camera=camera)
 
     def render_aovs_device(self, rgb_device_ptr, aov_device_ptrs, strata_x, strata_y, depth, seed, tile=None, samples_per_pass=0,
                            counters=False, timing=False, bands=None, integrator="path"):
@@ -880,6 +954,129 @@ class Context:
             if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
                 raise PbrsError("hipMemcpy of the plain image failed")
             return out, noisy, stats
+        finally:
+            for ptr in dev.values():
+                hip.hipFree(ptr)
+
+    @staticmethod
+    def _temporal_host(layout, arrays, shape, what):
+        """{name: array or None} -> ({name: pointer}, the contiguous arrays to keep alive), each checked against the (h, w) image."""
+        ptrs, keep = {}, []
+        for n, a in arrays.items():
+            if n not in layout:
+                raise ValueError(f"unknown {what} plane {n!r}; known: {list(layout)}")
+            if a is None:
+                continue
+            ch, dt = layout[n]
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != (shape + (ch,) if ch > 1 else shape):
+                raise ValueError(f"{what} plane {n} of shape {a.shape} beside an image of {shape}")
+            keep.append(a)
+            ptrs[n] = a.ctypes.data
+        return ptrs, keep
+
+    def temporal_accumulate(self, rgb, depth, camera, variance=None, normal=None, instance=None, history=None, prev=None, camera_prev=None,
+                            return_variance=True, **params):
+        """Temporal accumulation (include/pbrs_gpu.h, pbrs_temporal_accumulate) of an (h, w, 3) f32 image, its depth AOV and what else
+        of its variance, normal and instance AOVs is given, rendered through `camera`.  `history` = the dict an earlier call returned
+        (None: the first frame of a sequence), `prev` = {"depth", "normal", "instance"} of that earlier frame, `camera_prev` its Camera.
+        -> ({"rgb": (h, w, 3), "moments": (h, w, 2), "length": (h, w)}, variance (h, w)), all f32: the new history, whose rgb is the
+        accumulated image, and the variance of its pixels' luminance (None with return_variance=False).  params: TemporalParams.make's
+        keywords."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        h, w, _ = rgb.shape
+        p = TemporalParams.make(w, h, **params)
+        fp, keep = self._temporal_host(TEMPORAL_FRAME, {"rgb": rgb, "variance": variance, "depth": depth, "normal": normal, "instance": instance},
+                                       (h, w), "frame")
+        frame = _temporal_struct(TemporalFrame, TEMPORAL_FRAME, fp, "frame")
+        hin = guides = None
+        if history is not None:
+            hp, k2 = self._temporal_host(TEMPORAL_HISTORY, history, (h, w), "history")
+            gp, k3 = self._temporal_host(TEMPORAL_GUIDES, prev or {}, (h, w), "previous guide")
+            keep += k2 + k3
+            hin = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, hp, "history")
+            guides = _temporal_struct(TemporalGuides, TEMPORAL_GUIDES, gp, "previous guide")
+        out = {n: np.empty((h, w, ch) if ch > 1 else (h, w), dtype=dt) for n, (ch, dt) in TEMPORAL_HISTORY.items()}
+        hout = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, {n: a.ctypes.data for n, a in out.items()}, "history")
+        vout = np.empty((h, w), dtype=np.float32) if return_variance else None
+        self._check(self._L.pbrs_temporal_accumulate(self._h, C.addressof(p), C.addressof(camera), C.addressof(camera_prev) if camera_prev else None,
+                                                     C.addressof(frame), C.addressof(guides) if guides else None, C.addressof(hin) if hin else None,
+                                                     C.addressof(hout), vout.ctypes.data if return_variance else None), "pbrs_temporal_accumulate")
+        return out, vout
+
+    def temporal_accumulate_device(self, frame_device_ptrs, history_out_device_ptrs, w, h, camera, history_in_device_ptrs=None,
+                                   prev_device_ptrs=None, camera_prev=None, variance_out_device_ptr=None, **params):
+        """temporal_accumulate() on caller-owned device memory: {name: pointer} dicts with the names of TemporalFrame, TemporalHistory
+        and TemporalGuides.  Runs on the context's stream behind whatever was queued there (a render_aovs_var_device before it and a
+        denoise_var_device after it need no synchronisation in between) and does not wait: valid after `collect_stats()`.  The history
+        written must not share a plane with the history read."""
+        p = TemporalParams.make(w, h, **params)
+        frame = _temporal_struct(TemporalFrame, TEMPORAL_FRAME, frame_device_ptrs, "frame")
+        hout = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, history_out_device_ptrs, "history")
+        hin = guides = None
+        if history_in_device_ptrs is not None:
+            hin = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, history_in_device_ptrs, "history")
+            guides = _temporal_struct(TemporalGuides, TEMPORAL_GUIDES, prev_device_ptrs or {}, "previous guide")
+        self._check(self._L.pbrs_temporal_accumulate_device(self._h, C.addressof(p), C.addressof(camera),
+                                                            C.addressof(camera_prev) if camera_prev else None, C.addressof(frame),
+                                                            C.addressof(guides) if guides else None, C.addressof(hin) if hin else None,
+                                                            C.addressof(hout), C.c_void_p(variance_out_device_ptr)),
+                    "pbrs_temporal_accumulate_device")
+
+    def render_temporal(self, cameras, strata_x, strata_y, depth, seeds, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                        temporal=None, **params):
+        """A sequence of frames of the uploaded scene, one per Camera of `cameras` with the seed of `seeds` at the same place, each
+        rendered with its guides and its variance, accumulated against the generator's own history (temporal_accumulate_device; the
+        history and the guides it is tested against live in ping-pong device buffers) and filtered (denoise_var_device on the
+        accumulated image with the accumulated variance): one stream, no synchronisation inside a frame, the images copied back behind
+        one wait per frame.  A generator of (denoised, accumulated, noisy, stats), (h, w, 3) f32 each; its device buffers are freed when
+        it ends or is closed.  `guides` must hold "depth"; `temporal`: TemporalParams.make's keywords; params: DenoiseVarParams.make's."""
+        self._denoise_guide_names(guides)
+        if "depth" not in guides:
+            raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
+        cameras, seeds = list(cameras), list(seeds)
+        if len(cameras) != len(seeds):
+            raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
+        tparams = dict(temporal or {})
+        TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
+        w, h = self.scene.width, self.scene.height
+        hip = hip_runtime()
+        n_rgb = 3 * w * h * 4
+        kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
+        sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, "acc_variance": w * h * 4}
+        for k in (0, 1):
+            sizes.update({f"{n}{k}": DENOISE_GUIDES[n][0] * w * h * 4 for n in kept})
+            sizes.update({f"h_{n}{k}": ch * w * h * 4 for n, (ch, _) in TEMPORAL_HISTORY.items()})
+        sizes.update({n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides if n not in kept})
+        dev = {}
+        try:
+            for n, nbytes in sizes.items():
+                ptr = C.c_void_p()
+                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
+                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_temporal failed")
+                dev[n] = ptr
+            cam_prev = None
+            for i, (cam, seed) in enumerate(zip(cameras, seeds)):
+                cur, old = i & 1, (i & 1) ^ 1
+                gp = {n: dev[f"{n}{cur}" if n in kept else n].value for n in guides}
+                bufs, _ = self._aov_device(gp)
+                self._render_device(self._params(strata_x, strata_y, depth, seed, None, samples_per_pass), dev["rgb"].value, bufs,
+                                    dev[VARIANCE].value, camera=cam)
+                frame = {"rgb": dev["rgb"].value, "variance": dev[VARIANCE].value, **{n: gp[n] for n in kept}}
+                hist = [{n: dev[f"h_{n}{k}"].value for n in TEMPORAL_HISTORY} for k in (0, 1)]
+                self.temporal_accumulate_device(frame, hist[cur], w, h, cam, hist[old] if i else None,
+                                                {n: dev[f"{n}{old}"].value for n in kept} if i else None, cam_prev,
+                                                dev["acc_variance"].value, **tparams)
+                self.denoise_var_device(hist[cur]["rgb"], dev["out"].value, w, h, dev["acc_variance"].value, gp, **params)
+                stats = self.collect_stats()  # waits for the stream
+                images = []
+                for src in (dev["out"], dev[f"h_rgb{cur}"], dev["rgb"]):
+                    img = np.empty((h, w, 3), dtype=np.float32)
+                    if hip.hipMemcpy(img.ctypes.data, src, n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
+                        raise PbrsError("hipMemcpy of a render_temporal image failed")
+                    images.append(img)
+                cam_prev = cam
+                yield images[0], images[1], images[2], stats
         finally:
             for ptr in dev.values():
                 hip.hipFree(ptr)

@@ -28,6 +28,7 @@
 #include "device/moments.h"
 #include "device/matte.h"
 #include "device/passes.h"
+#include "device/temporal.h"
 
 namespace {
 
@@ -189,6 +190,9 @@ enum BufferId {
     // into (PBRS_PASS_STATE_WORDS per pixel, planar), the host variants' staging (the four of pbrs_pass_buffers, one after the other) and the
     // D column of each pass set (PassSet::direct: one float4 per path beside its PathState), held only by a context that has rendered passes
     BUF_PASS_STATE, BUF_PASS_OUT, BUF_PASS_DIRECT, BUF_PASS_DIRECT_SET1,
+    // temporal accumulation (pbrs_temporal_accumulate, device/temporal.h): the host variant's staging (the frame, the previous guides,
+    // the history in and out, the variance out, one after the other); the device variant needs nothing
+    BUF_TEMPORAL_STAGE,
     N_BUFFERS
 };
 
@@ -2044,6 +2048,110 @@ int pbrs_combine_passes(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct
     if (!rc) rc = combine_launch(c, P, s[0].as<float>(), s[1].as<float>(), s[0].as<float>());
     Staged out{rgb_out_host, 3, s[0].dev};
     if (!rc) rc = copy_staged(c, &out, 1, P, hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
+}
+
+// ---- temporal accumulation (include/pbrs_gpu.h, device/temporal.h) ----
+static_assert(sizeof(pbrs_temporal_params) == 32, "pbrs_temporal_params is 32 B");
+
+namespace {
+
+using TemporalKernel = void (*)(TemporalIn, TemporalOut, TemporalConst);
+// [normal test][id test], with a history; without one no tap is read
+constexpr TemporalKernel kTemporal[2][2] = {{k_temporal<true, false, false>, k_temporal<true, false, true>},
+                                            {k_temporal<true, true, false>, k_temporal<true, true, true>}};
+
+int check_temporal(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
+                   const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout) {
+    if (!p || !cam || !f || !hout) return fail(c, PBRS_E_INVALID, "null temporal params, camera, frame or history_out");
+    if (!f->rgb || !f->depth) return fail(c, PBRS_E_INVALID, "the temporal frame needs rgb and depth");
+    if (!hout->rgb || !hout->moments || !hout->length) return fail(c, PBRS_E_INVALID, "history_out with a null plane");
+    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty image");
+    if (p->flags & ~PBRS_TEMPORAL_ID_TEST) return fail(c, PBRS_E_INVALID, "unknown temporal flag bits");
+    if ((p->flags & PBRS_TEMPORAL_ID_TEST) && !f->instance) return fail(c, PBRS_E_INVALID, "PBRS_TEMPORAL_ID_TEST without instance ids");
+    if (!pn_isfinite(p->max_history) || !(p->max_history >= 1.0f)) return fail(c, PBRS_E_INVALID, "max_history must be finite and >= 1");
+    const float tol[2] = {p->depth_tolerance, p->normal_tolerance};
+    for (float t : tol)
+        if (!pn_isfinite(t) || !(t > 0.0f)) return fail(c, PBRS_E_INVALID, "a temporal tolerance must be finite and > 0");
+    if (!pn_isfinite(p->min_temporal) || !(p->min_temporal >= 2.0f)) return fail(c, PBRS_E_INVALID, "min_temporal must be finite and >= 2");
+    if (cam->width != p->w || cam->height != p->h) return fail(c, PBRS_E_INVALID, "the camera's size is not w x h");
+    if (hin) {
+        if (!hin->rgb || !hin->moments || !hin->length) return fail(c, PBRS_E_INVALID, "history_in with a null plane");
+        if (!cam_prev || !prev || !prev->depth) return fail(c, PBRS_E_INVALID, "history_in without the previous camera or the previous depth");
+        if (cam_prev->width != p->w || cam_prev->height != p->h) return fail(c, PBRS_E_INVALID, "the previous camera's size is not w x h");
+        if (!f->normal != !prev->normal || !f->instance != !prev->instance)
+            return fail(c, PBRS_E_INVALID, "a normal or an instance guide given for only one of the two frames");
+        if (hin->rgb == hout->rgb || hin->moments == hout->moments || hin->length == hout->length)
+            return fail(c, PBRS_E_INVALID, "temporal accumulation cannot run in place: history_out shares a plane with history_in");
+    }
+    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The one launch on the context's stream (arguments checked; device pointers).  What depends on the cameras alone is computed here, in
+// the header's order (this file is compiled without contraction, host side included).
+int temporal_launch(pbrs_ctx* c, const pbrs_temporal_params& p, const pbrs_camera& cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame& f,
+                    const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history& hout, float* variance_out) {
+    TemporalConst k{};
+    k.w = p.w, k.h = p.h;
+    k.max_history = p.max_history, k.depth_tolerance = p.depth_tolerance, k.min_temporal = p.min_temporal;
+    k.normal_tolerance2 = p.normal_tolerance * p.normal_tolerance;
+    for (int i = 0; i < 3; ++i) k.center[i] = cam.center[i], k.c[i] = cam.c[i], k.a[i] = cam.a[i], k.b[i] = cam.b[i];
+    TemporalIn in{f.rgb, f.variance, f.depth, f.normal, f.instance, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    TemporalKernel fn = k_temporal<false, false, false>;
+    if (hin) {
+        for (int i = 0; i < 3; ++i) k.center_prev[i] = cam_prev->center[i];
+        temporal_cross(cam_prev->b, cam_prev->c, k.nu);
+        temporal_cross(cam_prev->c, cam_prev->a, k.nv);
+        temporal_cross(cam_prev->a, cam_prev->b, k.nw);
+        k.D = temporal_dot(cam_prev->a, k.nu);
+        in.depth_prev = prev->depth, in.normal_prev = prev->normal, in.instance_prev = prev->instance;
+        in.rgb_hist = hin->rgb, in.moments_hist = hin->moments, in.length_hist = hin->length;
+        fn = kTemporal[f.normal != nullptr][(p.flags & PBRS_TEMPORAL_ID_TEST) != 0];
+    }
+    const uint32_t P = p.w * p.h;
+    hipLaunchKernelGGL(fn, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, in, TemporalOut{hout.rgb, hout.moments, hout.length, variance_out}, k);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_temporal_accumulate_device(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                    const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
+                                    const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
+                                    float* variance_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_temporal(c, p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return temporal_launch(c, *p, *cam, cam_prev, *frame_device, prev_device, history_in_device, *history_out_device, variance_out_device);
+}
+
+int pbrs_temporal_accumulate(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                             const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
+                             const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host, float* variance_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_temporal(c, p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)p->w * p->h;
+    const pbrs_temporal_frame& f = *frame_host;
+    const pbrs_temporal_history& ho = *history_out_host;
+    const pbrs_temporal_guides g = history_in_host ? *prev_host : pbrs_temporal_guides{};  // without a history the previous frame is not read
+    const pbrs_temporal_history hi = history_in_host ? *history_in_host : pbrs_temporal_history{};
+    Staged s[15] = {{f.rgb, 3}, {f.variance, 1}, {f.depth, 1}, {f.normal, 3}, {f.instance, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1},
+                    {hi.rgb, 3}, {hi.moments, 2}, {hi.length, 1}, {ho.rgb, 3}, {ho.moments, 2}, {ho.length, 1}, {variance_out_host, 1}};
+    rc = stage(c, c->buf[BUF_TEMPORAL_STAGE], "the temporal accumulation's staging", s, 15, P);
+    if (!rc) rc = copy_staged(c, s, 11, P, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    const pbrs_temporal_frame fd{s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
+    const pbrs_temporal_guides gd{s[5].as<float>(), s[6].as<float>(), s[7].as<uint32_t>()};
+    const pbrs_temporal_history hid{s[8].as<float>(), s[9].as<float>(), s[10].as<float>()}, hod{s[11].as<float>(), s[12].as<float>(), s[13].as<float>()};
+    rc = temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>());
+    if (!rc) rc = copy_staged(c, s + 11, 4, P, hipMemcpyDeviceToHost);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;

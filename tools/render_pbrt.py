@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -19,12 +19,18 @@ ids kept per pixel.  --matte-select i,j,...: also writes <out>.mask.png, the ant
 --passes: also writes <out>.direct.exr and <out>.indirect.exr, the light of the same samples that reaches the camera after one path
 vertex and after more (include/pbrs_gpu.h, pbrs_render_tile_passes; the path integrator only).
 --denoise-passes: also writes <out>.denoised_passes.<ext>: direct and indirect light each through the variance-guided denoiser with its
-own variance, summed again (pbrs_combine_passes); --denoise-var's parameters apply."""
+own variance, summed again (pbrs_combine_passes); --denoise-var's parameters apply.
+--frames N: a sequence of N frames instead of one image, frame k with the seed 1 + k and the camera turned by k * DEG degrees (--orbit,
+default 0) about the file's look-at point around its up vector; one image per frame, <out>.0000.<ext>, <out>.0001.<ext>, ...  (the path
+integrator; the other options above do not apply).  With --temporal every frame is accumulated over the frames before it and filtered
+(include/pbrs_gpu.h, pbrs_temporal_accumulate; Context.render_temporal): the frame's image is then the accumulated and filtered one,
+and <out>.NNNN.accumulated.<ext> and <out>.NNNN.noisy.<ext> are written beside it; --denoise-var's parameters apply."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pbrs_amd
 
+temporal = "--temporal" in sys.argv
 aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
 denoise = "--denoise" in sys.argv
@@ -33,12 +39,17 @@ passes = "--passes" in sys.argv
 denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
-for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+frames, orbit = 0, 0.0
+for flag in ("--frames", "--orbit", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
         del sys.argv[k:k + 2]
-        if flag == "--denoise-iterations":
+        if flag == "--frames":
+            frames = int(value)
+        elif flag == "--orbit":
+            orbit = float(value)
+        elif flag == "--denoise-iterations":
             denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
         elif flag == "--matte":
             matte_key = value
@@ -51,14 +62,31 @@ for flag in ("--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminan
         else:
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
             denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
-sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes")]
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal")]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
 integrator = sys.argv[5] if len(sys.argv) > 5 else "path"
 ls = pbrs_amd.load_pbrt(scene)
 ctx = pbrs_amd.Context(0)
-ctx.upload(pbrs_amd.HostScene(ls))
+hs = pbrs_amd.HostScene(ls)
+ctx.upload(hs)
+if frames:
+    spec = ls.build().camera
+    cams = [pbrs_amd.api.orbited(hs.camera, list(spec.target), list(spec.up), orbit * k) for k in range(frames)]
+    stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
+    if temporal:
+        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), **denoise_var_params)
+    else:
+        sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
+    for k, images in enumerate(sequence):
+        pbrs_amd.write_image(f"{stem}.{k:04d}{ext}", images[0])
+        if temporal:
+            pbrs_amd.write_image(f"{stem}.{k:04d}.accumulated{ext}", images[1])
+            pbrs_amd.write_image(f"{stem}.{k:04d}.noisy{ext}", images[2])
+    print(f"{frames} frames of {hs.width}x{hs.height} at {msaa * msaa} spp, {orbit} degrees per frame"
+          f"{', accumulated and filtered' if temporal else ''} -> {stem}.0000{ext} ..")
+    sys.exit(0)
 if integrator in ("materials", "normals"):  # --visualize-materials / --visualize-normals (src/main.rs:180-185): one ray per pixel
     msaa = 1
 guides = ("albedo", "normal", "depth") + (("instance",) if denoise or denoise_var or denoise_passes else ())
