@@ -707,7 +707,8 @@ int pbrs_combine_passes_device(pbrs_ctx*, uint32_t w, uint32_t h, const float* d
 /* The temporal half of SVGF (Schied et al., HPG 2017): the previous frame's accumulated colour, luminance moments and history length
  * are reprojected to this frame through the two cameras and the depth AOV, tested against the previous frame's guides, and blended
  * with this frame's image; the variance of the accumulated pixel comes from the moments once the history is long enough.  Only the
- * camera moves (instances have no motion here), and a miss pixel (depth +inf) gets no history.  An image operation like pbrs_denoise:
+ * camera moves (instances have no motion here; pbrs_temporal_accumulate_motion below carries a surface point through its instance's
+ * own motion), and a miss pixel (depth +inf) gets no history.  An image operation like pbrs_denoise:
  * it needs a context (device, stream) and no uploaded scene.  All arithmetic is f32 without fused multiply-add, in the order written;
  * pn_* is include/pbrs_numeric.h; lum is the variance AOV's; dot(p, q) = (p.x * q.x + p.y * q.y) + p.z * q.z;
  * cross(p, q) = (p.y * q.z - p.z * q.y, p.z * q.x - p.x * q.z, p.x * q.y - p.y * q.x); d2 is pbrs_denoise's squared distance.
@@ -783,6 +784,64 @@ int pbrs_temporal_accumulate_device(pbrs_ctx*, const pbrs_temporal_params*, cons
                                     const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
                                     const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
                                     float* variance_out_device);
+
+/* ---- moving instances and motion vectors ---------------------------------------------------------------- */
+/* Temporal accumulation that follows moving instances.  A sequence in which an object moves is rendered by uploading a new scene per
+ * frame; instance ids are stable (`instance` indexes pbrs_scene_desc::instances, which keeps the scene spec's order), so a table with one
+ * record per instance says where each surface point was one frame ago.  The caller computes the records (for rigid or affine motion
+ * m = fwd_prev * inv_cur, n = the inverse transpose of m's linear part).
+ * The rule is rule B of pbrs_temporal_accumulate with these lines changed, the same f32 arithmetic without fused multiply-add:
+ *   After P = center + dir * z let i = instance(p).
+ *   If motion != NULL && i < n_motion && !(motion[i].flags & PBRS_MOTION_IDENTITY), with m, n of motion[i] and nrm = normal(p):
+ *     Pm.r = ((m[r][0] * P.x + m[r][1] * P.y) + m[r][2] * P.z) + m[r][3]      r = 0, 1, 2
+ *     nm.r = (n[r][0] * nrm.x + n[r][1] * nrm.y) + n[r][2] * nrm.z            (only with both normals given)
+ *   Otherwise Pm = P and nm = normal(p), their own bits.
+ *   Then e = Pm - center', and the normal test reads d2(normal'(q) - nm) <= normal_tolerance * normal_tolerance.
+ * An id at or above n_motion (the miss id 0xFFFFFFFF included) is a static instance: a table shorter than the scene is legal.  A
+ * non-finite record needs no rule of its own: wq is not finite and the pixel has no history.  The id test, where asked for, still compares
+ * instance'(q) with instance(p).  The scale rule holds unchanged (the records are not scaled).  Lights that move, and shadows or
+ * reflections of a moving instance on other surfaces, are not followed: the history of such a pixel is stale until the depth, normal or
+ * id test refuses it, as in SVGF.
+ * pbrs_temporal_accumulate_motion[_device] are pbrs_temporal_accumulate[_device] plus the table; motion == NULL with n_motion == 0 is
+ * exactly that call (which forwards here), bit for bit.  The table is HOST memory in both variants and is read before the call returns:
+ * the library copies it on the context's stream into a buffer of the context that grows on first need, so the device variant stays
+ * asynchronous and the copy is ordered against the kernels of earlier calls (two calls with different tables need no wait in between).
+ * Refused beside what pbrs_temporal_accumulate refuses: motion != NULL without frame->instance (with or without the id test) or with
+ * n_motion == 0, motion == NULL with n_motion != 0: PBRS_E_INVALID; n_motion above 2^24: PBRS_E_LIMIT. */
+#define PBRS_MOTION_IDENTITY 1u
+typedef struct pbrs_instance_motion {
+    float m[3][4];   /* a world point of THIS frame -> where the same material point was in the PREVIOUS frame's world */
+    float n[3][3];   /* a normal of this frame -> the previous frame's (the caller's inverse transpose; not renormalised) */
+    uint32_t flags;  /* PBRS_MOTION_IDENTITY: the record is not applied (P and the normal keep their own bits) */
+    uint32_t pad[2];
+} pbrs_instance_motion;  /* 96 B */
+int pbrs_temporal_accumulate_motion(pbrs_ctx*, const pbrs_temporal_params*, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                    const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
+                                    const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host,
+                                    float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion);
+int pbrs_temporal_accumulate_motion_device(pbrs_ctx*, const pbrs_temporal_params*, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                           const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
+                                           const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
+                                           float* variance_out_device, const pbrs_instance_motion* motion, uint32_t n_motion);
+
+/* The screen-space motion vector AOV: the same reprojection written out per pixel, what a compositor's vector blur and an external
+ * temporal denoiser take as their flow.  Rule B up to (wq, xq, yq) with the motion rule above (z = depth(p), i = instance(p)), then
+ *   motion_out(p) = (xq - x, yq - yc)   where the point was minus where it is, in pixels; 2 x f32 per pixel
+ *   prev_depth_out(p) = wq              the depth the previous frame would have recorded
+ * without rejection by the film's bounds (a point that was off-screen still has a vector).  Where z is not finite or not > 0, or wq is
+ * not finite or not > 0: motion_out(p) = (+0, +0) and prev_depth_out(p) = +inf.  prev_depth_out may be NULL; instance may be NULL only
+ * when motion is NULL (it is then not read).  An image operation like pbrs_denoise: no uploaded scene is needed.  depth, instance and
+ * the outputs are host memory for pbrs_motion_vectors (which stages 20 B per pixel on first use and synchronises before it returns),
+ * device memory for pbrs_motion_vectors_device, which runs on the context's stream and does not wait; the table is host memory in both.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL cam, cam_prev, depth or motion_out; w or h 0; a camera whose size is not
+ * w x h; motion != NULL without instance or with n_motion == 0; motion == NULL with n_motion != 0.  w * h above 2^28 or n_motion above
+ * 2^24: PBRS_E_LIMIT. */
+int pbrs_motion_vectors(pbrs_ctx*, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth_host,
+                        const uint32_t* instance_host, const pbrs_instance_motion* motion, uint32_t n_motion, float* motion_out_host,
+                        float* prev_depth_out_host);
+int pbrs_motion_vectors_device(pbrs_ctx*, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                               const float* depth_device, const uint32_t* instance_device, const pbrs_instance_motion* motion,
+                               uint32_t n_motion, float* motion_out_device, float* prev_depth_out_device);
 
 #ifdef __cplusplus
 }

@@ -270,6 +270,13 @@ class TemporalHistory(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rgb", "moments", "length")]
 
 
+class InstanceMotion(C.Structure):
+    """pbrs_instance_motion (include/pbrs_gpu.h, "moving instances and motion vectors"): where a point of one instance was one frame
+    ago (m, rows of an affine map), what that does to a normal (n) and IDENTITY = the record is not applied.  96 bytes."""
+    IDENTITY = 1
+    _fields_ = [("m", (C.c_float * 4) * 3), ("n", (C.c_float * 3) * 3), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
 # name -> (channels, dtype) of the planes of each struct above
 TEMPORAL_FRAME = {"rgb": (3, np.float32), "variance": (1, np.float32), "depth": (1, np.float32), "normal": (3, np.float32),
                   "instance": (1, np.uint32)}
@@ -312,7 +319,8 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device",
                "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device",
                "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device",
-               "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device"]
+               "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device", "pbrs_temporal_accumulate_motion",
+               "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -401,6 +409,10 @@ def gpu_lib():
         L.pbrs_combine_passes_device.argtypes = L.pbrs_combine_passes.argtypes
         L.pbrs_temporal_accumulate.argtypes = [C.c_void_p] * 9
         L.pbrs_temporal_accumulate_device.argtypes = [C.c_void_p] * 9
+        L.pbrs_temporal_accumulate_motion.argtypes = [C.c_void_p] * 10 + [C.c_uint32]
+        L.pbrs_temporal_accumulate_motion_device.argtypes = L.pbrs_temporal_accumulate_motion.argtypes
+        L.pbrs_motion_vectors.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]
+        L.pbrs_motion_vectors_device.argtypes = L.pbrs_motion_vectors.argtypes
         _gpu = L
     return _gpu
 
@@ -438,6 +450,39 @@ def orbited(camera, about, axis, degrees):
     for n in ("c", "a", "b"):
         getattr(out, n)[:] = [float(v) for v in rot(np.array(list(getattr(camera, n)), dtype=np.float64))]
     return out
+
+
+def instance_motion(scene, scene_prev):
+    """The motion table (a ctypes array of InstanceMotion, one per instance) that carries a surface point of `scene` to where it was in
+    `scene_prev`, two HostScenes of the same instances in the same order: m = fwd_prev . inv_cur and n = transpose(lin(fwd_cur) .
+    lin(inv_prev)) (the inverse transpose of m's linear part), computed in float64 from the scenes' f32 records and rounded once.  An
+    instance whose fwd and inv are bitwise equal in both scenes is flagged IDENTITY."""
+    fwd, inv = scene.instance_transforms()
+    fwd_p, inv_p = scene_prev.instance_transforms()
+    if len(fwd) != len(fwd_p):
+        raise ValueError(f"instance_motion: {len(fwd)} instances beside {len(fwd_p)} in the previous scene")
+    table = (InstanceMotion * max(len(fwd), 1))()
+    bottom = np.array([[0.0, 0.0, 0.0, 1.0]])
+    for i in range(len(fwd)):
+        r = table[i]
+        if fwd[i].tobytes() == fwd_p[i].tobytes() and inv[i].tobytes() == inv_p[i].tobytes():
+            m, n, r.flags = np.eye(3, 4), np.eye(3), InstanceMotion.IDENTITY
+        else:
+            m = (np.vstack([fwd_p[i].astype(np.float64), bottom]) @ np.vstack([inv[i].astype(np.float64), bottom]))[:3]
+            n = (fwd[i, :, :3].astype(np.float64) @ inv_p[i, :, :3].astype(np.float64)).T
+        for a in range(3):
+            r.m[a][:] = [float(v) for v in m[a].astype(np.float32)]
+            r.n[a][:] = [float(v) for v in n[a].astype(np.float32)]
+    return table
+
+
+def _motion_args(motion):
+    """(pointer, record count) of a motion table: a ctypes array of InstanceMotion, or None."""
+    if motion is None:
+        return None, 0
+    if not isinstance(motion, C.Array) or motion._type_ is not InstanceMotion:
+        raise ValueError("a motion table is a ctypes array of InstanceMotion (api.instance_motion)")
+    return C.addressof(motion), len(motion)
 
 
 INTEGRATORS = {"path": 0, "direct": 1, "materials": 2, "normals": 3}  # PBRS_INTEGRATOR_*
@@ -516,6 +561,15 @@ class HostScene:
         return (32 * (d.n_tlas_nodes + d.n_blas_nodes) + 128 * d.n_instances + 48 * d.n_shapes + 32 * d.n_meshes +
                 (48 + 64) * d.n_triangles + 32 * d.n_materials + 64 * d.n_bxdfs + 64 * d.n_area_lights + 32 * d.n_delta_lights +
                 48 * d.n_textures + 4 * (d.n_tex_floats + d.n_tex_words) + 48 * d.n_fourier_tables)
+
+    def instance_transforms(self):
+        """(fwd, inv): the instances' object-to-world and world-to-object transforms as (n, 3, 4) f32 arrays, rows of the affine
+        matrices as pbrs_instance holds them, in the order of the scene spec (the `instance` AOV indexes them)."""
+        n = self.desc.n_instances
+        if n == 0 or not self.desc.instances:
+            return np.zeros((0, 3, 4), dtype=np.float32), np.zeros((0, 3, 4), dtype=np.float32)
+        rec = np.ctypeslib.as_array(C.cast(self.desc.instances, C.POINTER(C.c_float)), shape=(n, 32))  # pbrs_instance: 128 B, inv then fwd
+        return rec[:, 12:24].reshape(n, 3, 4).copy(), rec[:, :12].reshape(n, 3, 4).copy()
 
     def nodes(self, which="tlas"):
         n, p = (self.desc.n_tlas_nodes, self.desc.tlas_nodes) if which == "tlas" else (self.desc.n_blas_nodes, self.desc.blas_nodes)
@@ -976,13 +1030,15 @@ class Context:
         return ptrs, keep
 
     def temporal_accumulate(self, rgb, depth, camera, variance=None, normal=None, instance=None, history=None, prev=None, camera_prev=None,
-                            return_variance=True, **params):
+                            return_variance=True, motion=None, **params):
         """Temporal accumulation (include/pbrs_gpu.h, pbrs_temporal_accumulate) of an (h, w, 3) f32 image, its depth AOV and what else
         of its variance, normal and instance AOVs is given, rendered through `camera`.  `history` = the dict an earlier call returned
         (None: the first frame of a sequence), `prev` = {"depth", "normal", "instance"} of that earlier frame, `camera_prev` its Camera.
         -> ({"rgb": (h, w, 3), "moments": (h, w, 2), "length": (h, w)}, variance (h, w)), all f32: the new history, whose rgb is the
-        accumulated image, and the variance of its pixels' luminance (None with return_variance=False).  params: TemporalParams.make's
-        keywords."""
+        accumulated image, and the variance of its pixels' luminance (None with return_variance=False).  `motion`: the table of
+        api.instance_motion for sequences in which instances move (pbrs_temporal_accumulate_motion; needs `instance`); None is the call
+        without one.  params: TemporalParams.make's keywords."""
+        table = _motion_args(motion)
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
         h, w, _ = rgb.shape
         p = TemporalParams.make(w, h, **params)
@@ -999,17 +1055,23 @@ class Context:
         out = {n: np.empty((h, w, ch) if ch > 1 else (h, w), dtype=dt) for n, (ch, dt) in TEMPORAL_HISTORY.items()}
         hout = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, {n: a.ctypes.data for n, a in out.items()}, "history")
         vout = np.empty((h, w), dtype=np.float32) if return_variance else None
-        self._check(self._L.pbrs_temporal_accumulate(self._h, C.addressof(p), C.addressof(camera), C.addressof(camera_prev) if camera_prev else None,
-                                                     C.addressof(frame), C.addressof(guides) if guides else None, C.addressof(hin) if hin else None,
-                                                     C.addressof(hout), vout.ctypes.data if return_variance else None), "pbrs_temporal_accumulate")
+        args = (self._h, C.addressof(p), C.addressof(camera), C.addressof(camera_prev) if camera_prev else None, C.addressof(frame),
+                C.addressof(guides) if guides else None, C.addressof(hin) if hin else None, C.addressof(hout),
+                vout.ctypes.data if return_variance else None)
+        if motion is None:
+            self._check(self._L.pbrs_temporal_accumulate(*args), "pbrs_temporal_accumulate")
+        else:
+            self._check(self._L.pbrs_temporal_accumulate_motion(*args, *table), "pbrs_temporal_accumulate_motion")
         return out, vout
 
     def temporal_accumulate_device(self, frame_device_ptrs, history_out_device_ptrs, w, h, camera, history_in_device_ptrs=None,
-                                   prev_device_ptrs=None, camera_prev=None, variance_out_device_ptr=None, **params):
+                                   prev_device_ptrs=None, camera_prev=None, variance_out_device_ptr=None, motion=None, **params):
         """temporal_accumulate() on caller-owned device memory: {name: pointer} dicts with the names of TemporalFrame, TemporalHistory
         and TemporalGuides.  Runs on the context's stream behind whatever was queued there (a render_aovs_var_device before it and a
         denoise_var_device after it need no synchronisation in between) and does not wait: valid after `collect_stats()`.  The history
-        written must not share a plane with the history read."""
+        written must not share a plane with the history read.  `motion` (host memory, as in temporal_accumulate) is copied on that
+        stream before the call returns."""
+        table = _motion_args(motion)
         p = TemporalParams.make(w, h, **params)
         frame = _temporal_struct(TemporalFrame, TEMPORAL_FRAME, frame_device_ptrs, "frame")
         hout = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, history_out_device_ptrs, "history")
@@ -1017,11 +1079,43 @@ class Context:
         if history_in_device_ptrs is not None:
             hin = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, history_in_device_ptrs, "history")
             guides = _temporal_struct(TemporalGuides, TEMPORAL_GUIDES, prev_device_ptrs or {}, "previous guide")
-        self._check(self._L.pbrs_temporal_accumulate_device(self._h, C.addressof(p), C.addressof(camera),
-                                                            C.addressof(camera_prev) if camera_prev else None, C.addressof(frame),
-                                                            C.addressof(guides) if guides else None, C.addressof(hin) if hin else None,
-                                                            C.addressof(hout), C.c_void_p(variance_out_device_ptr)),
-                    "pbrs_temporal_accumulate_device")
+        args = (self._h, C.addressof(p), C.addressof(camera), C.addressof(camera_prev) if camera_prev else None, C.addressof(frame),
+                C.addressof(guides) if guides else None, C.addressof(hin) if hin else None, C.addressof(hout), C.c_void_p(variance_out_device_ptr))
+        if motion is None:
+            self._check(self._L.pbrs_temporal_accumulate_device(*args), "pbrs_temporal_accumulate_device")
+        else:
+            self._check(self._L.pbrs_temporal_accumulate_motion_device(*args, *table), "pbrs_temporal_accumulate_motion_device")
+
+    def motion_vectors(self, depth, camera, camera_prev, instance=None, motion=None, return_prev_depth=False):
+        """The motion vector AOV (include/pbrs_gpu.h, pbrs_motion_vectors) of an (h, w) f32 depth AOV rendered through `camera`: per
+        pixel where its surface point was on `camera_prev`'s film minus where it is, in pixels -> (h, w, 2) f32, and with
+        return_prev_depth also the depth the previous frame would have recorded, (h, w) f32.  `motion` (api.instance_motion) with the
+        `instance` AOV follows moving instances; without them only the camera moves."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.ndim != 2:
+            raise ValueError(f"the depth AOV is (h, w), not {depth.shape}")
+        h, w = depth.shape
+        if instance is not None:
+            instance = np.ascontiguousarray(instance, dtype=np.uint32)
+            if instance.shape != (h, w):
+                raise ValueError(f"instance plane of shape {instance.shape} beside a depth of {(h, w)}")
+        out = np.empty((h, w, 2), dtype=np.float32)
+        wq = np.empty((h, w), dtype=np.float32) if return_prev_depth else None
+        mp, n = _motion_args(motion)
+        self._check(self._L.pbrs_motion_vectors(self._h, w, h, C.addressof(camera), C.addressof(camera_prev) if camera_prev else None,
+                                                depth.ctypes.data, instance.ctypes.data if instance is not None else None, mp, n,
+                                                out.ctypes.data, wq.ctypes.data if return_prev_depth else None), "pbrs_motion_vectors")
+        return (out, wq) if return_prev_depth else out
+
+    def motion_vectors_device(self, depth_device_ptr, motion_out_device_ptr, w, h, camera, camera_prev, instance_device_ptr=None, motion=None,
+                              prev_depth_out_device_ptr=None):
+        """motion_vectors() on caller-owned device memory, on the context's stream without waiting: valid after `collect_stats()`.  The
+        table stays host memory."""
+        mp, n = _motion_args(motion)
+        self._check(self._L.pbrs_motion_vectors_device(self._h, w, h, C.addressof(camera), C.addressof(camera_prev) if camera_prev else None,
+                                                       C.c_void_p(depth_device_ptr), C.c_void_p(instance_device_ptr), mp, n,
+                                                       C.c_void_p(motion_out_device_ptr), C.c_void_p(prev_depth_out_device_ptr)),
+                    "pbrs_motion_vectors_device")
 
     def render_temporal(self, cameras, strata_x, strata_y, depth, seeds, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
                         temporal=None, **params):
@@ -1037,26 +1131,63 @@ class Context:
         cameras, seeds = list(cameras), list(seeds)
         if len(cameras) != len(seeds):
             raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
+        frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False):
+            yield out[:4]
+
+    def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                         temporal=None, motion_vectors=False, **params):
+        """render_temporal for sequences in which instances move.  `frames` yields (HostScene, Camera or None, seed): every frame's scene
+        is uploaded (the same instances in the same order as the frame before, moved: instance ids are stable), rendered through the
+        Camera (None: the scene's own) with its guides and its variance, accumulated with the table of instance_motion(scene, previous
+        scene), and filtered: one stream, one wait per frame.  A generator of (denoised, accumulated, noisy, stats), and with
+        motion_vectors=True a fifth entry, the (h, w, 2) motion vector AOV of the frame (zeros for the first one, which has no previous
+        frame; motion_vectors="prev_depth": (h, w, 3), the depth the previous frame would have recorded as the third channel, +inf where
+        there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
+        shadows of moving instances are not followed (include/pbrs_gpu.h)."""
+        self._denoise_guide_names(guides)
+        if "depth" not in guides or "instance" not in guides:
+            raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors):
+            yield out if motion_vectors else out[:4]
+
+    def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors):
+        """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
+        accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
+        brings its motion table; None keeps the uploaded scene (no table: only the camera moves)."""
         tparams = dict(temporal or {})
         TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
-        w, h = self.scene.width, self.scene.height
         hip = hip_runtime()
-        n_rgb = 3 * w * h * 4
         kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
-        sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, "acc_variance": w * h * 4}
-        for k in (0, 1):
-            sizes.update({f"{n}{k}": DENOISE_GUIDES[n][0] * w * h * 4 for n in kept})
-            sizes.update({f"h_{n}{k}": ch * w * h * 4 for n, (ch, _) in TEMPORAL_HISTORY.items()})
-        sizes.update({n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides if n not in kept})
         dev = {}
         try:
-            for n, nbytes in sizes.items():
-                ptr = C.c_void_p()
-                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_temporal failed")
-                dev[n] = ptr
-            cam_prev = None
-            for i, (cam, seed) in enumerate(zip(cameras, seeds)):
+            cam_prev = scene_prev = None
+            w = h = n_rgb = 0
+            for i, (scene, cam, seed) in enumerate(frames):
+                table = None
+                if scene is not None:
+                    self.upload(scene)
+                    if scene_prev is not None:
+                        table = instance_motion(scene, scene_prev)
+                    scene_prev = scene
+                cam = Camera.from_buffer_copy(cam if cam is not None else self.scene.camera)  # (a scene's own camera lives in the scene)
+                if i == 0:
+                    w, h = self.scene.width, self.scene.height
+                    n_rgb = 3 * w * h * 4
+                    sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, "acc_variance": w * h * 4}
+                    for k in (0, 1):
+                        sizes.update({f"{n}{k}": DENOISE_GUIDES[n][0] * w * h * 4 for n in kept})
+                        sizes.update({f"h_{n}{k}": ch * w * h * 4 for n, (ch, _) in TEMPORAL_HISTORY.items()})
+                    sizes.update({n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides if n not in kept})
+                    if motion_vectors:
+                        sizes["motion"], sizes["prev_depth"] = 2 * w * h * 4, w * h * 4
+                    for n, nbytes in sizes.items():
+                        ptr = C.c_void_p()
+                        if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
+                            raise PbrsError(f"hipMalloc of {nbytes} bytes for a temporal sequence failed")
+                        dev[n] = ptr
+                elif (self.scene.width, self.scene.height) != (w, h):
+                    raise ValueError(f"frame {i} has a film of {self.scene.width} x {self.scene.height}, the sequence {w} x {h}")
                 cur, old = i & 1, (i & 1) ^ 1
                 gp = {n: dev[f"{n}{cur}" if n in kept else n].value for n in guides}
                 bufs, _ = self._aov_device(gp)
@@ -1066,17 +1197,28 @@ class Context:
                 hist = [{n: dev[f"h_{n}{k}"].value for n in TEMPORAL_HISTORY} for k in (0, 1)]
                 self.temporal_accumulate_device(frame, hist[cur], w, h, cam, hist[old] if i else None,
                                                 {n: dev[f"{n}{old}"].value for n in kept} if i else None, cam_prev,
-                                                dev["acc_variance"].value, **tparams)
+                                                dev["acc_variance"].value, motion=table if i else None, **tparams)
+                if motion_vectors and i:
+                    self.motion_vectors_device(gp["depth"], dev["motion"].value, w, h, cam, cam_prev, gp.get("instance") if table else None, table,
+                                               dev["prev_depth"].value)
                 self.denoise_var_device(hist[cur]["rgb"], dev["out"].value, w, h, dev["acc_variance"].value, gp, **params)
                 stats = self.collect_stats()  # waits for the stream
                 images = []
                 for src in (dev["out"], dev[f"h_rgb{cur}"], dev["rgb"]):
                     img = np.empty((h, w, 3), dtype=np.float32)
                     if hip.hipMemcpy(img.ctypes.data, src, n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
-                        raise PbrsError("hipMemcpy of a render_temporal image failed")
+                        raise PbrsError("hipMemcpy of a temporal sequence's image failed")
                     images.append(img)
+                mv = None
+                if motion_vectors:
+                    mv, wq = np.zeros((h, w, 2), dtype=np.float32), np.full((h, w), np.inf, dtype=np.float32)
+                    if i and (hip.hipMemcpy(mv.ctypes.data, dev["motion"], mv.nbytes, 2) != 0 or
+                              hip.hipMemcpy(wq.ctypes.data, dev["prev_depth"], wq.nbytes, 2) != 0):
+                        raise PbrsError("hipMemcpy of the motion vectors failed")
+                    if motion_vectors == "prev_depth":
+                        mv = np.concatenate([mv, wq[:, :, None]], axis=2)
                 cam_prev = cam
-                yield images[0], images[1], images[2], stats
+                yield images[0], images[1], images[2], stats, mv
         finally:
             for ptr in dev.values():
                 hip.hipFree(ptr)

@@ -8,6 +8,14 @@
 // pixel pays one round trip, not one per test; neighbouring lanes reproject to neighbouring pixels, so the taps of a wave fall into a
 // few lines.  A guide the call does not have is a template parameter, not a test per tap; the first frame (no history) is the
 // instantiation without any tap.  No atomics, no LDS.
+//
+// Moving instances (pbrs_temporal_accumulate_motion*, pbrs_motion_vectors*): temporal_reproject is the one place that turns a pixel and
+// its depth into (wq, xq, yq), with the instance's motion record applied to the surface point when MOTION is set; k_temporal<.., MOTION>
+// and k_motion_vectors both call it, so the AOV and the accumulation cannot disagree.  The record is a 96-byte gather by instance id
+// through plain global loads (six 16-byte loads: the table is the context's own allocation, so every record is 16-byte aligned);
+// neighbouring lanes mostly share an id, so a wave touches a few lines.  The dependency chain of a MOTION pixel is
+// {depth, instance, normal, colour}(p) -> record(instance) -> the four taps: the id travels with the first round trip, the record is a
+// second one (the tap addresses depend on it), the taps the third; without MOTION there are two.
 #pragma once
 #include "denoise.h"  // denoise_finite_flag
 
@@ -39,6 +47,8 @@ struct TemporalIn {
     const float* rgb_hist;
     const float* moments_hist;
     const float* length_hist;
+    const pbrs_instance_motion* motion;  // read with MOTION: the context's copy of the caller's table, n_motion records
+    uint32_t n_motion;
 };
 struct TemporalOut {
     float* rgb;
@@ -47,7 +57,35 @@ struct TemporalOut {
     float* variance;  // null: not wanted
 };
 
-template <bool HISTORY, bool NORMAL, bool IDS>
+// Rule B from the pixel and its depth (finite and > 0: the caller's test) to (wq, xq, yq), without any rejection: xq and yq mean
+// something only where the caller finds wq finite and > 0.  MOTION: the surface point goes through record `id` of the table unless the id
+// lies at or above n_motion or the record is flagged PBRS_MOTION_IDENTITY; with NORMAL `nrm` (normal(p) on entry) becomes nm.
+template <bool MOTION, bool NORMAL>
+__device__ __forceinline__ void temporal_reproject(const TemporalConst& k, uint32_t px, uint32_t py, float z, const pbrs_instance_motion* motion,
+                                                   uint32_t n_motion, uint32_t id, f3& nrm, float& wq, float& xq, float& yq) {
+    const float x = (float)px + 0.5f, yc = (float)py + 0.5f;
+    const f3 dir = ld3(k.c) + ld3(k.a) * x + ld3(k.b) * yc;
+    f3 P = ld3(k.center) + dir * z;
+    if constexpr (MOTION) {
+        if (id < n_motion) {
+            const float4* rec = reinterpret_cast<const float4*>(motion + id);
+            const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4], r5 = rec[5];
+            if (!(__float_as_uint(r5.y) & PBRS_MOTION_IDENTITY)) {
+                P = mk3(((r0.x * P.x + r0.y * P.y) + r0.z * P.z) + r0.w, ((r1.x * P.x + r1.y * P.y) + r1.z * P.z) + r1.w,
+                        ((r2.x * P.x + r2.y * P.y) + r2.z * P.z) + r2.w);
+                if (NORMAL)
+                    nrm = mk3((r3.x * nrm.x + r3.y * nrm.y) + r3.z * nrm.z, (r3.w * nrm.x + r4.x * nrm.y) + r4.y * nrm.z,
+                              (r4.z * nrm.x + r4.w * nrm.y) + r5.x * nrm.z);
+            }
+        }
+    }
+    const f3 e = P - ld3(k.center_prev);
+    wq = dot(e, ld3(k.nw)) / k.D;
+    xq = (dot(e, ld3(k.nu)) / k.D) / wq;
+    yq = (dot(e, ld3(k.nv)) / k.D) / wq;
+}
+
+template <bool HISTORY, bool NORMAL, bool IDS, bool MOTION = false>
 __global__ void __launch_bounds__(256) k_temporal(TemporalIn in, TemporalOut out, TemporalConst k) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= k.w * k.h) return;
@@ -68,22 +106,19 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalIn in, TemporalOut out
         const uint32_t py = p / k.w, px = p - py * k.w;
         const float z = in.depth[p];
         if (pn_isfinite(z) && z > 0.0f) {
-            const float x = (float)px + 0.5f, yc = (float)py + 0.5f;
-            const f3 dir = ld3(k.c) + ld3(k.a) * x + ld3(k.b) * yc;
-            const f3 P = ld3(k.center) + dir * z;
-            const f3 e = P - ld3(k.center_prev);
-            const float wq = dot(e, ld3(k.nw)) / k.D;
+            // this pixel's normal and id travel with its depth: with MOTION the record's address waits for the id
+            f3 np = mk3(0.0f, 0.0f, 0.0f);
+            uint32_t idp = 0u;
+            if (NORMAL) np = ld3(in.normal + 3 * p);
+            if (IDS || MOTION) idp = in.instance[p];
+            float wq, xq, yq;
+            temporal_reproject<MOTION, NORMAL>(k, px, py, z, in.motion, in.n_motion, idp, np, wq, xq, yq);  // np is nm from here on
             if (pn_isfinite(wq) && wq > 0.0f) {
-                const float xq = (dot(e, ld3(k.nu)) / k.D) / wq, yq = (dot(e, ld3(k.nv)) / k.D) / wq;
                 const float fx = xq - 0.5f, fy = yq - 0.5f;
                 if (fx > -1.0f && fx < (float)k.w && fy > -1.0f && fy < (float)k.h) {
                     const float flx = pn_floor(fx), fly = pn_floor(fy);
                     const int ix = pn_f32_to_i32(flx), iy = pn_f32_to_i32(fly);  // -1 .. w-1, -1 .. h-1
                     const float tx = fx - flx, ty = fy - fly;
-                    f3 np = mk3(0.0f, 0.0f, 0.0f);
-                    uint32_t idp = 0u;
-                    if (NORMAL) np = ld3(in.normal + 3 * p);
-                    if (IDS) idp = in.instance[p];
                     // the four taps' records, fetched together; a tap outside the image reads pixel p's and does not count
                     f3 cq[4], nq[4];
                     float m1q[4], m2q[4], lq[4], zq[4];
@@ -158,4 +193,28 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalIn in, TemporalOut out
         }
         out.variance[p] = v * (1.0f / len);
     }
+}
+
+// pbrs_motion_vectors*: temporal_reproject written out per pixel.  One thread per pixel; no LDS, no atomics.
+template <bool MOTION>
+__global__ void __launch_bounds__(256) k_motion_vectors(const float* depth, const uint32_t* instance, const pbrs_instance_motion* motion, uint32_t n_motion,
+                                                        float* motion_out, float* prev_depth_out, TemporalConst k) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= k.w * k.h) return;
+    const uint32_t py = p / k.w, px = p - py * k.w;
+    const float z = depth[p];
+    float mx = 0.0f, my = 0.0f, wo = pn_inf();
+    if (pn_isfinite(z) && z > 0.0f) {
+        uint32_t id = 0u;
+        if (MOTION) id = instance[p];
+        f3 unused = mk3(0.0f, 0.0f, 0.0f);
+        float wq, xq, yq;
+        temporal_reproject<MOTION, false>(k, px, py, z, motion, n_motion, id, unused, wq, xq, yq);
+        if (pn_isfinite(wq) && wq > 0.0f) {
+            mx = xq - ((float)px + 0.5f), my = yq - ((float)py + 0.5f);
+            wo = wq;
+        }
+    }
+    motion_out[2 * p] = mx, motion_out[2 * p + 1] = my;
+    if (prev_depth_out) prev_depth_out[p] = wo;
 }

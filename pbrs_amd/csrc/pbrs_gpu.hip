@@ -193,6 +193,9 @@ enum BufferId {
     // temporal accumulation (pbrs_temporal_accumulate, device/temporal.h): the host variant's staging (the frame, the previous guides,
     // the history in and out, the variance out, one after the other); the device variant needs nothing
     BUF_TEMPORAL_STAGE,
+    // moving instances (pbrs_temporal_accumulate_motion*, pbrs_motion_vectors*): the context's copy of the caller's motion table, and
+    // the staging of pbrs_motion_vectors' host variant (depth, instance, the vectors, the previous depth, one after the other)
+    BUF_MOTION_TABLE, BUF_MOTION_STAGE,
     N_BUFFERS
 };
 
@@ -2055,6 +2058,8 @@ int pbrs_combine_passes(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct
 
 // ---- temporal accumulation (include/pbrs_gpu.h, device/temporal.h) ----
 static_assert(sizeof(pbrs_temporal_params) == 32, "pbrs_temporal_params is 32 B");
+static_assert(sizeof(pbrs_instance_motion) == 96 && offsetof(pbrs_instance_motion, n) == 48 && offsetof(pbrs_instance_motion, flags) == 84,
+              "pbrs_instance_motion is 96 B: temporal_reproject reads it as six float4");
 
 namespace {
 
@@ -2062,6 +2067,41 @@ using TemporalKernel = void (*)(TemporalIn, TemporalOut, TemporalConst);
 // [normal test][id test], with a history; without one no tap is read
 constexpr TemporalKernel kTemporal[2][2] = {{k_temporal<true, false, false>, k_temporal<true, false, true>},
                                             {k_temporal<true, true, false>, k_temporal<true, true, true>}};
+// the same with a motion table
+constexpr TemporalKernel kTemporalMotion[2][2] = {{k_temporal<true, false, false, true>, k_temporal<true, false, true, true>},
+                                                  {k_temporal<true, true, false, true>, k_temporal<true, true, true, true>}};
+
+int check_motion_table(pbrs_ctx* c, const pbrs_instance_motion* motion, uint32_t n_motion, const uint32_t* instance) {
+    if (!motion) return n_motion ? fail(c, PBRS_E_INVALID, "n_motion without a motion table") : PBRS_OK;
+    if (n_motion == 0) return fail(c, PBRS_E_INVALID, "a motion table of 0 records");
+    if (!instance) return fail(c, PBRS_E_INVALID, "a motion table without this frame's instance ids");
+    if (n_motion > (1u << 24)) return fail(c, PBRS_E_LIMIT, "more than 2^24 motion records");
+    return PBRS_OK;
+}
+
+// The caller's table (host memory) into the context's copy, on the context's stream: ordered behind the kernels of earlier calls that read
+// the copy, and the runtime has taken the bytes when the call returns.  -> the device table in *dev (null without a table).
+int upload_motion_table(pbrs_ctx* c, const pbrs_instance_motion* motion, uint32_t n_motion, const pbrs_instance_motion** dev) {
+    *dev = nullptr;
+    if (!motion) return PBRS_OK;
+    DeviceBuffer& b = c->buf[BUF_MOTION_TABLE];
+    const int rc = b.grow(c, (size_t)n_motion * sizeof(pbrs_instance_motion), "the instance motion table");
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(b.p, motion, (size_t)n_motion * sizeof(pbrs_instance_motion), hipMemcpyHostToDevice, c->stream));
+    *dev = b.as<pbrs_instance_motion>();
+    return PBRS_OK;
+}
+
+// What depends on the cameras alone, in the header's order (this file is compiled without contraction, host side included).
+void temporal_cameras(TemporalConst& k, const pbrs_camera& cam, const pbrs_camera* cam_prev) {
+    for (int i = 0; i < 3; ++i) k.center[i] = cam.center[i], k.c[i] = cam.c[i], k.a[i] = cam.a[i], k.b[i] = cam.b[i];
+    if (!cam_prev) return;
+    for (int i = 0; i < 3; ++i) k.center_prev[i] = cam_prev->center[i];
+    temporal_cross(cam_prev->b, cam_prev->c, k.nu);
+    temporal_cross(cam_prev->c, cam_prev->a, k.nv);
+    temporal_cross(cam_prev->a, cam_prev->b, k.nw);
+    k.D = temporal_dot(cam_prev->a, k.nu);
+}
 
 int check_temporal(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
                    const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout) {
@@ -2090,26 +2130,25 @@ int check_temporal(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera
     return PBRS_OK;
 }
 
-// The one launch on the context's stream (arguments checked; device pointers).  What depends on the cameras alone is computed here, in
-// the header's order (this file is compiled without contraction, host side included).
+// The one launch on the context's stream (arguments checked; device pointers, the motion table the caller's host memory).  Without a
+// history no tap is read and the table is not needed.
 int temporal_launch(pbrs_ctx* c, const pbrs_temporal_params& p, const pbrs_camera& cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame& f,
-                    const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history& hout, float* variance_out) {
+                    const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history& hout, float* variance_out,
+                    const pbrs_instance_motion* motion, uint32_t n_motion) {
     TemporalConst k{};
     k.w = p.w, k.h = p.h;
     k.max_history = p.max_history, k.depth_tolerance = p.depth_tolerance, k.min_temporal = p.min_temporal;
     k.normal_tolerance2 = p.normal_tolerance * p.normal_tolerance;
-    for (int i = 0; i < 3; ++i) k.center[i] = cam.center[i], k.c[i] = cam.c[i], k.a[i] = cam.a[i], k.b[i] = cam.b[i];
-    TemporalIn in{f.rgb, f.variance, f.depth, f.normal, f.instance, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    temporal_cameras(k, cam, hin ? cam_prev : nullptr);
+    TemporalIn in{f.rgb, f.variance, f.depth, f.normal, f.instance, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
     TemporalKernel fn = k_temporal<false, false, false>;
     if (hin) {
-        for (int i = 0; i < 3; ++i) k.center_prev[i] = cam_prev->center[i];
-        temporal_cross(cam_prev->b, cam_prev->c, k.nu);
-        temporal_cross(cam_prev->c, cam_prev->a, k.nv);
-        temporal_cross(cam_prev->a, cam_prev->b, k.nw);
-        k.D = temporal_dot(cam_prev->a, k.nu);
         in.depth_prev = prev->depth, in.normal_prev = prev->normal, in.instance_prev = prev->instance;
         in.rgb_hist = hin->rgb, in.moments_hist = hin->moments, in.length_hist = hin->length;
-        fn = kTemporal[f.normal != nullptr][(p.flags & PBRS_TEMPORAL_ID_TEST) != 0];
+        const int rc = upload_motion_table(c, motion, n_motion, &in.motion);
+        if (rc) return rc;
+        in.n_motion = in.motion ? n_motion : 0u;
+        fn = (in.motion ? kTemporalMotion : kTemporal)[f.normal != nullptr][(p.flags & PBRS_TEMPORAL_ID_TEST) != 0];
     }
     const uint32_t P = p.w * p.h;
     hipLaunchKernelGGL(fn, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, in, TemporalOut{hout.rgb, hout.moments, hout.length, variance_out}, k);
@@ -2119,22 +2158,40 @@ int temporal_launch(pbrs_ctx* c, const pbrs_temporal_params& p, const pbrs_camer
 
 }  // namespace
 
+int pbrs_temporal_accumulate_motion_device(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                           const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
+                                           const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
+                                           float* variance_out_device, const pbrs_instance_motion* motion, uint32_t n_motion) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_temporal(c, p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device);
+    if (!rc) rc = check_motion_table(c, motion, n_motion, frame_device->instance);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return temporal_launch(c, *p, *cam, cam_prev, *frame_device, prev_device, history_in_device, *history_out_device, variance_out_device, motion,
+                           n_motion);
+}
+
 int pbrs_temporal_accumulate_device(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
                                     const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
                                     const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
                                     float* variance_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_temporal(c, p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    return temporal_launch(c, *p, *cam, cam_prev, *frame_device, prev_device, history_in_device, *history_out_device, variance_out_device);
+    return pbrs_temporal_accumulate_motion_device(c, p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device,
+                                                  variance_out_device, nullptr, 0);
 }
 
 int pbrs_temporal_accumulate(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
                              const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
                              const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host, float* variance_out_host) {
+    return pbrs_temporal_accumulate_motion(c, p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host, variance_out_host, nullptr, 0);
+}
+
+int pbrs_temporal_accumulate_motion(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                    const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
+                                    const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host,
+                                    float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion) {
     if (!c) return PBRS_E_INVALID;
     int rc = check_temporal(c, p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host);
+    if (!rc) rc = check_motion_table(c, motion, n_motion, frame_host->instance);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)p->w * p->h;
@@ -2150,8 +2207,69 @@ int pbrs_temporal_accumulate(pbrs_ctx* c, const pbrs_temporal_params* p, const p
     const pbrs_temporal_frame fd{s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
     const pbrs_temporal_guides gd{s[5].as<float>(), s[6].as<float>(), s[7].as<uint32_t>()};
     const pbrs_temporal_history hid{s[8].as<float>(), s[9].as<float>(), s[10].as<float>()}, hod{s[11].as<float>(), s[12].as<float>(), s[13].as<float>()};
-    rc = temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>());
+    rc = temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>(), motion, n_motion);
     if (!rc) rc = copy_staged(c, s + 11, 4, P, hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
+}
+
+// ---- motion vectors (include/pbrs_gpu.h, device/temporal.h) ----
+namespace {
+
+int check_motion_vectors(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth,
+                         const uint32_t* instance, const pbrs_instance_motion* motion, uint32_t n_motion, const float* motion_out) {
+    if (!cam || !cam_prev || !depth || !motion_out) return fail(c, PBRS_E_INVALID, "null cameras, depth or motion_out");
+    if (w == 0 || h == 0) return fail(c, PBRS_E_INVALID, "empty image");
+    if (cam->width != w || cam->height != h || cam_prev->width != w || cam_prev->height != h)
+        return fail(c, PBRS_E_INVALID, "a camera's size is not w x h");
+    const int rc = check_motion_table(c, motion, n_motion, instance);
+    if (rc) return rc;
+    if ((uint64_t)w * h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The table's copy and the one launch on the context's stream (arguments checked; device pointers, the table host memory).
+int motion_vectors_launch(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera& cam, const pbrs_camera& cam_prev, const float* depth,
+                          const uint32_t* instance, const pbrs_instance_motion* motion, uint32_t n_motion, float* motion_out, float* prev_depth_out) {
+    TemporalConst k{};
+    k.w = w, k.h = h;
+    temporal_cameras(k, cam, &cam_prev);
+    const pbrs_instance_motion* table = nullptr;
+    const int rc = upload_motion_table(c, motion, n_motion, &table);
+    if (rc) return rc;
+    const uint32_t P = w * h;
+    hipLaunchKernelGGL(table ? k_motion_vectors<true> : k_motion_vectors<false>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, depth,
+                       instance, table, table ? n_motion : 0u, motion_out, prev_depth_out, k);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_motion_vectors_device(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth_device,
+                               const uint32_t* instance_device, const pbrs_instance_motion* motion, uint32_t n_motion, float* motion_out_device,
+                               float* prev_depth_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_motion_vectors(c, w, h, cam, cam_prev, depth_device, instance_device, motion, n_motion, motion_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return motion_vectors_launch(c, w, h, *cam, *cam_prev, depth_device, instance_device, motion, n_motion, motion_out_device, prev_depth_out_device);
+}
+
+int pbrs_motion_vectors(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth_host,
+                        const uint32_t* instance_host, const pbrs_instance_motion* motion, uint32_t n_motion, float* motion_out_host,
+                        float* prev_depth_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_motion_vectors(c, w, h, cam, cam_prev, depth_host, instance_host, motion, n_motion, motion_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)w * h;
+    Staged s[4] = {{depth_host, 1}, {instance_host, 1}, {motion_out_host, 2}, {prev_depth_out_host, 1}};
+    rc = stage(c, c->buf[BUF_MOTION_STAGE], "the motion vectors' staging", s, 4, P);
+    if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
+    if (!rc) rc = motion_vectors_launch(c, w, h, *cam, *cam_prev, s[0].as<float>(), s[1].as<uint32_t>(), motion, n_motion, s[2].as<float>(), s[3].as<float>());
+    if (!rc) rc = copy_staged(c, s + 2, 2, P, hipMemcpyDeviceToHost);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -24,13 +24,20 @@ own variance, summed again (pbrs_combine_passes); --denoise-var's parameters app
 default 0) about the file's look-at point around its up vector; one image per frame, <out>.0000.<ext>, <out>.0001.<ext>, ...  (the path
 integrator; the other options above do not apply).  With --temporal every frame is accumulated over the frames before it and filtered
 (include/pbrs_gpu.h, pbrs_temporal_accumulate; Context.render_temporal): the frame's image is then the accumulated and filtered one,
-and <out>.NNNN.accumulated.<ext> and <out>.NNNN.noisy.<ext> are written beside it; --denoise-var's parameters apply."""
+and <out>.NNNN.accumulated.<ext> and <out>.NNNN.noisy.<ext> are written beside it; --denoise-var's parameters apply.
+--spin ID[,ID...] --spin-deg DEG (with --frames and --temporal): the named instances (ids as the instance AOV counts them; mesh instances)
+turn by DEG degrees per frame about the vertical axis through the centre of their world box; every frame's scene is uploaded and the
+accumulation follows the instances through a motion table (Context.render_animation; include/pbrs_gpu.h, pbrs_temporal_accumulate_motion).
+--motion-vectors (with --temporal): also writes <out>.NNNN.motion.exr per frame, the screen-space motion vectors (pbrs_motion_vectors):
+x and y in R and G (where the pixel's surface point was one frame ago minus where it is, in pixels), the previous depth in B."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pbrs_amd
 
 temporal = "--temporal" in sys.argv
+motion_vectors = "--motion-vectors" in sys.argv
+spin, spin_deg = [], 0.0
 aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
 denoise = "--denoise" in sys.argv
@@ -40,7 +47,7 @@ denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 frames, orbit = 0, 0.0
-for flag in ("--frames", "--orbit", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -49,6 +56,10 @@ for flag in ("--frames", "--orbit", "--denoise-iterations", "--denoise-sigma", "
             frames = int(value)
         elif flag == "--orbit":
             orbit = float(value)
+        elif flag == "--spin":
+            spin = [int(v) for v in value.split(",") if v]
+        elif flag == "--spin-deg":
+            spin_deg = float(value)
         elif flag == "--denoise-iterations":
             denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
         elif flag == "--matte":
@@ -62,11 +73,54 @@ for flag in ("--frames", "--orbit", "--denoise-iterations", "--denoise-sigma", "
         else:
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
             denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
-sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal")]
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal", "--motion-vectors")]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
 integrator = sys.argv[5] if len(sys.argv) > 5 else "path"
+class _Spec:
+    """A scene spec under HostScene's eyes."""
+
+    def __init__(self, spec):
+        self.spec = spec
+
+    def build(self):
+        return self.spec
+
+
+def _mat(a):
+    return np.array(list(a), dtype=np.float64).reshape(4, 4).T  # (column-major in the spec)
+
+
+def spun_scenes(spec, ids, deg, cams):
+    """Frame k's (HostScene, Camera, seed): the file's scene with the instances `ids` turned by k * deg degrees about the vertical axis
+    through the centre of their world box (the instance transforms of the spec are rewritten in place for every frame)."""
+    from pbrs_amd.spec import SHAPE_MESH as MESH
+    start, pivots = {}, {}
+    for i in ids:
+        if not 0 <= i < spec.n_instances or spec.shapes[spec.instances[i].shape].kind != MESH:
+            sys.exit(f"--spin: instance {i} is not a mesh instance of this scene")
+        inst = spec.instances[i]
+        shape = spec.shapes[inst.shape]
+        mesh = spec.meshes[shape.mesh]
+        v = np.ctypeslib.as_array(mesh.positions, shape=(mesh.n_vertices, 3)).astype(np.float64)
+        start[i] = (_mat(inst.forward), _mat(inst.inverse))
+        world = (start[i][0] @ np.hstack([v, np.ones((len(v), 1))]).T).T[:, :3]
+        pivots[i] = 0.5 * (world.min(axis=0) + world.max(axis=0))
+    for k, cam in enumerate(cams):
+        t = np.radians(deg * k)
+        for i in ids:
+            def about(angle, c=pivots[i]):
+                R = np.array([[np.cos(angle), 0.0, np.sin(angle)], [0.0, 1.0, 0.0], [-np.sin(angle), 0.0, np.cos(angle)]])
+                M = np.eye(4)
+                M[:3, :3], M[:3, 3] = R, c - R @ c
+                return M
+            fwd, inv = about(t) @ start[i][0], start[i][1] @ about(-t)
+            spec.instances[i].forward[:] = [float(x) for x in fwd.T.reshape(-1)]
+            spec.instances[i].inverse[:] = [float(x) for x in inv.T.reshape(-1)]
+        yield pbrs_amd.HostScene(_Spec(spec)), cam, 1 + k
+
+
 ls = pbrs_amd.load_pbrt(scene)
 ctx = pbrs_amd.Context(0)
 hs = pbrs_amd.HostScene(ls)
@@ -75,7 +129,12 @@ if frames:
     spec = ls.build().camera
     cams = [pbrs_amd.api.orbited(hs.camera, list(spec.target), list(spec.up), orbit * k) for k in range(frames)]
     stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
-    if temporal:
+    if (spin or motion_vectors) and not temporal:
+        sys.exit("--spin and --motion-vectors go with --frames N --temporal")
+    if spin or motion_vectors:
+        sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
+                                        **denoise_var_params)
+    elif temporal:
         sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), **denoise_var_params)
     else:
         sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
@@ -84,6 +143,8 @@ if frames:
         if temporal:
             pbrs_amd.write_image(f"{stem}.{k:04d}.accumulated{ext}", images[1])
             pbrs_amd.write_image(f"{stem}.{k:04d}.noisy{ext}", images[2])
+        if motion_vectors:
+            pbrs_amd.write_image(f"{stem}.{k:04d}.motion.exr", images[4])
     print(f"{frames} frames of {hs.width}x{hs.height} at {msaa * msaa} spp, {orbit} degrees per frame"
           f"{', accumulated and filtered' if temporal else ''} -> {stem}.0000{ext} ..")
     sys.exit(0)
