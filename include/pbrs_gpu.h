@@ -843,6 +843,66 @@ int pbrs_motion_vectors_device(pbrs_ctx*, uint32_t w, uint32_t h, const pbrs_cam
                                const float* depth_device, const uint32_t* instance_device, const pbrs_instance_motion* motion,
                                uint32_t n_motion, float* motion_out_device, float* prev_depth_out_device);
 
+/* ---- spatial variance estimate for short histories -------------------------------------------------------- */
+/* The piece of SVGF (Schied et al., HPG 2017) that joins its temporal and its spatial half.  Rule D of pbrs_temporal_accumulate takes the
+ * variance from the temporal moments only from min_temporal frames on; before that it falls back on the frame's own variance AOV, which
+ * at a few samples is +inf ("unknown") or very noisy, and pbrs_denoise_var then filters those pixels with its luminance stop open: every
+ * pixel of the first frames of a sequence, and every pixel that is disoccluded later.  For exactly those pixels this call replaces the
+ * variance by a guide-weighted estimate of the luminance moments over the (2 * radius + 1)^2 neighbourhood.  An image operation like
+ * pbrs_denoise: it needs a context (device, stream) and no uploaded scene.  All arithmetic is f32 without fused multiply-add, in the order
+ * written; pn_* is include/pbrs_numeric.h.  m1(q), m2(q) are the two words of `moments` at q (the layout of pbrs_temporal_history),
+ * n = length(p).
+ *   Pass-through.  variance_out(p) = variance_in(p), bit for bit, when
+ *     p is not short: short means n > 0 && n < min_temporal (a NaN length is not short); or
+ *     PBRS_SPATIAL_ONLY_UNKNOWN is set and variance_in(p) is known: neither NaN, nor < 0, nor +inf; or
+ *     the sum W below comes out 0 (only a non-finite guide at p itself, or depth(p) == 0, or no valid pixel under the window does that).
+ *   Estimate.  From M1 = +0, M2 = +0, W = +0, for dy = -radius .. radius (outer), for dx = -radius .. radius (inner), q = p + (dx, dy):
+ *     q outside the image is skipped; q is skipped unless length(q) > 0 (a NaN fails) and m1(q), m2(q) are finite (pn_isfinite).
+ *     wgt = (1.0f * wn) * wd, with wn and wd exactly pbrs_denoise's normal and depth stops at s = 1 (the both-infinite and the
+ *     exactly-one-infinite depth cases included); a NULL guide gives 1.0f.  With PBRS_SPATIAL_ID_STOP, instance(q) != instance(p) makes
+ *     wgt = +0.  A tap whose wgt is NaN is skipped.  Otherwise M1 = M1 + wgt * m1(q), M2 = M2 + wgt * m2(q), W = W + wgt.
+ *     iw = 1.0f / W; a = M1 * iw; b = M2 * iw; v = b - a * a; v = v < 0 ? +0 : v; a NaN v becomes +inf;
+ *     variance_out(p) = v * (1.0f / n).
+ * What it estimates.  There is no luminance stop and no spline: a box window over the surface the guides delimit.  v is the variance of one
+ * frame's pixel luminance, divided by the history length like rule D.  On flat noise it has 1 - 1 / taps of the true variance (the
+ * window's own mean is subtracted), and it counts texture under the window as variance, so it errs toward more blur, never toward less.
+ * Like the variance AOV's, the one-pass form cancels for a nearly constant neighbourhood (b and a * a round separately); the clamp catches
+ * the negative results, and a constant neighbourhood gives +0 or a value within rounding of it.
+ * Scale rule.  For an integer j, moments times (2^j, 4^j) and variance_in times 4^j give variance_out times 4^j bit for bit, with
+ * pbrs_denoise_var's proviso (no product or sum that depends on the scale overflows or is a nonzero value below the smallest normal f32 at
+ * either scale): every weight depends on the guides only.
+ * In place.  variance_out may equal variance_in: a pixel reads only its own variance_in.  It may not alias the moments or the length
+ * (the same pointer is refused).
+ * Pointers are host memory for pbrs_spatial_variance, which stages what it copies (up to 36 B per pixel) on first use and synchronises
+ * before it returns; device memory for pbrs_spatial_variance_device, which needs no scratch, runs on the context's stream (pbrs_set_stream
+ * honoured) and does not wait: queued between pbrs_temporal_accumulate[_motion]_device and pbrs_denoise_var_device on the same context it
+ * needs no synchronisation.  A context that never calls it allocates nothing.  `guides` may be NULL (every stop off), and so may each of
+ * its pointers.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, moments, length, variance_in or variance_out; w or h 0; radius 0 or
+ * above PBRS_SPATIAL_MAX_RADIUS; a sigma that is not finite or not > 0; min_temporal not finite or < 1; unknown flag bits;
+ * PBRS_SPATIAL_ID_STOP without guides->instance; variance_out equal to moments or length.  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_SPATIAL_ID_STOP 1u      /* a tap on another instance id has weight 0 */
+#define PBRS_SPATIAL_ONLY_UNKNOWN 2u /* a short pixel whose variance_in is known keeps it */
+#define PBRS_SPATIAL_MAX_RADIUS 3u
+typedef struct pbrs_spatial_variance_params {
+    uint32_t w, h;        /* image size; every plane is w*h pixels, row-major */
+    uint32_t radius;      /* 1 .. PBRS_SPATIAL_MAX_RADIUS: the window is (2 * radius + 1)^2 (SVGF: 3) */
+    uint32_t flags;       /* PBRS_SPATIAL_* */
+    float sigma_normal, sigma_depth; /* finite and > 0: pbrs_denoise's */
+    float min_temporal;   /* finite, >= 1: the temporal accumulation's; shorter histories are estimated */
+    uint32_t pad;
+} pbrs_spatial_variance_params; /* 32 B */
+typedef struct pbrs_spatial_variance_guides { /* layouts of pbrs_aov_buffers; any pointer may be NULL: that stop is off */
+    const float* depth;
+    const float* normal;
+    const uint32_t* instance;
+} pbrs_spatial_variance_guides;
+int pbrs_spatial_variance(pbrs_ctx*, const pbrs_spatial_variance_params*, const float* moments_host, const float* length_host,
+                          const pbrs_spatial_variance_guides* guides_host, const float* variance_in_host, float* variance_out_host);
+int pbrs_spatial_variance_device(pbrs_ctx*, const pbrs_spatial_variance_params*, const float* moments_device, const float* length_device,
+                                 const pbrs_spatial_variance_guides* guides_device, const float* variance_in_device,
+                                 float* variance_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,11 +277,37 @@ class InstanceMotion(C.Structure):
     _fields_ = [("m", (C.c_float * 4) * 3), ("n", (C.c_float * 3) * 3), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
 
 
+class SpatialVarianceParams(C.Structure):
+    """pbrs_spatial_variance_params (include/pbrs_gpu.h, "spatial variance estimate for short histories"): image size, the window's
+    radius, flags, the two guide sigmas of the denoisers and the history length below which a pixel's variance is estimated."""
+    ID_STOP, ONLY_UNKNOWN = 1, 2
+    MAX_RADIUS = 3
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("min_temporal", C.c_float), ("pad", C.c_uint32)]
+
+    @classmethod
+    def make(cls, w, h, radius=3, sigma_normal=0.3, sigma_depth=0.2, min_temporal=4.0, id_stop=False, only_unknown=False):
+        p = cls()
+        p.w, p.h, p.radius = w, h, radius
+        p.flags = (cls.ID_STOP if id_stop else 0) | (cls.ONLY_UNKNOWN if only_unknown else 0)
+        p.sigma_normal, p.sigma_depth, p.min_temporal = sigma_normal, sigma_depth, min_temporal
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SpatialVarianceGuides(C.Structure):
+    """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]
+
+
 # name -> (channels, dtype) of the planes of each struct above
 TEMPORAL_FRAME = {"rgb": (3, np.float32), "variance": (1, np.float32), "depth": (1, np.float32), "normal": (3, np.float32),
                   "instance": (1, np.uint32)}
 TEMPORAL_GUIDES = {n: TEMPORAL_FRAME[n] for n in ("depth", "normal", "instance")}
 TEMPORAL_HISTORY = {"rgb": (3, np.float32), "moments": (2, np.float32), "length": (1, np.float32)}
+SPATIAL_VARIANCE_PLANES = {"moments": (2, np.float32), "length": (1, np.float32), "variance": (1, np.float32)}
 
 
 def _temporal_struct(cls, layout, ptrs, what):
@@ -320,7 +346,8 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device",
                "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device",
                "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device", "pbrs_temporal_accumulate_motion",
-               "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device"]
+               "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device",
+               "pbrs_spatial_variance", "pbrs_spatial_variance_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -413,6 +440,8 @@ def gpu_lib():
         L.pbrs_temporal_accumulate_motion_device.argtypes = L.pbrs_temporal_accumulate_motion.argtypes
         L.pbrs_motion_vectors.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]
         L.pbrs_motion_vectors_device.argtypes = L.pbrs_motion_vectors.argtypes
+        L.pbrs_spatial_variance.argtypes = [C.c_void_p] * 7
+        L.pbrs_spatial_variance_device.argtypes = [C.c_void_p] * 7
         _gpu = L
     return _gpu
 
@@ -1117,14 +1146,72 @@ class Context:
                                                        C.c_void_p(motion_out_device_ptr), C.c_void_p(prev_depth_out_device_ptr)),
                     "pbrs_motion_vectors_device")
 
+    def spatial_variance(self, moments, length, variance, depth=None, normal=None, instance=None, **params):
+        """The spatial variance estimate for pixels with a short history (include/pbrs_gpu.h, pbrs_spatial_variance): the (h, w, 2)
+        moments and (h, w) length of the history temporal_accumulate returned, the (h, w) variance it returned beside them, and the
+        frame's guides (None = that stop is off) -> (h, w) f32: `variance` with the short pixels' entries replaced by the estimate
+        over their neighbourhood.  params: SpatialVarianceParams.make's keywords; by default taps stop at instance edges when there
+        are ids."""
+        length = np.ascontiguousarray(length, dtype=np.float32)
+        if length.ndim != 2:
+            raise ValueError(f"the length plane is (h, w), not {length.shape}")
+        h, w = length.shape
+        params.setdefault("id_stop", instance is not None)
+        p = SpatialVarianceParams.make(w, h, **params)
+        ptrs, keep = self._temporal_host(SPATIAL_VARIANCE_PLANES, {"moments": moments, "length": length, "variance": variance}, (h, w),  # noqa: F841
+                                         "spatial variance")
+        for n in SPATIAL_VARIANCE_PLANES:
+            if n not in ptrs:
+                raise ValueError(f"spatial variance plane {n} is missing")
+        gp, k2 = self._temporal_host(TEMPORAL_GUIDES, {"depth": depth, "normal": normal, "instance": instance}, (h, w), "spatial variance guide")  # noqa: F841
+        g = _temporal_struct(SpatialVarianceGuides, TEMPORAL_GUIDES, gp, "spatial variance guide")
+        out = np.empty((h, w), dtype=np.float32)
+        self._check(self._L.pbrs_spatial_variance(self._h, C.addressof(p), ptrs["moments"], ptrs["length"], C.addressof(g), ptrs["variance"],
+                                                  out.ctypes.data), "pbrs_spatial_variance")
+        return out
+
+    def spatial_variance_device(self, moments_device_ptr, length_device_ptr, variance_in_device_ptr, variance_out_device_ptr, w, h,
+                                guide_device_ptrs=None, **params):
+        """spatial_variance() on caller-owned device memory: `guide_device_ptrs` = {name: pointer} of depth / normal / instance.  Runs on
+        the context's stream behind whatever was queued there (a temporal_accumulate_device before it and a denoise_var_device after
+        it need no synchronisation in between) and does not wait: valid after `collect_stats()`.  The output pointer may be the
+        variance input's."""
+        for n, ptr in (("moments", moments_device_ptr), ("length", length_device_ptr), ("variance", variance_in_device_ptr),
+                       ("variance_out", variance_out_device_ptr)):
+            if not ptr:
+                raise ValueError(f"spatial variance plane {n} is a null pointer")
+        ptrs = {n: ptr for n, ptr in dict(guide_device_ptrs or {}).items() if ptr}
+        g = _temporal_struct(SpatialVarianceGuides, TEMPORAL_GUIDES, ptrs, "spatial variance guide")
+        params.setdefault("id_stop", "instance" in ptrs)
+        p = SpatialVarianceParams.make(w, h, **params)
+        self._check(self._L.pbrs_spatial_variance_device(self._h, C.addressof(p), C.c_void_p(moments_device_ptr), C.c_void_p(length_device_ptr),
+                                                         C.addressof(g), C.c_void_p(variance_in_device_ptr), C.c_void_p(variance_out_device_ptr)),
+                    "pbrs_spatial_variance_device")
+
+    @staticmethod
+    def _spatial_params(spatial, tparams, guides):
+        """render_temporal's / render_animation's `spatial` -> SpatialVarianceParams.make's keywords, or None: min_temporal follows the
+        temporal params unless given, the id stop the presence of the instance guide.  An unknown keyword fails here."""
+        if spatial is None or spatial is False:
+            return None
+        sp = {} if spatial is True else dict(spatial)
+        sp.setdefault("min_temporal", tparams.get("min_temporal", TemporalParams.make(1, 1).min_temporal))
+        sp.setdefault("id_stop", "instance" in guides)
+        SpatialVarianceParams.make(1, 1, **sp)
+        return sp
+
     def render_temporal(self, cameras, strata_x, strata_y, depth, seeds, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                        temporal=None, **params):
+                        temporal=None, spatial=None, **params):
         """A sequence of frames of the uploaded scene, one per Camera of `cameras` with the seed of `seeds` at the same place, each
         rendered with its guides and its variance, accumulated against the generator's own history (temporal_accumulate_device; the
         history and the guides it is tested against live in ping-pong device buffers) and filtered (denoise_var_device on the
         accumulated image with the accumulated variance): one stream, no synchronisation inside a frame, the images copied back behind
         one wait per frame.  A generator of (denoised, accumulated, noisy, stats), (h, w, 3) f32 each; its device buffers are freed when
-        it ends or is closed.  `guides` must hold "depth"; `temporal`: TemporalParams.make's keywords; params: DenoiseVarParams.make's."""
+        it ends or is closed.  `guides` must hold "depth"; `temporal`: TemporalParams.make's keywords; params: DenoiseVarParams.make's.
+        `spatial`: None is that chain; True, or a dict of SpatialVarianceParams.make's keywords, queues spatial_variance_device in place on
+        the accumulated variance between the accumulation and the filter, so that pixels with a history shorter than min_temporal are
+        filtered with an estimated variance instead of an unknown one (min_temporal follows `temporal` unless given, the id stop the
+        presence of the instance guide)."""
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -1132,11 +1219,11 @@ class Context:
         if len(cameras) != len(seeds):
             raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial):
             yield out[:4]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                         temporal=None, motion_vectors=False, **params):
+                         temporal=None, motion_vectors=False, spatial=None, **params):
         """render_temporal for sequences in which instances move.  `frames` yields (HostScene, Camera or None, seed): every frame's scene
         is uploaded (the same instances in the same order as the frame before, moved: instance ids are stable), rendered through the
         Camera (None: the scene's own) with its guides and its variance, accumulated with the table of instance_motion(scene, previous
@@ -1144,19 +1231,21 @@ class Context:
         motion_vectors=True a fifth entry, the (h, w, 2) motion vector AOV of the frame (zeros for the first one, which has no previous
         frame; motion_vectors="prev_depth": (h, w, 3), the depth the previous frame would have recorded as the third channel, +inf where
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
-        shadows of moving instances are not followed (include/pbrs_gpu.h)."""
+        shadows of moving instances are not followed (include/pbrs_gpu.h).  `spatial`: as render_temporal's."""
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial):
             yield out if motion_vectors else out[:4]
 
-    def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors):
+    def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
-        brings its motion table; None keeps the uploaded scene (no table: only the camera moves)."""
+        brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  `spatial`: None, or what queues the
+        spatial variance estimate between the accumulation and the filter (_spatial_params)."""
         tparams = dict(temporal or {})
         TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
+        sparams = self._spatial_params(spatial, tparams, guides)
         hip = hip_runtime()
         kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
         dev = {}
@@ -1201,6 +1290,9 @@ class Context:
                 if motion_vectors and i:
                     self.motion_vectors_device(gp["depth"], dev["motion"].value, w, h, cam, cam_prev, gp.get("instance") if table else None, table,
                                                dev["prev_depth"].value)
+                if sparams is not None:
+                    self.spatial_variance_device(hist[cur]["moments"], hist[cur]["length"], dev["acc_variance"].value, dev["acc_variance"].value,
+                                                 w, h, {n: gp[n] for n in kept}, **sparams)
                 self.denoise_var_device(hist[cur]["rgb"], dev["out"].value, w, h, dev["acc_variance"].value, gp, **params)
                 stats = self.collect_stats()  # waits for the stream
                 images = []

@@ -29,6 +29,7 @@
 #include "device/matte.h"
 #include "device/passes.h"
 #include "device/temporal.h"
+#include "device/spatial_variance.h"
 
 namespace {
 
@@ -196,6 +197,9 @@ enum BufferId {
     // moving instances (pbrs_temporal_accumulate_motion*, pbrs_motion_vectors*): the context's copy of the caller's motion table, and
     // the staging of pbrs_motion_vectors' host variant (depth, instance, the vectors, the previous depth, one after the other)
     BUF_MOTION_TABLE, BUF_MOTION_STAGE,
+    // spatial variance estimate (pbrs_spatial_variance, device/spatial_variance.h): the host variant's staging (moments, length, the three
+    // guides, the variance, which is estimated in place, one after the other); the device variant needs nothing
+    BUF_SPATIAL_STAGE,
     N_BUFFERS
 };
 
@@ -2270,6 +2274,86 @@ int pbrs_motion_vectors(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* 
     if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
     if (!rc) rc = motion_vectors_launch(c, w, h, *cam, *cam_prev, s[0].as<float>(), s[1].as<uint32_t>(), motion, n_motion, s[2].as<float>(), s[3].as<float>());
     if (!rc) rc = copy_staged(c, s + 2, 2, P, hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
+}
+
+// ---- spatial variance estimate (include/pbrs_gpu.h, device/spatial_variance.h) ----
+static_assert(sizeof(pbrs_spatial_variance_params) == 32, "pbrs_spatial_variance_params is 32 B");
+static_assert(PBRS_SPATIAL_MAX_TILE == PBRS_DENOISE_CELL + 2u * PBRS_SPATIAL_MAX_RADIUS, "k_spatial_variance's LDS tile holds the largest halo");
+
+namespace {
+
+using SpatialVarKernel = void (*)(SpatialVarIn, float*, SpatialVarConst);
+// [normal stop][id stop]
+constexpr SpatialVarKernel kSpatialVar[2][2] = {{k_spatial_variance<false, false>, k_spatial_variance<false, true>},
+                                                {k_spatial_variance<true, false>, k_spatial_variance<true, true>}};
+
+int check_spatial_variance(pbrs_ctx* c, const pbrs_spatial_variance_params* p, const float* moments, const float* length,
+                           const pbrs_spatial_variance_guides* g, const float* variance_in, const float* variance_out) {
+    if (!p || !moments || !length || !variance_in || !variance_out)
+        return fail(c, PBRS_E_INVALID, "null spatial variance params, moments, length, variance_in or variance_out");
+    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty image");
+    if (p->radius == 0 || p->radius > PBRS_SPATIAL_MAX_RADIUS) return fail(c, PBRS_E_INVALID, "the spatial variance radius must be 1 .. 3");
+    if (p->flags & ~(PBRS_SPATIAL_ID_STOP | PBRS_SPATIAL_ONLY_UNKNOWN)) return fail(c, PBRS_E_INVALID, "unknown spatial variance flag bits");
+    if ((p->flags & PBRS_SPATIAL_ID_STOP) && !(g && g->instance)) return fail(c, PBRS_E_INVALID, "PBRS_SPATIAL_ID_STOP without instance ids");
+    const float sig[2] = {p->sigma_normal, p->sigma_depth};
+    for (float s : sig)
+        if (!pn_isfinite(s) || !(s > 0.0f)) return fail(c, PBRS_E_INVALID, "a spatial variance sigma must be finite and > 0");
+    if (!pn_isfinite(p->min_temporal) || !(p->min_temporal >= 1.0f)) return fail(c, PBRS_E_INVALID, "min_temporal must be finite and >= 1");
+    if (variance_out == moments || variance_out == length)
+        return fail(c, PBRS_E_INVALID, "the spatial variance estimate cannot write over the moments or the length");
+    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
+    return PBRS_OK;
+}
+
+// The one launch on the context's stream (arguments checked; device pointers).
+int spatial_variance_launch(pbrs_ctx* c, const pbrs_spatial_variance_params& p, const float* moments, const float* length,
+                            const pbrs_spatial_variance_guides& g, const float* variance_in, float* variance_out) {
+    SpatialVarConst k{};
+    k.w = p.w, k.h = p.h, k.radius = p.radius;
+    k.only_unknown = (p.flags & PBRS_SPATIAL_ONLY_UNKNOWN) ? 1u : 0u;
+    k.in = 1.0f / (p.sigma_normal * p.sigma_normal);
+    k.id = 1.0f / (p.sigma_depth * p.sigma_depth);
+    k.min_temporal = p.min_temporal;
+    const bool ids = (p.flags & PBRS_SPATIAL_ID_STOP) != 0;
+    const SpatialVarIn in{moments, length, g.depth, g.normal, ids ? g.instance : nullptr, variance_in};
+    const dim3 grid((p.w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p.h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
+    hipLaunchKernelGGL(kSpatialVar[g.normal != nullptr][ids], grid, dim3(kBlock), 0, c->stream, in, variance_out, k);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_spatial_variance_device(pbrs_ctx* c, const pbrs_spatial_variance_params* p, const float* moments_device, const float* length_device,
+                                 const pbrs_spatial_variance_guides* guides_device, const float* variance_in_device, float* variance_out_device) {
+    if (!c) return PBRS_E_INVALID;
+    const int rc = check_spatial_variance(c, p, moments_device, length_device, guides_device, variance_in_device, variance_out_device);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return spatial_variance_launch(c, *p, moments_device, length_device, guides_device ? *guides_device : pbrs_spatial_variance_guides{},
+                                   variance_in_device, variance_out_device);
+}
+
+int pbrs_spatial_variance(pbrs_ctx* c, const pbrs_spatial_variance_params* p, const float* moments_host, const float* length_host,
+                          const pbrs_spatial_variance_guides* guides_host, const float* variance_in_host, float* variance_out_host) {
+    if (!c) return PBRS_E_INVALID;
+    int rc = check_spatial_variance(c, p, moments_host, length_host, guides_host, variance_in_host, variance_out_host);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)p->w * p->h;
+    const pbrs_spatial_variance_guides g = guides_host ? *guides_host : pbrs_spatial_variance_guides{};
+    // the variance is estimated in place in its staging plane
+    Staged s[6] = {{moments_host, 2}, {length_host, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1}, {variance_in_host, 1}};
+    rc = stage(c, c->buf[BUF_SPATIAL_STAGE], "the spatial variance estimate's staging", s, 6, P);
+    if (!rc) rc = copy_staged(c, s, 6, P, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    const pbrs_spatial_variance_guides gd{s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
+    rc = spatial_variance_launch(c, *p, s[0].as<float>(), s[1].as<float>(), gd, s[5].as<float>(), s[5].as<float>());
+    const Staged out{variance_out_host, 1, s[5].dev};
+    if (!rc) rc = copy_staged(c, &out, 1, P, hipMemcpyDeviceToHost);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -29,7 +29,10 @@ and <out>.NNNN.accumulated.<ext> and <out>.NNNN.noisy.<ext> are written beside i
 turn by DEG degrees per frame about the vertical axis through the centre of their world box; every frame's scene is uploaded and the
 accumulation follows the instances through a motion table (Context.render_animation; include/pbrs_gpu.h, pbrs_temporal_accumulate_motion).
 --motion-vectors (with --temporal): also writes <out>.NNNN.motion.exr per frame, the screen-space motion vectors (pbrs_motion_vectors):
-x and y in R and G (where the pixel's surface point was one frame ago minus where it is, in pixels), the previous depth in B."""
+x and y in R and G (where the pixel's surface point was one frame ago minus where it is, in pixels), the previous depth in B.
+--spatial-variance (with --temporal): pixels whose history is shorter than the accumulation's min_temporal (the first frames, and
+disocclusions later) are filtered with a variance estimated over their neighbourhood instead of an unknown one (include/pbrs_gpu.h,
+pbrs_spatial_variance; render_temporal's spatial=True)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -37,6 +40,7 @@ import pbrs_amd
 
 temporal = "--temporal" in sys.argv
 motion_vectors = "--motion-vectors" in sys.argv
+spatial_variance = "--spatial-variance" in sys.argv
 spin, spin_deg = [], 0.0
 aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
@@ -73,7 +77,7 @@ for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--denoise-iteration
         else:
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
             denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
-sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal", "--motion-vectors")]
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal", "--motion-vectors", "--spatial-variance")]
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -131,11 +135,14 @@ if frames:
     stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
     if (spin or motion_vectors) and not temporal:
         sys.exit("--spin and --motion-vectors go with --frames N --temporal")
+    if spatial_variance and not temporal:
+        sys.exit("--spatial-variance goes with --frames N --temporal")
+    spatial = True if spatial_variance else None
     if spin or motion_vectors:
         sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
-                                        **denoise_var_params)
+                                        spatial=spatial, **denoise_var_params)
     elif temporal:
-        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), **denoise_var_params)
+        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, **denoise_var_params)
     else:
         sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
     for k, images in enumerate(sequence):
