@@ -25,6 +25,12 @@ struct PathState {
     //   q[.][0][i] = origin.xyz, slot | specular_bounce << 31        (t_max is always +inf for path rays: Ray::new)
     //   q[.][1][i] = dir.xyz,    RNG state, low word
     //   q[.][2][i] = beta.xyz,   RNG state, high word
+    // Bounce 0 has no q[0][2] record and reads no q[0][0] in k_shade: every camera path starts at cam.center with beta 1, no
+    // specular flag, L = 0 and slot = queue position, so k_raygen writes q[0][0] (k_extend's ray), q[0][1] and the one word
+    // of the third record that carries information, into a column of the pass set that only k_raygen and k_shade are given:
+    //   rng_hi0[i] = RNG state, high word, of the camera sample at slot i
+    // (an argument of those two kernels, like the nee queue, and no member: a member moves the arguments of every kernel
+    // that takes this struct, the traversal kernels among them)
     float4* q[2][3];
     float4* hit;  // [i] = t, inst (0xffffffff: miss), prim, shading class   written by k_extend at the ray's queue position
     uint8_t* cls;     // [queue position] shading class of the hit, a byte beside hit[].w for the class sort's two passes
@@ -35,6 +41,8 @@ struct PathState {
     uint32_t* tile_hist;
     uint2* class_range;
     float4* L;    // [slot] = radiance.xyz, w: the direct integrator's 1 / mass (src/directlighting.rs:37), else unused
+                  // First written by bounce 0's k_shade (every path it shades), by k_class_scatter<2u> for the paths a split queue
+                  // drops at bounce 0, and by run_pass's memset when the pass has no bounce: nobody reads a slot before that.
     // Next-event estimation hand-off.  Shadow rays by position j in the bounce's shadow queue:
     //   sr[0][j] = origin.xyz, t_max        sr[1][j] = dir.xyz, item
     //   sr[2][j] = lone ray: the path's radiance if the ray is unoccluded (k_shade has stored the occluded outcome in L)
@@ -45,7 +53,7 @@ struct PathState {
     float4* nee[3];   // [slot]: c1.xyz, 1 / light_pdf | c2.xyz, post factor | beta at the time of the estimate, -
     uint8_t* occ[2];  // [slot], written by k_shadow: 1 = the ray is occluded
 };
-#define PBRS_STATE_BYTES_PER_PATH (2u * 48u + 16u + 4u + 1u + 16u + 2u * 48u + 48u + 2u + 4u + 8u)  // records above + the nee queue entry + two slow-list entries
+#define PBRS_STATE_BYTES_PER_PATH (2u * 48u + 4u + 16u + 4u + 1u + 16u + 2u * 48u + 48u + 2u + 4u + 8u)  // records above + the nee queue entry + two slow-list entries
 
 struct RenderConst {
     pbrs_camera cam;
@@ -123,7 +131,7 @@ PD uint32_t order_of_pixel(uint32_t pix, uint32_t w, uint32_t tiles8_per_row) {
 }
 
 // ---- raygen --------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_raygen(PathState st, RenderConst rc) {
+__global__ void __launch_bounds__(256) k_raygen(PathState st, RenderConst rc, uint32_t* rng_hi0) {
     uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= rc.n_slots) return;
     uint32_t k, pix;
@@ -142,11 +150,11 @@ __global__ void __launch_bounds__(256) k_raygen(PathState st, RenderConst rc) {
     float x = (float)col + pn_fract(jx);
     float y = (float)row + pn_fract(jy);
     f3 dir = ld3(rc.cam.c) + ld3(rc.cam.a) * x + ld3(rc.cam.b) * y;
-    // bounce 0: the queue position of a path is its slot
+    // bounce 0: the queue position of a path is its slot.  beta = 1, L = 0 and the origin are the same for every camera path:
+    // bounce 0's k_shade takes them without a record (PathState), so only the RNG's high word travels beside the ray.
     st_stream(&st.q[0][0][slot], pack4(ld3(rc.cam.center), slot));
     st_stream(&st.q[0][1][slot], pack4(dir, (uint32_t)rng));
-    st_stream(&st.q[0][2][slot], pack4(gray(1.0f), (uint32_t)(rng >> 32)));
-    st_stream(&st.L[slot], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    __builtin_nontemporal_store((uint32_t)(rng >> 32), &rng_hi0[slot]);
 }
 
 struct GlobalCounters {  // instrumented variant only
@@ -444,7 +452,7 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_SHADING_CHE
                     // emission and the empty light estimate and ends.  A miss that sees the environment (the first bounce or after a
                     // specular one, :19-22) is kept: it adds the environment and ends.  Any other miss adds nothing (`break` at
                     // :25-27 with nothing before it) and is dropped — in an open scene most of a bounce's queue; so is a miss of the
-                    // first bounce under a black environment: L = 0 + 1 * 0 there, which is what k_raygen left in L.  (After a
+                    // first bounce under a black environment: L = 0 + 1 * 0 there, which k_class_scatter stores for it.  (After a
                     // specular bounce under a black environment beta may be infinite: beta * 0 is kept for k_shade to add.)
                     cls = 1u;
                     if (h.inst == 0xffffffffu) {
@@ -548,7 +556,8 @@ static_assert(sizeof(pbrs_material) % 16 == 0 && sizeof(pbrs_bxdf) % 16 == 0 && 
               "stage_shade_scene copies 16-byte pieces");
 template <uint32_t INTEG, bool TEX, uint32_t SPEC>
 __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : PBRS_SHADE_WAVES) k_shade(DevScene G, PathState st, RenderConst rc, uint32_t bounce, const uint32_t* count, uint32_t n_direct,
-                                              uint32_t* count_out, uint32_t* nee_queue, unsigned long long* nee_shadow_count, uint32_t sorted, const uint2* range) {
+                                              uint32_t* count_out, uint32_t* nee_queue, unsigned long long* nee_shadow_count, uint32_t sorted, const uint2* range,
+                                              const uint32_t* rng_hi0) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_shade_scene[];
     // per-hit lobe lists of textured materials (Bsdf::hit_lobe / hit_albedo); absent from the untextured instantiation
     __shared__ uint32_t s_hit_lobe[TEX ? PBRS_MAX_BXDFS * 256 : 1];
@@ -587,20 +596,39 @@ __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : 
         // several shading classes: lanes take the paths in class order (k_class_sort), so that a wave runs one material's code; a
         // queue k_extend split into kept and dropped paths: lanes take the kept positions (class 1 of a class-major order)
         const uint32_t src = sorted ? st.perm[i] : i;
-        const float4 r0 = ld_stream(&st.q[set][0][src]), r1 = ld_stream(&st.q[set][1][src]), r2 = ld_stream(&st.q[set][2][src]), rh = ld_stream(&st.hit[src]);
-        slot = __float_as_uint(r0.w) & PBRS_SLOT_MASK;
-        const float4 rl = st.L[slot];
-        f3 o = xyz(r0), d = xyz(r1);
-        f3 beta = xyz(r2);
-        f3 L = xyz(rl);
-        float post_w = rl.w;  // the direct integrator's 1 / mass rides next to the radiance
-        const uint64_t rng_in = ((uint64_t)__float_as_uint(r2.w) << 32) | (uint64_t)__float_as_uint(r1.w);
+        const float4 r1 = ld_stream(&st.q[set][1][src]), rh = ld_stream(&st.hit[src]);
+        f3 o, beta, L;
+        float post_w;  // the direct integrator's 1 / mass rides next to the radiance
+        uint32_t rng_hi;
+        bool specular_bounce;
+        if (bounce == 0) {
+            // a camera path (wave-uniform: `bounce` is a kernel argument): what k_raygen would have stored for it is the same for every
+            // path but the RNG's high word — no q[0][0] / q[0][2] fetch, and no L round trip behind the slot
+            slot = src;
+            o = ld3(rc.cam.center);
+            specular_bounce = false;
+            beta = gray(1.0f);
+            L = gray(0.0f);
+            post_w = 0.0f;
+            rng_hi = __builtin_nontemporal_load(&rng_hi0[src]);
+        } else {
+            const float4 r0 = ld_stream(&st.q[set][0][src]), r2 = ld_stream(&st.q[set][2][src]);
+            slot = __float_as_uint(r0.w) & PBRS_SLOT_MASK;
+            const float4 rl = st.L[slot];
+            o = xyz(r0);
+            specular_bounce = (__float_as_uint(r0.w) >> 31) != 0;
+            beta = xyz(r2);
+            L = xyz(rl);
+            post_w = rl.w;
+            rng_hi = __float_as_uint(r2.w);
+        }
+        f3 d = xyz(r1);
+        const uint64_t rng_in = ((uint64_t)rng_hi << 32) | (uint64_t)__float_as_uint(r1.w);
         Hit h;
         h.t = rh.x;
         h.inst = __float_as_uint(rh.y);
         h.prim = __float_as_uint(rh.z);
         bool has_hit = h.inst != 0xffffffffu;
-        bool specular_bounce = (__float_as_uint(r0.w) >> 31) != 0;
         const pbrs_material* mat = nullptr;
         if (has_hit) mat = S.mats + S.inst[h.inst].material;
         // The direct-lighting integrator (INTEG 1, src/directlighting.rs:14-56) runs on the same stage: bounce 0 is
@@ -1096,8 +1124,10 @@ __global__ void __launch_bounds__(64 * PBRS_MAX_CLASSES) k_class_scan(PathState 
         }
     }
 }
+// `zero_dropped` (two classes, bounce 0 of a split queue only: queue position = slot): the paths the split drops are shaded by nobody, and
+// bounce 0's k_shade is what first writes a slot's L — their radiance, 0, is stored here, before any reader of L runs.
 template <uint32_t NC>
-__global__ void __launch_bounds__(256) k_class_scatter(PathState st, const uint32_t* count, uint32_t n_direct) {
+__global__ void __launch_bounds__(256) k_class_scatter(PathState st, const uint32_t* count, uint32_t n_direct, uint32_t zero_dropped) {
     const uint32_t n = count ? *count : n_direct;
     const uint32_t base = blockIdx.x * PBRS_SORT_TILE;
     if (base >= n) return;
@@ -1124,6 +1154,7 @@ __global__ void __launch_bounds__(256) k_class_scatter(PathState st, const uint3
             for (uint32_t w = 0; w < wave; ++w) pos += s_wave[w][cls];
             st.perm[pos] = i;
         }
+        if (NC == 2u && zero_dropped && valid && cls == 0u) st_stream(&st.L[i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
         __syncthreads();
         if (threadIdx.x < NC) s_tot[threadIdx.x] += s_wave[0][threadIdx.x] + s_wave[1][threadIdx.x] + s_wave[2][threadIdx.x] + s_wave[3][threadIdx.x];
         __syncthreads();

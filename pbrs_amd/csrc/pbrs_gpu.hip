@@ -107,7 +107,8 @@ DevOverrides read_dev_overrides() {
 
 typedef void (*extend_fn_t)(DevScene, PathState, uint32_t, const uint32_t*, uint32_t, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
 typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*);
-typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*);
+typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*,
+                           const uint32_t*);
 
 // What pbrs_upload_scene finds out about a scene that decides which kernels render it (plan_kernels).
 struct SceneFacts {
@@ -226,6 +227,7 @@ struct pbrs_ctx {
         size_t cap_slots = 0;
         PathState st{};
         uint32_t* neeq = nullptr;     // cap_slots: slots of the paths whose estimate waits for two shadow rays
+        uint32_t* rng_hi0 = nullptr;  // cap_slots: the RNG's high word of every camera sample, from k_raygen to bounce 0's k_shade (kernels.h, PathState)
         uint32_t* slow = nullptr;     // 2 * cap_slots: queue positions the wide-walk k_shadow handed to the binary-walk kernel
         uint32_t* counters = nullptr; // kCounterWords: act, ns (u64), extend work heads, shadow work heads
         float4* direct = nullptr;     // light passes: the D column, [slot] = L[slot] as bounce 0 left it (device/passes.h); null unless the render asks for passes
@@ -324,6 +326,7 @@ void free_paths(pbrs_ctx::PassSet& set) {
     set.cap_slots = 0;
     set.st = PathState{};
     set.neeq = nullptr;
+    set.rng_hi0 = nullptr;
     set.slow = nullptr;
     if (set.state_mem) (void)hipFree(set.state_mem);
     set.state_mem = nullptr;
@@ -347,11 +350,11 @@ int ensure_work(pbrs_ctx* c, pbrs_ctx::PassSet& set, size_t n_slots, size_t n_pi
         free_paths(set);
         auto align = [](size_t b) { return (b + 255) / 256 * 256; };
         const size_t v16 = align(n_slots * sizeof(float4));
-        // q[2][3], hit, L, nee[3]: one float4 per path each; sr[3]: two per path; occ: two bytes; nee queue: one word
+        // q[2][3], hit, L, nee[3]: one float4 per path each; sr[3]: two per path; occ: two bytes; nee queue, rng_hi0: one word each
         const size_t n_tiles = n_slots / PBRS_SORT_TILE + 1;
         const size_t sort_bytes = align(n_tiles * PBRS_MAX_CLASSES * sizeof(uint32_t)) + align((PBRS_MAX_CLASSES + 1) * sizeof(uint2));
         const size_t total = (6 + 1 + 1 + 3) * v16 + 3 * 2 * v16 + align(2 * n_slots) + align(n_slots * sizeof(uint32_t)) + align(n_slots * sizeof(uint32_t)) +
-                             sort_bytes + align(n_slots) + align(2 * n_slots * sizeof(uint32_t));
+                             sort_bytes + align(n_slots) + align(2 * n_slots * sizeof(uint32_t)) + align(n_slots * sizeof(uint32_t));
         void* mem = nullptr;
         hipError_t e = hipMalloc(&mem, total);
         if (e != hipSuccess) {
@@ -377,6 +380,7 @@ int ensure_work(pbrs_ctx* c, pbrs_ctx::PassSet& set, size_t n_slots, size_t n_pi
         set.slow = reinterpret_cast<uint32_t*>(take(align(2 * n_slots * sizeof(uint32_t))));
         s.tile_hist = reinterpret_cast<uint32_t*>(take(align(n_tiles * PBRS_MAX_CLASSES * sizeof(uint32_t))));
         s.class_range = reinterpret_cast<uint2*>(take(align((PBRS_MAX_CLASSES + 1) * sizeof(uint2))));
+        set.rng_hi0 = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
         set.st = s;
         set.cap_slots = n_slots;
     }
@@ -886,10 +890,12 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
     if (!(xS.features & PBRS_FEAT_FLAT_TLAS)) xS.n_flat = 0u;
     HIPCHK(c, hipMemsetAsync(set.counters, 0, kCounterWords * sizeof(uint32_t), c->stream));
     if (tm.begin(0)) return fail(c, PBRS_E_DEVICE, "event record failed");
-    hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, c->stream, set.st, rc);
+    hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, c->stream, set.st, rc, set.rng_hi0);
     tm.end();
     poll_split_probe(c);
     const uint32_t n_bounces = bounce_count(rc);
+    // L is first written by bounce 0 (k_shade, and k_class_scatter for what a split queue drops): a pass without a bounce is all zeros
+    if (n_bounces == 0) HIPCHK(c, hipMemsetAsync(set.st.L, 0, (size_t)N * sizeof(float4), c->stream));
     // this pass counts what k_extend's queue split keeps (the first path-integrator pass of an uploaded one-class scene)
     const bool probe_split = c->split_decision == 0 && !c->split_probe_in_flight && rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && n_bounces > 0;
     for (uint32_t b = 0; b < n_bounces; ++b) {
@@ -926,8 +932,9 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
             else hipLaunchKernelGGL(k_class_count<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
             hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, set.st, cnt_in, N, qsplit ? 1u : ip.last_class,
                                (qsplit && probe_split) ? c->bounce_acc + 2 * PBRS_STATS_MAX_BOUNCES : nullptr);
-            if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
-            else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
+            // bounce 0 of a split queue: the scatter also stores L = 0 for the dropped paths, which no k_shade lane visits
+            if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, b == 0 ? 1u : 0u);
+            else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, 0u);
         } else if (order == IntegratorPlan::CLASS_SORT) {
             hipLaunchKernelGGL(k_class_sort, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
         }
@@ -936,7 +943,7 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
             const ShadeLaunch& l = ip.shade[k];
             // one class range of a class-major queue; a split queue: the kept paths
             const uint2* range = l.range ? set.st.class_range + l.range : qsplit ? set.st.class_range + 1 : nullptr;
-            hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), l.lds, c->stream, c->S, set.st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b, sorted, range);
+            hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), l.lds, c->stream, c->S, set.st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b, sorted, range, set.rng_hi0);
         }
         tm.end();
         if (tm.begin(3)) return fail(c, PBRS_E_DEVICE, "event record failed");
@@ -2452,7 +2459,7 @@ int pbrs_camera_rays(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
     k.tiles8_per_row = 0u;  // one sample index, exported by pixel: slot = pixel
     k.pass_first_sample = sample_index;
     k.n_slots = P;
-    hipLaunchKernelGGL(k_raygen, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, k);
+    hipLaunchKernelGGL(k_raygen, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, k, cur(c).rng_hi0);  // (the rays are read back, nothing else)
     float *d_o = nullptr, *d_d = nullptr;
     auto cleanup = [&]() { (void)hipFree(d_o); (void)hipFree(d_d); };
     TRY(hipMalloc(reinterpret_cast<void**>(&d_o), (size_t)P * 12));
