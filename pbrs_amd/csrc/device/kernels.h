@@ -15,6 +15,7 @@
 // queue", compacted with __ballot + mbcnt prefixes summed per block in LDS (two atomics per block).
 #pragma once
 #include "lights.h"
+#include "scene.h"
 #include "textures.h"
 #include "traverse.h"
 #include "../../../include/pbrs_numeric_probe.h"
@@ -175,19 +176,7 @@ PD void flush_counters(const Cnt<STATS>& cnt, GlobalCounters* g, bool valid, uin
 }
 
 // ---- extend ----------------------------------------------------------------------------------------------------
-// A wave takes new rays when fewer than DevScene::refill_below of its lanes are walking (pbrs_upload_scene): short walks
-// (a small TLAS scanned by the wave, BLASes of a few nodes) favour late, large refills — the shared scan of the new rays
-// fills its windows and the step kernels run on fuller waves less often; long walks (C4's 18-level BLAS) favour early ones.
-#ifndef PBRS_REFILL_BELOW_SHORT
-#define PBRS_REFILL_BELOW_SHORT 20u  // C2 extend 9.23 / 8.92 / 9.04 ms per 16 spp at 40 / 24 / 16
-#endif
-#ifndef PBRS_REFILL_BELOW_LONG
-#define PBRS_REFILL_BELOW_LONG 48u   // C4 extend 25.9 / 24.5 / 23.8 ms per 16 spp at 24 / 40 / 48; per frame 398.5 / 392.4 / 418.3 / 452.5 ms at 40 / 48 / 56 / 60 (round 4)
-#endif
-#ifndef PBRS_REFILL_BELOW_LONG_SHADOW
-#define PBRS_REFILL_BELOW_LONG_SHADOW 40u  // C4 shadow 205.3 / 209.9 / 231.5 ms per frame at 40 / 48 / 56 (profiles/r04j_ab_refill_thresholds_c4.log)
-#endif
-#define PBRS_LONG_WALK_HEIGHT 12u    // a mesh whose BLAS is at least this high makes the scene's walks "long"
+// PBRS_REFILL_BELOW_* (when a wave takes new rays) and PBRS_LONG_WALK_HEIGHT: device/scene.h
 #ifndef PBRS_NODE_STEPS_LONG
 #define PBRS_NODE_STEPS_LONG 3u
 #endif
@@ -498,29 +487,7 @@ PD float power_heuristic2(float f_pdf, float g_pdf) {  // src/directlighting.rs:
 }
 
 // ---- shade -----------------------------------------------------------------------------------------------------
-// SPEC: what the scene's materials and lights allow the stage to leave out (derived at upload, pbrs_upload_scene):
-//   PBRS_SHADE_LAMBERT        every lobe is an untextured Lambertian DiffuseReflect, at most one per material
-//   PBRS_SHADE_LIGHT_SPHERE / _TRIANGLE   every area light has that shape
-// Code a scene cannot reach still costs the loads that decide not to take it (a lobe's kind, a light's shape kind), the
-// registers of its longest path and the instructions around it: C2 (Lambert + triangle lights) shades in 87.7 instead of
-// 110.5 ms per frame, C4 (Lambert + sphere lights: 96 VGPRs, five waves per SIMD) in 116.7 instead of 150.6.
-#define PBRS_SHADE_LAMBERT 1u
-#define PBRS_SHADE_LIGHT_SPHERE 2u
-#define PBRS_SHADE_LIGHT_TRIANGLE 4u
-//   PBRS_SHADE_FOURIER        the other way round: some material is a Fourier BSDF (device/fourier.h), whose code only the
-//                             kernels with this bit contain (its f64 series sums and Newton loops are long and register-hungry)
-#define PBRS_SHADE_FOURIER 8u
-//   PBRS_SHADE_FOURIER_ONLY   (with PBRS_SHADE_FOURIER) every vertex the launch meets is on a Fourier material, whose one lobe is the
-//                             Fourier BSDF: the launch over that class of a class-major queue (pbrs_gpu.hip)
-#define PBRS_SHADE_FOURIER_ONLY 16u
-//   PBRS_SHADE_LDS_RECORDS    the scene's instance records, analytic shapes, materials, lobes and lights are copied into the block's LDS
-//   PBRS_SHADE_LDS_TRIS       ... and its triangle vertex and shading records (scenes of a few KB)
-// at kernel start (stage_shade_scene): a vertex's ~25 record fetches — the instance's two matrices, the triangle's seven vectors, material,
-// lobe and light — are gathers that cost the CU's texture path a cycle or two per lane each (k_shade's texture data unit was 0.93-0.95
-// busy on C2 / C3) and the LDS a third of that, at a third of the latency (tools/microbench/gather_lds_coop.hip).  Chosen per scene by what fits
-// (pbrs_upload_scene): C2 / C3 both, C4 (a million triangles, six instances) the records.
-#define PBRS_SHADE_LDS_RECORDS 32u
-#define PBRS_SHADE_LDS_TRIS 64u
+// SPEC: what the scene's materials and lights allow the stage to leave out, and what it stages in LDS: the PBRS_SHADE_* bits of device/scene.h
 #ifndef PBRS_FOURIER_AK_ROWS
 #define PBRS_FOURIER_AK_ROWS 48u  // terms of a luminance series kept in LDS per lane; longer series are recomputed where they are consumed
 #endif
@@ -1009,7 +976,6 @@ __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : 
 // 4 x 16 bytes per path; inside a class the order is the queue's, so the gathers stay near-sequential) and tiles keep
 // the spatial order of the queue at large.  The result of a path does not depend on which lane shades it.
 #define PBRS_SORT_TILE 16384u
-#define PBRS_MAX_CLASSES 16u
 // Class sizes of the queue positions [base, end) into s_tot[] (zeroed, block-wide).  Sixteen ballots per 64 paths, lane c of a
 // wave keeping class c's count, and one LDS add per lane at the end: one LDS atomic per PATH on sixteen words at most was
 // what the counting pass spent its time on (0.39 ms per 200 M paths reading bytes, as much as when it read 16-byte records).

@@ -11,91 +11,7 @@
 #include "../../../include/pbrs_gpu.h"
 #include "../../../include/pbrs_scene_spec.h"
 #include "dmath.h"
-
-struct pbrs_wnode;  // device/wide.h
-struct DevScene {
-    // Every BVH node of the scene in one array with absolute links: the TLAS at 0 (root = node 0), its leaves again at
-    // flat_off when the TLAS is small (below), then the BLASes; a mesh instance's blas_root is an index into it.
-    const pbrs_node* nodes;
-    const pbrs_instance* inst;
-    const pbrs_shape* shapes;
-    const pbrs_mesh* meshes;
-    const pbrs_tri_verts* tv;
-    const pbrs_tri_shade* ts;
-    const pbrs_material* mats;
-    const pbrs_bxdf* bxdfs;
-    const pbrs_area_light* alights;
-    const pbrs_delta_light* dlights;
-    uint32_t n_area, n_delta;
-    float env[3];
-    uint32_t has_env;
-    uint32_t fast_slab;  // node coordinates are inside the range the division-free box test is exact for (traverse.h)
-    uint32_t exact_extent;  // a ParallelQuad instance (hits outside its own box, D1) next to a mesh (hits beyond the extent it was given): the closest-hit walks take PBRS_FEAT_EXTENT
-    // Small TLAS (PBRS_FLAT_TLAS_MIN..MAX instances): its leaves alone, in pre-order = the order the tree walk reaches them.
-    // A box inside a box that a ray misses is missed too (each slab bound is a correctly rounded, hence monotonic,
-    // function of the box coordinate), so testing the leaf boxes in this order — each against the t_max of its turn —
-    // processes exactly the leaves, in exactly the order, of the reference's recursion (tlas/src/bvh.rs:84-88) without
-    // visiting the inner nodes.  The wave runs those tests for its new rays together (traverse.h, FlatScan).  Only for
-    // rays on the division-free box test (no NaN quotients); other rays walk the tree.  n_flat = 0 outside the range
-    // (kernels without PBRS_FEAT_FLAT_TLAS do not contain the scan).
-    uint32_t flat_off, n_flat;
-    uint32_t features;   // PBRS_FEAT_*: what the traversal kernels must be able to do for this scene
-    uint32_t refill_below;  // a wave of a traversal kernel takes new rays when fewer of its lanes than this are walking
-    uint32_t refill_below_shadow;  // ... of k_shadow (any-hit walks end at the first occluder: later, larger refills)
-    // texture/src/lib.rs (device/textures.h) and the environment light (scene/src/lib.rs:105-117)
-    const pbrs_texture* textures;
-    const float* tex_floats;
-    const uint32_t* tex_words;
-    uint32_t env_kind, env_texture;
-    float env_scale[3];
-    const pbrs_fourier_table* fourier;  // geometry/src/fourier.rs tables (device/fourier.h); their arrays are in the texture pools
-    // Shading classes: materials with the same lobe signature (kinds, Fresnel forms, textured or not) share one; the device
-    // copy of an instance carries its material's class in pad[0].  More than one class with lobes: the bounce queues are
-    // ordered by class before k_shade (kernels.h, k_class_sort).
-    uint32_t n_classes;
-    // Four-wide nodes over every BLAS (device/wide.h; a mesh instance's wide root is in the device copy of its record, pad[1])
-    // and the entries a lane's stack may hold in the kernels that walk them (beyond that a ray goes to the binary-walk kernels)
-    const pbrs_wnode* wnodes;
-    uint32_t wide_cap;
-    // Scenes of a few KB (a Cornell box: 8 KB): what the walks read — every node, triangle-vertex record, instance record and analytic
-    // shape — is copied into each block's LDS behind its stack rows at kernel start (PBRS_FEAT_LDS_SCENE kernels; kernels.h,
-    // stage_scene): element counts, and the word offset of the copy in the block's dynamic LDS (a multiple of 4).  0 nodes: not staged.
-    uint32_t lds_off_words, lds_nodes, lds_tris, lds_inst, lds_shapes;
-    // PBRS_FEAT_LDS_TOP kernels: only the first lds_nodes nodes (the TLAS) are staged, and read through this pointer (nullptr in the uploaded
-    // scene; the kernel points it at its block's copy): nodes[i] for i < lds_nodes comes from the LDS, every other node from DevScene::nodes
-    const pbrs_node* nodes_top;
-    // element counts of the arrays k_shade may stage in LDS (kernels.h, stage_shade_scene); n_area / n_delta above
-    uint32_t n_inst, n_shapes, n_tris, n_mats, n_bxdfs;
-};
-
-// Scene features the traversal kernels are specialised on (pbrs_upload_scene derives them from the arrays it checks).
-// Code a scene cannot reach still costs registers and issue slots on every wave, so each combination is its own
-// instantiation: a mesh-only scene whose meshes all carry a PBRS_MESH_*_SHADING_OK flag runs the leanest one.
-// pbrs_instance::flags bit set by pbrs_upload_scene on the device copy (not part of the ABI): the 3x3 part of `inv` is
-// bit-exactly the identity, i.e. the instance is only translated (traverse.h, enter_instance)
-#define PBRS_INSTANCE_TRANSLATION 0x100u
-#define PBRS_FEAT_ANALYTIC 1u       // some instance is an analytic shape (sphere, disk, quad, cuboid, triangle)
-#define PBRS_FEAT_SHADING_CHECK 2u  // some mesh needs the tangent check of blas.rs:193-200 evaluated per candidate hit
-#define PBRS_FEAT_FLAT_TLAS 4u      // the leaf copies at DevScene::flat_off are built: rays on the division-free box test scan the TLAS leaves
-#define PBRS_FEAT_ALL 7u
-#define PBRS_FEAT_EXTENT 256u        // closest-hit walk only (one k_extend each way, pbrs_gpu.hip kExtentFeatures): the TLAS extent is the reference's ray.t_max to the letter, rises included
-                                    // (traverse.h, ClosestWalk::EXT): scenes with a ParallelQuad next to a mesh (pbrs_upload_scene)
-#define PBRS_FEAT_LONG_WALKS 8u     // kernels only (not a property of the walks): several node steps per loop round (kernels.h)
-#define PBRS_FEAT_WIDE 16u          // kernels only: the walks over four-wide nodes (device/wide.h); needs PBRS_FEAT_FLAT_TLAS
-#define PBRS_FEAT_LDS_TOP 128u      // kernels only: the head of DevScene::nodes — a TLAS too large to scan — is copied into the block's LDS (scenes whose arrays do not fit as a whole)
-#define PBRS_FEAT_LDS_SCENE 64u     // kernels only: the arrays the walks read are copied into the block's LDS at kernel start (scenes of a few KB; kernels.h)
-#define PBRS_FEAT_FULL_STEPS 32u    // kernels only (with PBRS_FEAT_LONG_WALKS): a round's further node steps are full steps (kernels.h): scenes outside the guarded range of the division-free box test
-#define PBRS_FLAT_TLAS_MIN 2u
-// Largest TLAS the wave scans instead of walking (tools/tlas_probe.py, C5's scene family at 960x540, ms per 64 spp, walk vs
-// scan): closest hit 4.84 / 4.74 at 20 instances, 5.10 / 5.28 at 24, 5.66 / 6.15 at 30 — the scan only filters there and every
-// surviving leaf is still visited; any hit 3.33 / 2.38 at 20, 3.58 / 2.53 at 24, 3.97 / 2.86 at 30 — there the scan is the test.
-// The candidate mask is one word: <= 32.
-#ifndef PBRS_FLAT_TLAS_MAX
-#define PBRS_FLAT_TLAS_MAX 20u         // k_extend
-#endif
-#ifndef PBRS_FLAT_TLAS_MAX_ANYHIT
-#define PBRS_FLAT_TLAS_MAX_ANYHIT 32u  // k_shadow
-#endif
+#include "scene.h"  // DevScene, PBRS_FEAT_*, PBRS_FLAT_TLAS_*, PBRS_INSTANCE_TRANSLATION
 
 // Per-lane work counters (instrumented kernel variant only; SURVEY.md §8(d) units).
 struct WorkCounters {

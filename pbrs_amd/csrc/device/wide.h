@@ -22,33 +22,10 @@
 // Rays outside the guarded range (a zero / denormal / huge direction or origin component, in the world or inside an instance)
 // never take this path: the wide kernels hand them to the binary-walk kernels through a list (kernels.h, slow list).
 #pragma once
+#include "scene.h"   // pbrs_wnode, PBRS_WREF_*, PBRS_WIDE_*
 #include "shapes.h"  // included by traverse.h once RaySpace exists
 
-// 128 bytes = one L2 line.  Planes as structure-of-arrays over the four slots so that a lane reads the planes its ray meets
-// first / last on each axis as one 16-byte vector each (the choice follows the sign of the direction: a per-lane byte offset).
-struct pbrs_wnode {
-    float lo[3][4];     // [axis][slot]: min planes   (bytes   0 ..  47)
-    float hi[3][4];     // [axis][slot]: max planes   (bytes  48 ..  95)
-    uint32_t child[4];  // PBRS_WREF_LEAF | index of the reference's leaf node in DevScene::nodes; else index of a wide node; PBRS_WREF_NONE
-                        // in a slot not in use (its box is inverted — lo = 2^60, hi = -2^60 — and fails the filter for every ray of the
-                        // guarded range, without an overflow).  Slots 0 and 2 are always in use and carry the three split axes above
-                        // the index (PBRS_WREF_AXIS_SHIFT): child[0] bits 27-28 X's, bits 29-30 its left child's; child[2] bits 27-28 its
-                        // right child's — a node step reads seven vectors, not eight (a load whose lanes name different lines costs
-                        // the L1 a cycle per lane whatever its width: C4 k_shadow 151 accesses per ray)
-    uint32_t pad[4];
-};
-#ifndef PBRS_WIDE_STACK_MAX
-#define PBRS_WIDE_STACK_MAX 16  // LDS stack entries per lane of the wide-walk kernels (C4's terrain: 12 at most over a frame's rays)
-#endif
-#ifndef PBRS_WIDE_MIN_LEVELS
-#define PBRS_WIDE_MIN_LEVELS 4u  // scenes whose deepest BLAS has fewer wide levels keep the binary-walk kernels
-#endif
-#define PBRS_WREF_LEAF 0x80000000u
-#define PBRS_WREF_NONE 0xffffffffu
-#define PBRS_WREF_INDEX 0x07ffffffu  // a leaf's index in DevScene::nodes (below 2^27: the node array is addressed with 32-bit byte offsets); a wide
-#define PBRS_WREF_AXIS_SHIFT 27      // node's index loses the bits above it in `index * sizeof(pbrs_wnode)` (below 2^25 for the same reason)
-#define PBRS_WIDE_UNUSED_PLANE 1152921504606846976.0f /* 2^60 */
-// slots 0, 1: the children of X's left child (or that child itself in slot 0, where it is a leaf); slots 2, 3: of its right child
+// pbrs_wnode, PBRS_WREF_* and the PBRS_WIDE_* constants: device/scene.h (the host builds the nodes: host/scene_prepare.cpp)
 
 struct WideRay {
     f3 r32;       // RN(1 / d) per component: the correctly rounded reciprocals of the direction (-RaySpace::nr)

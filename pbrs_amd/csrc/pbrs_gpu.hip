@@ -13,7 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <utility>
 #include <mutex>
 #include <optional>
@@ -22,6 +21,7 @@
 
 #include "../../include/pbrs_gpu.h"
 #include "device/kernels.h"
+#include "host/scene_prepare.h"
 #include "device/aov.h"
 #include "device/film.h"
 #include "device/denoise.h"
@@ -31,9 +31,10 @@
 #include "device/temporal.h"
 #include "device/spatial_variance.h"
 
+using namespace pbrs;  // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h)
+
 namespace {
 
-constexpr uint32_t kBlock = 256;
 constexpr uint32_t kMaxDepth = 64;
 constexpr uint32_t kHeadWords = PBRS_WORK_HEADS * PBRS_WORK_HEAD_STRIDE;
 // per bounce: act, ns (u64), the slow-list length of k_shadow; then three sets of work heads (the two stages, and the binary-walk
@@ -45,34 +46,13 @@ constexpr uint32_t kSlowGrid = 64;
 #endif  // blocks of a binary-walk launch over a slow list (empty in nearly every launch)
 constexpr uint32_t kStreamGridCap = 4096;  // blocks of k_nee_resolve, whose work is counted on the device (kernels.h)
 constexpr uint32_t kPersistentBlocks = PBRS_PERSISTENT_BLOCKS;  // 256 CUs x up to 6 resident 256-thread blocks (VGPR/LDS permitting)
-constexpr size_t kLdsBytesPerCU = 160 * 1024;
 
 struct StageEvent {
     int stage;  // 0 raygen, 1 extend, 2 shade, 3 shadow, 4 accumulate
     hipEvent_t a, b;
 };
 
-// Developer overrides (A/B timing of kernel selection: tools/ab_env.sh): environment variables that builds made with
-// -DPBRS_DEV_OVERRIDES read once per context (pbrs_create); every other build leaves the defaults, which bend nothing.  The shipped
-// library never reads the environment: a bench line must not depend on the box it ran on.
-struct DevOverrides {
-    bool overlap_passes = true;   // PBRS_OVERLAP_PASSES=0: every pass on the main stream, as in rounds 1-3
-    bool sort_classes = true;     // PBRS_SORT_CLASSES=0: no class sort
-    bool split_lambert = true;    // PBRS_SPLIT_LAMBERT=0: one general k_shade launch for all classes
-    bool split_fourier = true;    // PBRS_SPLIT_FOURIER=0: one launch of the Fourier variants over every class, as in round 2
-    bool split_queue = true;      // PBRS_SPLIT_QUEUE=0: k_extend never splits the path integrator's queue
-    bool wide_shadow = true;      // PBRS_WIDE without bit 1: k_shadow keeps the binary walk
-    bool lds_scene = true;        // PBRS_LDS_SCENE=0: the traversal kernels never stage the whole scene in LDS
-    bool lds_top = true;          // PBRS_LDS_TOP=0: ... nor the TLAS alone
-    bool raygen_tiles8 = true;    // PBRS_RAYGEN_TILES8=0: no 8 x 8 pixel tiles in the slot order
-    uint32_t shade_spec = ~0u;    // PBRS_SHADE_SPEC: a mask of the path integrator's k_shade specialisation
-    uint32_t shade_lds = ~0u;     // PBRS_SHADE_LDS: a mask of what k_shade stages in LDS
-    std::optional<bool> long_walks, full_steps;         // PBRS_LONG_WALKS / PBRS_FULL_STEPS
-    std::optional<uint32_t> overlap_from, refill_below;  // PBRS_OVERLAP_FROM / PBRS_REFILL_BELOW
-    std::optional<uint32_t> raygen_chunk;  // PBRS_RAYGEN_CHUNK: pixels per slot-order chunk (0: the sample index outermost, as in round 1)
-    size_t lds_min = 0;           // PBRS_LDS_MIN: dynamic LDS bytes the traversal kernels take at least (lowers their occupancy)
-};
-
+// The developer overrides (host/kernel_choice.h, DevOverrides) of builds made with -DPBRS_DEV_OVERRIDES: read once per context (pbrs_create).
 #ifdef PBRS_DEV_OVERRIDES
 const char* dev_env(const char* name) { return std::getenv(name); }
 
@@ -110,30 +90,7 @@ typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, Glo
 typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*,
                            const uint32_t*);
 
-// What pbrs_upload_scene finds out about a scene that decides which kernels render it (plan_kernels).
-struct SceneFacts {
-    uint32_t features = 0;      // DevScene::features: PBRS_FEAT_ANALYTIC, _SHADING_CHECK, and _FLAT_TLAS where k_extend scans the TLAS leaves
-    bool tlas_scanned = false;  // the TLAS leaf copies exist (DevScene::n_flat): k_shadow scans them
-    bool exact_extent = false;  // DevScene::exact_extent: the closest-hit walks follow ray.t_max to the letter (PBRS_FEAT_EXTENT)
-    bool long_walks = false;    // a walk of PBRS_LONG_WALK_HEIGHT levels or more: the PBRS_FEAT_LONG_WALKS kernels
-    bool full_steps = false;    // ... whose further node steps are full ones (PBRS_FEAT_FULL_STEPS): coordinates outside the guarded range of the division-free box test
-    bool wide_ok = false;       // k_shadow may walk the four-wide nodes (a scanned TLAS, built wide nodes, a BLAS deep enough)
-    size_t stack_bytes = 0;     // a block's stack rows: DevScene::lds_off_words
-    size_t wide_stack_bytes = 0;  // ... of the four-wide walk: DevScene::wide_cap rows
-    size_t scene_bytes = 0;     // the arrays the walks read, as stage_scene copies them
-    size_t top_bytes = 0;       // the TLAS nodes, as stage_top copies them
-    uint32_t n_classes = 0;     // DevScene::n_classes
-    uint32_t lambert_class = 0; // shading class of the materials that are one untextured Lambertian DiffuseReflect (0: none)
-    uint32_t fourier_class = 0; // shading class of the materials that are one Fourier BSDF (0: none)
-    bool textured = false;      // some lobe evaluates a non-Solid texture: k_shade<.., true, ..>
-    bool fourier = false;       // some lobe is a Fourier BSDF: k_shade<.., PBRS_SHADE_FOURIER>
-    bool lambert = false;       // every lobe is an untextured Lambertian DiffuseReflect, at most one per material
-    uint32_t light_spec = 0;    // PBRS_SHADE_LIGHT_*: every area light has that shape
-    uint32_t shade_lds = 0;     // PBRS_SHADE_LDS_*: what fits k_shade's LDS budget
-    size_t shade_rec_bytes = 0, shade_tri_bytes = 0;  // what stage_shade_scene copies for PBRS_SHADE_LDS_RECORDS, and for _TRIS on top
-};
-
-// The kernels that render the uploaded scene, chosen once per upload (plan_kernels) from the tables below.
+// The kernels that render the uploaded scene, bound once per upload (bind_kernels) to what choose_kernels names (host/kernel_choice.h).
 template <class Fn>
 struct StageKernel {
     Fn fn = nullptr;
@@ -146,7 +103,7 @@ struct ShadeLaunch {
     uint32_t range = 0;  // the st.class_range entry the launch covers (PBRS_MAX_CLASSES: the classes before the last one), 0: the queue
 };
 struct IntegratorPlan {
-    enum Order { NO_ORDER, CLASS_SORT, CLASS_MAJOR } order = NO_ORDER;  // how the queue is ordered before k_shade
+    IntegratorChoice::Order order = IntegratorChoice::NO_ORDER;  // how the queue is ordered before k_shade
     uint32_t last_class = 0;  // CLASS_MAJOR: the class that goes last, over PBRS_MAX_CLASSES classes
     uint32_t n_shade = 0;     // one or two k_shade launches
     ShadeLaunch shade[2];
@@ -260,7 +217,7 @@ struct pbrs_ctx {
     pbrs_stats pending{};
     bool pending_counters = false, pending_times = false;
     DevOverrides dev;  // read in pbrs_create (-DPBRS_DEV_OVERRIDES builds)
-    KernelPlan plan;   // the kernels that render the uploaded scene (plan_kernels)
+    KernelPlan plan;   // the kernels that render the uploaded scene (bind_kernels)
     // k_extend splits the path integrator's queue of one-class scenes (shaded / terminal / dropped: KernelPlan::split_queue), which
     // pays where many paths are dropped (an open scene: C4 shades in 84 instead of 117 ms per frame) and costs where none are (a
     // closed box: the gathered records cost C2 4 %).  Decided once per uploaded scene, from the counts of the first pass rendered
@@ -519,48 +476,6 @@ int pass_size(pbrs_ctx* c, const pbrs_render_params* p, uint32_t& K, bool with_d
     return PBRS_OK;
 }
 
-// Four-wide nodes over the binary subtree of inner node x (device/wide.h): the boxes of x's grandchildren — or of a child that is
-// a leaf — in left-first order, with the three split axes that order them.  Returns the index of x's wide node in `out`.
-// `nodes`: DevScene::nodes as uploaded (absolute links; checked: children come after their parent, so the recursion ends).
-uint32_t build_wide(const std::vector<pbrs_node>& nodes, uint32_t x, std::vector<pbrs_wnode>& out, uint32_t level, uint32_t& levels) {
-    const uint32_t me = (uint32_t)out.size();
-    out.push_back(pbrs_wnode{});
-    levels = std::max(levels, level + 1u);
-    uint32_t slot_node[4] = {0, 0, 0, 0};
-    uint32_t used = 0, info = nodes[x].b & 3u;
-    const uint32_t child[2] = {x + 1u, nodes[x].a};
-    for (uint32_t s = 0; s < 2; ++s) {
-        const pbrs_node& ch = nodes[child[s]];
-        if (ch.b & PBRS_LEAF_FLAG) {
-            slot_node[2 * s] = child[s];
-            used |= 1u << (2 * s);
-        } else {
-            info |= (ch.b & 3u) << (2 + 2 * s);
-            slot_node[2 * s] = child[s] + 1u;
-            slot_node[2 * s + 1] = ch.a;
-            used |= 3u << (2 * s);
-        }
-    }
-    pbrs_wnode w{};
-    for (uint32_t k = 0; k < 4; ++k) {
-        w.child[k] = PBRS_WREF_NONE;
-        if (!((used >> k) & 1u)) {  // never passes the filter (device/wide.h)
-            for (int a = 0; a < 3; ++a) w.lo[a][k] = PBRS_WIDE_UNUSED_PLANE, w.hi[a][k] = -PBRS_WIDE_UNUSED_PLANE;
-            continue;
-        }
-        const pbrs_node& n = nodes[slot_node[k]];
-        for (int a = 0; a < 3; ++a) {
-            w.lo[a][k] = n.min[a];
-            w.hi[a][k] = n.max[a];
-        }
-        w.child[k] = (n.b & PBRS_LEAF_FLAG) ? (PBRS_WREF_LEAF | slot_node[k]) : build_wide(nodes, slot_node[k], out, level + 1u, levels);
-    }
-    w.child[0] |= (info & 15u) << PBRS_WREF_AXIS_SHIFT;  // slots 0 and 2 are always in use
-    w.child[2] |= ((info >> 4) & 3u) << PBRS_WREF_AXIS_SHIFT;
-    out[me] = w;
-    return me;
-}
-
 struct Timer {
     pbrs_ctx* c;
     bool on;
@@ -633,36 +548,7 @@ uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p, b
     return (uint32_t)k;
 }
 
-// The traversal kernels are instantiated per key (device/shapes.h PBRS_FEAT_*): one table entry per valid key, filled at compile
-// time; configure_kernels walks the tables and plan_kernels takes its pointers from them alone.  A key is a feature set, plus
-// kStatsKey for the instrumented variants, of which there is one per table and scene kind.  k_shadow never evaluates shading frames
-// nor follows the extent, so PBRS_FEAT_SHADING_CHECK and _EXTENT do not select it; k_extend walks binary nodes only (PBRS_FEAT_WIDE:
-// k_shadow's walk over four-wide nodes, scenes with a scanned TLAS).  `indirect` / `slow_*`: see kernels.h.
-constexpr uint32_t kStatsKey = 512u;  // above the PBRS_FEAT_* bits 0 .. 8
-constexpr uint32_t kTraversalKeys = 2u * kStatsKey;
-// a scene whose closest-hit walks follow the extent: no leaf scan, no staging, one k_extend each way
-constexpr uint32_t kExtentFeatures = PBRS_FEAT_ANALYTIC | PBRS_FEAT_SHADING_CHECK | PBRS_FEAT_EXTENT;
-constexpr uint32_t kShadowStatsFeatures = PBRS_FEAT_ANALYTIC | PBRS_FEAT_FLAT_TLAS;
-constexpr bool extend_key_ok(uint32_t k) {
-    const uint32_t f = k & ~kStatsKey;
-    if (f & PBRS_FEAT_EXTENT) return f == kExtentFeatures;
-    if (k & kStatsKey) return f == PBRS_FEAT_ALL;  // the instrumented kernel carries every feature
-    if (f & PBRS_FEAT_WIDE) return false;
-    if ((f & PBRS_FEAT_FULL_STEPS) && !(f & PBRS_FEAT_LONG_WALKS)) return false;  // further node steps exist in the long-walk kernels only
-    if ((f & PBRS_FEAT_LDS_SCENE) && (f & PBRS_FEAT_FULL_STEPS)) return false;  // a scene of a few KB
-    if ((f & PBRS_FEAT_LDS_TOP) && (f & (PBRS_FEAT_LDS_SCENE | PBRS_FEAT_FULL_STEPS | PBRS_FEAT_FLAT_TLAS))) return false;  // a TLAS too large to scan
-    return true;
-}
-constexpr bool shadow_key_ok(uint32_t k) {
-    const uint32_t f = k & ~kStatsKey;
-    if (k & kStatsKey) return f == kShadowStatsFeatures;
-    if (f & (PBRS_FEAT_SHADING_CHECK | PBRS_FEAT_EXTENT)) return false;
-    if ((f & PBRS_FEAT_FULL_STEPS) && !(f & PBRS_FEAT_LONG_WALKS)) return false;
-    if ((f & PBRS_FEAT_LDS_SCENE) && (f & (PBRS_FEAT_WIDE | PBRS_FEAT_FULL_STEPS))) return false;
-    if ((f & PBRS_FEAT_LDS_TOP) && (f & (PBRS_FEAT_LDS_SCENE | PBRS_FEAT_WIDE | PBRS_FEAT_FULL_STEPS | PBRS_FEAT_FLAT_TLAS))) return false;
-    if ((f & PBRS_FEAT_WIDE) && !(f & PBRS_FEAT_FLAT_TLAS)) return false;
-    return true;
-}
+// The traversal kernels, one per valid key (host/kernel_choice.h: extend_key_ok, shadow_key_ok), in tables filled at compile time.
 template <uint32_t K>
 constexpr extend_fn_t extend_fn_of() {
     if constexpr (extend_key_ok(K)) return &k_extend<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
@@ -686,134 +572,49 @@ const shadow_fn_t* shadow_table(std::integer_sequence<uint32_t, K...>) {
 const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
 const shadow_fn_t* shadow_fns() { return shadow_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
 template <class Fn>
-StageKernel<Fn> stage_kernel(const Fn* table, uint32_t key, size_t lds) {
-    return StageKernel<Fn>{table[key], (key & ~kStatsKey) | ((key & kStatsKey) ? 0x80000000u : 0u), lds};
+StageKernel<Fn> stage_kernel(const Fn* table, const TraversalKey& k) {
+    return StageKernel<Fn>{table[k.key], (k.key & ~kStatsKey) | ((k.key & kStatsKey) ? 0x80000000u : 0u), k.lds};
 }
 
-// The k_shade instantiations (kernels.h: INTEG, TEX, SPEC) the plans choose from.
+// The k_shade instantiations (kernels.h: INTEG, TEX, SPEC) the choices name: host/kernel_choice.h, PBRS_SHADE_KERNELS.
 struct ShadeKernel {
     uint32_t integ;
     bool tex;
     uint32_t spec;
     shade_fn_t fn;
 };
-template <uint32_t I, bool T, uint32_t SP>
-ShadeKernel shade_kernel() { return ShadeKernel{I, T, SP, &k_shade<I, T, SP>}; }
-constexpr uint32_t kShadeLdsAll = PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS;
-constexpr uint32_t kShadeFourierOnly = PBRS_SHADE_FOURIER | PBRS_SHADE_FOURIER_ONLY;
-const ShadeKernel kShadeKernels[] = {
-    // the path integrator's untextured variants, specialised on Lambert-only scenes and their light shape, with the shading records (and
-    // the triangle records) staged in LDS
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, 0u>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LAMBERT>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LAMBERT>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll | PBRS_SHADE_LAMBERT>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_SPHERE>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeLdsAll | PBRS_SHADE_LAMBERT | PBRS_SHADE_LIGHT_TRIANGLE>(),
-    // textures, the Fourier lobe, the Fourier materials' class alone
-    shade_kernel<PBRS_INTEGRATOR_PATH, true, 0u>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, true, PBRS_SHADE_FOURIER>(),
-    shade_kernel<PBRS_INTEGRATOR_PATH, false, kShadeFourierOnly>(),
-    shade_kernel<PBRS_INTEGRATOR_DIRECT, false, 0u>(),
-    shade_kernel<PBRS_INTEGRATOR_DIRECT, true, 0u>(),
-    shade_kernel<PBRS_INTEGRATOR_DIRECT, true, PBRS_SHADE_FOURIER>(),
-    shade_kernel<PBRS_INTEGRATOR_DIRECT, false, kShadeFourierOnly>(),
-    // the visualisers
-    shade_kernel<PBRS_INTEGRATOR_MATERIALS, false, 0u>(),
-    shade_kernel<PBRS_INTEGRATOR_NORMALS, false, 0u>(),
-};
-shade_fn_t shade_fn(uint32_t integ, bool tex, uint32_t spec) {
+#define PBRS_SHADE_KERNEL_ENTRY(I, T, SP) ShadeKernel{I, T, SP, &k_shade<I, T, SP>},
+const ShadeKernel kShadeKernels[] = {PBRS_SHADE_KERNELS(PBRS_SHADE_KERNEL_ENTRY)};
+#undef PBRS_SHADE_KERNEL_ENTRY
+shade_fn_t shade_fn(const ShadeKey& key) {
     for (const ShadeKernel& k : kShadeKernels)
-        if (k.integ == integ && k.tex == tex && k.spec == spec) return k.fn;
+        if (k.integ == key.integ && k.tex == key.tex && k.spec == key.spec) return k.fn;
     return nullptr;
 }
 
-// The kernels that render a scene, from what pbrs_upload_scene found out about it, bent by the developer overrides.  False where a
-// table lacks a kernel the choice names.
-bool plan_kernels(const SceneFacts& f, const DevOverrides& dev, KernelPlan& p) {
+// The kernels a choice names (choose_kernels), from the tables above.  False where a table lacks one.
+bool bind_kernels(const KernelChoice& ch, KernelPlan& p) {
     p = KernelPlan{};
-    const bool long_walks = dev.long_walks.value_or(f.long_walks);
-    const bool full_steps = dev.full_steps.value_or(f.full_steps);
-    const uint32_t steps = long_walks ? PBRS_FEAT_LONG_WALKS | (full_steps ? PBRS_FEAT_FULL_STEPS : 0u) : 0u;
-    p.wide_shadow = f.tlas_scanned && f.wide_ok && dev.wide_shadow;
-    // The arrays the walks read, staged in every block's LDS (kernels.h, stage_scene) where they fit next to the stack rows with
-    // eight blocks to a CU: scenes of a few KB whose walks are short (no wide nodes, lean-step choice irrelevant) ...
-    const bool lds_scene = dev.lds_scene && !p.wide_shadow && !full_steps && f.stack_bytes + f.scene_bytes <= kLdsBytesPerCU / 8;
-    // ... or the TLAS alone, where it is too large for the wave's shared scan (no leaf copies) and fits with seven blocks to a CU
-    const bool lds_top = dev.lds_top && !lds_scene && !f.tlas_scanned && !full_steps && f.stack_bytes + f.top_bytes + 512 <= kLdsBytesPerCU / 7;
-    p.lds_staging = lds_scene ? PBRS_FEAT_LDS_SCENE : lds_top ? PBRS_FEAT_LDS_TOP : 0u;
-    const size_t stack = std::max(f.stack_bytes, dev.lds_min);
-    const size_t staged = stack + (lds_scene ? f.scene_bytes : lds_top ? f.top_bytes : 0u);
-    if (f.exact_extent) {  // (scenes with a ParallelQuad next to a mesh: no benchmark holds one)
-        p.extend[0] = stage_kernel(extend_fns(), kExtentFeatures, stack);
-        p.extend[1] = stage_kernel(extend_fns(), kStatsKey | kExtentFeatures, stack);
-    } else {
-        p.extend[0] = stage_kernel(extend_fns(), (f.features & PBRS_FEAT_ALL) | steps | p.lds_staging, staged);
-        p.extend[1] = stage_kernel(extend_fns(), kStatsKey | PBRS_FEAT_ALL, stack);
+    for (int s = 0; s < 2; ++s) {
+        p.extend[s] = stage_kernel(extend_fns(), ch.extend[s]);
+        p.shadow[s] = stage_kernel(shadow_fns(), ch.shadow[s]);
     }
-    const uint32_t shadow_feat = (f.features & PBRS_FEAT_ANALYTIC) | (f.tlas_scanned ? PBRS_FEAT_FLAT_TLAS : 0u) | steps;
-    if (p.wide_shadow) {
-        p.shadow[0] = stage_kernel(shadow_fns(), shadow_feat | PBRS_FEAT_WIDE, f.wide_stack_bytes);
-        p.shadow_slow = stage_kernel(shadow_fns(), shadow_feat, stack);
-    } else {
-        p.shadow[0] = stage_kernel(shadow_fns(), shadow_feat | p.lds_staging, staged);
-    }
-    p.shadow[1] = stage_kernel(shadow_fns(), kStatsKey | kShadowStatsFeatures, stack);
+    p.wide_shadow = ch.wide_shadow;
+    if (ch.wide_shadow) p.shadow_slow = stage_kernel(shadow_fns(), ch.shadow_slow);
+    p.split_queue = ch.split_queue;
+    p.lds_staging = ch.lds_staging;
     bool ok = p.extend[0].fn && p.extend[1].fn && p.shadow[0].fn && p.shadow[1].fn && (!p.wide_shadow || p.shadow_slow.fn);
-    p.split_queue = f.n_classes <= 1u && dev.split_queue;
-
-    // k_shade.  The path integrator's untextured variants stage the scene's shading records (and triangle records) in LDS where they fit,
-    // and leave out what the scene's materials and lights do not need (the light shape alone does not pay: without the Lambert cut the
-    // kernel grows to 135-141 VGPRs, three waves per SIMD; C2 shade 110.5 -> 117.0 ms, C4 150.6 -> 169.3)
-    const uint32_t shade_lds = f.shade_lds & dev.shade_lds;
-    const uint32_t path_lds = (shade_lds == kShadeLdsAll || shade_lds == PBRS_SHADE_LDS_RECORDS) ? shade_lds : 0u;
-    const size_t path_lds_bytes = path_lds == kShadeLdsAll ? f.shade_rec_bytes + f.shade_tri_bytes : path_lds ? f.shade_rec_bytes : 0u;
-    uint32_t spec = f.lambert ? (PBRS_SHADE_LAMBERT | f.light_spec) & dev.shade_spec : 0u;
-    if (!(spec & PBRS_SHADE_LAMBERT)) spec = 0u;
-    auto shade = [&](IntegratorPlan& ip, uint32_t integ, bool tex, uint32_t sp, size_t lds, uint32_t range) {
-        ip.shade[ip.n_shade++] = ShadeLaunch{shade_fn(integ, tex, sp), lds, range};
-        ok = ok && ip.shade[ip.n_shade - 1].fn;
-    };
-    auto path_untextured = [&](IntegratorPlan& ip, uint32_t sp, uint32_t range) { shade(ip, PBRS_INTEGRATOR_PATH, false, sp | path_lds, path_lds_bytes, range); };
-    // several shading classes (and an integrator that shades): the queue is ordered by class first; counted as shade time
-    const bool sorted = f.n_classes > 1u && dev.sort_classes;
-    for (uint32_t i = PBRS_INTEGRATOR_PATH; i <= PBRS_INTEGRATOR_DIRECT; ++i) {
+    for (uint32_t i = 0; i <= PBRS_INTEGRATOR_NORMALS; ++i) {
+        const IntegratorChoice& ic = ch.integ[i];
         IntegratorPlan& ip = p.integ[i];
-        const bool path = i == PBRS_INTEGRATOR_PATH;
-        // ... and where one of the classes is Lambertian (and the integrator has a Lambert variant), class-major over the whole
-        // queue, so that the class gets a launch of that variant and the other classes one of the general kernel
-        const bool split = sorted && path && f.lambert_class && dev.split_lambert && !f.textured && !f.fourier;
-        // ... or a Fourier BSDF: its lobe's code (168 registers and scratch in k_shade's variants that carry it) then runs over
-        // the vertices on such a material only, the other classes take the kernels without it
-        const bool fsplit = sorted && f.fourier && f.fourier_class && dev.split_fourier;
-        ip.order = (split || fsplit) ? IntegratorPlan::CLASS_MAJOR : sorted ? IntegratorPlan::CLASS_SORT : IntegratorPlan::NO_ORDER;
-        ip.last_class = split ? f.lambert_class : fsplit ? f.fourier_class : 0u;
-        if (fsplit) {  // (one untextured Fourier lobe per material: the variant cut down to it)
-            shade(ip, i, false, kShadeFourierOnly, 0, f.fourier_class);
-            shade(ip, i, f.textured, 0u, 0, PBRS_MAX_CLASSES);
-        } else if (f.fourier && f.fourier_class && f.n_classes == 1u) {  // every material with lobes is a Fourier BSDF
-            shade(ip, i, false, kShadeFourierOnly, 0, 0u);
-        } else if (f.fourier) {  // some material is a Fourier BSDF: the kernels that carry the lobe (and textures)
-            shade(ip, i, true, PBRS_SHADE_FOURIER, 0, 0u);
-        } else if (f.textured) {  // some material evaluates a non-Solid texture per hit
-            shade(ip, i, true, 0u, 0, 0u);
-        } else if (!path) {
-            shade(ip, i, false, 0u, 0, 0u);
-        } else if (split) {
-            path_untextured(ip, PBRS_SHADE_LAMBERT | f.light_spec, f.lambert_class);
-            path_untextured(ip, 0u, PBRS_MAX_CLASSES);
-        } else {
-            path_untextured(ip, spec, 0u);
+        ip.order = ic.order;
+        ip.last_class = ic.last_class;
+        ip.n_shade = ic.n_shade;
+        for (uint32_t k = 0; k < ic.n_shade; ++k) {
+            ip.shade[k] = ShadeLaunch{shade_fn(ic.shade[k]), ic.shade[k].lds, ic.shade[k].range};
+            ok = ok && ip.shade[k].fn;
         }
     }
-    shade(p.integ[PBRS_INTEGRATOR_MATERIALS], PBRS_INTEGRATOR_MATERIALS, false, 0u, 0, 0u);
-    shade(p.integ[PBRS_INTEGRATOR_NORMALS], PBRS_INTEGRATOR_NORMALS, false, 0u, 0, 0u);
     return ok;
 }
 
@@ -925,9 +726,9 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
                                c->buf[BUF_MATTE_STATE].as<uint32_t>(), P, kc, rc.chunk_pixels, qsplit, t.matte->key);
         if (tm.begin(2)) return fail(c, PBRS_E_DEVICE, "event record failed");
         // the queue in the order the plan asks for; a queue k_extend split: class-major over its two classes, class 1 = the kept paths, last
-        const IntegratorPlan::Order order = qsplit ? IntegratorPlan::CLASS_MAJOR : ip.order;
+        const IntegratorChoice::Order order = qsplit ? IntegratorChoice::CLASS_MAJOR : ip.order;
         const uint32_t n_tiles = (N + PBRS_SORT_TILE - 1) / PBRS_SORT_TILE;
-        if (order == IntegratorPlan::CLASS_MAJOR) {
+        if (order == IntegratorChoice::CLASS_MAJOR) {
             if (qsplit) hipLaunchKernelGGL(k_class_count<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
             else hipLaunchKernelGGL(k_class_count<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
             hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, set.st, cnt_in, N, qsplit ? 1u : ip.last_class,
@@ -935,10 +736,10 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
             // bounce 0 of a split queue: the scatter also stores L = 0 for the dropped paths, which no k_shade lane visits
             if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, b == 0 ? 1u : 0u);
             else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, 0u);
-        } else if (order == IntegratorPlan::CLASS_SORT) {
+        } else if (order == IntegratorChoice::CLASS_SORT) {
             hipLaunchKernelGGL(k_class_sort, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
         }
-        const uint32_t sorted = order != IntegratorPlan::NO_ORDER ? 1u : 0u;
+        const uint32_t sorted = order != IntegratorChoice::NO_ORDER ? 1u : 0u;
         for (uint32_t k = 0; k < ip.n_shade; ++k) {
             const ShadeLaunch& l = ip.shade[k];
             // one class range of a class-major queue; a split queue: the kept paths
@@ -1116,9 +917,9 @@ int collect(pbrs_ctx* c, pbrs_stats* out) {
 
 // The traversal kernels take their per-lane stacks from dynamic LDS.  The limit a kernel may ask for is per-function state
 // of the PROCESS (hipFuncSetAttribute), not of a context: it is raised once per device, to the most any scene may need
-// (pbrs_upload_scene refuses stacks above kLdsBytesPerCU / 2), so that contexts holding scenes with different stack depths
+// (check_scene refuses stacks above kLdsBytesPerCU / 2), so that contexts holding scenes with different stack depths
 // can render side by side — rewriting it per upload let the last upload decide for every context of the process.  Every traversal
-// kernel a plan can name sits in the tables (plan_kernels).
+// kernel a plan can name sits in the tables (bind_kernels).
 std::mutex g_kernel_cfg_mutex;
 bool g_kernel_cfg_done[64] = {};
 int configure_kernels(pbrs_ctx* c) {
@@ -1387,259 +1188,26 @@ int pbrs_set_pass_overlap(pbrs_ctx* c, int enabled) {
     return PBRS_OK;
 }
 
+// Check, prepare and choose on the host (host/scene_prepare.h, host/kernel_choice.h), then bind, and only then touch the device: a
+// refusal leaves the context's previous scene in place.  A failing hipMalloc or copy leaves the context without a scene.
 int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     if (!c || !d) return PBRS_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    if (d->n_tlas_nodes == 0 || d->n_instances == 0) return fail(c, PBRS_E_INVALID, "scene without instances");
-    // Host-side shape checks: every index the kernels dereference must be in range before any launch.
-    for (uint32_t i = 0; i < d->n_tlas_nodes; ++i) {
-        const pbrs_node& n = d->tlas_nodes[i];
-        if (n.b & PBRS_LEAF_FLAG) {
-            if (n.a >= d->n_instances) return fail(c, PBRS_E_INVALID, "tlas leaf references a missing instance");
-        } else if (n.a >= d->n_tlas_nodes || i + 1 >= d->n_tlas_nodes) {
-            return fail(c, PBRS_E_INVALID, "tlas child out of range");
-        }
-    }
-    for (uint32_t i = 0; i < d->n_blas_nodes; ++i) {
-        const pbrs_node& n = d->blas_nodes[i];
-        if (n.b & PBRS_LEAF_FLAG) {
-            uint32_t cnt = n.b & ~PBRS_LEAF_FLAG;
-            if ((uint64_t)n.a + cnt > d->n_triangles) return fail(c, PBRS_E_INVALID, "blas leaf range out of range");
-        } else if (n.a >= d->n_blas_nodes || i + 1 >= d->n_blas_nodes || (n.b & 3u) > 2u) {
-            return fail(c, PBRS_E_INVALID, "blas child out of range");
-        }
-    }
-    uint32_t max_blas_height = 0;
-    for (uint32_t i = 0; i < d->n_meshes; ++i) {
-        if (d->meshes[i].root >= d->n_blas_nodes) return fail(c, PBRS_E_INVALID, "mesh root out of range");
-        if (d->meshes[i].height > max_blas_height) max_blas_height = d->meshes[i].height;
-    }
-    for (uint32_t i = 0; i < d->n_instances; ++i) {
-        const pbrs_instance& in = d->instances[i];
-        if (in.material >= d->n_materials) return fail(c, PBRS_E_INVALID, "instance material out of range");
-        if (in.shape_kind > PBRS_SHAPE_MESH) return fail(c, PBRS_E_INVALID, "unknown shape kind");
-        if (in.shape_kind == PBRS_SHAPE_MESH ? in.shape_index >= d->n_meshes : in.shape_index >= d->n_shapes)
-            return fail(c, PBRS_E_INVALID, "instance shape out of range");
-        if (in.shape_kind == PBRS_SHAPE_MESH ? in.blas_root >= d->n_blas_nodes : (in.shape_kind == PBRS_SHAPE_TRIANGLE && in.blas_root >= d->n_triangles))
-            return fail(c, PBRS_E_INVALID, "instance blas_root out of range");
-    }
-    bool vis_records = d->n_materials > 0;
-    for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const pbrs_material& m = d->materials[i];
-        if (m.n_bxdfs > PBRS_MAX_BXDFS || (uint64_t)m.first_bxdf + m.n_bxdfs > d->n_bxdfs) return fail(c, PBRS_E_INVALID, "material lobes out of range");
-        if (m.vis_bxdf > d->n_bxdfs) return fail(c, PBRS_E_INVALID, "material visualiser record out of range");
-        if (m.vis_bxdf == 0) vis_records = false;
-    }
-    bool textured = false, fourier = false;
-    for (uint32_t i = 0; i < d->n_bxdfs; ++i) {
-        const uint32_t t = d->bxdfs[i].tex & ~PBRS_BXDF_TEX_DROP_IF_BLACK;
-        if (t > d->n_textures) return fail(c, PBRS_E_INVALID, "lobe texture out of range");
-        textured = textured || t != 0;
-        if (d->bxdfs[i].kind > PBRS_BXDF_FOURIER) return fail(c, PBRS_E_INVALID, "unknown lobe kind");
-        if (d->bxdfs[i].kind == PBRS_BXDF_FOURIER) {
-            if (d->bxdfs[i].intrusion >= d->n_fourier_tables) return fail(c, PBRS_E_INVALID, "Fourier lobe table out of range");
-            fourier = true;
-        }
-    }
-    // Fourier tables (geometry/src/fourier.rs:99-151): every array inside the pools, every series inside the coefficients;
-    // with finite, strictly ascending nodes the interpolation weights are finite for every direction the lobe accepts (a NaN
-    // direction is refused there), and the lobe skips neighbours outside the table: no lane indexes outside the pools
-    for (uint32_t i = 0; i < d->n_fourier_tables; ++i) {
-        const pbrs_fourier_table& t = d->fourier_tables[i];
-        const uint64_t n = t.n_mu, nn = n * n, nf = d->n_tex_floats, nw = d->n_tex_words;
-        if (n < 3 || (t.n_channels != 1 && t.n_channels != 3)) return fail(c, PBRS_E_INVALID, "Fourier table: sizes");
-        if (t.mu + n > nf || t.cdf + nn > nf || t.a0 + nn > nf || (uint64_t)t.a + t.n_coeffs > nf || (uint64_t)t.recip + t.m_max > nf ||
-            t.a_offset + nn > nw || t.m_lookup + nn > nw)
-            return fail(c, PBRS_E_INVALID, "Fourier table: arrays out of range");
-        for (uint64_t k = 0; k < n; ++k) {  // finite, strictly ascending nodes: no interval of zero width, no NaN weight (device/fourier.h)
-            const float m0 = d->tex_floats[t.mu + k];
-            if (!pn_isfinite(m0) || (k + 1 < n && !(m0 < d->tex_floats[t.mu + k + 1]))) return fail(c, PBRS_E_INVALID, "Fourier table: mu is not finite and strictly ascending");
-        }
-        for (uint64_t k = 0; k < nn; ++k) {
-            const uint64_t off = d->tex_words[t.a_offset + k], len = d->tex_words[t.m_lookup + k];
-            if (len > t.m_max || off + len * t.n_channels > t.n_coeffs) return fail(c, PBRS_E_INVALID, "Fourier table: series out of range");
-        }
-    }
-    for (uint32_t i = 0; i < d->n_textures; ++i) {
-        const pbrs_texture& t = d->textures[i];
-        if (t.kind == PBRS_TEX_PERLIN) {
-            if ((uint64_t)t.data + 768 > d->n_tex_floats || (uint64_t)t.perm + 768 > d->n_tex_words) return fail(c, PBRS_E_INVALID, "perlin tables out of range");
-            for (uint32_t k = 0; k < 768; ++k)
-                if (d->tex_words[t.perm + k] > 255u) return fail(c, PBRS_E_INVALID, "perlin permutation entry above 255");
-        } else if (t.kind == PBRS_TEX_IMAGE) {
-            if (t.width == 0 || t.height == 0 || (uint64_t)t.data + 3ull * t.width * t.height > d->n_tex_floats)
-                return fail(c, PBRS_E_INVALID, "image texels out of range");
-        } else if (t.kind != PBRS_TEX_CHECKER) {
-            return fail(c, PBRS_E_INVALID, "unknown texture kind");
-        }
-    }
-    if (d->env_kind > PBRS_ENV_DUSK) return fail(c, PBRS_E_INVALID, "unknown environment kind");
-    if (d->env_kind == PBRS_ENV_IMAGE && (d->env_texture >= d->n_textures || d->textures[d->env_texture].kind != PBRS_TEX_IMAGE))
-        return fail(c, PBRS_E_INVALID, "environment map is not an image texture");
-    for (uint32_t i = 0; i < d->n_area_lights; ++i) {
-        uint32_t k = d->area_lights[i].shape_kind;
-        if (!(k == PBRS_SHAPE_SPHERE || k == PBRS_SHAPE_DISK || k == PBRS_SHAPE_TRIANGLE || k == PBRS_SHAPE_QUAD))
-            return fail(c, PBRS_E_INVALID, "area light shape kind");
-    }
-    // Depth of the per-lane stack, from the trees themselves (the heights in the description are not trusted: an entry
-    // too few would let a lane write into its neighbour's LDS).  h = levels of a tree (a lone leaf: 1).  A walk pops a node
-    // of level l with l - 1 entries pending and pushes two: at most h_tlas entries in the TLAS, h_tlas - 1 pending below an
-    // instance, and h_blas more inside it — max(h_tlas, h_tlas - 1 + h_blas) entries.  One level matters: C4's 4 + 23 levels
-    // need 26 KB per block, six blocks per CU instead of five.
-    auto tree_heights = [](const pbrs_node* nodes, uint32_t n, std::vector<uint32_t>& h) {
-        h.assign(n, 1u);  // children come after their parent (left = i + 1, right = a > i, checked above): one reverse pass
-        for (uint32_t i = n; i-- > 0;)
-            if (!(nodes[i].b & PBRS_LEAF_FLAG)) h[i] = std::max(h[i + 1], h[nodes[i].a]) + 1u;
-    };
-    for (uint32_t i = 0; i < d->n_tlas_nodes; ++i)
-        if (!(d->tlas_nodes[i].b & PBRS_LEAF_FLAG) && d->tlas_nodes[i].a <= i) return fail(c, PBRS_E_INVALID, "tlas nodes are not in pre-order");
-    for (uint32_t i = 0; i < d->n_blas_nodes; ++i)
-        if (!(d->blas_nodes[i].b & PBRS_LEAF_FLAG) && d->blas_nodes[i].a <= i) return fail(c, PBRS_E_INVALID, "blas nodes are not in pre-order");
-    std::vector<uint32_t> th, bh;
-    tree_heights(d->tlas_nodes, d->n_tlas_nodes, th);
-    tree_heights(d->blas_nodes, d->n_blas_nodes, bh);
-    const uint32_t tlas_levels = th[0];
-    max_blas_height = 0;
-    for (uint32_t i = 0; i < d->n_meshes; ++i) max_blas_height = std::max(max_blas_height, bh[d->meshes[i].root]);
-    // a walk enters a BLAS through the instance's own blas_root (range-checked above), which need not be a listed mesh root
-    for (uint32_t i = 0; i < d->n_instances; ++i)
-        if (d->instances[i].shape_kind == PBRS_SHAPE_MESH) max_blas_height = std::max(max_blas_height, bh[d->instances[i].blas_root]);
-    uint32_t depth = std::max(tlas_levels, tlas_levels - 1u + max_blas_height);
-    // A ParallelQuad reports hits in the mirrored quadrants of its plane, outside its own box (D1); a mesh may return a hit beyond the
-    // extent it was given, which RAISES ray.t_max when its subtree is a left one (bvh.rs:84-88).  Together they make the rise visible
-    // (a box the best hit would have pruned is entered and holds a nearer hit: fuzz seed 211699), so the closest-hit walks of such a
-    // scene follow ray.t_max to the letter (PBRS_FEAT_EXTENT): a pending TLAS entry then takes two stack words.
-    bool has_quad = false, has_mesh = false;
-    for (uint32_t i = 0; i < d->n_instances; ++i) {
-        has_quad = has_quad || d->instances[i].shape_kind == PBRS_SHAPE_QUAD;
-        has_mesh = has_mesh || d->instances[i].shape_kind == PBRS_SHAPE_MESH;
-    }
-    const bool exact_extent = has_quad && has_mesh;
-    if (exact_extent) depth += tlas_levels + 1u;
-    if ((size_t)depth * kBlock * sizeof(uint32_t) > kLdsBytesPerCU / 2) return fail(c, PBRS_E_LIMIT, "traversal stack exceeds the LDS budget");
+    const SceneCheck chk = check_scene(*d);
+    if (chk.code != PBRS_OK) return fail(c, chk.code, chk.message);
+    PreparedScene P = prepare_scene(*d, chk.levels, c->dev);
+    const KernelChoice choice = choose_kernels(P.facts, c->dev);
+    KernelPlan plan;
+    if (!bind_kernels(choice, plan)) return fail(c, PBRS_E_DEVICE, "no kernel instantiation for this scene's feature set");
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->second_stream);
     free_scene(c);
-    DevScene S{};
-    SceneFacts f{};
+    c->plan = plan;
+    DevScene S = P.S;
     int rc;
-    // The division-free box test (device/traverse.h) is exact when every node coordinate b is finite, |b| <= 2^40 and (b == 0 or
-    // |b| >= 2^-60) — the range of a ray's origin components (origin_in_range); otherwise every lane uses the literal divisions.
-    // With o and b both zero or at least 2^-60 the numerator RN(o - b) is zero or at least 2^-83, its first quotient q0 = nn nr at least
-    // 2^-123 (normal: rounded at full precision), the residual e = d q0 + nn a multiple of 2^-131 (exact, if subnormal: the kernels run
-    // with f32 denormals on, .amdhsa_float_denorm_mode_32 3) and the result normal: the three instructions return RN(n / d) as they
-    // do at any other scale (tools/microbench/div_exhaustive.hip).  Rounds 1-3 asked 2^-20 of the box coordinates — a bound of the
-    // f64 route of rounds 1-2 that the f32 quotient inherited: c4xl's 8.4 M vertices hold three heights below it (1.6e-7, 7.4e-7,
-    // -9.8e-8), and the WHOLE scene walked on the literal divisions, its lean node steps sitting idle (round 3's "-11 % out of cache").
-    {
-        auto coord_ok = [](float b) {
-            uint32_t u = pn_bits(b) & 0x7fffffffu, e = u >> 23;
-            return u == 0u || (e >= 127u - 60u && e <= 127u + 40u);
-        };
-        bool ok = true;
-        for (uint32_t i = 0; i < d->n_tlas_nodes && ok; ++i)
-            for (int a = 0; a < 3; ++a) ok = ok && coord_ok(d->tlas_nodes[i].min[a]) && coord_ok(d->tlas_nodes[i].max[a]);
-        for (uint32_t i = 0; i < d->n_blas_nodes && ok; ++i)
-            for (int a = 0; a < 3; ++a) ok = ok && coord_ok(d->blas_nodes[i].min[a]) && coord_ok(d->blas_nodes[i].max[a]);
-        S.fast_slab = ok ? 1u : 0u;
-    }
-    S.exact_extent = exact_extent ? 1u : 0u;
-    uint32_t wide_levels = 0;  // wide nodes on the longest way down a BLAS (0: no wide nodes were built)
-    uint64_t walk_bytes = 0;   // what the walks read: nodes, wide nodes, triangle vertices, instance records
-    size_t n_scene_nodes = 0;  // DevScene::nodes: TLAS + its leaf copies + every BLAS
-    {
-        // DevScene::nodes: the TLAS, then its leaves alone in pre-order when the TLAS is small (the shared scan), then every
-        // BLAS, in one array with absolute links — a walk reads nodes + index whatever tree it is in.
-        const bool scan = d->n_instances >= PBRS_FLAT_TLAS_MIN && d->n_instances <= PBRS_FLAT_TLAS_MAX_ANYHIT;
-        std::vector<pbrs_node> nodes(d->tlas_nodes, d->tlas_nodes + d->n_tlas_nodes);
-        S.flat_off = (uint32_t)nodes.size();
-        if (scan)
-            for (uint32_t i = 0; i < d->n_tlas_nodes; ++i)
-                if (d->tlas_nodes[i].b & PBRS_LEAF_FLAG) nodes.push_back(d->tlas_nodes[i]);
-        S.n_flat = (uint32_t)nodes.size() - S.flat_off;
-        const uint64_t blas_off = nodes.size();
-        if (blas_off + d->n_blas_nodes > 0x7fffffffull) return fail(c, PBRS_E_LIMIT, "too many BVH nodes");
-        nodes.insert(nodes.end(), d->blas_nodes, d->blas_nodes + d->n_blas_nodes);
-        for (size_t i = blas_off; i < nodes.size(); ++i)
-            if (!(nodes[i].b & PBRS_LEAF_FLAG)) nodes[i].a += (uint32_t)blas_off;  // right child; the left one is i + 1
-        if (nodes.size() * sizeof(pbrs_node) >= (1ull << 32)) return fail(c, PBRS_E_LIMIT, "too many BVH nodes (the walks address them with 32-bit byte offsets)");
-        if ((rc = upload(c, nodes.data(), nodes.size(), &S.nodes))) return rc;
-        n_scene_nodes = nodes.size();
-        walk_bytes = nodes.size() * sizeof(pbrs_node) + (uint64_t)d->n_triangles * sizeof(pbrs_tri_verts) + (uint64_t)d->n_instances * sizeof(pbrs_instance);
-        std::vector<pbrs_instance> inst(d->instances, d->instances + d->n_instances);
-        // Shading classes: one per distinct lobe signature among the materials (class 0: no lobes — emitters — and misses)
-        std::vector<uint32_t> mat_class(d->n_materials, 0u);
-        {
-            std::vector<std::string> sigs;
-            for (uint32_t m = 0; m < d->n_materials; ++m) {
-                const pbrs_material& mt = d->materials[m];
-                if (mt.n_bxdfs == 0) continue;
-                std::string sig;
-                for (uint32_t k = 0; k < mt.n_bxdfs; ++k) {
-                    const pbrs_bxdf& bx = d->bxdfs[mt.first_bxdf + k];
-                    sig += (char)('a' + bx.kind);
-                    sig += (char)('a' + (bx.kind == PBRS_BXDF_SPECULAR ? bx.intrusion : 0u));
-                    sig += (char)('a' + (bx.kind == PBRS_BXDF_DIFFUSE ? bx.oren_nayar : bx.fresnel));
-                    sig += (char)('a' + (bx.kind == PBRS_BXDF_MICROFACET && bx.alpha_x != bx.alpha_y ? 1 : 0));
-                    sig += bx.tex ? 't' : '-';
-                }
-                size_t at = 0;
-                while (at < sigs.size() && sigs[at] != sig) ++at;
-                if (at == sigs.size()) sigs.push_back(sig);
-                mat_class[m] = (uint32_t)std::min<size_t>(at + 1, PBRS_MAX_CLASSES - 1);
-            }
-            S.n_classes = (uint32_t)std::min<size_t>(sigs.size(), PBRS_MAX_CLASSES - 1);
-            // the class of the materials that are one untextured Lambertian DiffuseReflect (signature: kind 1, not Oren-Nayar)
-            const std::string lam_sig = {(char)('a' + PBRS_BXDF_DIFFUSE), 'a', 'a', 'a', '-'};
-            for (size_t at = 0; at < sigs.size() && at + 1 < PBRS_MAX_CLASSES - 1; ++at)
-                if (sigs[at] == lam_sig) f.lambert_class = (uint32_t)at + 1;
-            // ... and of the materials that are one Fourier BSDF (material/src/lib.rs:451-475: whatever their tables, one signature)
-            const std::string fou_sig = {(char)('a' + PBRS_BXDF_FOURIER), 'a', 'a', 'a', '-'};
-            for (size_t at = 0; at < sigs.size() && at + 1 < PBRS_MAX_CLASSES - 1; ++at)
-                if (sigs[at] == fou_sig) f.fourier_class = (uint32_t)at + 1;
-        }
-        for (pbrs_instance& in : inst) {
-            in.pad[0] = mat_class[in.material];
-            if (in.shape_kind == PBRS_SHAPE_MESH) in.blas_root += (uint32_t)blas_off;
-            bool linear_identity = true;  // bit patterns: -0.0 would not do
-            for (int r = 0; r < 3; ++r)
-                for (int k = 0; k < 3; ++k) linear_identity = linear_identity && pn_bits(in.inv[r][k]) == pn_bits(r == k ? 1.0f : 0.0f);
-            in.flags &= ~PBRS_INSTANCE_TRANSLATION;
-            if (linear_identity) in.flags |= PBRS_INSTANCE_TRANSLATION;
-        }
-        // Four-wide nodes over every BLAS a mesh instance enters (device/wide.h): pad[1] of the device copy of the instance is
-        // the wide node of its root, PBRS_WREF_NONE where the mesh is a single leaf.  Built and uploaded only for scenes whose
-        // k_shadow can walk them: a scanned TLAS and coordinates inside the guarded range of the division-free box test (the
-        // deciding PBRS_WIDE_MIN_LEVELS is known once they are built).  A wide array of 4 GiB or more (32-bit byte offsets) is not
-        // an error: the scene keeps the binary walks.
-        for (pbrs_instance& in : inst) in.pad[1] = PBRS_WREF_NONE;
-        S.wide_cap = 4u;
-        if (scan && S.fast_slab != 0u) {
-            std::vector<pbrs_wnode> wide;
-            std::map<uint32_t, uint32_t> wide_of_root;
-            uint32_t levels = 0;
-            for (pbrs_instance& in : inst) {
-                if (in.shape_kind != PBRS_SHAPE_MESH || (nodes[in.blas_root].b & PBRS_LEAF_FLAG)) continue;
-                auto it = wide_of_root.find(in.blas_root);
-                if (it == wide_of_root.end()) it = wide_of_root.emplace(in.blas_root, build_wide(nodes, in.blas_root, wide, 0u, levels)).first;
-                in.pad[1] = it->second;
-            }
-            const bool use = levels >= PBRS_WIDE_MIN_LEVELS && wide.size() * sizeof(pbrs_wnode) < (1ull << 32);
-            if (use) {
-                const pbrs_wnode* dev = nullptr;
-                if ((rc = upload(c, wide.data(), wide.size(), &dev))) return rc;
-                S.wnodes = dev;
-                walk_bytes += wide.size() * sizeof(pbrs_wnode);
-                // a node step pushes up to three survivors per level; deeper stacks than PBRS_WIDE_STACK_MAX entries are not given LDS:
-                // a ray that would need one (none on the BASELINE scenes) is traced by the binary-walk kernel instead
-                S.wide_cap = std::max(4u, std::min(3u * levels + 1u, (uint32_t)PBRS_WIDE_STACK_MAX));
-                wide_levels = levels;
-            } else {
-                for (pbrs_instance& in : inst) in.pad[1] = PBRS_WREF_NONE;
-            }
-        }
-        if ((rc = upload(c, inst.data(), inst.size(), &S.inst))) return rc;
-    }
+    if ((rc = upload(c, P.nodes.data(), P.nodes.size(), &S.nodes))) return rc;
+    if (!P.wide.empty() && (rc = upload(c, P.wide.data(), P.wide.size(), &S.wnodes))) return rc;
+    if ((rc = upload(c, P.inst.data(), P.inst.size(), &S.inst))) return rc;
     if ((rc = upload(c, d->shapes, d->n_shapes, &S.shapes))) return rc;
     if ((rc = upload(c, d->meshes, d->n_meshes, &S.meshes))) return rc;
     if ((rc = upload(c, d->tri_verts, d->n_triangles, &S.tv))) return rc;
@@ -1648,96 +1216,23 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     if ((rc = upload(c, d->bxdfs, d->n_bxdfs, &S.bxdfs))) return rc;
     if ((rc = upload(c, d->area_lights, d->n_area_lights, &S.alights))) return rc;
     if ((rc = upload(c, d->delta_lights, d->n_delta_lights, &S.dlights))) return rc;
-    S.n_area = d->n_area_lights;
-    S.n_delta = d->n_delta_lights;
     if ((rc = upload(c, d->textures, d->n_textures, &S.textures))) return rc;
     if ((rc = upload(c, d->tex_floats, d->n_tex_floats, &S.tex_floats))) return rc;
     if ((rc = upload(c, d->tex_words, d->n_tex_words, &S.tex_words))) return rc;
     if ((rc = upload(c, d->fourier_tables, d->n_fourier_tables, &S.fourier))) return rc;
-    S.env_kind = d->env_kind;
-    S.env_texture = d->env_texture;
-    std::memcpy(S.env_scale, d->env_scale, sizeof S.env_scale);
-    std::memcpy(S.env, d->env_constant, sizeof S.env);
-    // Scene::has_env_light for EnvLight::Constant (scene/src/lib.rs:96-102): !c.is_black()
-    S.has_env = (d->env_kind != PBRS_ENV_CONSTANT || !(S.env[0] <= 0.0f && S.env[1] <= 0.0f && S.env[2] <= 0.0f)) ? 1u : 0u;
-    S.refill_below = max_blas_height >= PBRS_LONG_WALK_HEIGHT ? PBRS_REFILL_BELOW_LONG : PBRS_REFILL_BELOW_SHORT;
-    S.refill_below_shadow = max_blas_height >= PBRS_LONG_WALK_HEIGHT ? PBRS_REFILL_BELOW_LONG_SHADOW : PBRS_REFILL_BELOW_SHORT;
-    if (c->dev.refill_below) S.refill_below = S.refill_below_shadow = *c->dev.refill_below;
-    // long walks: the levels a ray actually walks — the deepest BLAS, plus the TLAS where it is not scanned
-    f.long_walks = (S.n_flat ? 0u : tlas_levels) + max_blas_height >= PBRS_LONG_WALK_HEIGHT;
-    // lean further node steps for rays on the division-free box test; a scene whose coordinates leave its guarded range walks every
-    // ray on the literal divisions, which the lean steps do not carry: full steps (kernels.h)
-    f.full_steps = S.fast_slab == 0u;
-    c->overlap_from = c->dev.overlap_from.value_or(walk_bytes <= (4ull << 20) ? 2u : 4u);  // one XCD's L2 holds the arrays the walks read, or not (pbrs_ctx::overlap_from)
-    // the leaf copies serve k_shadow up to PBRS_FLAT_TLAS_MAX_ANYHIT instances, k_extend up to PBRS_FLAT_TLAS_MAX
-    f.tlas_scanned = S.n_flat != 0u;
-    S.features = (S.n_flat != 0u && d->n_instances <= PBRS_FLAT_TLAS_MAX) ? PBRS_FEAT_FLAT_TLAS : 0u;
-    // the walks over four-wide nodes: scenes whose TLAS the stage scans and whose coordinates admit the division-free box test
-    // ... and that have a BLAS deep enough for it to matter (PBRS_WIDE_MIN_LEVELS wide nodes on the way down: meshes of a few
-    // triangles are a leaf or two, where the binary walks at their six waves per SIMD are faster — C2: 105 against 140 ms)
-    // k_shadow gains (C4: 250 -> 236 ms per frame at five waves per SIMD); k_extend keeps the binary walk (a four-wide closest-hit
-    // walk needed 117 registers, four waves per SIMD, and lost against the binary walk at six: 459 -> 506 ms)
-    f.wide_ok = S.fast_slab != 0u && S.wnodes != nullptr && wide_levels >= PBRS_WIDE_MIN_LEVELS;
-    for (uint32_t i = 0; i < d->n_instances; ++i) {
-        const pbrs_instance& in = d->instances[i];
-        if (in.shape_kind == PBRS_SHAPE_MESH) {
-            if (!(in.mesh_flags & PBRS_MESH_SHADING_OK_MASK)) S.features |= PBRS_FEAT_SHADING_CHECK;
-        } else if (in.shape_kind != PBRS_SHAPE_TRIANGLE) {  // isolated triangles go through the triangle-record path
-            S.features |= PBRS_FEAT_ANALYTIC;
-        }
-    }
-    f.features = S.features;
-    f.exact_extent = exact_extent;
-    f.n_classes = S.n_classes;
-    f.textured = textured;
-    f.fourier = fourier;
-    // k_shade specialisation: every lobe an untextured Lambertian DiffuseReflect (at most one per material); every area light
-    // of one shape
-    f.lambert = !textured;
-    for (uint32_t i = 0; i < d->n_materials && f.lambert; ++i) {
-        const pbrs_material& m = d->materials[i];  // its lobes only: the array also holds the visualisers' records
-        f.lambert = m.n_bxdfs <= 1;
-        for (uint32_t k = 0; k < m.n_bxdfs && f.lambert; ++k) {
-            const pbrs_bxdf& bx = d->bxdfs[m.first_bxdf + k];
-            f.lambert = bx.kind == PBRS_BXDF_DIFFUSE && bx.oren_nayar == 0 && bx.tex == 0;
-        }
-    }
-    if (d->n_area_lights) {
-        const uint32_t k0 = d->area_lights[0].shape_kind;
-        bool same = true;
-        for (uint32_t i = 1; i < d->n_area_lights; ++i) same = same && d->area_lights[i].shape_kind == k0;
-        if (same && k0 == PBRS_SHAPE_SPHERE) f.light_spec = PBRS_SHADE_LIGHT_SPHERE;
-        if (same && k0 == PBRS_SHAPE_TRIANGLE) f.light_spec = PBRS_SHADE_LIGHT_TRIANGLE;
-    }
-    // what the traversal kernels may stage in LDS next to the stack rows (plan_kernels)
-    f.stack_bytes = (size_t)depth * kBlock * sizeof(uint32_t);
-    f.wide_stack_bytes = (size_t)S.wide_cap * kBlock * sizeof(uint32_t);
-    f.scene_bytes = n_scene_nodes * sizeof(pbrs_node) + (size_t)d->n_triangles * sizeof(pbrs_tri_verts) + (size_t)d->n_instances * sizeof(pbrs_instance) +
-                    (size_t)d->n_shapes * sizeof(pbrs_shape);
-    f.top_bytes = (size_t)d->n_tlas_nodes * sizeof(pbrs_node);
-    // k_shade: the shading records (instances, shapes, materials, lobes, lights) in LDS where they are a few KB, the triangle records
-    // too where everything is (kernels.h, stage_shade_scene); five blocks of the Lambert variants share a CU's 160 KB with the rest
-    {
-        S.n_inst = d->n_instances; S.n_shapes = d->n_shapes; S.n_tris = d->n_triangles; S.n_mats = d->n_materials; S.n_bxdfs = d->n_bxdfs;
-        f.shade_rec_bytes = (size_t)d->n_instances * sizeof(pbrs_instance) + (size_t)d->n_shapes * sizeof(pbrs_shape) + (size_t)d->n_materials * sizeof(pbrs_material) +
-                            (size_t)d->n_bxdfs * sizeof(pbrs_bxdf) + (size_t)d->n_area_lights * sizeof(pbrs_area_light) + (size_t)d->n_delta_lights * sizeof(pbrs_delta_light);
-        f.shade_tri_bytes = (size_t)d->n_triangles * (sizeof(pbrs_tri_verts) + sizeof(pbrs_tri_shade));
-        const size_t budget = 16u << 10;
-        f.shade_lds = f.shade_rec_bytes + f.shade_tri_bytes <= budget ? (PBRS_SHADE_LDS_RECORDS | PBRS_SHADE_LDS_TRIS) : f.shade_rec_bytes <= budget ? PBRS_SHADE_LDS_RECORDS : 0u;
-    }
-    if (!plan_kernels(f, c->dev, c->plan)) return fail(c, PBRS_E_DEVICE, "no kernel instantiation for this scene's feature set");
     // what the plan's traversal kernels stage (kernels.h, stage_scene / stage_top)
-    const bool lds_scene = c->plan.lds_staging == PBRS_FEAT_LDS_SCENE;
-    S.lds_off_words = depth * kBlock;
-    S.lds_nodes = lds_scene ? (uint32_t)n_scene_nodes : c->plan.lds_staging == PBRS_FEAT_LDS_TOP ? d->n_tlas_nodes : 0u;
+    const bool lds_scene = plan.lds_staging == PBRS_FEAT_LDS_SCENE;
+    S.lds_off_words = P.stack_depth * kBlock;
+    S.lds_nodes = lds_scene ? (uint32_t)P.nodes.size() : plan.lds_staging == PBRS_FEAT_LDS_TOP ? d->n_tlas_nodes : 0u;
     S.lds_tris = lds_scene ? d->n_triangles : 0u;
     S.lds_inst = lds_scene ? d->n_instances : 0u;
     S.lds_shapes = lds_scene ? d->n_shapes : 0u;
     c->S = S;
-    c->has_vis_records = vis_records;
-    c->stack_depth = depth;
+    c->overlap_from = c->dev.overlap_from.value_or(P.walk_bytes <= (4ull << 20) ? 2u : 4u);  // one XCD's L2 holds the arrays the walks read, or not (pbrs_ctx::overlap_from)
+    c->has_vis_records = P.has_vis_records;
+    c->stack_depth = P.stack_depth;
     c->has_scene = true;
-    c->split_decision = 0;  // (the stream was synchronised above: no probe of the previous scene is in flight)
+    c->split_decision = 0;  // (the streams were synchronised above: no probe of the previous scene is in flight)
     c->split_probe_in_flight = false;
     return PBRS_OK;
 }
