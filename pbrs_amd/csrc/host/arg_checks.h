@@ -1,0 +1,63 @@
+// host/arg_checks.h — the argument checks of the C ABI's render and image-space entry points (include/pbrs_gpu.h): plain C++, no HIP
+// header and no pbrs_ctx, so that tests/arg_checks_check.cpp runs every refusal on a CPU under AddressSanitizer.
+//
+// A check reads its arguments and nothing else: it dereferences the parameter structs and the selection of check_matte_mask, never an
+// image plane.  It returns the first refusal in the order of its source lines, or `{PBRS_OK, nullptr}`.  pbrs_gpu.hip turns a refusal
+// into the entry point's return code and pbrs_last_error (`fail`) before it touches the device.
+#pragma once
+#include <cstdint>
+
+#include "../../../include/pbrs_gpu.h"
+
+namespace pbrs {
+
+struct Refusal {
+    int code = PBRS_OK;             // PBRS_OK, or the code the entry point returns
+    const char* message = nullptr;  // ... and its pbrs_last_error
+};
+
+constexpr uint32_t kMaxDepth = 64;  // bounces a render may ask for (check_params); sizes the per-bounce counters of pbrs_gpu.hip
+
+// ---- renders ----
+// What check_params needs to know of the context.
+struct SceneState {
+    bool has_scene = false;
+    bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
+};
+Refusal check_params(const SceneState& s, const pbrs_camera* cam, const pbrs_render_params* p);
+
+// What a render is to produce beside the image, as far as check_targets cares.
+struct WantedOutputs {
+    bool aovs = false, variance = false, passes = false;
+    bool matte = false;                               // a matte, with:
+    const pbrs_matte_params* matte_params = nullptr;  // ... its parameters (required)
+    bool matte_ids_and_coverage = false;              // ... both required buffers are given
+};
+// `p` has passed check_params.
+Refusal check_targets(const pbrs_render_params* p, const WantedOutputs& t);
+// A filtered render of the tile `p` (which has passed check_params) through `f` (not null).  The traced region, the tile plus its
+// halo, is the caller's to compute and to pass through check_params again.
+Refusal check_filter(const pbrs_render_params* p, const pbrs_pixel_filter* f);
+
+// ---- image operations ----
+Refusal check_denoise(const pbrs_denoise_params* p, const float* rgb_in, const pbrs_denoise_guides* g, const float* rgb_out);
+// The variance-guided denoiser's parameters as the plain one's: sigma_luminance in the place of sigma_color (one layout).
+pbrs_denoise_params plain_params(const pbrs_denoise_var_params& p);
+Refusal check_denoise_var(const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, const float* rgb_out);
+Refusal check_matte_mask(uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids, const float* coverage, const uint32_t* select, uint32_t n_select,
+                         const float* mask_out);
+Refusal check_combine(uint32_t w, uint32_t h, const float* direct, const float* indirect, const float* rgb_out);
+// `instance`: this frame's instance ids, which a motion table is indexed by.
+Refusal check_motion_table(const pbrs_instance_motion* motion, uint32_t n_motion, const uint32_t* instance);
+Refusal check_temporal(const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
+                       const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout);
+// check_temporal, then check_motion_table with the frame's instance ids: pbrs_temporal_accumulate_motion*.
+Refusal check_temporal_motion(const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
+                              const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout,
+                              const pbrs_instance_motion* motion, uint32_t n_motion);
+Refusal check_motion_vectors(uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth, const uint32_t* instance,
+                             const pbrs_instance_motion* motion, uint32_t n_motion, const float* motion_out);
+Refusal check_spatial_variance(const pbrs_spatial_variance_params* p, const float* moments, const float* length, const pbrs_spatial_variance_guides* g,
+                               const float* variance_in, const float* variance_out);
+
+}  // namespace pbrs

@@ -22,6 +22,7 @@
 #include "../../include/pbrs_gpu.h"
 #include "device/kernels.h"
 #include "host/scene_prepare.h"
+#include "host/arg_checks.h"
 #include "device/aov.h"
 #include "device/film.h"
 #include "device/denoise.h"
@@ -31,11 +32,10 @@
 #include "device/temporal.h"
 #include "device/spatial_variance.h"
 
-using namespace pbrs;  // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h)
+using namespace pbrs;  // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h) and argument checks (host/arg_checks.h)
 
 namespace {
 
-constexpr uint32_t kMaxDepth = 64;
 constexpr uint32_t kHeadWords = PBRS_WORK_HEADS * PBRS_WORK_HEAD_STRIDE;
 // per bounce: act, ns (u64), the slow-list length of k_shadow; then three sets of work heads (the two stages, and the binary-walk
 // launch that works off k_shadow's slow list)
@@ -250,6 +250,17 @@ int fail(pbrs_ctx* c, int code, const char* msg) {
     c->error = msg;
     return code;
 }
+// The verdict of a check of host/arg_checks.h as an entry point returns it.
+int fail(pbrs_ctx* c, const Refusal& r) { return r.code ? fail(c, r.code, r.message) : PBRS_OK; }
+
+// How every image operation begins: no context, the refusal of its check (which has touched neither context nor device), and only
+// then the context's device.
+int enter(pbrs_ctx* c, const Refusal& r) {
+    if (!c) return PBRS_E_INVALID;
+    if (r.code) return fail(c, r);
+    HIPCHK(c, hipSetDevice(c->device));
+    return PBRS_OK;
+}
 
 template <class T>
 int upload(pbrs_ctx* c, const T* src, size_t n, const T** dst) {
@@ -382,40 +393,58 @@ int ensure_direct(pbrs_ctx* c, int k, size_t n_slots, bool wanted) {
     return PBRS_OK;
 }
 
-// One buffer of a host variant's device staging: the caller's host pointer (null: not given, or not wanted), its words per pixel, and
-// where `stage` put it on the device (null with the host pointer).
+// One plane of a host variant's device staging: the host memory copied up into it before the launches (`up`; null: not given), its
+// words per pixel, the host memory it is copied back to after them (`down`; null: not wanted), and where `stage` put it on the device
+// (null where neither is given).  A result that lands in an input's place is one row with both.
 struct Staged {
-    const void* host;
+    const void* up;
     size_t words;
+    void* down = nullptr;
     void* dev = nullptr;
     template <class T>
     T* as() const { return static_cast<T*>(dev); }
 };
 
-// Lays the n buffers of `s` out in `buf`, one after the other in the order of `s`, for P pixels.  `buf` is grown to hold all n, given or
-// not: neither its size nor where a buffer sits depends on which ones a call asks for.  The allocation, the device pointers and
+// Lays the planes of `s` out in `buf`, one after the other in the order of `s`, for P pixels.  `buf` is grown to hold all of them, given
+// or not: neither its size nor where a plane sits depends on which ones a call asks for.  The allocation, the device pointers and
 // (copy_staged) the copies all follow from the words per pixel in `s`.
-int stage(pbrs_ctx* c, DeviceBuffer& buf, const char* what, Staged* s, size_t n, size_t P) {
+template <size_t N>
+int stage(pbrs_ctx* c, BufferId id, const char* what, Staged (&s)[N], size_t P) {
     size_t words = 0;
-    for (size_t k = 0; k < n; ++k) words += s[k].words;
+    for (const Staged& r : s) words += r.words;
+    DeviceBuffer& buf = c->buf[id];
     int rc = buf.grow(c, words * P * sizeof(uint32_t), what);
     if (rc) return rc;
     uint32_t* at = buf.as<uint32_t>();
-    for (size_t k = 0; k < n; ++k) {
-        s[k].dev = s[k].host ? at : nullptr;
-        at += s[k].words * P;
+    for (Staged& r : s) {
+        r.dev = (r.up || r.down) ? at : nullptr;
+        at += r.words * P;
     }
     return PBRS_OK;
 }
 
-// The given buffers of `s` to the device (hipMemcpyHostToDevice) or back to the host, on the context's stream.
-int copy_staged(pbrs_ctx* c, const Staged* s, size_t n, size_t P, hipMemcpyKind kind) {
-    for (size_t k = 0; k < n; ++k) {
-        if (!s[k].host) continue;
-        void* host = const_cast<void*>(s[k].host);
+// The planes of `s` that have an `up` to the device (hipMemcpyHostToDevice), or those that have a `down` back to the host, in the order of
+// `s` on the context's stream.
+template <size_t N>
+int copy_staged(pbrs_ctx* c, const Staged (&s)[N], size_t P, hipMemcpyKind kind) {
+    for (const Staged& r : s) {
         const bool up = kind == hipMemcpyHostToDevice;
-        HIPCHK(c, hipMemcpyAsync(up ? s[k].dev : host, up ? host : s[k].dev, s[k].words * P * sizeof(uint32_t), kind, c->stream));
+        if (!(up ? r.up != nullptr : r.down != nullptr)) continue;
+        HIPCHK(c, hipMemcpyAsync(up ? r.dev : r.down, up ? r.up : r.dev, r.words * P * sizeof(uint32_t), kind, c->stream));
     }
+    return PBRS_OK;
+}
+
+// A host variant of an image operation, whole: lay `s` out in the operation's staging buffer, copy the given inputs up, queue the
+// operation's launches on the staged planes (`launch`, which reads the device pointers from `s`), copy the wanted outputs back, and wait.
+template <size_t N, class Launch>
+int run_staged(pbrs_ctx* c, BufferId id, const char* what, Staged (&s)[N], size_t P, Launch launch) {
+    int rc = stage(c, id, what, s, P);
+    if (!rc) rc = copy_staged(c, s, P, hipMemcpyHostToDevice);
+    if (!rc) rc = launch();
+    if (!rc) rc = copy_staged(c, s, P, hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
 
@@ -432,7 +461,7 @@ struct RenderTargets {
     const pbrs_matte_params* matte = nullptr;
     pbrs_matte_buffers matte_out{};
     pbrs_pass_buffers passes{};  // the light passes wanted (all null: none), from the state in BUF_PASS_STATE
-    // a filtered render: the params are then its traced region (check_filter) and the pass is folded into BUF_FILTER_SUM
+    // a filtered render: the params are then its traced region (filter_setup) and the pass is folded into BUF_FILTER_SUM
     const FilterConst* filt = nullptr;
 
     bool want_aovs() const {
@@ -440,32 +469,14 @@ struct RenderTargets {
         return a.albedo || a.normal || a.coverage || a.depth || a.instance || a.material || a.prim;
     }
     bool want_passes() const { return passes.direct || passes.indirect || passes.direct_variance || passes.indirect_variance; }
+    // as check_targets reads them (host/arg_checks.h)
+    WantedOutputs wanted() const { return {want_aovs(), variance != nullptr, want_passes(), want_matte, matte, matte_out.ids && matte_out.coverage}; }
 };
 
 uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p, bool with_direct);
 
-int check_params(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p) {
-    if (!cam || !p) return fail(c, PBRS_E_INVALID, "null camera or params");
-    if (!c->has_scene) return fail(c, PBRS_E_NO_SCENE, "no scene uploaded");
-    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty tile");
-    if (p->band_count > 1) {
-        if (p->band_rows == 0 || p->band_index >= p->band_count) return fail(c, PBRS_E_INVALID, "bad row-band parameters");
-        uint64_t vr = p->h - 1;
-        uint64_t last = p->y0 + ((vr / p->band_rows) * p->band_count + p->band_index) * (uint64_t)p->band_rows + vr % p->band_rows;
-        if (p->x0 + p->w > cam->width || last >= cam->height) return fail(c, PBRS_E_INVALID, "row bands outside the film");
-    } else if (p->x0 + p->w > cam->width || p->y0 + p->h > cam->height) {
-        return fail(c, PBRS_E_INVALID, "tile outside the film");
-    }
-    if (p->strata_x == 0 || p->strata_y == 0) return fail(c, PBRS_E_INVALID, "zero strata");
-    if (p->max_depth > kMaxDepth) return fail(c, PBRS_E_LIMIT, "max_depth above 64");
-    if (p->integrator > PBRS_INTEGRATOR_NORMALS) return fail(c, PBRS_E_INVALID, "unknown integrator");
-    if (p->integrator >= PBRS_INTEGRATOR_MATERIALS && (p->strata_x != 1 || p->strata_y != 1))
-        return fail(c, PBRS_E_INVALID, "a visualiser takes one un-jittered ray per pixel (strata 1 x 1)");
-    if (p->integrator == PBRS_INTEGRATOR_NORMALS && !c->has_vis_records)
-        return fail(c, PBRS_E_INVALID, "the scene's materials carry no pbrs_material::vis_bxdf records");
-    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "tile above 2^28 pixels");
-    return PBRS_OK;
-}
+// What check_params (host/arg_checks.h) needs to know of the context.
+SceneState scene_state(const pbrs_ctx* c) { return {c->has_scene, c->has_vis_records}; }
 
 // The samples per pass of a render of `p` (checked by check_params), from the memory that is free on the current device NOW: whatever the
 // call allocates beside the path state comes first.  `with_direct`: every path carries a record of the D column as well (light passes).
@@ -936,40 +947,11 @@ int configure_kernels(pbrs_ctx* c) {
     return PBRS_OK;
 }
 
-// The checks of what a render is to produce, beyond check_params's.
-int check_targets(pbrs_ctx* c, const pbrs_render_params* p, const RenderTargets& t) {
-    // a render that traces no camera ray has no first hits to report
-    const bool no_camera_ray = p->integrator <= PBRS_INTEGRATOR_DIRECT && p->max_depth == 0;
-    if ((t.want_aovs() || t.variance) && no_camera_ray)
-        return fail(c, PBRS_E_INVALID, "AOVs requested from a render that traces no camera ray (max_depth 0)");
-    if (t.want_passes()) {
-        if (p->integrator != PBRS_INTEGRATOR_PATH)
-            return fail(c, PBRS_E_INVALID, "light passes need the path integrator (the direct integrator has its own depth semantics, the visualisers bypass the film)");
-        if (p->max_depth == 0) return fail(c, PBRS_E_INVALID, "light passes requested from a render that traces no camera ray (max_depth 0)");
-    }
-    if (!t.want_matte) return PBRS_OK;
-    const pbrs_matte_params* mp = t.matte;
-    if (!mp) return fail(c, PBRS_E_INVALID, "a matte without pbrs_matte_params");
-    if (mp->key != PBRS_MATTE_INSTANCE && mp->key != PBRS_MATTE_MATERIAL) return fail(c, PBRS_E_INVALID, "unknown matte key");
-    if (mp->slots == 0 || mp->slots > PBRS_MATTE_MAX_SLOTS) return fail(c, PBRS_E_INVALID, "matte slots must be 1 .. 8");
-    if (!t.matte_out.ids || !t.matte_out.coverage) return fail(c, PBRS_E_INVALID, "a matte needs ids and coverage");
-    if (no_camera_ray) return fail(c, PBRS_E_INVALID, "a matte requested from a render that traces no camera ray (max_depth 0)");
-    return PBRS_OK;
-}
-
-// The checks of a filtered render beyond check_params's; fills the kernel's constants and `region`, the tile plus its halo clipped to
-// the film: the params the render traces (the pass size and ensure_work see the region).
-int check_filter(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, FilterConst& fc, pbrs_render_params& region) {
-    if (p->band_count > 1) return fail(c, PBRS_E_INVALID, "a filtered render takes a rectangular tile, not interleaved row bands");
-    if (p->integrator >= PBRS_INTEGRATOR_MATERIALS) return fail(c, PBRS_E_INVALID, "the visualisers bypass the film: no pixel filter");
-    if (f->kind > PBRS_FILTER_LANCZOS) return fail(c, PBRS_E_INVALID, "unknown pixel filter kind");
-    for (int a = 0; a < 2; ++a)
-        if (!pn_isfinite(f->radius[a]) || !(f->radius[a] > 0.0f)) return fail(c, PBRS_E_INVALID, "a pixel filter radius must be finite and > 0");
-    const uint32_t n_params = f->kind == PBRS_FILTER_MITCHELL ? 2u : (f->kind == PBRS_FILTER_GAUSSIAN || f->kind == PBRS_FILTER_LANCZOS) ? 1u : 0u;
-    if ((n_params > 0 && !pn_isfinite(f->a)) || (n_params > 1 && !pn_isfinite(f->b)))
-        return fail(c, PBRS_E_INVALID, "non-finite pixel filter parameter");
-    if (f->radius[0] > PBRS_FILTER_MAX_RADIUS || f->radius[1] > PBRS_FILTER_MAX_RADIUS)
-        return fail(c, PBRS_E_LIMIT, "pixel filter radius above 4 (the halo's LDS budget)");
+// A filtered render beyond check_params: check_filter's refusals (host/arg_checks.h), then the kernel's constants and `region`, the tile
+// plus its halo clipped to the film: the params the render traces (the pass size and ensure_work see the region), checked in their turn.
+int filter_setup(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, const pbrs_pixel_filter* f, FilterConst& fc, pbrs_render_params& region) {
+    const int rc = fail(c, check_filter(p, f));
+    if (rc) return rc;
     fc = FilterConst{};
     fc.kind = f->kind;
     fc.rx = f->radius[0], fc.ry = f->radius[1], fc.a = f->a, fc.b = f->b;
@@ -980,7 +962,7 @@ int check_filter(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* 
     region.y0 = p->y0 > fc.hy ? p->y0 - fc.hy : 0u;
     region.w = std::min(p->x0 + p->w + fc.hx, cam->width) - region.x0;
     region.h = std::min(p->y0 + p->h + fc.hy, cam->height) - region.y0;
-    return check_params(c, cam, &region);
+    return fail(c, check_params(scene_state(c), cam, &region));
 }
 
 // Every render entry point, after its own argument checks.  `filter`: null, or a filtered render of the tile `p`.  `t`: what the caller
@@ -990,41 +972,44 @@ int render(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, con
     HIPCHK(c, hipSetDevice(c->device));  // first: the buffers below and the pass size, which reads the free memory, are THIS device's
     FilterConst fc;
     pbrs_render_params region;
-    int rc = check_params(c, cam, p);
+    int rc = fail(c, check_params(scene_state(c), cam, p));
     if (rc) return rc;
     const size_t PT = (size_t)p->w * p->h;  // the tile's pixels
     if (filter) {
-        if ((rc = check_filter(c, cam, p, filter, fc, region))) return rc;
+        if ((rc = filter_setup(c, cam, p, filter, fc, region))) return rc;
         t.filt = &fc;
         p = &region;
     }
-    if ((rc = check_targets(c, p, t))) return rc;
+    if ((rc = fail(c, check_targets(p, t.wanted())))) return rc;
     const size_t P = (size_t)p->w * p->h;  // the pixels traced: a filtered render's region, else the tile
     // Each feature's state and, for a host render, the staging of what it writes: before the pass size reads the free memory.  The staging
-    // layouts are these tables: one buffer after the other, in the order of pbrs_aov_buffers, pbrs_matte_buffers and pbrs_pass_buffers.
+    // layouts are these tables: one buffer after the other, in the order of pbrs_aov_buffers, pbrs_matte_buffers and pbrs_pass_buffers;
+    // nothing goes up, every buffer given comes back.
     const pbrs_aov_buffers& a = t.aovs;
-    Staged aovs[] = {{a.albedo, 3}, {a.normal, 3}, {a.coverage, 1}, {a.depth, 1}, {a.instance, 1}, {a.material, 1}, {a.prim, 1}};
-    Staged variance[] = {{t.variance, 1}};
+    Staged aovs[] = {{nullptr, 3, a.albedo}, {nullptr, 3, a.normal}, {nullptr, 1, a.coverage}, {nullptr, 1, a.depth}, {nullptr, 1, a.instance},
+                     {nullptr, 1, a.material}, {nullptr, 1, a.prim}};
+    Staged variance[] = {{nullptr, 1, t.variance}};
     const size_t slots = t.want_matte ? t.matte->slots : 0;
-    Staged matte[] = {{t.matte_out.ids, slots}, {t.matte_out.coverage, slots}, {t.matte_out.residual, 1}};
-    Staged passes[] = {{t.passes.direct, 3}, {t.passes.indirect, 3}, {t.passes.direct_variance, 1}, {t.passes.indirect_variance, 1}};
+    Staged matte[] = {{nullptr, slots, t.matte_out.ids}, {nullptr, slots, t.matte_out.coverage}, {nullptr, 1, t.matte_out.residual}};
+    Staged passes[] = {{nullptr, 3, t.passes.direct}, {nullptr, 3, t.passes.indirect}, {nullptr, 1, t.passes.direct_variance},
+                       {nullptr, 1, t.passes.indirect_variance}};
     float* const rgb_host = t.rgb;
     if (t.filt) rc = c->buf[BUF_FILTER_SUM].grow(c, 4 * PT * sizeof(float), "the filter sums");
     if (t.want_aovs()) {
         if (!rc) rc = c->buf[BUF_AOV_STATE].grow(c, PBRS_AOV_STATE_WORDS * P * sizeof(float), "the AOV state");
-        if (!rc && host) rc = stage(c, c->buf[BUF_AOV_OUT], "the AOV buffers", aovs, std::size(aovs), P);
+        if (!rc && host) rc = stage(c, BUF_AOV_OUT, "the AOV buffers", aovs, P);
     }
     if (t.variance) {
         if (!rc) rc = c->buf[BUF_MOMENT_STATE].grow(c, PBRS_MOMENT_STATE_WORDS * P * sizeof(float), "the variance AOV's moments");
-        if (!rc && host) rc = stage(c, c->buf[BUF_VARIANCE_OUT], "the variance buffer", variance, std::size(variance), P);
+        if (!rc && host) rc = stage(c, BUF_VARIANCE_OUT, "the variance buffer", variance, P);
     }
     if (t.want_matte) {
         if (!rc) rc = c->buf[BUF_MATTE_STATE].grow(c, PBRS_MATTE_STATE_WORDS(slots) * P * sizeof(uint32_t), "the matte state");
-        if (!rc && host) rc = stage(c, c->buf[BUF_MATTE_OUT], "the matte buffers", matte, std::size(matte), P);
+        if (!rc && host) rc = stage(c, BUF_MATTE_OUT, "the matte buffers", matte, P);
     }
     if (t.want_passes()) {
         if (!rc) rc = c->buf[BUF_PASS_STATE].grow(c, PBRS_PASS_STATE_WORDS * P * sizeof(float), "the light passes' state");
-        if (!rc && host) rc = stage(c, c->buf[BUF_PASS_OUT], "the light pass buffers", passes, std::size(passes), P);
+        if (!rc && host) rc = stage(c, BUF_PASS_OUT, "the light pass buffers", passes, P);
     }
     uint32_t K = 0;
     if (!rc) rc = pass_size(c, p, K, t.want_passes());
@@ -1042,10 +1027,10 @@ int render(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, con
     if (rc) return rc;
     if (!host) return stats_out ? collect(c, stats_out) : PBRS_OK;
     HIPCHK(c, hipMemcpyAsync(rgb_host, t.rgb, 3 * PT * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = copy_staged(c, variance, std::size(variance), P, hipMemcpyDeviceToHost))) return rc;
-    if ((rc = copy_staged(c, aovs, std::size(aovs), P, hipMemcpyDeviceToHost))) return rc;
-    if ((rc = copy_staged(c, matte, std::size(matte), P, hipMemcpyDeviceToHost))) return rc;
-    if ((rc = copy_staged(c, passes, std::size(passes), P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, variance, P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, aovs, P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, matte, P, hipMemcpyDeviceToHost))) return rc;
+    if ((rc = copy_staged(c, passes, P, hipMemcpyDeviceToHost))) return rc;
     return collect(c, stats_out);
 }
 
@@ -1323,36 +1308,6 @@ constexpr DenoiseKernel kDenoiseAtrous[2][2][PBRS_DENOISE_MAX_ITERATIONS] = {{PB
                                                                              {PBRS_DENOISE_ROW(false, true), PBRS_DENOISE_ROW(true, true)}};
 #undef PBRS_DENOISE_ROW
 
-int check_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in, const pbrs_denoise_guides* g, const float* rgb_out) {
-    if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
-    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty image");
-    if (p->iterations == 0 || p->iterations > PBRS_DENOISE_MAX_ITERATIONS) return fail(c, PBRS_E_INVALID, "denoise iterations must be 1 .. 6");
-    const float sigma[3] = {p->sigma_color, p->sigma_normal, p->sigma_depth};
-    for (float s : sigma)
-        if (!pn_isfinite(s) || !(s > 0.0f)) return fail(c, PBRS_E_INVALID, "a denoise sigma must be finite and > 0");
-    if (!pn_isfinite(p->albedo_floor) || !(p->albedo_floor >= 0.0f)) return fail(c, PBRS_E_INVALID, "the albedo floor must be finite and >= 0");
-    if (p->flags & ~(PBRS_DENOISE_DEMODULATE | PBRS_DENOISE_ID_STOP)) return fail(c, PBRS_E_INVALID, "unknown denoise flag bits");
-    if ((p->flags & PBRS_DENOISE_DEMODULATE) && !g->albedo) return fail(c, PBRS_E_INVALID, "PBRS_DENOISE_DEMODULATE without an albedo guide");
-    if ((p->flags & PBRS_DENOISE_ID_STOP) && !g->instance) return fail(c, PBRS_E_INVALID, "PBRS_DENOISE_ID_STOP without an instance guide");
-    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
-    return PBRS_OK;
-}
-
-// The variance-guided denoiser's parameters and guides as the plain one's: sigma_luminance in the place of sigma_color (the two
-// parameter structs have one layout), the variance left out.
-pbrs_denoise_params plain_params(const pbrs_denoise_var_params& p) {
-    return {p.w, p.h, p.iterations, p.flags, p.sigma_luminance, p.sigma_normal, p.sigma_depth, p.albedo_floor};
-}
-
-int check_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in, const pbrs_denoise_var_guides* g, const float* rgb_out) {
-    if (!p || !rgb_in || !rgb_out || !g) return fail(c, PBRS_E_INVALID, "null denoise params, image or guides");
-    if (!g->variance) return fail(c, PBRS_E_INVALID, "the variance-guided denoiser needs guides.variance");
-    // the rest is the plain denoiser's list
-    const pbrs_denoise_params q = plain_params(*p);
-    const pbrs_denoise_guides gq{g->albedo, g->normal, g->depth, g->instance};
-    return check_denoise(c, &q, rgb_in, &gq, rgb_out);
-}
-
 // The launches of one denoise on the context's stream (arguments checked, scratch there): pack, the iterations ping-pong, unpack.
 // g.variance chooses the filter: given, the variance-guided one, whose first sigma is sigma_luminance.
 int denoise_launch(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_in, const DenoiseGuides& g, float* rgb_out, float* variance_out) {
@@ -1392,68 +1347,53 @@ int grow_denoise(pbrs_ctx* c, bool var, size_t P) {
     return c->buf[BUF_DENOISE + var].grow(c, P * kDenoiseBytesPerPixel, var ? "the variance-guided denoiser's scratch" : "the denoiser's scratch");
 }
 
-// The host variants: the image and the given guides go through the denoiser's device staging (rgb in and out, the guides, variance-guided:
-// the variance in and out), and the call waits for the result.
+// The host variants: the image and the given guides go through the denoiser's device staging (the image, filtered in place; the guides;
+// variance-guided: the variance in and out — the plain denoiser's staging ends with the instance ids), and the call waits for the result.
 int denoise_staged(pbrs_ctx* c, const pbrs_denoise_params& p, const float* rgb_in_host, const DenoiseGuides& host, float* rgb_out_host,
                    float* variance_out_host) {
     const bool var = host.variance != nullptr;
     const size_t P = (size_t)p.w * p.h;
-    int rc = grow_denoise(c, var, P);
+    const int rc = grow_denoise(c, var, P);
     if (rc) return rc;
-    // the plain denoiser's staging ends with the instance ids
-    Staged s[7] = {{rgb_in_host, 3}, {host.albedo, 3}, {host.normal, 3}, {host.depth, 1}, {host.instance, 1}, {host.variance, 1}, {variance_out_host, 1}};
-    rc = stage(c, c->buf[BUF_DENOISE_STAGE + var], var ? "the variance-guided denoiser's staging" : "the denoiser's staging", s, var ? 7 : 5, P);
-    if (!rc) rc = copy_staged(c, s, 6, P, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    float* rgb = s[0].as<float>();
-    rc = denoise_launch(c, p, rgb, {s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>(), s[5].as<float>()}, rgb, s[6].as<float>());
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgb_out_host, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = copy_staged(c, s + 6, 1, P, hipMemcpyDeviceToHost))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    const size_t v = var ? 1 : 0;
+    Staged s[] = {{rgb_in_host, 3, rgb_out_host}, {host.albedo, 3}, {host.normal, 3}, {host.depth, 1}, {host.instance, 1}, {host.variance, v},
+                  {nullptr, v, variance_out_host}};
+    return run_staged(c, BufferId(BUF_DENOISE_STAGE + var), var ? "the variance-guided denoiser's staging" : "the denoiser's staging", s, P, [&] {
+        float* rgb = s[0].as<float>();
+        return denoise_launch(c, p, rgb, {s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>(), s[5].as<float>()}, rgb, s[6].as<float>());
+    });
 }
 
 }  // namespace
 
 int pbrs_denoise_device(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_device, const pbrs_denoise_guides* guides_device,
                         float* rgb_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_denoise(c, p, rgb_in_device, guides_device, rgb_out_device);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = grow_denoise(c, false, (size_t)p->w * p->h);
+    int rc = enter(c, check_denoise(p, rgb_in_device, guides_device, rgb_out_device));
+    if (!rc) rc = grow_denoise(c, false, (size_t)p->w * p->h);
     if (rc) return rc;
     const pbrs_denoise_guides& g = *guides_device;
     return denoise_launch(c, *p, rgb_in_device, {g.albedo, g.normal, g.depth, g.instance, nullptr}, rgb_out_device, nullptr);
 }
 
 int pbrs_denoise(pbrs_ctx* c, const pbrs_denoise_params* p, const float* rgb_in_host, const pbrs_denoise_guides* guides_host, float* rgb_out_host) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_denoise(c, p, rgb_in_host, guides_host, rgb_out_host);
+    const int rc = enter(c, check_denoise(p, rgb_in_host, guides_host, rgb_out_host));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const pbrs_denoise_guides& g = *guides_host;
     return denoise_staged(c, *p, rgb_in_host, {g.albedo, g.normal, g.depth, g.instance, nullptr}, rgb_out_host, nullptr);
 }
 
 int pbrs_denoise_var_device(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in_device, const pbrs_denoise_var_guides* guides_device,
                             float* rgb_out_device, float* variance_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_denoise_var(c, p, rgb_in_device, guides_device, rgb_out_device);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = grow_denoise(c, true, (size_t)p->w * p->h);
+    int rc = enter(c, check_denoise_var(p, rgb_in_device, guides_device, rgb_out_device));
+    if (!rc) rc = grow_denoise(c, true, (size_t)p->w * p->h);
     if (rc) return rc;
     return denoise_launch(c, plain_params(*p), rgb_in_device, *guides_device, rgb_out_device, variance_out_device);
 }
 
 int pbrs_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float* rgb_in_host, const pbrs_denoise_var_guides* guides_host,
                      float* rgb_out_host, float* variance_out_host) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_denoise_var(c, p, rgb_in_host, guides_host, rgb_out_host);
+    const int rc = enter(c, check_denoise_var(p, rgb_in_host, guides_host, rgb_out_host));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     return denoise_staged(c, plain_params(*p), rgb_in_host, *guides_host, rgb_out_host, variance_out_host);
 }
 
@@ -1461,19 +1401,6 @@ int pbrs_denoise_var(pbrs_ctx* c, const pbrs_denoise_var_params* p, const float*
 static_assert(sizeof(pbrs_matte_params) == 8, "pbrs_matte_params is 8 B");
 
 namespace {
-
-int check_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids, const float* coverage, const uint32_t* select, uint32_t n_select,
-                     const float* mask_out) {
-    if (!ids || !coverage || !mask_out) return fail(c, PBRS_E_INVALID, "null matte layers or mask");
-    if (w == 0 || h == 0) return fail(c, PBRS_E_INVALID, "empty image");
-    if (slots == 0 || slots > PBRS_MATTE_MAX_SLOTS) return fail(c, PBRS_E_INVALID, "matte slots must be 1 .. 8");
-    if (n_select > PBRS_MATTE_MAX_SELECT) return fail(c, PBRS_E_INVALID, "more than PBRS_MATTE_MAX_SELECT selected ids");
-    if (n_select && !select) return fail(c, PBRS_E_INVALID, "null selection");
-    for (uint32_t i = 1; i < n_select; ++i)
-        if (select[i - 1] >= select[i]) return fail(c, PBRS_E_INVALID, "the selected ids must be strictly ascending");
-    if ((uint64_t)w * h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
-    return PBRS_OK;
-}
 
 // The selection to the device and the kernel, on the context's stream (arguments checked).
 int matte_mask_launch(pbrs_ctx* c, uint32_t P, uint32_t slots, const uint32_t* ids, const float* coverage, const uint32_t* select, uint32_t n_select, float* mask) {
@@ -1492,38 +1419,22 @@ int matte_mask_launch(pbrs_ctx* c, uint32_t P, uint32_t slots, const uint32_t* i
 
 int pbrs_matte_mask_device(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_device, const float* coverage_device,
                            const uint32_t* select, uint32_t n_select, float* mask_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_matte_mask(c, w, h, slots, ids_device, coverage_device, select, n_select, mask_out_device);
+    const int rc = enter(c, check_matte_mask(w, h, slots, ids_device, coverage_device, select, n_select, mask_out_device));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     return matte_mask_launch(c, w * h, slots, ids_device, coverage_device, select, n_select, mask_out_device);
 }
 
 int pbrs_matte_mask(pbrs_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const uint32_t* ids_host, const float* coverage_host,
                     const uint32_t* select, uint32_t n_select, float* mask_out_host) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_matte_mask(c, w, h, slots, ids_host, coverage_host, select, n_select, mask_out_host);
+    const int rc = enter(c, check_matte_mask(w, h, slots, ids_host, coverage_host, select, n_select, mask_out_host));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)w * h;
-    Staged s[3] = {{ids_host, slots}, {coverage_host, slots}, {mask_out_host, 1}};  // the staging of a matte render, the mask in the residual's place
-    rc = stage(c, c->buf[BUF_MATTE_OUT], "the matte buffers", s, 3, P);
-    if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
-    if (!rc) rc = matte_mask_launch(c, (uint32_t)P, slots, s[0].as<uint32_t>(), s[1].as<float>(), select, n_select, s[2].as<float>());
-    if (!rc) rc = copy_staged(c, s + 2, 1, P, hipMemcpyDeviceToHost);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    Staged s[] = {{ids_host, slots}, {coverage_host, slots}, {nullptr, 1, mask_out_host}};  // the staging of a matte render, the mask in the residual's place
+    return run_staged(c, BUF_MATTE_OUT, "the matte buffers", s, P,
+                      [&] { return matte_mask_launch(c, (uint32_t)P, slots, s[0].as<uint32_t>(), s[1].as<float>(), select, n_select, s[2].as<float>()); });
 }
 
 namespace {
-
-int check_combine(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct, const float* indirect, const float* rgb_out) {
-    if (!direct || !indirect || !rgb_out) return fail(c, PBRS_E_INVALID, "null light passes or output");
-    if (w == 0 || h == 0) return fail(c, PBRS_E_INVALID, "empty image");
-    if ((uint64_t)w * h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
-    return PBRS_OK;
-}
 
 // The add over the 3 * P words of an image, on the context's stream (arguments checked).
 int combine_launch(pbrs_ctx* c, size_t P, const float* direct, const float* indirect, float* rgb_out) {
@@ -1537,29 +1448,18 @@ int combine_launch(pbrs_ctx* c, size_t P, const float* direct, const float* indi
 }  // namespace
 
 int pbrs_combine_passes_device(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct_device, const float* indirect_device, float* rgb_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_combine(c, w, h, direct_device, indirect_device, rgb_out_device);
+    const int rc = enter(c, check_combine(w, h, direct_device, indirect_device, rgb_out_device));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     return combine_launch(c, (size_t)w * h, direct_device, indirect_device, rgb_out_device);
 }
 
 int pbrs_combine_passes(pbrs_ctx* c, uint32_t w, uint32_t h, const float* direct_host, const float* indirect_host, float* rgb_out_host) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_combine(c, w, h, direct_host, indirect_host, rgb_out_host);
+    const int rc = enter(c, check_combine(w, h, direct_host, indirect_host, rgb_out_host));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)w * h;
     // the staging of a render with passes; the sum lands in the direct layer's place
-    Staged s[4] = {{direct_host, 3}, {indirect_host, 3}, {nullptr, 1}, {nullptr, 1}};
-    rc = stage(c, c->buf[BUF_PASS_OUT], "the light pass buffers", s, 4, P);
-    if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
-    if (!rc) rc = combine_launch(c, P, s[0].as<float>(), s[1].as<float>(), s[0].as<float>());
-    Staged out{rgb_out_host, 3, s[0].dev};
-    if (!rc) rc = copy_staged(c, &out, 1, P, hipMemcpyDeviceToHost);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    Staged s[] = {{direct_host, 3, rgb_out_host}, {indirect_host, 3}, {nullptr, 1}, {nullptr, 1}};
+    return run_staged(c, BUF_PASS_OUT, "the light pass buffers", s, P, [&] { return combine_launch(c, P, s[0].as<float>(), s[1].as<float>(), s[0].as<float>()); });
 }
 
 // ---- temporal accumulation (include/pbrs_gpu.h, device/temporal.h) ----
@@ -1576,14 +1476,6 @@ constexpr TemporalKernel kTemporal[2][2] = {{k_temporal<true, false, false>, k_t
 // the same with a motion table
 constexpr TemporalKernel kTemporalMotion[2][2] = {{k_temporal<true, false, false, true>, k_temporal<true, false, true, true>},
                                                   {k_temporal<true, true, false, true>, k_temporal<true, true, true, true>}};
-
-int check_motion_table(pbrs_ctx* c, const pbrs_instance_motion* motion, uint32_t n_motion, const uint32_t* instance) {
-    if (!motion) return n_motion ? fail(c, PBRS_E_INVALID, "n_motion without a motion table") : PBRS_OK;
-    if (n_motion == 0) return fail(c, PBRS_E_INVALID, "a motion table of 0 records");
-    if (!instance) return fail(c, PBRS_E_INVALID, "a motion table without this frame's instance ids");
-    if (n_motion > (1u << 24)) return fail(c, PBRS_E_LIMIT, "more than 2^24 motion records");
-    return PBRS_OK;
-}
 
 // The caller's table (host memory) into the context's copy, on the context's stream: ordered behind the kernels of earlier calls that read
 // the copy, and the runtime has taken the bytes when the call returns.  -> the device table in *dev (null without a table).
@@ -1607,33 +1499,6 @@ void temporal_cameras(TemporalConst& k, const pbrs_camera& cam, const pbrs_camer
     temporal_cross(cam_prev->c, cam_prev->a, k.nv);
     temporal_cross(cam_prev->a, cam_prev->b, k.nw);
     k.D = temporal_dot(cam_prev->a, k.nu);
-}
-
-int check_temporal(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
-                   const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout) {
-    if (!p || !cam || !f || !hout) return fail(c, PBRS_E_INVALID, "null temporal params, camera, frame or history_out");
-    if (!f->rgb || !f->depth) return fail(c, PBRS_E_INVALID, "the temporal frame needs rgb and depth");
-    if (!hout->rgb || !hout->moments || !hout->length) return fail(c, PBRS_E_INVALID, "history_out with a null plane");
-    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty image");
-    if (p->flags & ~PBRS_TEMPORAL_ID_TEST) return fail(c, PBRS_E_INVALID, "unknown temporal flag bits");
-    if ((p->flags & PBRS_TEMPORAL_ID_TEST) && !f->instance) return fail(c, PBRS_E_INVALID, "PBRS_TEMPORAL_ID_TEST without instance ids");
-    if (!pn_isfinite(p->max_history) || !(p->max_history >= 1.0f)) return fail(c, PBRS_E_INVALID, "max_history must be finite and >= 1");
-    const float tol[2] = {p->depth_tolerance, p->normal_tolerance};
-    for (float t : tol)
-        if (!pn_isfinite(t) || !(t > 0.0f)) return fail(c, PBRS_E_INVALID, "a temporal tolerance must be finite and > 0");
-    if (!pn_isfinite(p->min_temporal) || !(p->min_temporal >= 2.0f)) return fail(c, PBRS_E_INVALID, "min_temporal must be finite and >= 2");
-    if (cam->width != p->w || cam->height != p->h) return fail(c, PBRS_E_INVALID, "the camera's size is not w x h");
-    if (hin) {
-        if (!hin->rgb || !hin->moments || !hin->length) return fail(c, PBRS_E_INVALID, "history_in with a null plane");
-        if (!cam_prev || !prev || !prev->depth) return fail(c, PBRS_E_INVALID, "history_in without the previous camera or the previous depth");
-        if (cam_prev->width != p->w || cam_prev->height != p->h) return fail(c, PBRS_E_INVALID, "the previous camera's size is not w x h");
-        if (!f->normal != !prev->normal || !f->instance != !prev->instance)
-            return fail(c, PBRS_E_INVALID, "a normal or an instance guide given for only one of the two frames");
-        if (hin->rgb == hout->rgb || hin->moments == hout->moments || hin->length == hout->length)
-            return fail(c, PBRS_E_INVALID, "temporal accumulation cannot run in place: history_out shares a plane with history_in");
-    }
-    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
-    return PBRS_OK;
 }
 
 // The one launch on the context's stream (arguments checked; device pointers, the motion table the caller's host memory).  Without a
@@ -1668,11 +1533,8 @@ int pbrs_temporal_accumulate_motion_device(pbrs_ctx* c, const pbrs_temporal_para
                                            const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
                                            const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
                                            float* variance_out_device, const pbrs_instance_motion* motion, uint32_t n_motion) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_temporal(c, p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device);
-    if (!rc) rc = check_motion_table(c, motion, n_motion, frame_device->instance);
+    const int rc = enter(c, check_temporal_motion(p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device, motion, n_motion));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     return temporal_launch(c, *p, *cam, cam_prev, *frame_device, prev_device, history_in_device, *history_out_device, variance_out_device, motion,
                            n_motion);
 }
@@ -1695,45 +1557,26 @@ int pbrs_temporal_accumulate_motion(pbrs_ctx* c, const pbrs_temporal_params* p, 
                                     const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
                                     const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host,
                                     float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_temporal(c, p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host);
-    if (!rc) rc = check_motion_table(c, motion, n_motion, frame_host->instance);
+    const int rc = enter(c, check_temporal_motion(p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host, motion, n_motion));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)p->w * p->h;
     const pbrs_temporal_frame& f = *frame_host;
     const pbrs_temporal_history& ho = *history_out_host;
     const pbrs_temporal_guides g = history_in_host ? *prev_host : pbrs_temporal_guides{};  // without a history the previous frame is not read
     const pbrs_temporal_history hi = history_in_host ? *history_in_host : pbrs_temporal_history{};
-    Staged s[15] = {{f.rgb, 3}, {f.variance, 1}, {f.depth, 1}, {f.normal, 3}, {f.instance, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1},
-                    {hi.rgb, 3}, {hi.moments, 2}, {hi.length, 1}, {ho.rgb, 3}, {ho.moments, 2}, {ho.length, 1}, {variance_out_host, 1}};
-    rc = stage(c, c->buf[BUF_TEMPORAL_STAGE], "the temporal accumulation's staging", s, 15, P);
-    if (!rc) rc = copy_staged(c, s, 11, P, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    const pbrs_temporal_frame fd{s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
-    const pbrs_temporal_guides gd{s[5].as<float>(), s[6].as<float>(), s[7].as<uint32_t>()};
-    const pbrs_temporal_history hid{s[8].as<float>(), s[9].as<float>(), s[10].as<float>()}, hod{s[11].as<float>(), s[12].as<float>(), s[13].as<float>()};
-    rc = temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>(), motion, n_motion);
-    if (!rc) rc = copy_staged(c, s + 11, 4, P, hipMemcpyDeviceToHost);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    Staged s[] = {{f.rgb, 3}, {f.variance, 1}, {f.depth, 1}, {f.normal, 3}, {f.instance, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1},
+                  {hi.rgb, 3}, {hi.moments, 2}, {hi.length, 1},
+                  {nullptr, 3, ho.rgb}, {nullptr, 2, ho.moments}, {nullptr, 1, ho.length}, {nullptr, 1, variance_out_host}};
+    return run_staged(c, BUF_TEMPORAL_STAGE, "the temporal accumulation's staging", s, P, [&] {
+        const pbrs_temporal_frame fd{s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
+        const pbrs_temporal_guides gd{s[5].as<float>(), s[6].as<float>(), s[7].as<uint32_t>()};
+        const pbrs_temporal_history hid{s[8].as<float>(), s[9].as<float>(), s[10].as<float>()}, hod{s[11].as<float>(), s[12].as<float>(), s[13].as<float>()};
+        return temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>(), motion, n_motion);
+    });
 }
 
 // ---- motion vectors (include/pbrs_gpu.h, device/temporal.h) ----
 namespace {
-
-int check_motion_vectors(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth,
-                         const uint32_t* instance, const pbrs_instance_motion* motion, uint32_t n_motion, const float* motion_out) {
-    if (!cam || !cam_prev || !depth || !motion_out) return fail(c, PBRS_E_INVALID, "null cameras, depth or motion_out");
-    if (w == 0 || h == 0) return fail(c, PBRS_E_INVALID, "empty image");
-    if (cam->width != w || cam->height != h || cam_prev->width != w || cam_prev->height != h)
-        return fail(c, PBRS_E_INVALID, "a camera's size is not w x h");
-    const int rc = check_motion_table(c, motion, n_motion, instance);
-    if (rc) return rc;
-    if ((uint64_t)w * h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
-    return PBRS_OK;
-}
 
 // The table's copy and the one launch on the context's stream (arguments checked; device pointers, the table host memory).
 int motion_vectors_launch(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera& cam, const pbrs_camera& cam_prev, const float* depth,
@@ -1756,29 +1599,21 @@ int motion_vectors_launch(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera
 int pbrs_motion_vectors_device(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth_device,
                                const uint32_t* instance_device, const pbrs_instance_motion* motion, uint32_t n_motion, float* motion_out_device,
                                float* prev_depth_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_motion_vectors(c, w, h, cam, cam_prev, depth_device, instance_device, motion, n_motion, motion_out_device);
+    const int rc = enter(c, check_motion_vectors(w, h, cam, cam_prev, depth_device, instance_device, motion, n_motion, motion_out_device));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     return motion_vectors_launch(c, w, h, *cam, *cam_prev, depth_device, instance_device, motion, n_motion, motion_out_device, prev_depth_out_device);
 }
 
 int pbrs_motion_vectors(pbrs_ctx* c, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth_host,
                         const uint32_t* instance_host, const pbrs_instance_motion* motion, uint32_t n_motion, float* motion_out_host,
                         float* prev_depth_out_host) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_motion_vectors(c, w, h, cam, cam_prev, depth_host, instance_host, motion, n_motion, motion_out_host);
+    const int rc = enter(c, check_motion_vectors(w, h, cam, cam_prev, depth_host, instance_host, motion, n_motion, motion_out_host));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)w * h;
-    Staged s[4] = {{depth_host, 1}, {instance_host, 1}, {motion_out_host, 2}, {prev_depth_out_host, 1}};
-    rc = stage(c, c->buf[BUF_MOTION_STAGE], "the motion vectors' staging", s, 4, P);
-    if (!rc) rc = copy_staged(c, s, 2, P, hipMemcpyHostToDevice);
-    if (!rc) rc = motion_vectors_launch(c, w, h, *cam, *cam_prev, s[0].as<float>(), s[1].as<uint32_t>(), motion, n_motion, s[2].as<float>(), s[3].as<float>());
-    if (!rc) rc = copy_staged(c, s + 2, 2, P, hipMemcpyDeviceToHost);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    Staged s[] = {{depth_host, 1}, {instance_host, 1}, {nullptr, 2, motion_out_host}, {nullptr, 1, prev_depth_out_host}};
+    return run_staged(c, BUF_MOTION_STAGE, "the motion vectors' staging", s, P, [&] {
+        return motion_vectors_launch(c, w, h, *cam, *cam_prev, s[0].as<float>(), s[1].as<uint32_t>(), motion, n_motion, s[2].as<float>(), s[3].as<float>());
+    });
 }
 
 // ---- spatial variance estimate (include/pbrs_gpu.h, device/spatial_variance.h) ----
@@ -1791,24 +1626,6 @@ using SpatialVarKernel = void (*)(SpatialVarIn, float*, SpatialVarConst);
 // [normal stop][id stop]
 constexpr SpatialVarKernel kSpatialVar[2][2] = {{k_spatial_variance<false, false>, k_spatial_variance<false, true>},
                                                 {k_spatial_variance<true, false>, k_spatial_variance<true, true>}};
-
-int check_spatial_variance(pbrs_ctx* c, const pbrs_spatial_variance_params* p, const float* moments, const float* length,
-                           const pbrs_spatial_variance_guides* g, const float* variance_in, const float* variance_out) {
-    if (!p || !moments || !length || !variance_in || !variance_out)
-        return fail(c, PBRS_E_INVALID, "null spatial variance params, moments, length, variance_in or variance_out");
-    if (p->w == 0 || p->h == 0) return fail(c, PBRS_E_INVALID, "empty image");
-    if (p->radius == 0 || p->radius > PBRS_SPATIAL_MAX_RADIUS) return fail(c, PBRS_E_INVALID, "the spatial variance radius must be 1 .. 3");
-    if (p->flags & ~(PBRS_SPATIAL_ID_STOP | PBRS_SPATIAL_ONLY_UNKNOWN)) return fail(c, PBRS_E_INVALID, "unknown spatial variance flag bits");
-    if ((p->flags & PBRS_SPATIAL_ID_STOP) && !(g && g->instance)) return fail(c, PBRS_E_INVALID, "PBRS_SPATIAL_ID_STOP without instance ids");
-    const float sig[2] = {p->sigma_normal, p->sigma_depth};
-    for (float s : sig)
-        if (!pn_isfinite(s) || !(s > 0.0f)) return fail(c, PBRS_E_INVALID, "a spatial variance sigma must be finite and > 0");
-    if (!pn_isfinite(p->min_temporal) || !(p->min_temporal >= 1.0f)) return fail(c, PBRS_E_INVALID, "min_temporal must be finite and >= 1");
-    if (variance_out == moments || variance_out == length)
-        return fail(c, PBRS_E_INVALID, "the spatial variance estimate cannot write over the moments or the length");
-    if ((uint64_t)p->w * p->h > (1ull << 28)) return fail(c, PBRS_E_LIMIT, "more than 2^28 pixels");
-    return PBRS_OK;
-}
 
 // The one launch on the context's stream (arguments checked; device pointers).
 int spatial_variance_launch(pbrs_ctx* c, const pbrs_spatial_variance_params& p, const float* moments, const float* length,
@@ -1831,34 +1648,24 @@ int spatial_variance_launch(pbrs_ctx* c, const pbrs_spatial_variance_params& p, 
 
 int pbrs_spatial_variance_device(pbrs_ctx* c, const pbrs_spatial_variance_params* p, const float* moments_device, const float* length_device,
                                  const pbrs_spatial_variance_guides* guides_device, const float* variance_in_device, float* variance_out_device) {
-    if (!c) return PBRS_E_INVALID;
-    const int rc = check_spatial_variance(c, p, moments_device, length_device, guides_device, variance_in_device, variance_out_device);
+    const int rc = enter(c, check_spatial_variance(p, moments_device, length_device, guides_device, variance_in_device, variance_out_device));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     return spatial_variance_launch(c, *p, moments_device, length_device, guides_device ? *guides_device : pbrs_spatial_variance_guides{},
                                    variance_in_device, variance_out_device);
 }
 
 int pbrs_spatial_variance(pbrs_ctx* c, const pbrs_spatial_variance_params* p, const float* moments_host, const float* length_host,
                           const pbrs_spatial_variance_guides* guides_host, const float* variance_in_host, float* variance_out_host) {
-    if (!c) return PBRS_E_INVALID;
-    int rc = check_spatial_variance(c, p, moments_host, length_host, guides_host, variance_in_host, variance_out_host);
+    const int rc = enter(c, check_spatial_variance(p, moments_host, length_host, guides_host, variance_in_host, variance_out_host));
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)p->w * p->h;
     const pbrs_spatial_variance_guides g = guides_host ? *guides_host : pbrs_spatial_variance_guides{};
     // the variance is estimated in place in its staging plane
-    Staged s[6] = {{moments_host, 2}, {length_host, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1}, {variance_in_host, 1}};
-    rc = stage(c, c->buf[BUF_SPATIAL_STAGE], "the spatial variance estimate's staging", s, 6, P);
-    if (!rc) rc = copy_staged(c, s, 6, P, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    const pbrs_spatial_variance_guides gd{s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
-    rc = spatial_variance_launch(c, *p, s[0].as<float>(), s[1].as<float>(), gd, s[5].as<float>(), s[5].as<float>());
-    const Staged out{variance_out_host, 1, s[5].dev};
-    if (!rc) rc = copy_staged(c, &out, 1, P, hipMemcpyDeviceToHost);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRS_OK;
+    Staged s[] = {{moments_host, 2}, {length_host, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1}, {variance_in_host, 1, variance_out_host}};
+    return run_staged(c, BUF_SPATIAL_STAGE, "the spatial variance estimate's staging", s, P, [&] {
+        const pbrs_spatial_variance_guides gd{s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
+        return spatial_variance_launch(c, *p, s[0].as<float>(), s[1].as<float>(), gd, s[5].as<float>(), s[5].as<float>());
+    });
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {
@@ -1942,7 +1749,7 @@ int pbrs_last_intersect_info(const pbrs_ctx* c, pbrs_intersect_info* out) {
 int pbrs_camera_rays(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, uint32_t sample_index, float* origins_out, float* dirs_out) {
     if (!c) return PBRS_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_params(c, cam, p);
+    int rc = fail(c, check_params(scene_state(c), cam, p));
     if (rc) return rc;
     if (!origins_out || !dirs_out) return fail(c, PBRS_E_INVALID, "null output");
     const uint32_t P = p->w * p->h;
@@ -2012,7 +1819,7 @@ int pbrs_numeric_eval_k(pbrs_ctx* c, uint32_t fn, uint32_t n, uint32_t k, const 
 int pbrs_render_sample_radiance(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params* p, uint32_t sample_index, float* rgb_out_host) {
     if (!c) return PBRS_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = check_params(c, cam, p);
+    int rc = fail(c, check_params(scene_state(c), cam, p));
     if (rc) return rc;
     if (!rgb_out_host) return fail(c, PBRS_E_INVALID, "null output");
     const uint32_t P = p->w * p->h;

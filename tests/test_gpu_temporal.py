@@ -284,3 +284,25 @@ def test_refusals_leave_the_context_usable(gpu_ctx):
             agree(got[1], want[1], size)
     finally:
         fresh.close()
+
+
+def test_a_refused_host_call_says_why_and_changes_no_later_result(gpu_ctx):
+    """13 x 7 (odd, less than one block, no multiple of the 16-pixel cell): a denoise and a two-frame accumulation through the host
+    variants, which stage every plane; then a call of each that the C checks refuse (host/arg_checks.cpp), with their messages; then
+    the same two calls again, to the same bits."""
+    from test_gpu_denoise import synthetic
+    w, h = 13, 7
+    rgb, guides = synthetic(w, h, 5)
+
+    def both():
+        seq = tm.run_sequence(gpu_step(gpu_ctx), w, h, 3, "pan", frames=2, id_test=True)
+        return bits(gpu_ctx.denoise(rgb, iterations=3, **guides)).tobytes(), sequence_bits(seq) + bits(seq[-1][1]).tobytes()
+    before = both()
+    want = tm.run_sequence(tm.accumulate, w, h, 3, "pan", frames=2, id_test=True)
+    assert before[1] == sequence_bits(want) + bits(want[-1][1]).tobytes()
+    with pytest.raises(pbrs_amd.PbrsError, match=r"pbrs_denoise failed \(-1\): denoise iterations must be 1 \.\. 6$"):
+        gpu_ctx.denoise(rgb, iterations=0, **guides)
+    cam, frame, _ = next(iter(tm.synthetic_sequence(w, h, 3, "pan", 2)))
+    with pytest.raises(pbrs_amd.PbrsError, match=r"pbrs_temporal_accumulate failed \(-1\): the temporal frame needs rgb and depth$"):
+        gpu_ctx.temporal_accumulate(frame["rgb"], None, api_camera(cam))
+    assert both() == before
