@@ -30,7 +30,7 @@ PD f3 aov_lobe_albedo(const DevScene& S, const pbrs_material& mat, const Isect& 
 }
 
 // One thread per pixel, by pixel order q: a sample index's loads are contiguous per wave (slot_of_sample).  The pass's kc sample
-// indices in order.  `qsplit`: k_extend split the queue (pbrs_gpu.hip, run_pass) and wrote no hit record for the paths it dropped —
+// indices in order.  `qsplit`: k_extend's split flags (PBRS_QSPLIT_*, device/scene.h; not 0: PBRS_QSPLIT_ON): it split the queue and wrote no hit record for the paths it dropped —
 // misses under a black environment, cls[slot] == 0.  S is the global scene: this kernel stages nothing in LDS.
 __global__ void __launch_bounds__(256) k_aov(DevScene S, PathState st, float* aov, uint32_t n_pixels, uint32_t k_count, uint32_t chunk, uint32_t qsplit) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;

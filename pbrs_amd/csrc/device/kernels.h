@@ -54,7 +54,7 @@ struct PathState {
     float4* nee[3];   // [slot]: c1.xyz, 1 / light_pdf | c2.xyz, post factor | beta at the time of the estimate, -
     uint8_t* occ[2];  // [slot], written by k_shadow: 1 = the ray is occluded
 };
-#define PBRS_STATE_BYTES_PER_PATH (2u * 48u + 4u + 16u + 4u + 1u + 16u + 2u * 48u + 48u + 2u + 4u + 8u)  // records above + the nee queue entry + two slow-list entries
+// (what a path holds of these and of the pass set's other columns: host/pass_plan.h, kPathColumns)
 
 struct RenderConst {
     pbrs_camera cam;
@@ -276,11 +276,7 @@ PD void flush_counters(const Cnt<STATS>& cnt, GlobalCounters* g, bool valid, uin
 // at chunk / 10 ns items per second, so the queue is cut into PBRS_WORK_HEADS contiguous segments, each with its own
 // head word on its own 128-byte line.  A block starts on segment blockIdx.x % 8 — blocks are dealt round-robin to
 // the 8 XCDs, so neighbouring rays stay within one XCD's L2 — and moves on to the next segment when its own is empty.
-// All values are wave-uniform.
-#ifndef PBRS_WORK_HEADS
-#define PBRS_WORK_HEADS 8u
-#endif
-#define PBRS_WORK_HEAD_STRIDE 32u  // u32 words between head words
+// All values are wave-uniform.  (PBRS_WORK_HEADS, PBRS_WORK_HEAD_STRIDE: device/scene.h)
 struct WaveWork {
     uint32_t cur, end, chunk;
     uint32_t head, tried;  // segment in use; segments found empty so far
@@ -448,7 +444,7 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_SHADING_CHE
                         // (the path record's flag rides in `item` since the ray was fetched: reading the record again here put a
                         // memory round trip into every refill of an open scene)
                         const bool specular = (item >> 31) != 0u;
-                        cls = (specular || ((split & 2u) && S.has_env != 0u)) ? 1u : 0u;
+                        cls = (specular || ((split & PBRS_QSPLIT_ENV) && S.has_env != 0u)) ? 1u : 0u;
                     }
                 }
                 const uint32_t pos = item & 0x7fffffffu;
@@ -974,8 +970,7 @@ __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : 
 // counting sort of the hit records' class word within tiles of PBRS_SORT_TILE queue positions (one block per tile), which
 // writes the permutation k_shade reads its paths through.  The records themselves stay where they are (k_shade gathers
 // 4 x 16 bytes per path; inside a class the order is the queue's, so the gathers stay near-sequential) and tiles keep
-// the spatial order of the queue at large.  The result of a path does not depend on which lane shades it.
-#define PBRS_SORT_TILE 16384u
+// the spatial order of the queue at large.  The result of a path does not depend on which lane shades it.  (PBRS_SORT_TILE: device/scene.h)
 // Class sizes of the queue positions [base, end) into s_tot[] (zeroed, block-wide).  Sixteen ballots per 64 paths, lane c of a
 // wave keeping class c's count, and one LDS add per lane at the end: one LDS atomic per PATH on sixteen words at most was
 // what the counting pass spent its time on (0.39 ms per 200 M paths reading bytes, as much as when it read 16-byte records).

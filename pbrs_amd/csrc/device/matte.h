@@ -18,7 +18,8 @@
 #define PBRS_MATTE_STATE_WORDS(slots) (2u * (slots) + 1u)
 
 // One thread per pixel, by pixel order q: a sample index's loads are contiguous per wave (slot_of_sample), as in k_aov.  `qsplit`:
-// k_extend split the queue and wrote no hit record for the paths it dropped (cls[slot] == 0): misses, as in k_aov.
+// k_extend's split flags (PBRS_QSPLIT_*, device/scene.h; not 0: PBRS_QSPLIT_ON): it split the queue and wrote no hit record for the paths it dropped
+// (cls[slot] == 0): misses, as in k_aov.
 template <uint32_t SLOTS>
 __global__ void __launch_bounds__(256) k_matte(const pbrs_instance* inst, PathState st, uint32_t* state, uint32_t n_pixels, uint32_t k_count, uint32_t chunk,
                                                uint32_t qsplit, uint32_t key) {

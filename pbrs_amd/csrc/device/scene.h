@@ -163,3 +163,17 @@ struct pbrs_wnode {
 #define PBRS_SHADE_LDS_TRIS 64u
 // Shading classes a scene may have (DevScene::n_classes; kernels.h, class sort)
 #define PBRS_MAX_CLASSES 16u
+
+// What the pass driver (host/pass_plan.h) and the kernels agree on: the sizes behind a pass's grids, counters and sort tables.
+// The traversal kernels are persistent: at most this many blocks, each lane keeps pulling rays (kernels.h).
+#define PBRS_PERSISTENT_BLOCKS 1536
+// Their work fetch (kernels.h, WaveWork): the queue is cut into this many segments, each with its own head word
+#ifndef PBRS_WORK_HEADS
+#define PBRS_WORK_HEADS 8u
+#endif
+#define PBRS_WORK_HEAD_STRIDE 32u  // u32 words between head words
+// Queue positions per tile of the class sort (kernels.h, k_class_sort): one block per tile
+#define PBRS_SORT_TILE 16384u
+// k_extend's `split` argument (kernels.h; k_aov's and k_matte's `qsplit`), 0 where the queue is not split:
+#define PBRS_QSPLIT_ON 1u   // the queue is split into kept and dropped paths
+#define PBRS_QSPLIT_ENV 2u  // ... at the first bounce, where a miss sees the environment

@@ -395,8 +395,7 @@ PD bool mesh_tri_pred(const pbrs_tri_verts& tv, f3 o, f3 d, float t_max) {
 // a wave's 64 accesses to one level hit 64 consecutive dwords — no bank conflicts; the constant stride folds the
 // index arithmetic into the ds_read/ds_write address).
 #define PBRS_TRAVERSAL_BLOCK 256
-// The traversal kernels are persistent: at most this many blocks, each lane keeps pulling rays (kernels.h).
-#define PBRS_PERSISTENT_BLOCKS 1536
+// The traversal kernels are persistent: at most PBRS_PERSISTENT_BLOCKS blocks (device/scene.h), each lane keeps pulling rays (kernels.h).
 #define PBRS_TRAVERSAL_LANES (PBRS_PERSISTENT_BLOCKS * PBRS_TRAVERSAL_BLOCK)
 struct LaneStack {
     uint32_t* base;    // &lds[threadIdx.x]

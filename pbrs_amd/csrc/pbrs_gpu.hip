@@ -23,6 +23,7 @@
 #include "device/kernels.h"
 #include "host/scene_prepare.h"
 #include "host/arg_checks.h"
+#include "host/pass_plan.h"
 #include "device/aov.h"
 #include "device/film.h"
 #include "device/denoise.h"
@@ -32,20 +33,14 @@
 #include "device/temporal.h"
 #include "device/spatial_variance.h"
 
-using namespace pbrs;  // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h) and argument checks (host/arg_checks.h)
+// the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
+using namespace pbrs;
 
 namespace {
 
-constexpr uint32_t kHeadWords = PBRS_WORK_HEADS * PBRS_WORK_HEAD_STRIDE;
-// per bounce: act, ns (u64), the slow-list length of k_shadow; then three sets of work heads (the two stages, and the binary-walk
-// launch that works off k_shadow's slow list)
-constexpr uint32_t kCounterWords = (4 + 3 * kHeadWords) * (kMaxDepth + 2);
-constexpr uint32_t kSlowGrid = 64;
 #ifndef PBRS_SPLIT_KEEP_PERCENT
 #define PBRS_SPLIT_KEEP_PERCENT 85u  // k_extend's queue split stays on where it keeps at most this share of a pass's rays for k_shade
-#endif  // blocks of a binary-walk launch over a slow list (empty in nearly every launch)
-constexpr uint32_t kStreamGridCap = 4096;  // blocks of k_nee_resolve, whose work is counted on the device (kernels.h)
-constexpr uint32_t kPersistentBlocks = PBRS_PERSISTENT_BLOCKS;  // 256 CUs x up to 6 resident 256-thread blocks (VGPR/LDS permitting)
+#endif
 
 struct StageEvent {
     int stage;  // 0 raygen, 1 extend, 2 shade, 3 shadow, 4 accumulate
@@ -90,33 +85,21 @@ typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, Glo
 typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*,
                            const uint32_t*);
 
-// The kernels that render the uploaded scene, bound once per upload (bind_kernels) to what choose_kernels names (host/kernel_choice.h).
-template <class Fn>
-struct StageKernel {
-    Fn fn = nullptr;
-    uint32_t features = 0;  // the instantiation's PBRS_FEAT_* as pbrs_stats::kernel_features_* reports them (0x80000000: instrumented)
-    size_t lds = 0;         // dynamic LDS: the lanes' stack rows and what the kernel stages
-};
-struct ShadeLaunch {
-    shade_fn_t fn = nullptr;
-    size_t lds = 0;
-    uint32_t range = 0;  // the st.class_range entry the launch covers (PBRS_MAX_CLASSES: the classes before the last one), 0: the queue
-};
+// The kernels that render the uploaded scene, bound once per upload (bind_kernels): what choose_kernels names (host/kernel_choice.h: the
+// keys, the dynamic LDS and the class range of every launch), and the instantiations the keys name.
 struct IntegratorPlan {
-    IntegratorChoice::Order order = IntegratorChoice::NO_ORDER;  // how the queue is ordered before k_shade
-    uint32_t last_class = 0;  // CLASS_MAJOR: the class that goes last, over PBRS_MAX_CLASSES classes
-    uint32_t n_shade = 0;     // one or two k_shade launches
-    ShadeLaunch shade[2];
+    IntegratorChoice choice;
+    shade_fn_t shade[2] = {};  // [launch], choice.n_shade of them
 };
 struct KernelPlan {
-    StageKernel<extend_fn_t> extend[2];  // [instrumented]
-    StageKernel<shadow_fn_t> shadow[2];
-    bool wide_shadow = false;               // the timed k_shadow walks four-wide nodes ...
-    StageKernel<shadow_fn_t> shadow_slow;   // ... and this binary-walk kernel works off the rays it refused
-    bool split_queue = false;               // k_extend may split the path integrator's queue (one shading class; run_pass decides)
-    uint32_t lds_staging = 0;               // PBRS_FEAT_LDS_SCENE, PBRS_FEAT_LDS_TOP or 0: what the traversal kernels stage in LDS
+    KernelChoice choice;  // (its integ[] are the IntegratorPlans' choices)
+    extend_fn_t extend[2] = {};  // [instrumented]
+    shadow_fn_t shadow[2] = {};
+    shadow_fn_t shadow_slow = nullptr;  // where choice.wide_shadow
     IntegratorPlan integ[PBRS_INTEGRATOR_NORMALS + 1];
 };
+// A traversal kernel's PBRS_FEAT_* as pbrs_stats::kernel_features_* reports them (0x80000000: instrumented).
+uint32_t reported_features(const TraversalKey& k) { return (k.key & ~kStatsKey) | ((k.key & kStatsKey) ? 0x80000000u : 0u); }
 
 // A device buffer of a feature that allocates on first use.  `grow` makes it hold at least `bytes`, grown (not copied): a failure leaves
 // the context without it (cap_bytes = 0), usable for every other call.
@@ -186,7 +169,7 @@ struct pbrs_ctx {
         uint32_t* neeq = nullptr;     // cap_slots: slots of the paths whose estimate waits for two shadow rays
         uint32_t* rng_hi0 = nullptr;  // cap_slots: the RNG's high word of every camera sample, from k_raygen to bounce 0's k_shade (kernels.h, PathState)
         uint32_t* slow = nullptr;     // 2 * cap_slots: queue positions the wide-walk k_shadow handed to the binary-walk kernel
-        uint32_t* counters = nullptr; // kCounterWords: act, ns (u64), extend work heads, shadow work heads
+        uint32_t* counters = nullptr; // kCounters.words: the regions of CounterLayout (host/pass_plan.h)
         float4* direct = nullptr;     // light passes: the D column, [slot] = L[slot] as bounce 0 left it (device/passes.h); null unless the render asks for passes
         hipEvent_t accumulated = nullptr;  // the set's last k_accumulate has run (late stream): the set's memory is free for its next pass
         hipEvent_t late = nullptr;         // the set's pass has run its bounces below pbrs_ctx::overlap_from (main stream): the late stream takes over
@@ -218,7 +201,7 @@ struct pbrs_ctx {
     bool pending_counters = false, pending_times = false;
     DevOverrides dev;  // read in pbrs_create (-DPBRS_DEV_OVERRIDES builds)
     KernelPlan plan;   // the kernels that render the uploaded scene (bind_kernels)
-    // k_extend splits the path integrator's queue of one-class scenes (shaded / terminal / dropped: KernelPlan::split_queue), which
+    // k_extend splits the path integrator's queue of one-class scenes (shaded / terminal / dropped: KernelChoice::split_queue), which
     // pays where many paths are dropped (an open scene: C4 shades in 84 instead of 117 ms per frame) and costs where none are (a
     // closed box: the gathered records cost C2 4 %).  Decided once per uploaded scene, from the counts of the first pass rendered
     // with the path integrator: 0 = not yet, 1 = split, 2 = do not.  The image does not depend on it.
@@ -309,46 +292,54 @@ void free_work(pbrs_ctx* c) {
     c->rgb_dev = nullptr;
 }
 
+// Column `col` of a layout (host/pass_plan.h) in the allocation `mem`.
+template <class T>
+T* column(void* mem, const PathLayout& lay, uint32_t col) {
+    return reinterpret_cast<T*>(static_cast<char*>(mem) + lay.offset[col]);
+}
+// The types ensure_work reads the columns as have the element sizes the table states: a kernel that indexes a column stays in its region.
+constexpr bool columns_hold(uint32_t first, uint32_t n, size_t elem) {
+    for (uint32_t i = first; i < first + n; ++i)
+        if (kPathColumns[i].elem != elem) return false;
+    return true;
+}
+static_assert(columns_hold(COL_Q, 14, sizeof(float4)) && columns_hold(COL_OCC, 1, sizeof(uint8_t)) && columns_hold(COL_NEEQ, 2, sizeof(uint32_t)) &&
+                  columns_hold(COL_CLS, 1, sizeof(uint8_t)) && columns_hold(COL_SLOW, 2, sizeof(uint32_t)) && columns_hold(COL_CLASS_RANGE, 1, sizeof(uint2)) &&
+                  columns_hold(COL_RNG_HI0, 1, sizeof(uint32_t)),
+              "kPathColumns and PathState disagree about a column's element");
+
 // The path state of `set` for n_slots paths, and the context's per-pixel sums for n_pixels.
-// Carves the per-path arrays of PathState out of one allocation; every array starts 256-byte aligned.  The new
+// The per-path arrays of PathState lie in one allocation, where path_layout (host/pass_plan.h) puts them.  The new
 // capacities are published only after every allocation has succeeded: a failure leaves the context without a working
 // set (cap_* = 0, PathState cleared), never with pointers into freed memory.
 int ensure_work(pbrs_ctx* c, pbrs_ctx::PassSet& set, size_t n_slots, size_t n_pixels) {
     if (n_slots > set.cap_slots) {
         free_paths(set);
-        auto align = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t v16 = align(n_slots * sizeof(float4));
-        // q[2][3], hit, L, nee[3]: one float4 per path each; sr[3]: two per path; occ: two bytes; nee queue, rng_hi0: one word each
-        const size_t n_tiles = n_slots / PBRS_SORT_TILE + 1;
-        const size_t sort_bytes = align(n_tiles * PBRS_MAX_CLASSES * sizeof(uint32_t)) + align((PBRS_MAX_CLASSES + 1) * sizeof(uint2));
-        const size_t total = (6 + 1 + 1 + 3) * v16 + 3 * 2 * v16 + align(2 * n_slots) + align(n_slots * sizeof(uint32_t)) + align(n_slots * sizeof(uint32_t)) +
-                             sort_bytes + align(n_slots) + align(2 * n_slots * sizeof(uint32_t)) + align(n_slots * sizeof(uint32_t));
+        const PathLayout lay = path_layout(n_slots);
         void* mem = nullptr;
-        hipError_t e = hipMalloc(&mem, total);
+        hipError_t e = hipMalloc(&mem, lay.total);
         if (e != hipSuccess) {
-            c->error = std::string("hipMalloc of the path state (") + std::to_string(total >> 20) + " MiB): " + hipGetErrorString(e);
+            c->error = std::string("hipMalloc of the path state (") + std::to_string(lay.total >> 20) + " MiB): " + hipGetErrorString(e);
             (void)hipGetLastError();  // reported: must not resurface in a later call's hipGetLastError()
             return PBRS_E_DEVICE;
         }
         set.state_mem = mem;
-        char* p = static_cast<char*>(mem);
-        auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
         PathState s{};
-        for (int half = 0; half < 2; ++half)
-            for (int k = 0; k < 3; ++k) s.q[half][k] = reinterpret_cast<float4*>(take(v16));
-        s.hit = reinterpret_cast<float4*>(take(v16));
-        s.L = reinterpret_cast<float4*>(take(v16));
-        for (int k = 0; k < 3; ++k) s.nee[k] = reinterpret_cast<float4*>(take(v16));
-        for (int k = 0; k < 3; ++k) s.sr[k] = reinterpret_cast<float4*>(take(2 * v16));
-        s.occ[0] = reinterpret_cast<uint8_t*>(take(align(2 * n_slots)));
+        for (uint32_t half = 0; half < 2; ++half)
+            for (uint32_t k = 0; k < 3; ++k) s.q[half][k] = column<float4>(mem, lay, COL_Q + 3 * half + k);
+        s.hit = column<float4>(mem, lay, COL_HIT);
+        s.L = column<float4>(mem, lay, COL_L);
+        for (uint32_t k = 0; k < 3; ++k) s.nee[k] = column<float4>(mem, lay, COL_NEE + k);
+        for (uint32_t k = 0; k < 3; ++k) s.sr[k] = column<float4>(mem, lay, COL_SR + k);
+        s.occ[0] = column<uint8_t>(mem, lay, COL_OCC);
         s.occ[1] = s.occ[0] + n_slots;
-        set.neeq = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
-        s.perm = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
-        s.cls = reinterpret_cast<uint8_t*>(take(align(n_slots)));
-        set.slow = reinterpret_cast<uint32_t*>(take(align(2 * n_slots * sizeof(uint32_t))));
-        s.tile_hist = reinterpret_cast<uint32_t*>(take(align(n_tiles * PBRS_MAX_CLASSES * sizeof(uint32_t))));
-        s.class_range = reinterpret_cast<uint2*>(take(align((PBRS_MAX_CLASSES + 1) * sizeof(uint2))));
-        set.rng_hi0 = reinterpret_cast<uint32_t*>(take(align(n_slots * sizeof(uint32_t))));
+        set.neeq = column<uint32_t>(mem, lay, COL_NEEQ);
+        s.perm = column<uint32_t>(mem, lay, COL_PERM);
+        s.cls = column<uint8_t>(mem, lay, COL_CLS);
+        set.slow = column<uint32_t>(mem, lay, COL_SLOW);
+        s.tile_hist = column<uint32_t>(mem, lay, COL_TILE_HIST);
+        s.class_range = column<uint2>(mem, lay, COL_CLASS_RANGE);
+        set.rng_hi0 = column<uint32_t>(mem, lay, COL_RNG_HI0);
         set.st = s;
         set.cap_slots = n_slots;
     }
@@ -473,15 +464,18 @@ struct RenderTargets {
     WantedOutputs wanted() const { return {want_aovs(), variance != nullptr, want_passes(), want_matte, matte, matte_out.ids && matte_out.coverage}; }
 };
 
-uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p, bool with_direct);
-
 // What check_params (host/arg_checks.h) needs to know of the context.
 SceneState scene_state(const pbrs_ctx* c) { return {c->has_scene, c->has_vis_records}; }
 
 // The samples per pass of a render of `p` (checked by check_params), from the memory that is free on the current device NOW: whatever the
 // call allocates beside the path state comes first.  `with_direct`: every path carries a record of the D column as well (light passes).
 int pass_size(pbrs_ctx* c, const pbrs_render_params* p, uint32_t& K, bool with_direct = false) {
-    K = auto_samples_per_pass(c, p, with_direct);
+    std::optional<uint64_t> free_bytes;  // (a requested size asks nothing)
+    size_t free_b = 0, total_b = 0;
+    if (p->samples_per_pass == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess) free_bytes = free_b;
+    K = samples_per_pass((uint64_t)p->w * p->h, (uint64_t)p->strata_x * p->strata_y, p->samples_per_pass, with_direct,
+                         (uint64_t)c->pass_set[0].cap_slots + c->pass_set[1].cap_slots,
+                         (uint64_t)c->buf[BUF_PASS_DIRECT].cap_bytes + c->buf[BUF_PASS_DIRECT_SET1].cap_bytes, free_bytes);
     // records keep two flag bits next to the slot index, and 16-byte records are addressed with 32-bit element indices
     if ((uint64_t)p->w * p->h * K >= (1ull << 28)) return fail(c, PBRS_E_LIMIT, "tile x samples_per_pass above 2^28 paths");
     return PBRS_OK;
@@ -526,39 +520,6 @@ RenderConst make_const(const pbrs_ctx* c, const pbrs_camera* cam, const pbrs_ren
     return rc;
 }
 
-uint32_t auto_samples_per_pass(const pbrs_ctx* c, const pbrs_render_params* p, bool with_direct) {
-    uint64_t P = (uint64_t)p->w * p->h, spp = (uint64_t)p->strata_x * p->strata_y;
-    uint64_t k = p->samples_per_pass;
-    if (k == 0) {
-        // ~240M paths in flight (~67 GB of the 288 GB HBM for path, hit, radiance, shadow-ray and nee records), less when
-        // that would exceed a quarter of the memory currently free.  Every bounce is a handful of launches and a persistent
-        // traversal kernel ends with the latency of its longest walks (hundreds of dependent node fetches on a deep BLAS): the
-        // fewer, larger launches a frame is cut into, the less of it is spent draining (C2, 256 spp: 617 / 629 / 637
-        // Msamples/s at 32 / 64 / 128 samples per pass; C4: 921 / 939 at 64 / 115).  Stays under the 2^28 paths of check_params.
-        uint64_t target = 240ull << 20;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            // path, hit, radiance, shadow-ray and nee records; a render with light passes: and the D column
-            const uint64_t per_path = PBRS_STATE_BYTES_PER_PATH + (with_direct ? sizeof(float4) : 0u);
-            // what this context already holds for paths counts as available: the answer must not change between calls
-            // (... in both of its pass sets: a set may take a quarter of the memory, the two of them half)
-            const uint64_t held = (uint64_t)c->pass_set[0].cap_slots + (uint64_t)c->pass_set[1].cap_slots;
-            const uint64_t held_direct = with_direct ? c->buf[BUF_PASS_DIRECT].cap_bytes + c->buf[BUF_PASS_DIRECT_SET1].cap_bytes : 0u;
-            const uint64_t fit = ((uint64_t)free_b + held * PBRS_STATE_BYTES_PER_PATH + held_direct) / 4 / per_path;
-            if (fit < target) target = fit < (4ull << 20) ? (4ull << 20) : fit;
-        }
-        k = P >= target ? 1 : target / P;
-        if (k < 1) k = 1;
-        if (k < spp) {  // passes of equal size: 256 spp at 240 per pass is 128 + 128, not 240 + 16
-            const uint64_t passes = (spp + k - 1) / k;
-            k = (spp + passes - 1) / passes;
-        }
-    }
-    if (k > spp) k = spp;
-    if (k < 1) k = 1;
-    return (uint32_t)k;
-}
-
 // The traversal kernels, one per valid key (host/kernel_choice.h: extend_key_ok, shadow_key_ok), in tables filled at compile time.
 template <uint32_t K>
 constexpr extend_fn_t extend_fn_of() {
@@ -582,10 +543,6 @@ const shadow_fn_t* shadow_table(std::integer_sequence<uint32_t, K...>) {
 }
 const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
 const shadow_fn_t* shadow_fns() { return shadow_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
-template <class Fn>
-StageKernel<Fn> stage_kernel(const Fn* table, const TraversalKey& k) {
-    return StageKernel<Fn>{table[k.key], (k.key & ~kStatsKey) | ((k.key & kStatsKey) ? 0x80000000u : 0u), k.lds};
-}
 
 // The k_shade instantiations (kernels.h: INTEG, TEX, SPEC) the choices name: host/kernel_choice.h, PBRS_SHADE_KERNELS.
 struct ShadeKernel {
@@ -606,24 +563,19 @@ shade_fn_t shade_fn(const ShadeKey& key) {
 // The kernels a choice names (choose_kernels), from the tables above.  False where a table lacks one.
 bool bind_kernels(const KernelChoice& ch, KernelPlan& p) {
     p = KernelPlan{};
+    p.choice = ch;
     for (int s = 0; s < 2; ++s) {
-        p.extend[s] = stage_kernel(extend_fns(), ch.extend[s]);
-        p.shadow[s] = stage_kernel(shadow_fns(), ch.shadow[s]);
+        p.extend[s] = extend_fns()[ch.extend[s].key];
+        p.shadow[s] = shadow_fns()[ch.shadow[s].key];
     }
-    p.wide_shadow = ch.wide_shadow;
-    if (ch.wide_shadow) p.shadow_slow = stage_kernel(shadow_fns(), ch.shadow_slow);
-    p.split_queue = ch.split_queue;
-    p.lds_staging = ch.lds_staging;
-    bool ok = p.extend[0].fn && p.extend[1].fn && p.shadow[0].fn && p.shadow[1].fn && (!p.wide_shadow || p.shadow_slow.fn);
+    if (ch.wide_shadow) p.shadow_slow = shadow_fns()[ch.shadow_slow.key];
+    bool ok = p.extend[0] && p.extend[1] && p.shadow[0] && p.shadow[1] && (!ch.wide_shadow || p.shadow_slow);
     for (uint32_t i = 0; i <= PBRS_INTEGRATOR_NORMALS; ++i) {
-        const IntegratorChoice& ic = ch.integ[i];
         IntegratorPlan& ip = p.integ[i];
-        ip.order = ic.order;
-        ip.last_class = ic.last_class;
-        ip.n_shade = ic.n_shade;
-        for (uint32_t k = 0; k < ic.n_shade; ++k) {
-            ip.shade[k] = ShadeLaunch{shade_fn(ic.shade[k]), ic.shade[k].lds, ic.shade[k].range};
-            ok = ok && ip.shade[k].fn;
+        ip.choice = ch.integ[i];
+        for (uint32_t k = 0; k < ip.choice.n_shade; ++k) {
+            ip.shade[k] = shade_fn(ip.choice.shade[k]);
+            ok = ok && ip.shade[k];
         }
     }
     return ok;
@@ -650,14 +602,6 @@ constexpr MatteKernels kMatte[PBRS_MATTE_MAX_SLOTS] = {PBRS_MATTE_KERNELS(1), PB
                                                        PBRS_MATTE_KERNELS(5), PBRS_MATTE_KERNELS(6), PBRS_MATTE_KERNELS(7), PBRS_MATTE_KERNELS(8)};
 #undef PBRS_MATTE_KERNELS
 
-// The bounces a pass runs: one k_extend, k_shade and k_shadow stage each.
-uint32_t bounce_count(const RenderConst& rc) {
-    // the direct-lighting integrator is at most two rays deep whatever `depth` says (directlighting.rs:15-17, :36, :49)
-    if (rc.integrator == PBRS_INTEGRATOR_DIRECT) return rc.max_depth ? 2u : 0u;
-    if (rc.integrator >= PBRS_INTEGRATOR_MATERIALS) return 1u;  // the visualisers: one cast, no lights
-    return rc.max_depth;
-}
-
 // One pass: kc sample indices starting at `first` for every pixel of the tile.
 // `handoff`: the pass moves to the late stream at bounce pbrs_ctx::overlap_from (at the latest for its k_accumulate: the late stream runs
 // the passes' accumulations in pass order, src/main.rs:205) and leaves the main stream to the next pass, which works in the other pass set.
@@ -665,6 +609,8 @@ uint32_t bounce_count(const RenderConst& rc) {
 // radiances into the moments of the variance AOV (k_moments) and, split at the first path vertex (k_pass_direct), into the state of the
 // light passes (k_pass_fold), each where asked for; a filtered render (rc is its traced region) folds
 // the pass into the filter sums (k_filter_accumulate) instead of k_accumulate.
+// Every launch, memset, event and stream call of a pass is here, in order; what they are given beside pointers — the grids, the counter
+// regions, and per bounce the split flags, the queue order and the class ranges — is decided in host/pass_plan.h.
 int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stats, Timer& tm, bool handoff, const RenderTargets& t) {
     pbrs_ctx::PassSet& set = cur(c);
     // the set's memory is free once the pass that used it last has accumulated (two passes back, on the late stream)
@@ -675,53 +621,47 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         return e != hipSuccess ? e : hipStreamWaitEvent(c->stream, set.late, 0);
     };
     const uint32_t P = rc.n_pixels;
-    const uint32_t N = P * kc;
+    const PassShape shape = pass_shape(P, kc);
+    const uint32_t N = shape.n_slots, grid = shape.grid, pgrid = shape.pgrid, n_tiles = shape.n_tiles;
     rc.pass_first_sample = first;
     rc.n_slots = N;
-    const uint32_t grid = (N + kBlock - 1) / kBlock;
-    const uint32_t sgrid = grid < kStreamGridCap ? grid : kStreamGridCap;
-    // persistent traversal kernels: enough blocks to fill the chip, each pulls work until the queue is empty
-    const uint32_t pgrid = grid < kPersistentBlocks ? grid : kPersistentBlocks;
-    const uint32_t stride = kMaxDepth + 2;
-    uint32_t* act = set.counters;               // act[b]: paths entering bounce b (b >= 1)
-    // ns[b]: one 64-bit word per bounce: low half = paths whose light estimate waits for visibility, high half = shadow rays
-    unsigned long long* ns = reinterpret_cast<unsigned long long*>(set.counters + stride);
-    uint32_t* slows = set.counters + 3 * stride;  // k_shadow's slow-list length per bounce
-    // work-fetch heads of k_extend / k_shadow: kHeadWords words per bounce (one head per queue segment, kernels.h)
-    uint32_t* xhead = set.counters + 4 * stride;
-    uint32_t* shead = xhead + stride * kHeadWords;
-    uint32_t* shead2 = shead + stride * kHeadWords;  // the binary-walk launch over k_shadow's slow list
+    // the regions of the set's counter block (host/pass_plan.h, CounterLayout)
+    uint32_t* act = set.counters + kCounters.act;
+    unsigned long long* ns = reinterpret_cast<unsigned long long*>(set.counters + kCounters.ns);
+    uint32_t* slows = set.counters + kCounters.slows;
+    uint32_t* xhead = set.counters + kCounters.xhead;
+    uint32_t* shead = set.counters + kCounters.shead;
+    uint32_t* shead2 = set.counters + kCounters.shead2;
     uint32_t* neeq = set.neeq;
     const KernelPlan& plan = c->plan;
+    const KernelChoice& choice = plan.choice;
     const IntegratorPlan& ip = plan.integ[rc.integrator];
-    const StageKernel<extend_fn_t>& xk = plan.extend[stats];
-    const StageKernel<shadow_fn_t>& sk = plan.shadow[stats];
+    const TraversalKey &xk = choice.extend[stats], &sk = choice.shadow[stats];
     // k_extend scans the TLAS leaves only up to PBRS_FLAT_TLAS_MAX instances (S.features); the leaf copies may exist for k_shadow
     // alone, and the instrumented variant, which carries every feature, must then walk the tree like the timed one
     DevScene xS = c->S;
     if (!(xS.features & PBRS_FEAT_FLAT_TLAS)) xS.n_flat = 0u;
-    HIPCHK(c, hipMemsetAsync(set.counters, 0, kCounterWords * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(set.counters, 0, kCounters.words * sizeof(uint32_t), c->stream));
     if (tm.begin(0)) return fail(c, PBRS_E_DEVICE, "event record failed");
     hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, c->stream, set.st, rc, set.rng_hi0);
     tm.end();
     poll_split_probe(c);
-    const uint32_t n_bounces = bounce_count(rc);
+    const uint32_t n_bounces = bounce_count(rc.integrator, rc.max_depth);
     // L is first written by bounce 0 (k_shade, and k_class_scatter for what a split queue drops): a pass without a bounce is all zeros
     if (n_bounces == 0) HIPCHK(c, hipMemsetAsync(set.st.L, 0, (size_t)N * sizeof(float4), c->stream));
     // this pass counts what k_extend's queue split keeps (the first path-integrator pass of an uploaded one-class scene)
-    const bool probe_split = c->split_decision == 0 && !c->split_probe_in_flight && rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && n_bounces > 0;
+    const bool probe_split = c->split_decision == 0 && !c->split_probe_in_flight && rc.integrator == PBRS_INTEGRATOR_PATH && choice.split_queue && n_bounces > 0;
     for (uint32_t b = 0; b < n_bounces; ++b) {
         if (handoff && b == c->overlap_from) HIPCHK(c, to_late_stream());
         // bounce b reads the path records of set b & 1 (k_raygen wrote set 0) and k_shade writes set (b + 1) & 1; the
         // queue length of bounce 0 is the pass size, later ones are counted on the device
         const uint32_t* cnt_in = b == 0 ? nullptr : act + b;
+        const BouncePlan bp = bounce_plan(rc.integrator, choice.split_queue, ip.choice, c->split_decision, b);
+        const uint32_t qsplit = bp.split;
         if (tm.begin(1)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        // the path integrator on a scene with one shading class (no class sort): k_extend splits its queue into the hits k_shade
-        // shades, the paths that only end (emitter hits, misses that see the environment) and the misses nothing happens to
-        const uint32_t qsplit = (rc.integrator == PBRS_INTEGRATOR_PATH && plan.split_queue && c->split_decision != 2) ? (1u | (b == 0 ? 2u : 0u)) : 0u;
-        hipLaunchKernelGGL(xk.fn, dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, set.st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr, nullptr,
-                           nullptr, qsplit);
-        c->pending.kernel_features_extend = xk.features;
+        hipLaunchKernelGGL(plan.extend[stats], dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, set.st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr,
+                           nullptr, nullptr, qsplit);
+        c->pending.kernel_features_extend = reported_features(xk);
         tm.end();
         // First-hit AOVs: bounce 0's rays (q[0], at their slots) and hit records, before bounce 1 overwrites them (k_shade writes set 0
         // at bounce 1, k_extend the hit records).  Outside the stage brackets: counted in ms_total only.  The state is shared by the
@@ -736,38 +676,31 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
             hipLaunchKernelGGL(kMatte[t.matte->slots - 1u].fold, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S.inst, set.st,
                                c->buf[BUF_MATTE_STATE].as<uint32_t>(), P, kc, rc.chunk_pixels, qsplit, t.matte->key);
         if (tm.begin(2)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        // the queue in the order the plan asks for; a queue k_extend split: class-major over its two classes, class 1 = the kept paths, last
-        const IntegratorChoice::Order order = qsplit ? IntegratorChoice::CLASS_MAJOR : ip.order;
-        const uint32_t n_tiles = (N + PBRS_SORT_TILE - 1) / PBRS_SORT_TILE;
-        if (order == IntegratorChoice::CLASS_MAJOR) {
-            if (qsplit) hipLaunchKernelGGL(k_class_count<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
+        if (bp.order == IntegratorChoice::CLASS_MAJOR) {
+            const bool two = bp.n_classes == 2u;  // the instantiation: a split queue's two classes, or all of them
+            if (two) hipLaunchKernelGGL(k_class_count<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
             else hipLaunchKernelGGL(k_class_count<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
-            hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, set.st, cnt_in, N, qsplit ? 1u : ip.last_class,
+            hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(64 * PBRS_MAX_CLASSES), 0, c->stream, set.st, cnt_in, N, bp.last,
                                (qsplit && probe_split) ? c->bounce_acc + 2 * PBRS_STATS_MAX_BOUNCES : nullptr);
-            // bounce 0 of a split queue: the scatter also stores L = 0 for the dropped paths, which no k_shade lane visits
-            if (qsplit) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, b == 0 ? 1u : 0u);
-            else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, 0u);
-        } else if (order == IntegratorChoice::CLASS_SORT) {
+            if (two) hipLaunchKernelGGL(k_class_scatter<2u>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, bp.zero_dropped);
+            else hipLaunchKernelGGL(k_class_scatter<PBRS_MAX_CLASSES>, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N, bp.zero_dropped);
+        } else if (bp.order == IntegratorChoice::CLASS_SORT) {
             hipLaunchKernelGGL(k_class_sort, dim3(n_tiles), dim3(kBlock), 0, c->stream, set.st, cnt_in, N);
         }
-        const uint32_t sorted = order != IntegratorChoice::NO_ORDER ? 1u : 0u;
-        for (uint32_t k = 0; k < ip.n_shade; ++k) {
-            const ShadeLaunch& l = ip.shade[k];
-            // one class range of a class-major queue; a split queue: the kept paths
-            const uint2* range = l.range ? set.st.class_range + l.range : qsplit ? set.st.class_range + 1 : nullptr;
-            hipLaunchKernelGGL(l.fn, dim3(grid), dim3(kBlock), l.lds, c->stream, c->S, set.st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b, sorted, range, set.rng_hi0);
+        for (uint32_t k = 0; k < ip.choice.n_shade; ++k) {
+            const uint2* range = bp.shade_range[k] ? set.st.class_range + bp.shade_range[k] : nullptr;
+            hipLaunchKernelGGL(ip.shade[k], dim3(grid), dim3(kBlock), ip.choice.shade[k].lds, c->stream, c->S, set.st, rc, b, cnt_in, N, act + b + 1, neeq, ns + b,
+                               bp.sorted, range, set.rng_hi0);
         }
         tm.end();
         if (tm.begin(3)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        hipLaunchKernelGGL(sk.fn, dim3(pgrid), dim3(kBlock), sk.lds, c->stream, c->S, set.st, reinterpret_cast<const uint32_t*>(ns + b), shead + b * kHeadWords, c->gcnt + 1,
-                           nullptr, set.slow, slows + b);
-        c->pending.kernel_features_shadow = sk.features;
-        if (plan.wide_shadow && !stats) {  // what the wide walks refused (rays outside the guarded range of the division-free box test, overlong stacks)
-            const StageKernel<shadow_fn_t>& slow = plan.shadow_slow;
-            hipLaunchKernelGGL(slow.fn, dim3(pgrid < kSlowGrid ? pgrid : kSlowGrid), dim3(kBlock), slow.lds, c->stream, c->S, set.st, slows + b, shead2 + b * kHeadWords,
+        hipLaunchKernelGGL(plan.shadow[stats], dim3(pgrid), dim3(kBlock), sk.lds, c->stream, c->S, set.st, reinterpret_cast<const uint32_t*>(ns + b),
+                           shead + b * kHeadWords, c->gcnt + 1, nullptr, set.slow, slows + b);
+        c->pending.kernel_features_shadow = reported_features(sk);
+        if (choice.wide_shadow && !stats)  // what the wide walks refused (rays outside the guarded range of the division-free box test, overlong stacks)
+            hipLaunchKernelGGL(plan.shadow_slow, dim3(shape.slow_grid), dim3(kBlock), choice.shadow_slow.lds, c->stream, c->S, set.st, slows + b, shead2 + b * kHeadWords,
                                c->gcnt + 1, set.slow, nullptr, nullptr);
-        }
-        hipLaunchKernelGGL(k_nee_resolve, dim3(sgrid), dim3(kBlock), 0, c->stream, set.st, neeq, reinterpret_cast<const uint32_t*>(ns + b));
+        hipLaunchKernelGGL(k_nee_resolve, dim3(shape.sgrid), dim3(kBlock), 0, c->stream, set.st, neeq, reinterpret_cast<const uint32_t*>(ns + b));
         tm.end();
         // light passes: L is now the radiance after the first path vertex; kept in the set's D column before bounce 1 adds to L.  On the
         // stream that ran bounce 0; k_pass_fold reads the column behind the pass's last bounce (the hand-over events order the two).
@@ -882,7 +815,7 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (c->pending_times) HIPCHK(c, hipEventRecord(c->total_ev[1], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending.passes = passes;
-    c->pending.launches_extend = c->pending.launches_shade = c->pending.launches_shadow = passes * bounce_count(rc);
+    c->pending.launches_extend = c->pending.launches_shade = c->pending.launches_shadow = passes * bounce_count(rc.integrator, rc.max_depth);
     return PBRS_OK;
 }
 
@@ -1111,7 +1044,7 @@ int pbrs_create(int device_ordinal, pbrs_ctx** out) {
         ok = hipEventCreate(&ev) == hipSuccess;
         if (ok) c->total_ev.push_back(ev);
     }
-    for (pbrs_ctx::PassSet& set : c->pass_set) ok = ok && hipMalloc(reinterpret_cast<void**>(&set.counters), kCounterWords * sizeof(uint32_t)) == hipSuccess;
+    for (pbrs_ctx::PassSet& set : c->pass_set) ok = ok && hipMalloc(reinterpret_cast<void**>(&set.counters), kCounters.words * sizeof(uint32_t)) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->gcnt), 2 * sizeof(GlobalCounters)) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&c->nonfinite), sizeof(unsigned long long)) == hipSuccess &&
          hipMalloc(reinterpret_cast<void**>(&c->bounce_acc), (2 * PBRS_STATS_MAX_BOUNCES + 2) * sizeof(unsigned long long)) == hipSuccess &&
@@ -1206,9 +1139,9 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     if ((rc = upload(c, d->tex_words, d->n_tex_words, &S.tex_words))) return rc;
     if ((rc = upload(c, d->fourier_tables, d->n_fourier_tables, &S.fourier))) return rc;
     // what the plan's traversal kernels stage (kernels.h, stage_scene / stage_top)
-    const bool lds_scene = plan.lds_staging == PBRS_FEAT_LDS_SCENE;
+    const bool lds_scene = choice.lds_staging == PBRS_FEAT_LDS_SCENE;
     S.lds_off_words = P.stack_depth * kBlock;
-    S.lds_nodes = lds_scene ? (uint32_t)P.nodes.size() : plan.lds_staging == PBRS_FEAT_LDS_TOP ? d->n_tlas_nodes : 0u;
+    S.lds_nodes = lds_scene ? (uint32_t)P.nodes.size() : choice.lds_staging == PBRS_FEAT_LDS_TOP ? d->n_tlas_nodes : 0u;
     S.lds_tris = lds_scene ? d->n_triangles : 0u;
     S.lds_inst = lds_scene ? d->n_instances : 0u;
     S.lds_shapes = lds_scene ? d->n_shapes : 0u;
@@ -1723,7 +1656,7 @@ int pbrs_intersect_rays(pbrs_ctx* c, uint32_t n, const float* origins, const flo
         const dim3 grid(std::min<uint32_t>((n + kBlock - 1) / kBlock, kPersistentBlocks));
         // each query through the walk its stage runs in the pipeline (KernelPlan): occlusion through the four-wide any-hit walk whenever
         // k_shadow takes it, closest hits through the binary walk
-        const bool wide = c->plan.wide_shadow;
+        const bool wide = c->plan.choice.wide_shadow;
         c->last_intersect = pbrs_intersect_info{wide ? 1u : 0u, 0u, 0u, 0u};
         const auto fn = wide ? &k_intersect_rays<true> : &k_intersect_rays<false>;
         hipLaunchKernelGGL(fn, grid, dim3(kBlock), lds, c->stream, c->S, n, d_o, d_d, d_t, d_h, d_occ, d_info);

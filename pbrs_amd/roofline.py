@@ -4,7 +4,7 @@ Every stage's algorithmic bytes are split in two:
 
 * queue_state bytes — ray / hit / shadow-ray records, path state and queue entries.  They are written by one kernel
   and read by the next, tens of GB apart: they MUST cross HBM.  The per-unit figures are those of the record layout the
-  kernels actually move (device/kernels.h, PathState; PBRS_STATE_BYTES_PER_PATH is the resident footprint of one path):
+  kernels actually move (device/kernels.h, PathState; kPathBytesPerSlot of host/pass_plan.h is the resident footprint of one path):
     closest-hit ray  48 B   32 B ray read (origin + slot, direction + RNG word: two 16-byte vectors) + 16 B hit record written
                             (+ 1 B class byte in scenes with several shading classes)
     shadow ray       44 B   32 B ray read + the lone ray's outcome: 16 B read, 12 B written when unoccluded (an occlusion byte

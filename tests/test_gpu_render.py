@@ -755,3 +755,41 @@ def test_passes_overlapped_on_two_streams_render_the_same_frame(gpu_ctx):
     a, _ = gpu_ctx.render(3, 3, c["depth"], 5, samples_per_pass=4)
     b, _ = gpu_ctx.render(3, 3, c["depth"], 5, samples_per_pass=4)
     assert (bits(a) == bits(b)).all()
+
+
+@pytest.fixture(scope="module")
+def pass_plan_cases():
+    """C3 (a class sort) and C4 (a split queue) at 96 x 64 with the oracle's frames at 3 x 3 and at 2 x 2 strata, rendered once."""
+    cases = []
+    for name, kw in (("c3", {}), ("c4", dict(nx=192, nz=192))):
+        sb, c = scenes.build_config(name, width=96, height=64, **kw)
+        osc = OracleScene(sb)
+        cases.append((name, sb, c["depth"], {s: osc.render(s, s, c["depth"], 31)[0] for s in (3, 2)}))
+    return cases
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+def test_path_state_columns_hold_odd_sizes_and_regrow_in_place(pass_plan_cases, overlap):
+    """The per-path columns of a pass set lie where host/pass_plan.h's table puts them.  On a fresh context per scene, in this order: a tile
+    of 13 x 7 pixels at 3 samples per pass (273 slots: no column is a multiple of 256 bytes), one of 64 x 64 at 4 (16 384 slots, the
+    sort-tile boundary; the allocation regrows), the frame at 2, and the first tile again: every image is the oracle's frame, cropped,
+    bit for bit, and the first tile comes out the same bits after the regrowth as before — with the passes on two streams (both pass
+    sets) and on one."""
+    for name, sb, depth, ref in pass_plan_cases:
+        ctx = pbrs_amd.Context(0)  # no path state yet: the first tile's 273 slots are the allocation
+        try:
+            ctx.set_pass_overlap(overlap)
+            ctx.upload(pbrs_amd.HostScene(sb))
+            small, st = ctx.render(3, 3, depth, 31, tile=(0, 0, 13, 7), samples_per_pass=3)
+            assert st["passes"] == 3
+            assert (bits(small) == bits(ref[3][:7, :13])).all(), (name, "13 x 7")
+            square, st = ctx.render(2, 2, depth, 31, tile=(0, 0, 64, 64), samples_per_pass=4)
+            assert st["passes"] == 1
+            assert (bits(square) == bits(ref[2][:64, :64])).all(), (name, "64 x 64")
+            frame, st = ctx.render(2, 2, depth, 31, samples_per_pass=2)
+            assert st["passes"] == 2
+            assert (bits(frame) == bits(ref[2])).all(), (name, "frame")
+            again, _ = ctx.render(3, 3, depth, 31, tile=(0, 0, 13, 7), samples_per_pass=3)
+            assert (bits(again) == bits(ref[3][:7, :13])).all() and (bits(again) == bits(small)).all(), (name, "13 x 7 again")
+        finally:
+            ctx.close()
