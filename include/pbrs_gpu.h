@@ -801,7 +801,7 @@ int pbrs_temporal_accumulate_device(pbrs_ctx*, const pbrs_temporal_params*, cons
  * non-finite record needs no rule of its own: wq is not finite and the pixel has no history.  The id test, where asked for, still compares
  * instance'(q) with instance(p).  The scale rule holds unchanged (the records are not scaled).  Lights that move, and shadows or
  * reflections of a moving instance on other surfaces, are not followed: the history of such a pixel is stale until the depth, normal or
- * id test refuses it, as in SVGF.
+ * id test refuses it, as in SVGF, unless the call clips it to this frame's colours ("history clipping" below).
  * pbrs_temporal_accumulate_motion[_device] are pbrs_temporal_accumulate[_device] plus the table; motion == NULL with n_motion == 0 is
  * exactly that call (which forwards here), bit for bit.  The table is HOST memory in both variants and is read before the call returns:
  * the library copies it on the context's stream into a buffer of the context that grows on first need, so the device variant stays
@@ -842,6 +842,54 @@ int pbrs_motion_vectors(pbrs_ctx*, uint32_t w, uint32_t h, const pbrs_camera* ca
 int pbrs_motion_vectors_device(pbrs_ctx*, uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev,
                                const float* depth_device, const uint32_t* instance_device, const pbrs_instance_motion* motion,
                                uint32_t n_motion, float* motion_out_device, float* prev_depth_out_device);
+
+/* ---- history clipping ------------------------------------------------------------------------------------ */
+/* Temporal accumulation that clips the reprojected history to this frame's colours.  The surface under a moving shadow or under a light
+ * that is switched does not move: its depth, normal and id never refuse the history, and the old lighting stays until the running mean
+ * forgets it, max_history frames later.  Neighbourhood clipping bounds that: before the blend the history colour is clamped to
+ * mean +- gamma * sigma of this frame's colours over the (2 * radius + 1)^2 window around the pixel, per channel.
+ * The rule sits between rules B and C of pbrs_temporal_accumulate (with the motion step of pbrs_temporal_accumulate_motion) and applies
+ * only to a pixel that has a history (W != 0).  The same f32 arithmetic without fused multiply-add, in the order written; rgb is
+ * frame->rgb, H, h1, h2, n are rule B's:
+ *   Box.  From s1 = s2 = (+0, +0, +0), cnt = +0, for dy = -radius .. radius (outer), for dx = -radius .. radius (inner), q = p + (dx, dy):
+ *     q outside the image is skipped; q is skipped if a channel of rgb(q) is not finite (pn_isfinite).  Otherwise, per channel c,
+ *     s1.c = s1.c + rgb(q).c, s2.c = s2.c + rgb(q).c * rgb(q).c, and cnt = cnt + 1.0f.  (p itself always counts: rule A has taken a
+ *     non-finite p.)  ic = 1.0f / cnt; mu.c = s1.c * ic; v.c = s2.c * ic - mu.c * mu.c; v.c = v.c < 0 ? +0 : v.c; sd.c = pn_sqrt(v.c);
+ *     lo.c = mu.c - gamma * sd.c; hi.c = mu.c + gamma * sd.c.
+ *   Clip.  Hc.c = lo.c <= hi.c ? pn_min(pn_max(H.c, lo.c), hi.c) : H.c: a NaN bound (an overflowed sum) clips nothing in that channel.
+ *   Moments and length.  If Hc.c == H.c for every c, then h1, h2 and n keep their bits.  Otherwise vh = h2 - h1 * h1;
+ *     vh = vh < 0 ? +0 : vh; a NaN vh becomes +0; h1 = lum(Hc); h2 = vh + h1 * h1; n = pn_min(n, clip_history): the mean moves and the
+ *     spread stays, and a shortened length sends the pixel back to the frame's variance, or to pbrs_spatial_variance, through rule D's
+ *     min_temporal.
+ *   Rule C then runs with Hc in the place of H; rule D is unchanged.
+ * A window that holds p alone gives sd = 0 and Hc = cur.  The box is of the noisy frame, so gamma trades the lag that is left against the
+ * noise the clip lets through: a history within gamma * sigma of the window's mean passes untouched.
+ * Scale rule.  As pbrs_temporal_accumulate's, under the same proviso: every box quantity scales with the colours (s1, mu, sd, lo, hi by
+ * 2^j; s2, v by 4^j; pn_sqrt of a value times 4^j is the root times 2^j), and cnt does not.
+ * pbrs_temporal_accumulate_clip[_device] are pbrs_temporal_accumulate_motion[_device] plus `clip`; clip == NULL is exactly that call
+ * (it forwards there), bit for bit.  The first frame of a sequence (history_in == NULL) has nothing to clip: `clip` is checked and not
+ * used.  Memory, stream and staging are the motion call's: the device variant allocates nothing, runs on the context's stream and does
+ * not wait.
+ * Refused with PBRS_E_INVALID beside what pbrs_temporal_accumulate_motion refuses: radius 0 or above PBRS_CLIP_MAX_RADIUS; gamma not
+ * finite or not > 0; clip_history NaN or < 1 (+inf is allowed: the length is never shortened); unknown flag bits; with clip != NULL,
+ * history_out->rgb == frame->rgb (the kernel gathers a halo of frame->rgb: what the unclipped call tolerates is a race here). */
+#define PBRS_CLIP_MAX_RADIUS 3u
+typedef struct pbrs_history_clip_params {
+    uint32_t radius;     /* 1 .. PBRS_CLIP_MAX_RADIUS: the window is (2 * radius + 1)^2 */
+    float gamma;         /* finite, > 0: the box is mean +- gamma * sigma */
+    float clip_history;  /* >= 1, +inf allowed: a clipped pixel's history length is at most this */
+    uint32_t flags;      /* none defined: must be 0 */
+} pbrs_history_clip_params; /* 16 B */
+int pbrs_temporal_accumulate_clip(pbrs_ctx*, const pbrs_temporal_params*, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                  const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
+                                  const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host,
+                                  float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion,
+                                  const pbrs_history_clip_params* clip);
+int pbrs_temporal_accumulate_clip_device(pbrs_ctx*, const pbrs_temporal_params*, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                         const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
+                                         const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
+                                         float* variance_out_device, const pbrs_instance_motion* motion, uint32_t n_motion,
+                                         const pbrs_history_clip_params* clip);
 
 /* ---- spatial variance estimate for short histories -------------------------------------------------------- */
 /* The piece of SVGF (Schied et al., HPG 2017) that joins its temporal and its spatial half.  Rule D of pbrs_temporal_accumulate takes the

@@ -277,6 +277,36 @@ class InstanceMotion(C.Structure):
     _fields_ = [("m", (C.c_float * 4) * 3), ("n", (C.c_float * 3) * 3), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
 
 
+class HistoryClipParams(C.Structure):
+    """pbrs_history_clip_params (include/pbrs_gpu.h, "history clipping"): the radius of the window whose colour box the reprojected
+    history is clipped to, the box's half width in standard deviations, and the most history a clipped pixel keeps (+inf: all of it)."""
+    MAX_RADIUS = 3
+    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float), ("clip_history", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def make(cls, radius=1, gamma=1.0, clip_history=None):
+        p = cls()
+        p.radius, p.gamma, p.clip_history = radius, gamma, float("inf") if clip_history is None else clip_history
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _history_clip(clip):
+    """temporal_accumulate's `clip` -> a HistoryClipParams or None: None or False is the call without a clip, True the defaults, a dict
+    HistoryClipParams.make's keywords (an unknown one fails here)."""
+    if clip is None or clip is False:
+        return None
+    if isinstance(clip, HistoryClipParams):
+        return clip
+    if clip is True:
+        return HistoryClipParams.make()
+    if isinstance(clip, dict):
+        return HistoryClipParams.make(**clip)
+    raise ValueError("clip is None, True, a dict of HistoryClipParams.make's keywords or a HistoryClipParams")
+
+
 class SpatialVarianceParams(C.Structure):
     """pbrs_spatial_variance_params (include/pbrs_gpu.h, "spatial variance estimate for short histories"): image size, the window's
     radius, flags, the two guide sigmas of the denoisers and the history length below which a pixel's variance is estimated."""
@@ -347,6 +377,7 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device",
                "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device", "pbrs_temporal_accumulate_motion",
                "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device",
+               "pbrs_temporal_accumulate_clip", "pbrs_temporal_accumulate_clip_device",
                "pbrs_spatial_variance", "pbrs_spatial_variance_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
@@ -438,6 +469,8 @@ def gpu_lib():
         L.pbrs_temporal_accumulate_device.argtypes = [C.c_void_p] * 9
         L.pbrs_temporal_accumulate_motion.argtypes = [C.c_void_p] * 10 + [C.c_uint32]
         L.pbrs_temporal_accumulate_motion_device.argtypes = L.pbrs_temporal_accumulate_motion.argtypes
+        L.pbrs_temporal_accumulate_clip.argtypes = L.pbrs_temporal_accumulate_motion.argtypes + [C.c_void_p]
+        L.pbrs_temporal_accumulate_clip_device.argtypes = L.pbrs_temporal_accumulate_clip.argtypes
         L.pbrs_motion_vectors.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]
         L.pbrs_motion_vectors_device.argtypes = L.pbrs_motion_vectors.argtypes
         L.pbrs_spatial_variance.argtypes = [C.c_void_p] * 7
@@ -1059,15 +1092,18 @@ class Context:
         return ptrs, keep
 
     def temporal_accumulate(self, rgb, depth, camera, variance=None, normal=None, instance=None, history=None, prev=None, camera_prev=None,
-                            return_variance=True, motion=None, **params):
+                            return_variance=True, motion=None, clip=None, **params):
         """Temporal accumulation (include/pbrs_gpu.h, pbrs_temporal_accumulate) of an (h, w, 3) f32 image, its depth AOV and what else
         of its variance, normal and instance AOVs is given, rendered through `camera`.  `history` = the dict an earlier call returned
         (None: the first frame of a sequence), `prev` = {"depth", "normal", "instance"} of that earlier frame, `camera_prev` its Camera.
         -> ({"rgb": (h, w, 3), "moments": (h, w, 2), "length": (h, w)}, variance (h, w)), all f32: the new history, whose rgb is the
         accumulated image, and the variance of its pixels' luminance (None with return_variance=False).  `motion`: the table of
         api.instance_motion for sequences in which instances move (pbrs_temporal_accumulate_motion; needs `instance`); None is the call
-        without one.  params: TemporalParams.make's keywords."""
+        without one.  `clip`: True, a dict of HistoryClipParams.make's keywords or a HistoryClipParams clips the reprojected history to
+        the colour box of this frame's neighbourhood (pbrs_temporal_accumulate_clip: shadows and lights that move); None is the call
+        without it.  params: TemporalParams.make's keywords."""
         table = _motion_args(motion)
+        cp = _history_clip(clip)
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
         h, w, _ = rgb.shape
         p = TemporalParams.make(w, h, **params)
@@ -1087,20 +1123,23 @@ class Context:
         args = (self._h, C.addressof(p), C.addressof(camera), C.addressof(camera_prev) if camera_prev else None, C.addressof(frame),
                 C.addressof(guides) if guides else None, C.addressof(hin) if hin else None, C.addressof(hout),
                 vout.ctypes.data if return_variance else None)
-        if motion is None:
+        if cp is not None:
+            self._check(self._L.pbrs_temporal_accumulate_clip(*args, *table, C.addressof(cp)), "pbrs_temporal_accumulate_clip")
+        elif motion is None:
             self._check(self._L.pbrs_temporal_accumulate(*args), "pbrs_temporal_accumulate")
         else:
             self._check(self._L.pbrs_temporal_accumulate_motion(*args, *table), "pbrs_temporal_accumulate_motion")
         return out, vout
 
     def temporal_accumulate_device(self, frame_device_ptrs, history_out_device_ptrs, w, h, camera, history_in_device_ptrs=None,
-                                   prev_device_ptrs=None, camera_prev=None, variance_out_device_ptr=None, motion=None, **params):
+                                   prev_device_ptrs=None, camera_prev=None, variance_out_device_ptr=None, motion=None, clip=None, **params):
         """temporal_accumulate() on caller-owned device memory: {name: pointer} dicts with the names of TemporalFrame, TemporalHistory
         and TemporalGuides.  Runs on the context's stream behind whatever was queued there (a render_aovs_var_device before it and a
         denoise_var_device after it need no synchronisation in between) and does not wait: valid after `collect_stats()`.  The history
         written must not share a plane with the history read.  `motion` (host memory, as in temporal_accumulate) is copied on that
-        stream before the call returns."""
+        stream before the call returns.  `clip`: as temporal_accumulate's; the history written must then not be the frame's rgb plane."""
         table = _motion_args(motion)
+        cp = _history_clip(clip)
         p = TemporalParams.make(w, h, **params)
         frame = _temporal_struct(TemporalFrame, TEMPORAL_FRAME, frame_device_ptrs, "frame")
         hout = _temporal_struct(TemporalHistory, TEMPORAL_HISTORY, history_out_device_ptrs, "history")
@@ -1110,7 +1149,9 @@ class Context:
             guides = _temporal_struct(TemporalGuides, TEMPORAL_GUIDES, prev_device_ptrs or {}, "previous guide")
         args = (self._h, C.addressof(p), C.addressof(camera), C.addressof(camera_prev) if camera_prev else None, C.addressof(frame),
                 C.addressof(guides) if guides else None, C.addressof(hin) if hin else None, C.addressof(hout), C.c_void_p(variance_out_device_ptr))
-        if motion is None:
+        if cp is not None:
+            self._check(self._L.pbrs_temporal_accumulate_clip_device(*args, *table, C.addressof(cp)), "pbrs_temporal_accumulate_clip_device")
+        elif motion is None:
             self._check(self._L.pbrs_temporal_accumulate_device(*args), "pbrs_temporal_accumulate_device")
         else:
             self._check(self._L.pbrs_temporal_accumulate_motion_device(*args, *table), "pbrs_temporal_accumulate_motion_device")
@@ -1201,7 +1242,7 @@ class Context:
         return sp
 
     def render_temporal(self, cameras, strata_x, strata_y, depth, seeds, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                        temporal=None, spatial=None, **params):
+                        temporal=None, spatial=None, clip=None, **params):
         """A sequence of frames of the uploaded scene, one per Camera of `cameras` with the seed of `seeds` at the same place, each
         rendered with its guides and its variance, accumulated against the generator's own history (temporal_accumulate_device; the
         history and the guides it is tested against live in ping-pong device buffers) and filtered (denoise_var_device on the
@@ -1211,7 +1252,8 @@ class Context:
         `spatial`: None is that chain; True, or a dict of SpatialVarianceParams.make's keywords, queues spatial_variance_device in place on
         the accumulated variance between the accumulation and the filter, so that pixels with a history shorter than min_temporal are
         filtered with an estimated variance instead of an unknown one (min_temporal follows `temporal` unless given, the id stop the
-        presence of the instance guide)."""
+        presence of the instance guide).  `clip`: None is that chain; True, a dict of HistoryClipParams.make's keywords or a
+        HistoryClipParams makes every accumulation after the first the clipped one (temporal_accumulate's `clip`)."""
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -1219,11 +1261,11 @@ class Context:
         if len(cameras) != len(seeds):
             raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip):
             yield out[:4]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                         temporal=None, motion_vectors=False, spatial=None, **params):
+                         temporal=None, motion_vectors=False, spatial=None, clip=None, **params):
         """render_temporal for sequences in which instances move.  `frames` yields (HostScene, Camera or None, seed): every frame's scene
         is uploaded (the same instances in the same order as the frame before, moved: instance ids are stable), rendered through the
         Camera (None: the scene's own) with its guides and its variance, accumulated with the table of instance_motion(scene, previous
@@ -1231,20 +1273,23 @@ class Context:
         motion_vectors=True a fifth entry, the (h, w, 2) motion vector AOV of the frame (zeros for the first one, which has no previous
         frame; motion_vectors="prev_depth": (h, w, 3), the depth the previous frame would have recorded as the third channel, +inf where
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
-        shadows of moving instances are not followed (include/pbrs_gpu.h).  `spatial`: as render_temporal's."""
+        shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
+        is `spatial`."""
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip):
             yield out if motion_vectors else out[:4]
 
-    def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None):
+    def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
+                         clip=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  `spatial`: None, or what queues the
-        spatial variance estimate between the accumulation and the filter (_spatial_params)."""
+        spatial variance estimate between the accumulation and the filter (_spatial_params).  `clip`: temporal_accumulate_device's."""
         tparams = dict(temporal or {})
         TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
+        clip = _history_clip(clip)
         sparams = self._spatial_params(spatial, tparams, guides)
         hip = hip_runtime()
         kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
@@ -1286,7 +1331,7 @@ class Context:
                 hist = [{n: dev[f"h_{n}{k}"].value for n in TEMPORAL_HISTORY} for k in (0, 1)]
                 self.temporal_accumulate_device(frame, hist[cur], w, h, cam, hist[old] if i else None,
                                                 {n: dev[f"{n}{old}"].value for n in kept} if i else None, cam_prev,
-                                                dev["acc_variance"].value, motion=table if i else None, **tparams)
+                                                dev["acc_variance"].value, motion=table if i else None, clip=clip, **tparams)
                 if motion_vectors and i:
                     self.motion_vectors_device(gp["depth"], dev["motion"].value, w, h, cam, cam_prev, gp.get("instance") if table else None, table,
                                                dev["prev_depth"].value)

@@ -55,6 +55,11 @@ Refusal check_temporal(const pbrs_temporal_params* p, const pbrs_camera* cam, co
 Refusal check_temporal_motion(const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
                               const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout,
                               const pbrs_instance_motion* motion, uint32_t n_motion);
+// check_temporal_motion, then the clip's own list (host/arg_checks_clip.cpp); clip == NULL is check_temporal_motion:
+// pbrs_temporal_accumulate_clip*.
+Refusal check_temporal_clip(const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame* f,
+                            const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history* hout,
+                            const pbrs_instance_motion* motion, uint32_t n_motion, const pbrs_history_clip_params* clip);
 Refusal check_motion_vectors(uint32_t w, uint32_t h, const pbrs_camera* cam, const pbrs_camera* cam_prev, const float* depth, const uint32_t* instance,
                              const pbrs_instance_motion* motion, uint32_t n_motion, const float* motion_out);
 Refusal check_spatial_variance(const pbrs_spatial_variance_params* p, const float* moments, const float* length, const pbrs_spatial_variance_guides* g,

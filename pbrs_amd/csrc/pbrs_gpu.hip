@@ -1410,6 +1410,12 @@ constexpr TemporalKernel kTemporal[2][2] = {{k_temporal<true, false, false>, k_t
 constexpr TemporalKernel kTemporalMotion[2][2] = {{k_temporal<true, false, false, true>, k_temporal<true, false, true, true>},
                                                   {k_temporal<true, true, false, true>, k_temporal<true, true, true, true>}};
 
+// with a clip (always with a history): [motion table][normal test][id test]
+using TemporalClipKernel = void (*)(TemporalIn, TemporalOut, TemporalConst, TemporalClipConst);
+constexpr TemporalClipKernel kTemporalClip[2][2][2] = {
+    {{k_temporal_clip<false, false, false>, k_temporal_clip<false, true, false>}, {k_temporal_clip<true, false, false>, k_temporal_clip<true, true, false>}},
+    {{k_temporal_clip<false, false, true>, k_temporal_clip<false, true, true>}, {k_temporal_clip<true, false, true>, k_temporal_clip<true, true, true>}}};
+
 // The caller's table (host memory) into the context's copy, on the context's stream: ordered behind the kernels of earlier calls that read
 // the copy, and the runtime has taken the bytes when the call returns.  -> the device table in *dev (null without a table).
 int upload_motion_table(pbrs_ctx* c, const pbrs_instance_motion* motion, uint32_t n_motion, const pbrs_instance_motion** dev) {
@@ -1435,10 +1441,11 @@ void temporal_cameras(TemporalConst& k, const pbrs_camera& cam, const pbrs_camer
 }
 
 // The one launch on the context's stream (arguments checked; device pointers, the motion table the caller's host memory).  Without a
-// history no tap is read and the table is not needed.
+// history no tap is read and the table is not needed, and there is nothing to clip.  With a history and a clip: k_temporal_clip, one
+// 16 x 16 block per cell of the image.
 int temporal_launch(pbrs_ctx* c, const pbrs_temporal_params& p, const pbrs_camera& cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame& f,
                     const pbrs_temporal_guides* prev, const pbrs_temporal_history* hin, const pbrs_temporal_history& hout, float* variance_out,
-                    const pbrs_instance_motion* motion, uint32_t n_motion) {
+                    const pbrs_instance_motion* motion, uint32_t n_motion, const pbrs_history_clip_params* clip = nullptr) {
     TemporalConst k{};
     k.w = p.w, k.h = p.h;
     k.max_history = p.max_history, k.depth_tolerance = p.depth_tolerance, k.min_temporal = p.min_temporal;
@@ -1453,11 +1460,38 @@ int temporal_launch(pbrs_ctx* c, const pbrs_temporal_params& p, const pbrs_camer
         if (rc) return rc;
         in.n_motion = in.motion ? n_motion : 0u;
         fn = (in.motion ? kTemporalMotion : kTemporal)[f.normal != nullptr][(p.flags & PBRS_TEMPORAL_ID_TEST) != 0];
+        if (clip) {
+            const dim3 grid((p.w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p.h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
+            hipLaunchKernelGGL(kTemporalClip[in.motion != nullptr][f.normal != nullptr][(p.flags & PBRS_TEMPORAL_ID_TEST) != 0], grid, dim3(kBlock), 0,
+                               c->stream, in, TemporalOut{hout.rgb, hout.moments, hout.length, variance_out}, k,
+                               TemporalClipConst{clip->radius, clip->gamma, clip->clip_history});
+            HIPCHK(c, hipGetLastError());
+            return PBRS_OK;
+        }
     }
     const uint32_t P = p.w * p.h;
     hipLaunchKernelGGL(fn, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, in, TemporalOut{hout.rgb, hout.moments, hout.length, variance_out}, k);
     HIPCHK(c, hipGetLastError());
     return PBRS_OK;
+}
+
+// The host variants' call (arguments checked): the frame, the previous guides and the history staged, the launch, the new history and
+// the variance copied back, one wait.
+int temporal_staged(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev, const pbrs_temporal_frame& f,
+                    const pbrs_temporal_guides* prev_host, const pbrs_temporal_history* history_in_host, const pbrs_temporal_history& ho,
+                    float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion, const pbrs_history_clip_params* clip) {
+    const size_t P = (size_t)p->w * p->h;
+    const pbrs_temporal_guides g = history_in_host ? *prev_host : pbrs_temporal_guides{};  // without a history the previous frame is not read
+    const pbrs_temporal_history hi = history_in_host ? *history_in_host : pbrs_temporal_history{};
+    Staged s[] = {{f.rgb, 3}, {f.variance, 1}, {f.depth, 1}, {f.normal, 3}, {f.instance, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1},
+                  {hi.rgb, 3}, {hi.moments, 2}, {hi.length, 1},
+                  {nullptr, 3, ho.rgb}, {nullptr, 2, ho.moments}, {nullptr, 1, ho.length}, {nullptr, 1, variance_out_host}};
+    return run_staged(c, BUF_TEMPORAL_STAGE, "the temporal accumulation's staging", s, P, [&] {
+        const pbrs_temporal_frame fd{s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
+        const pbrs_temporal_guides gd{s[5].as<float>(), s[6].as<float>(), s[7].as<uint32_t>()};
+        const pbrs_temporal_history hid{s[8].as<float>(), s[9].as<float>(), s[10].as<float>()}, hod{s[11].as<float>(), s[12].as<float>(), s[13].as<float>()};
+        return temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>(), motion, n_motion, clip);
+    });
 }
 
 }  // namespace
@@ -1492,20 +1526,38 @@ int pbrs_temporal_accumulate_motion(pbrs_ctx* c, const pbrs_temporal_params* p, 
                                     float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion) {
     const int rc = enter(c, check_temporal_motion(p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host, motion, n_motion));
     if (rc) return rc;
-    const size_t P = (size_t)p->w * p->h;
-    const pbrs_temporal_frame& f = *frame_host;
-    const pbrs_temporal_history& ho = *history_out_host;
-    const pbrs_temporal_guides g = history_in_host ? *prev_host : pbrs_temporal_guides{};  // without a history the previous frame is not read
-    const pbrs_temporal_history hi = history_in_host ? *history_in_host : pbrs_temporal_history{};
-    Staged s[] = {{f.rgb, 3}, {f.variance, 1}, {f.depth, 1}, {f.normal, 3}, {f.instance, 1}, {g.depth, 1}, {g.normal, 3}, {g.instance, 1},
-                  {hi.rgb, 3}, {hi.moments, 2}, {hi.length, 1},
-                  {nullptr, 3, ho.rgb}, {nullptr, 2, ho.moments}, {nullptr, 1, ho.length}, {nullptr, 1, variance_out_host}};
-    return run_staged(c, BUF_TEMPORAL_STAGE, "the temporal accumulation's staging", s, P, [&] {
-        const pbrs_temporal_frame fd{s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
-        const pbrs_temporal_guides gd{s[5].as<float>(), s[6].as<float>(), s[7].as<uint32_t>()};
-        const pbrs_temporal_history hid{s[8].as<float>(), s[9].as<float>(), s[10].as<float>()}, hod{s[11].as<float>(), s[12].as<float>(), s[13].as<float>()};
-        return temporal_launch(c, *p, *cam, cam_prev, fd, &gd, history_in_host ? &hid : nullptr, hod, s[14].as<float>(), motion, n_motion);
-    });
+    return temporal_staged(c, p, cam, cam_prev, *frame_host, prev_host, history_in_host, *history_out_host, variance_out_host, motion, n_motion, nullptr);
+}
+
+// ---- history clipping (include/pbrs_gpu.h, device/temporal.h) ----
+static_assert(sizeof(pbrs_history_clip_params) == 16, "pbrs_history_clip_params is 16 B");
+static_assert(PBRS_CLIP_MAX_TILE <= PBRS_CLIP_PITCH && PBRS_CLIP_PITCH % 16u == 0, "k_temporal_clip's LDS rows hold the largest halo at a conflict-free pitch");
+
+int pbrs_temporal_accumulate_clip_device(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                         const pbrs_temporal_frame* frame_device, const pbrs_temporal_guides* prev_device,
+                                         const pbrs_temporal_history* history_in_device, const pbrs_temporal_history* history_out_device,
+                                         float* variance_out_device, const pbrs_instance_motion* motion, uint32_t n_motion,
+                                         const pbrs_history_clip_params* clip) {
+    if (!clip)
+        return pbrs_temporal_accumulate_motion_device(c, p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device,
+                                                      variance_out_device, motion, n_motion);
+    const int rc = enter(c, check_temporal_clip(p, cam, cam_prev, frame_device, prev_device, history_in_device, history_out_device, motion, n_motion, clip));
+    if (rc) return rc;
+    return temporal_launch(c, *p, *cam, cam_prev, *frame_device, prev_device, history_in_device, *history_out_device, variance_out_device, motion,
+                           n_motion, clip);
+}
+
+int pbrs_temporal_accumulate_clip(pbrs_ctx* c, const pbrs_temporal_params* p, const pbrs_camera* cam, const pbrs_camera* cam_prev,
+                                  const pbrs_temporal_frame* frame_host, const pbrs_temporal_guides* prev_host,
+                                  const pbrs_temporal_history* history_in_host, const pbrs_temporal_history* history_out_host,
+                                  float* variance_out_host, const pbrs_instance_motion* motion, uint32_t n_motion,
+                                  const pbrs_history_clip_params* clip) {
+    if (!clip)
+        return pbrs_temporal_accumulate_motion(c, p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host, variance_out_host, motion,
+                                               n_motion);
+    const int rc = enter(c, check_temporal_clip(p, cam, cam_prev, frame_host, prev_host, history_in_host, history_out_host, motion, n_motion, clip));
+    if (rc) return rc;
+    return temporal_staged(c, p, cam, cam_prev, *frame_host, prev_host, history_in_host, *history_out_host, variance_out_host, motion, n_motion, clip);
 }
 
 // ---- motion vectors (include/pbrs_gpu.h, device/temporal.h) ----

@@ -32,7 +32,10 @@ accumulation follows the instances through a motion table (Context.render_animat
 x and y in R and G (where the pixel's surface point was one frame ago minus where it is, in pixels), the previous depth in B.
 --spatial-variance (with --temporal): pixels whose history is shorter than the accumulation's min_temporal (the first frames, and
 disocclusions later) are filtered with a variance estimated over their neighbourhood instead of an unknown one (include/pbrs_gpu.h,
-pbrs_spatial_variance; render_temporal's spatial=True)."""
+pbrs_spatial_variance; render_temporal's spatial=True).
+--history-clip GAMMA [--history-clip-radius R] (with --temporal): the reprojected history is clipped to mean +- GAMMA * sigma of the
+frame's colours over the (2 R + 1)^2 window around the pixel (R 1 .. 3, default 1) before the blend, so that shadows of moving instances
+and lights that change do not lag (include/pbrs_gpu.h, pbrs_temporal_accumulate_clip; render_temporal's clip=)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -41,6 +44,7 @@ import pbrs_amd
 temporal = "--temporal" in sys.argv
 motion_vectors = "--motion-vectors" in sys.argv
 spatial_variance = "--spatial-variance" in sys.argv
+history_clip = None  # HistoryClipParams.make's keywords
 spin, spin_deg = [], 0.0
 aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
@@ -51,7 +55,7 @@ denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 frames, orbit = 0, 0.0
-for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -64,6 +68,10 @@ for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--denoise-iteration
             spin = [int(v) for v in value.split(",") if v]
         elif flag == "--spin-deg":
             spin_deg = float(value)
+        elif flag == "--history-clip":
+            history_clip = dict(history_clip or {}, gamma=float(value))
+        elif flag == "--history-clip-radius":
+            history_clip = dict(history_clip or {}, radius=int(value))
         elif flag == "--denoise-iterations":
             denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
         elif flag == "--matte":
@@ -137,12 +145,14 @@ if frames:
         sys.exit("--spin and --motion-vectors go with --frames N --temporal")
     if spatial_variance and not temporal:
         sys.exit("--spatial-variance goes with --frames N --temporal")
+    if history_clip is not None and (not temporal or "gamma" not in history_clip):
+        sys.exit("--history-clip GAMMA goes with --frames N --temporal, --history-clip-radius with --history-clip")
     spatial = True if spatial_variance else None
     if spin or motion_vectors:
         sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
-                                        spatial=spatial, **denoise_var_params)
+                                        spatial=spatial, clip=history_clip, **denoise_var_params)
     elif temporal:
-        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, **denoise_var_params)
+        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, clip=history_clip, **denoise_var_params)
     else:
         sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
     for k, images in enumerate(sequence):
