@@ -951,6 +951,94 @@ int pbrs_spatial_variance_device(pbrs_ctx*, const pbrs_spatial_variance_params*,
                                  const pbrs_spatial_variance_guides* guides_device, const float* variance_in_device,
                                  float* variance_out_device);
 
+/* ---- display transform ----------------------------------------------------------------------------------------- */
+/* The last step of the image pipeline on the device: an f32 radiance plane (a render, an accumulated or a filtered image) becomes 8-bit
+ * RGBA, 4 B per pixel ready to show, through an exposure, a tone curve, a transfer function and a quantiser.  The exposure is given, or
+ * follows the image (PBRS_DISPLAY_AUTO_EXPOSURE): the trimmed log-average luminance of the frame, read from a 512-bin histogram, is mapped
+ * to `key`, and a sequence eases from one frame's exposure to the next.  An image operation like pbrs_denoise: it needs a context (device,
+ * stream) and no uploaded scene.
+ * Nothing below depends on the order in which pixels arrive, and there is no float reduction: the histogram and its resolve are integer
+ * arithmetic, the per-pixel part is f32 without fused multiply-add, in the order written.  pn_* is include/pbrs_numeric.h;
+ * lum(c) = (0.21267127f * c.r + 0.71515972f * c.g) + 0.07216883f * c.b.  rgb is w * h pixels, row-major, 3 floats each; rgba8_out is
+ * w * h words, row-major.
+ *   Histogram.  Runs when PBRS_DISPLAY_AUTO_EXPOSURE is set or io->histogram_out is given.  Y = lum(rgb(p)) of the input as given,
+ *     u = pn_bits(Y).  A pixel is counted iff 0x2F800000 <= u < 0x7F800000: Y is finite and >= 2^-32 (zeros, negatives, NaN, +-inf and
+ *     smaller values are not).  Its bin is min((u - 0x2F800000) >> 20, 511): eight bins per octave from 2^-32 on, taken from the exponent
+ *     and three mantissa bits, without a logarithm; bin 511, [2^31.875, 2^32), also holds everything above.  Counts n_b are u32 and only
+ *     ever added as integers.  histogram_out receives the PBRS_DISPLAY_BINS counts.
+ *   Resolve (PBRS_DISPLAY_AUTO_EXPOSURE).  Integers, 64-bit where needed, until the last step.  N = sum of n_b.
+ *     lo = (N * low_q16) >> 16, hi = (N * high_q16) >> 16; if hi == lo then lo = 0, hi = N.  K = hi - lo.  With c_b the exclusive prefix
+ *     sum of n (the rank of the bin's first pixel), k_b = the size of [c_b, c_b + n_b) intersected with [lo, hi): the pixels of the bin
+ *     whose rank is kept.  S = sum of k_b * (2 * b + 1).  Q = (S << 8) / K (integer division): the mean log2 luminance of the kept
+ *     pixels plus 32, in 1/4096 octave, every pixel counted at the middle of its bin.
+ *     Lavg = pn_ldexp(pn_exp((float)(Q & 4095) * (0.6931472f * 0.000244140625f)), (int)(Q >> 12) - 32).
+ *     a = pn_clamp(key / Lavg, min_exposure, max_exposure).  With io->exposure_in whose value prev is finite and > 0:
+ *     e = prev + (a - prev) * adapt; otherwise e = a.  With N == 0 (nothing counted): e = prev if it is finite and > 0, else 1.0f.
+ *     Without PBRS_DISPLAY_AUTO_EXPOSURE: e = 1.0f, and exposure_in is not read.
+ *     exposure_out receives e.  scale = e * exposure.
+ *   Per pixel at (x, y) and per channel c of rgb(p):
+ *     v = c * scale; v = v > 0 ? v : +0 (NaN, negatives and -0 become +0); v = pn_min(v, 65504.0f).
+ *     Curve.  PBRS_CURVE_NONE: t = v.  PBRS_CURVE_REINHARD: t = (v * (1.0f + v * iw2)) / (1.0f + v) with iw2 = 1.0f / (white * white),
+ *       which is +0 for white = +inf (plain Reinhard).  PBRS_CURVE_ACES (Narkowicz' fit):
+ *       t = (v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f).  Then t = t < 1.0f ? t : 1.0f.
+ *     Encode.  PBRS_ENCODE_SQRT: g = sqrtf(t), correctly rounded (the reference's gamma_encode).  PBRS_ENCODE_SRGB: t <= 0.0031308f gives
+ *       g = 12.92f * t; t >= 1.0f gives g = 1.0f; otherwise g = 1.055f * pn_exp(pn_ln(t) * (1.0f / 2.4f)) - 0.055f.  (The formula gives
+ *       0.99999994 at t = 1, which truncation would turn into 254: hence the middle case.)
+ *     Quantise.  q = g * 255.0f + d; byte = q >= 255.0f ? 255 : (uint32_t)q.  PBRS_QUANT_TRUNC: d = 0 (the reference's to_u8).
+ *       PBRS_QUANT_ROUND: d = 0.5f.  PBRS_QUANT_DITHER: d = ((float)M[y & 3][x & 3] + 0.5f) * 0.0625f with the 4 x 4 Bayer matrix
+ *       M = {{0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}}.
+ *     rgba8_out(p) = r | g << 8 | b << 16 | 255u << 24.
+ * Scale rule.  With PBRS_DISPLAY_AUTO_EXPOSURE, no exposure_in, the clamp inactive (min_exposure < key / Lavg < max_exposure at both
+ * scales) and no counted pixel's luminance leaving [2^-32, 2^32) at either scale (nor a product that depends on the scale overflowing
+ * or falling below the smallest normal f32), the image times 2^j gives the same bytes bit for bit: every bin moves by exactly 8 * j, Q by
+ * 4096 * j, Lavg by 2^j and e by 2^-j.  The resolve is integer so that this holds.
+ * With the reference's settings (exposure 1, PBRS_CURVE_NONE, PBRS_ENCODE_SQRT, PBRS_QUANT_TRUNC, no flag) the bytes are those
+ * pbrs_host_write_png writes (include/pbrs_host.h).
+ * Pointers are host memory for pbrs_display, which stages the image and the result (12 + 4 B per pixel) on first use and synchronises
+ * before it returns; device memory for pbrs_display_device (the io struct itself is host memory, its pointers device memory), which runs
+ * on the context's stream (pbrs_set_stream honoured) and does not wait.  The applied exposure travels in a device word: a sequence that
+ * hands one frame's exposure_out to the next frame's exposure_in needs no synchronisation between frames.  `io` may be NULL, and so may
+ * each of its pointers; exposure_out may be exposure_in.  A context that never calls this allocates nothing; one that does holds one small
+ * scratch (the histogram and the exposure word, about 2 KiB), zeroed on the stream before each call that fills it.  The vector path of the
+ * per-pixel kernel needs rgb and rgba8_out 16-byte aligned; other pointers take a scalar path with the same bytes.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, rgb or rgba8_out; w or h 0; an unknown curve, encode or quantize
+ * value; unknown flag bits; exposure or key not finite or <= 0; white NaN or <= 0; min_exposure or max_exposure not finite or <= 0, or
+ * min_exposure > max_exposure; adapt outside (0, 1]; low_q16 >= high_q16 or high_q16 > 65536; rgba8_out equal to rgb.  key, min_exposure,
+ * max_exposure, adapt, low_q16 and high_q16 are checked only with PBRS_DISPLAY_AUTO_EXPOSURE.  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_DISPLAY_BINS 512u
+#define PBRS_CURVE_NONE 0u
+#define PBRS_CURVE_REINHARD 1u
+#define PBRS_CURVE_ACES 2u
+#define PBRS_ENCODE_SQRT 0u /* the reference's gamma_encode */
+#define PBRS_ENCODE_SRGB 1u
+#define PBRS_QUANT_TRUNC 0u /* the reference's to_u8 */
+#define PBRS_QUANT_ROUND 1u
+#define PBRS_QUANT_DITHER 2u
+#define PBRS_DISPLAY_AUTO_EXPOSURE 1u
+typedef struct pbrs_display_params {
+    uint32_t w, h;                    /* image size */
+    uint32_t curve, encode, quantize; /* PBRS_CURVE_*, PBRS_ENCODE_*, PBRS_QUANT_* */
+    uint32_t flags;                   /* PBRS_DISPLAY_* */
+    float exposure;                   /* finite, > 0: multiplies the image (with AUTO_EXPOSURE: a compensation on top) */
+    float key;                        /* AUTO_EXPOSURE: the value the trimmed log-average luminance is mapped to (0.18) */
+    float white;                      /* REINHARD: the value mapped to 1; > 0, +inf allowed (plain Reinhard) */
+    float min_exposure, max_exposure; /* AUTO_EXPOSURE: finite, 0 < min <= max */
+    float adapt;                      /* AUTO_EXPOSURE with exposure_in: in (0, 1]; 1 = jump to the new exposure */
+    uint32_t low_q16, high_q16;       /* AUTO_EXPOSURE: ranks kept, in 1/65536 of the counted pixels; low < high <= 65536 */
+    uint32_t pad[2];
+} pbrs_display_params; /* 64 B */
+typedef struct pbrs_display_io { /* each pointer may be NULL */
+    const float* exposure_in;  /* one float: the previous frame's exposure_out */
+    float* exposure_out;       /* one float: e */
+    uint32_t* histogram_out;   /* PBRS_DISPLAY_BINS words */
+} pbrs_display_io;
+/* ACES, sRGB, rounding, no flag, exposure 1, key 0.18, white +inf, exposure limits 2^-20 and 2^20, adapt 1, ranks 6554 .. 62259 (the
+ * darkest 10 % and the brightest 5 % are trimmed); `out` NULL does nothing.  Host code: needs no context. */
+void pbrs_display_params_default(uint32_t w, uint32_t h, pbrs_display_params* out);
+int pbrs_display(pbrs_ctx*, const pbrs_display_params*, const float* rgb_host, const pbrs_display_io* io_host, uint32_t* rgba8_out_host);
+int pbrs_display_device(pbrs_ctx*, const pbrs_display_params*, const float* rgb_device, const pbrs_display_io* io_device,
+                        uint32_t* rgba8_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,9 @@ int pbrs_loaded_scene_filter(const pbrs_loaded_scene*, pbrs_pixel_filter* out);
  * row-major, 3 floats per pixel, as pbrs_render_tile returns it. */
 int pbrs_host_write_exr(const char* path, const float* rgb, uint32_t width, uint32_t height);
 int pbrs_host_write_png(const char* path, const float* rgb, uint32_t width, uint32_t height);
+/* The PNG of pixels that are 8-bit already: `rgba8` is row-major, one word r | g << 8 | b << 16 | a << 24 per pixel, as pbrs_display
+ * (include/pbrs_gpu.h) returns it; alpha is dropped. */
+int pbrs_host_write_png_rgba8(const char* path, const uint32_t* rgba8, uint32_t width, uint32_t height);
 const char* pbrs_host_io_error(void);
 
 #ifdef __cplusplus

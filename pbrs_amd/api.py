@@ -327,6 +327,56 @@ class SpatialVarianceParams(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DisplayParams(C.Structure):
+    """pbrs_display_params (include/pbrs_gpu.h, "display transform"): image size, tone curve, transfer function, quantiser, flags, the
+    exposure, and what the auto exposure reads (key, exposure limits, adapt, the ranks kept); white is the Reinhard curve's."""
+    CURVES = {"none": 0, "reinhard": 1, "aces": 2}
+    ENCODES = {"sqrt": 0, "srgb": 1}
+    QUANTIZERS = {"trunc": 0, "round": 1, "dither": 2}
+    AUTO_EXPOSURE = 1
+    BINS = 512
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("curve", C.c_uint32), ("encode", C.c_uint32), ("quantize", C.c_uint32),
+                ("flags", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("white", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adapt", C.c_float), ("low_q16", C.c_uint32), ("high_q16", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, w, h, curve="aces", encode="srgb", quantize="round", auto=False, exposure=1.0, key=0.18, white=None, min_exposure=2.0 ** -20,
+             max_exposure=2.0 ** 20, adapt=1.0, low_q16=6554, high_q16=62259):
+        """The defaults are pbrs_display_params_default's; curve, encode and quantize by name (or by their number); white None = +inf."""
+        p = cls()
+        p.w, p.h = w, h
+        p.curve = cls.CURVES[curve] if isinstance(curve, str) else curve
+        p.encode = cls.ENCODES[encode] if isinstance(encode, str) else encode
+        p.quantize = cls.QUANTIZERS[quantize] if isinstance(quantize, str) else quantize
+        p.flags = cls.AUTO_EXPOSURE if auto else 0
+        p.exposure, p.key, p.white = exposure, key, float("inf") if white is None else white
+        p.min_exposure, p.max_exposure, p.adapt = min_exposure, max_exposure, adapt
+        p.low_q16, p.high_q16 = low_q16, high_q16
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+class DisplayIO(C.Structure):
+    """pbrs_display_io: the previous exposure (one float), where this call's goes, where the 512 histogram counts go; each may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("exposure_in", "exposure_out", "histogram_out")]
+
+
+def _display_params(display):
+    """render_temporal's / render_animation's `display` -> DisplayParams.make's keywords, or None: None or False is the sequence
+    without a display transform, True the defaults with the auto exposure, a dict the keywords (auto=True unless it says otherwise).  An
+    unknown keyword fails here."""
+    if display is None or display is False:
+        return None
+    if display is not True and not isinstance(display, dict):
+        raise ValueError("display is None, True or a dict of DisplayParams.make's keywords")
+    dp = {} if display is True else dict(display)
+    dp.setdefault("auto", True)
+    DisplayParams.make(1, 1, **dp)
+    return dp
+
+
 class SpatialVarianceGuides(C.Structure):
     """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]
@@ -378,11 +428,12 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device", "pbrs_temporal_accumulate_motion",
                "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device",
                "pbrs_temporal_accumulate_clip", "pbrs_temporal_accumulate_clip_device",
-               "pbrs_spatial_variance", "pbrs_spatial_variance_device"]
+               "pbrs_spatial_variance", "pbrs_spatial_variance_device",
+               "pbrs_display_params_default", "pbrs_display", "pbrs_display_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
-                "pbrs_host_write_exr", "pbrs_host_write_png", "pbrs_host_io_error"]
+                "pbrs_host_write_exr", "pbrs_host_write_png", "pbrs_host_write_png_rgba8", "pbrs_host_io_error"]
 
 _host = None
 _gpu = None
@@ -417,6 +468,7 @@ def host_lib():
         L.pbrs_host_load_error.restype = C.c_char_p
         L.pbrs_host_write_exr.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.pbrs_host_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.pbrs_host_write_png_rgba8.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.pbrs_host_io_error.restype = C.c_char_p
         _host = L
     return _host
@@ -475,6 +527,10 @@ def gpu_lib():
         L.pbrs_motion_vectors_device.argtypes = L.pbrs_motion_vectors.argtypes
         L.pbrs_spatial_variance.argtypes = [C.c_void_p] * 7
         L.pbrs_spatial_variance_device.argtypes = [C.c_void_p] * 7
+        L.pbrs_display_params_default.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+        L.pbrs_display_params_default.restype = None
+        L.pbrs_display.argtypes = [C.c_void_p] * 5
+        L.pbrs_display_device.argtypes = [C.c_void_p] * 5
         _gpu = L
     return _gpu
 
@@ -593,6 +649,21 @@ def write_image(path, rgb):
     h, w, _ = rgb.shape
     fn = host_lib().pbrs_host_write_exr if str(path).lower().endswith(".exr") else host_lib().pbrs_host_write_png
     rc = fn(os.fsencode(path), rgb.ctypes.data, w, h)
+    if rc != 0:
+        raise PbrsError(f"writing {path} failed ({rc}): {host_lib().pbrs_host_io_error().decode()}")
+
+
+def write_image_u8(path, rgba8):
+    """The 8-bit PNG of an (h, w, 4) or (h, w, 3) uint8 image that is display-ready already (Context.display): the bytes go into the
+    file as they are, alpha is dropped."""
+    img = np.asarray(rgba8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError(f"an 8-bit image is (h, w, 4) or (h, w, 3) uint8, not {img.dtype} {img.shape}")
+    h, w, ch = img.shape
+    if ch == 3:
+        img = np.concatenate([img, np.full((h, w, 1), 255, dtype=np.uint8)], axis=2)
+    words = np.ascontiguousarray(img).view("<u4")
+    rc = host_lib().pbrs_host_write_png_rgba8(os.fsencode(path), words.ctypes.data, w, h)
     if rc != 0:
         raise PbrsError(f"writing {path} failed ({rc}): {host_lib().pbrs_host_io_error().decode()}")
 
@@ -1229,6 +1300,41 @@ class Context:
                                                          C.addressof(g), C.c_void_p(variance_in_device_ptr), C.c_void_p(variance_out_device_ptr)),
                     "pbrs_spatial_variance_device")
 
+    def display(self, rgb, exposure_in=None, return_exposure=False, return_histogram=False, **params):
+        """The display transform (include/pbrs_gpu.h, pbrs_display) of an (h, w, 3) f32 image -> an (h, w, 4) uint8 array, RGBA with alpha
+        255: exposure, tone curve, transfer function, quantiser.  params: DisplayParams.make's keywords (auto=True: the exposure follows
+        the image's trimmed log-average luminance; `exposure_in`, a float, is then the previous frame's exposure, which `adapt` eases
+        from).  With return_exposure and / or return_histogram the result is a tuple: the image, then the applied auto exposure e (a
+        float32; 1 without auto), then the 512 counts of the luminance histogram (uint32)."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"the image is (h, w, 3), not {rgb.shape}")
+        h, w, _ = rgb.shape
+        p = DisplayParams.make(w, h, **params)
+        out = np.empty((h, w), dtype="<u4")
+        e_in = np.array([exposure_in], dtype=np.float32) if exposure_in is not None else None
+        e_out = np.zeros(1, dtype=np.float32) if return_exposure else None
+        hist = np.zeros(DisplayParams.BINS, dtype=np.uint32) if return_histogram else None
+        io = DisplayIO(*(a.ctypes.data if a is not None else None for a in (e_in, e_out, hist)))
+        self._check(self._L.pbrs_display(self._h, C.addressof(p), rgb.ctypes.data, C.addressof(io), out.ctypes.data), "pbrs_display")
+        img = out.view(np.uint8).reshape(h, w, 4)
+        if not (return_exposure or return_histogram):
+            return img
+        return (img,) + ((e_out[0],) if return_exposure else ()) + ((hist,) if return_histogram else ())
+
+    def display_device(self, rgb_device_ptr, rgba8_device_ptr, w, h, io_device_ptrs=None, **params):
+        """display() on caller-owned device memory: `io_device_ptrs` = {name: pointer} of exposure_in / exposure_out / histogram_out (one
+        float, one float, 512 words).  Runs on the context's stream behind whatever was queued there and does not wait: valid after
+        `collect_stats()`.  exposure_out may be exposure_in: a sequence carries its exposure in one device word."""
+        p = DisplayParams.make(w, h, **params)
+        io = DisplayIO()
+        for n, ptr in dict(io_device_ptrs or {}).items():
+            if n not in ("exposure_in", "exposure_out", "histogram_out"):
+                raise ValueError(f"unknown display io pointer {n!r}; known: exposure_in, exposure_out, histogram_out")
+            setattr(io, n, ptr)
+        self._check(self._L.pbrs_display_device(self._h, C.addressof(p), C.c_void_p(rgb_device_ptr), C.addressof(io), C.c_void_p(rgba8_device_ptr)),
+                    "pbrs_display_device")
+
     @staticmethod
     def _spatial_params(spatial, tparams, guides):
         """render_temporal's / render_animation's `spatial` -> SpatialVarianceParams.make's keywords, or None: min_temporal follows the
@@ -1242,7 +1348,7 @@ class Context:
         return sp
 
     def render_temporal(self, cameras, strata_x, strata_y, depth, seeds, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                        temporal=None, spatial=None, clip=None, **params):
+                        temporal=None, spatial=None, clip=None, display=None, **params):
         """A sequence of frames of the uploaded scene, one per Camera of `cameras` with the seed of `seeds` at the same place, each
         rendered with its guides and its variance, accumulated against the generator's own history (temporal_accumulate_device; the
         history and the guides it is tested against live in ping-pong device buffers) and filtered (denoise_var_device on the
@@ -1253,7 +1359,10 @@ class Context:
         the accumulated variance between the accumulation and the filter, so that pixels with a history shorter than min_temporal are
         filtered with an estimated variance instead of an unknown one (min_temporal follows `temporal` unless given, the id stop the
         presence of the instance guide).  `clip`: None is that chain; True, a dict of HistoryClipParams.make's keywords or a
-        HistoryClipParams makes every accumulation after the first the clipped one (temporal_accumulate's `clip`)."""
+        HistoryClipParams makes every accumulation after the first the clipped one (temporal_accumulate's `clip`).  `display`: None is
+        that chain; True, or a dict of DisplayParams.make's keywords (auto=True unless it says otherwise), queues display_device on each
+        frame's filtered image on the same stream, the exposure carried from frame to frame in a device word: the frame's stats gain
+        "display", the (h, w, 4) uint8 image, and "exposure", the auto exposure applied to it."""
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -1261,11 +1370,11 @@ class Context:
         if len(cameras) != len(seeds):
             raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display):
             yield out[:4]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                         temporal=None, motion_vectors=False, spatial=None, clip=None, **params):
+                         temporal=None, motion_vectors=False, spatial=None, clip=None, display=None, **params):
         """render_temporal for sequences in which instances move.  `frames` yields (HostScene, Camera or None, seed): every frame's scene
         is uploaded (the same instances in the same order as the frame before, moved: instance ids are stable), rendered through the
         Camera (None: the scene's own) with its guides and its variance, accumulated with the table of instance_motion(scene, previous
@@ -1274,23 +1383,25 @@ class Context:
         frame; motion_vectors="prev_depth": (h, w, 3), the depth the previous frame would have recorded as the third channel, +inf where
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
-        is `spatial`."""
+        are `spatial` and `display`."""
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display):
             yield out if motion_vectors else out[:4]
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None):
+                         clip=None, display=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  `spatial`: None, or what queues the
-        spatial variance estimate between the accumulation and the filter (_spatial_params).  `clip`: temporal_accumulate_device's."""
+        spatial variance estimate between the accumulation and the filter (_spatial_params).  `clip`: temporal_accumulate_device's.  `display`: None, or what queues the
+        display transform behind the filter (_display_params); only then are its two buffers allocated."""
         tparams = dict(temporal or {})
         TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
         clip = _history_clip(clip)
         sparams = self._spatial_params(spatial, tparams, guides)
+        dparams = _display_params(display)
         hip = hip_runtime()
         kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
         dev = {}
@@ -1315,6 +1426,8 @@ class Context:
                     sizes.update({n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides if n not in kept})
                     if motion_vectors:
                         sizes["motion"], sizes["prev_depth"] = 2 * w * h * 4, w * h * 4
+                    if dparams is not None:
+                        sizes["display"], sizes["exposure"] = w * h * 4, 4
                     for n, nbytes in sizes.items():
                         ptr = C.c_void_p()
                         if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
@@ -1339,7 +1452,15 @@ class Context:
                     self.spatial_variance_device(hist[cur]["moments"], hist[cur]["length"], dev["acc_variance"].value, dev["acc_variance"].value,
                                                  w, h, {n: gp[n] for n in kept}, **sparams)
                 self.denoise_var_device(hist[cur]["rgb"], dev["out"].value, w, h, dev["acc_variance"].value, gp, **params)
+                if dparams is not None:  # the first frame has no previous exposure; later ones read the word the last one wrote
+                    self.display_device(dev["out"].value, dev["display"].value, w, h,
+                                        {"exposure_in": dev["exposure"].value if i else None, "exposure_out": dev["exposure"].value}, **dparams)
                 stats = self.collect_stats()  # waits for the stream
+                if dparams is not None:
+                    shown, e = np.empty((h, w, 4), dtype=np.uint8), np.zeros(1, dtype=np.float32)
+                    if hip.hipMemcpy(shown.ctypes.data, dev["display"], shown.nbytes, 2) != 0 or hip.hipMemcpy(e.ctypes.data, dev["exposure"], 4, 2) != 0:
+                        raise PbrsError("hipMemcpy of a temporal sequence's display image failed")
+                    stats["display"], stats["exposure"] = shown, e[0]
                 images = []
                 for src in (dev["out"], dev[f"h_rgb{cur}"], dev["rgb"]):
                     img = np.empty((h, w, 3), dtype=np.float32)

@@ -64,5 +64,8 @@ Refusal check_motion_vectors(uint32_t w, uint32_t h, const pbrs_camera* cam, con
                              const pbrs_instance_motion* motion, uint32_t n_motion, const float* motion_out);
 Refusal check_spatial_variance(const pbrs_spatial_variance_params* p, const float* moments, const float* length, const pbrs_spatial_variance_guides* g,
                                const float* variance_in, const float* variance_out);
+// pbrs_display* (host/arg_checks_display.cpp, beside the filler pbrs_display_params_default).  `io` and its pointers may be NULL; the
+// fields only the auto exposure reads are checked only with PBRS_DISPLAY_AUTO_EXPOSURE.
+Refusal check_display(const pbrs_display_params* p, const float* rgb, const pbrs_display_io* io, const uint32_t* rgba8_out);
 
 }  // namespace pbrs

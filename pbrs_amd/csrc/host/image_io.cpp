@@ -49,6 +49,32 @@ unsigned char saturate_cast_u8(float f) {
     if (f >= 0.0f) return (unsigned char)(f * 255.0f);
     return 0;  // negative or NaN
 }
+// An 8-bit RGB PNG from `raw`: per row a filter byte (0) and 3 * width bytes; one zlib stream of unfiltered rows
+bool write_png_rows(const char* path, const std::vector<unsigned char>& raw, uint32_t width, uint32_t height) {
+    uLongf zlen = compressBound((uLong)raw.size());
+    std::vector<unsigned char> z(zlen);
+    if (compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) != Z_OK) {
+        g_io_error = "deflate failed";
+        return false;
+    }
+    z.resize(zlen);
+    std::vector<unsigned char> b = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    auto chunk = [&](const char* type, const std::vector<unsigned char>& data) {
+        put_be32(b, (uint32_t)data.size());
+        const size_t start = b.size();
+        b.insert(b.end(), type, type + 4);
+        b.insert(b.end(), data.begin(), data.end());
+        put_be32(b, (uint32_t)crc32(0L, b.data() + start, (uInt)(b.size() - start)));
+    };
+    std::vector<unsigned char> ihdr;
+    put_be32(ihdr, width);
+    put_be32(ihdr, height);
+    ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});  // 8-bit RGB, deflate, adaptive filtering, no interlace
+    chunk("IHDR", ihdr);
+    chunk("IDAT", z);
+    chunk("IEND", {});
+    return write_all(path, b);
+}
 
 }  // namespace
 
@@ -116,29 +142,22 @@ int pbrs_host_write_png(const char* path, const float* rgb, uint32_t width, uint
         raw.push_back(0);  // filter: none
         for (size_t k = 0; k < 3 * (size_t)width; ++k) raw.push_back(saturate_cast_u8(pn_sqrt(rgb[3 * (size_t)y * width + k])));
     }
-    uLongf zlen = compressBound((uLong)raw.size());
-    std::vector<unsigned char> z(zlen);
-    if (compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) != Z_OK) {
-        g_io_error = "deflate failed";
-        return PBRS_E_INVALID;
+    return write_png_rows(path, raw, width, height) ? PBRS_OK : PBRS_E_INVALID;
+}
+
+// The same file from pixels that are 8-bit already (pbrs_display's words, r | g << 8 | b << 16 | a << 24): alpha is dropped
+int pbrs_host_write_png_rgba8(const char* path, const uint32_t* rgba8, uint32_t width, uint32_t height) {
+    if (!path || !rgba8 || width == 0 || height == 0) return PBRS_E_INVALID;
+    std::vector<unsigned char> raw;
+    raw.reserve((size_t)height * (1 + 3 * (size_t)width));
+    for (uint32_t y = 0; y < height; ++y) {
+        raw.push_back(0);  // filter: none
+        for (uint32_t x = 0; x < width; ++x) {
+            const uint32_t v = rgba8[(size_t)y * width + x];
+            for (int k = 0; k < 3; ++k) raw.push_back((unsigned char)(v >> (8 * k)));
+        }
     }
-    z.resize(zlen);
-    std::vector<unsigned char> b = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-    auto chunk = [&](const char* type, const std::vector<unsigned char>& data) {
-        put_be32(b, (uint32_t)data.size());
-        const size_t start = b.size();
-        b.insert(b.end(), type, type + 4);
-        b.insert(b.end(), data.begin(), data.end());
-        put_be32(b, (uint32_t)crc32(0L, b.data() + start, (uInt)(b.size() - start)));
-    };
-    std::vector<unsigned char> ihdr;
-    put_be32(ihdr, width);
-    put_be32(ihdr, height);
-    ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});  // 8-bit RGB, deflate, adaptive filtering, no interlace
-    chunk("IHDR", ihdr);
-    chunk("IDAT", z);
-    chunk("IEND", {});
-    return write_all(path, b) ? PBRS_OK : PBRS_E_INVALID;
+    return write_png_rows(path, raw, width, height) ? PBRS_OK : PBRS_E_INVALID;
 }
 
 }  // extern "C"

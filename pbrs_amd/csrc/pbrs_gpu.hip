@@ -32,6 +32,7 @@
 #include "device/passes.h"
 #include "device/temporal.h"
 #include "device/spatial_variance.h"
+#include "device/display.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -141,6 +142,9 @@ enum BufferId {
     // spatial variance estimate (pbrs_spatial_variance, device/spatial_variance.h): the host variant's staging (moments, length, the three
     // guides, the variance, which is estimated in place, one after the other); the device variant needs nothing
     BUF_SPATIAL_STAGE,
+    // display transform (pbrs_display, device/display.h): the 512-word histogram, the scale word and the host variant's two exposure
+    // words (kDisplayScratchWords), and the host variant's staging (the image, the 8-bit result)
+    BUF_DISPLAY, BUF_DISPLAY_STAGE,
     N_BUFFERS
 };
 
@@ -1650,6 +1654,94 @@ int pbrs_spatial_variance(pbrs_ctx* c, const pbrs_spatial_variance_params* p, co
     return run_staged(c, BUF_SPATIAL_STAGE, "the spatial variance estimate's staging", s, P, [&] {
         const pbrs_spatial_variance_guides gd{s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
         return spatial_variance_launch(c, *p, s[0].as<float>(), s[1].as<float>(), gd, s[5].as<float>(), s[5].as<float>());
+    });
+}
+
+// ---- display transform (include/pbrs_gpu.h, device/display.h) ----
+static_assert(sizeof(pbrs_display_params) == 64, "pbrs_display_params is 64 B");
+static_assert(PBRS_DISPLAY_BINS == 512u && PBRS_DISPLAY_BINS % 64u == 0, "k_display_resolve holds the bins in one wave, eight per lane");
+
+namespace {
+
+using DisplayApplyKernel = void (*)(const float*, uint32_t*, DisplayApply);
+// [curve][encode][both planes 16-byte aligned]
+#define PBRS_DISPLAY_ROW(C) {{k_display_apply<C, PBRS_ENCODE_SQRT, false>, k_display_apply<C, PBRS_ENCODE_SQRT, true>}, \
+                             {k_display_apply<C, PBRS_ENCODE_SRGB, false>, k_display_apply<C, PBRS_ENCODE_SRGB, true>}}
+constexpr DisplayApplyKernel kDisplayApply[3][2][2] = {PBRS_DISPLAY_ROW(PBRS_CURVE_NONE), PBRS_DISPLAY_ROW(PBRS_CURVE_REINHARD), PBRS_DISPLAY_ROW(PBRS_CURVE_ACES)};
+#undef PBRS_DISPLAY_ROW
+
+uint32_t display_grid(uint32_t work, uint32_t cap = kDisplayMaxBlocks) { return std::min((work + kDisplayBlock - 1) / kDisplayBlock, cap); }
+
+// The launches on the context's stream (arguments checked; device pointers, `io` by value with NULL for what is not given).  Without the
+// auto exposure and without `histogram` (the caller wants the counts) only k_display_apply runs and the scratch is not touched.
+int display_launch(pbrs_ctx* c, const pbrs_display_params& p, const float* rgb, const pbrs_display_io& io, uint32_t* out, bool histogram) {
+    const uint32_t P = p.w * p.h;
+    const bool auto_exposure = (p.flags & PBRS_DISPLAY_AUTO_EXPOSURE) != 0;
+    DisplayApply a{};
+    a.w = p.w, a.P = P;
+    a.scale = p.exposure;  // e = 1
+    a.iw2 = 1.0f / (p.white * p.white);
+    a.d = p.quantize == PBRS_QUANT_ROUND ? 0.5f : 0.0f;
+    a.dither = p.quantize == PBRS_QUANT_DITHER;
+    a.exposure_out = io.exposure_out;
+    if (auto_exposure || histogram) {
+        uint32_t* scratch = c->buf[BUF_DISPLAY].as<uint32_t>();
+        HIPCHK(c, hipMemsetAsync(scratch, 0, PBRS_DISPLAY_BINS * sizeof(uint32_t), c->stream));
+        const bool rgb_aligned = (reinterpret_cast<uintptr_t>(rgb) & 15u) == 0;
+        hipLaunchKernelGGL(rgb_aligned ? k_display_hist<true> : k_display_hist<false>, dim3(display_grid((P + 3u) / 4u, kDisplayHistMaxBlocks)),
+                           dim3(kDisplayBlock), 0, c->stream, rgb, P, scratch);
+        HIPCHK(c, hipGetLastError());
+        float* scale_word = reinterpret_cast<float*>(scratch + kDisplayScaleWord);
+        const DisplayResolve r{auto_exposure ? 1u : 0u, p.exposure, p.key, p.min_exposure, p.max_exposure, p.adapt, p.low_q16, p.high_q16,
+                               auto_exposure ? io.exposure_in : nullptr, io.exposure_out, io.histogram_out};
+        hipLaunchKernelGGL(k_display_resolve, dim3(1), dim3(64), 0, c->stream, scratch, scale_word, r);
+        HIPCHK(c, hipGetLastError());
+        a.scale_word = scale_word;
+        a.exposure_out = nullptr;  // the resolve has written it
+    }
+    const bool aligned = ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+    hipLaunchKernelGGL(kDisplayApply[p.curve][p.encode][aligned], dim3(display_grid((P + 3u) / 4u)), dim3(kDisplayBlock), 0, c->stream, rgb, out, a);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+// The scratch, for the calls that fill it.
+int display_scratch(pbrs_ctx* c, bool needed) {
+    return needed ? c->buf[BUF_DISPLAY].grow(c, kDisplayScratchWords * sizeof(uint32_t), "the display transform's histogram") : PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_display_device(pbrs_ctx* c, const pbrs_display_params* p, const float* rgb_device, const pbrs_display_io* io_device, uint32_t* rgba8_out_device) {
+    int rc = enter(c, check_display(p, rgb_device, io_device, rgba8_out_device));
+    if (rc) return rc;
+    const pbrs_display_io io = io_device ? *io_device : pbrs_display_io{};
+    if ((rc = display_scratch(c, (p->flags & PBRS_DISPLAY_AUTO_EXPOSURE) || io.histogram_out))) return rc;
+    return display_launch(c, *p, rgb_device, io, rgba8_out_device, io.histogram_out != nullptr);
+}
+
+int pbrs_display(pbrs_ctx* c, const pbrs_display_params* p, const float* rgb_host, const pbrs_display_io* io_host, uint32_t* rgba8_out_host) {
+    int rc = enter(c, check_display(p, rgb_host, io_host, rgba8_out_host));
+    if (rc) return rc;
+    const pbrs_display_io io = io_host ? *io_host : pbrs_display_io{};
+    const bool auto_exposure = (p->flags & PBRS_DISPLAY_AUTO_EXPOSURE) != 0;
+    // the io words pass through the scratch: the histogram is copied back from where it was counted
+    if ((rc = display_scratch(c, auto_exposure || io.histogram_out || io.exposure_out))) return rc;
+    const size_t P = (size_t)p->w * p->h;
+    Staged s[] = {{rgb_host, 3}, {nullptr, 1, rgba8_out_host}};
+    return run_staged(c, BUF_DISPLAY_STAGE, "the display transform's staging", s, P, [&] {
+        uint32_t* scratch = c->buf[BUF_DISPLAY].as<uint32_t>();
+        pbrs_display_io iod{};
+        if (auto_exposure && io.exposure_in) {
+            iod.exposure_in = reinterpret_cast<const float*>(scratch + kDisplayPrevWord);
+            HIPCHK(c, hipMemcpyAsync(scratch + kDisplayPrevWord, io.exposure_in, sizeof(float), hipMemcpyHostToDevice, c->stream));
+        }
+        if (io.exposure_out) iod.exposure_out = reinterpret_cast<float*>(scratch + kDisplayExposureWord);
+        const int lrc = display_launch(c, *p, s[0].as<float>(), iod, s[1].as<uint32_t>(), io.histogram_out != nullptr);
+        if (lrc) return lrc;
+        if (io.exposure_out) HIPCHK(c, hipMemcpyAsync(io.exposure_out, scratch + kDisplayExposureWord, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (io.histogram_out) HIPCHK(c, hipMemcpyAsync(io.histogram_out, scratch, PBRS_DISPLAY_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        return (int)PBRS_OK;
     });
 }
 

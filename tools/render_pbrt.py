@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]] [--display none|reinhard|aces [--encode sqrt|srgb] [--auto-exposure] [--exposure X]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -35,7 +35,12 @@ disocclusions later) are filtered with a variance estimated over their neighbour
 pbrs_spatial_variance; render_temporal's spatial=True).
 --history-clip GAMMA [--history-clip-radius R] (with --temporal): the reprojected history is clipped to mean +- GAMMA * sigma of the
 frame's colours over the (2 R + 1)^2 window around the pixel (R 1 .. 3, default 1) before the blend, so that shadows of moving instances
-and lights that change do not lag (include/pbrs_gpu.h, pbrs_temporal_accumulate_clip; render_temporal's clip=)."""
+and lights that change do not lag (include/pbrs_gpu.h, pbrs_temporal_accumulate_clip; render_temporal's clip=).
+--display CURVE: also writes <out>.display.png, the image through the display transform on the GPU (include/pbrs_gpu.h, pbrs_display): the
+exposure (--exposure X, default 1; with --auto-exposure the trimmed log-average luminance is mapped to 0.18 and X is a compensation on
+top), the tone curve, the transfer function (--encode, default srgb) and rounding to 8 bits; the file holds the GPU's bytes.  With
+--frames N --temporal every frame's filtered image goes through it on the frame's stream (render_temporal's display=) and
+<out>.NNNN.display.png is written; the auto exposure then eases from frame to frame."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -45,6 +50,8 @@ temporal = "--temporal" in sys.argv
 motion_vectors = "--motion-vectors" in sys.argv
 spatial_variance = "--spatial-variance" in sys.argv
 history_clip = None  # HistoryClipParams.make's keywords
+display = None  # DisplayParams.make's keywords
+auto_exposure = "--auto-exposure" in sys.argv
 spin, spin_deg = [], 0.0
 aovs = "--aovs" in sys.argv
 filtered = "--pixel-filter" in sys.argv
@@ -55,7 +62,7 @@ denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 frames, orbit = 0, 0.0
-for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -72,6 +79,12 @@ for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "-
             history_clip = dict(history_clip or {}, gamma=float(value))
         elif flag == "--history-clip-radius":
             history_clip = dict(history_clip or {}, radius=int(value))
+        elif flag == "--display":
+            display = dict(display or {}, curve=value)
+        elif flag == "--encode":
+            display = dict(display or {}, encode=value)
+        elif flag == "--exposure":
+            display = dict(display or {}, exposure=float(value))
         elif flag == "--denoise-iterations":
             denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
         elif flag == "--matte":
@@ -85,7 +98,13 @@ for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "-
         else:
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
             denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
-sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal", "--motion-vectors", "--spatial-variance")]
+sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal", "--motion-vectors", "--spatial-variance", "--auto-exposure")]
+if display is not None or auto_exposure:
+    if "curve" not in (display or {}):
+        sys.exit("--encode, --exposure and --auto-exposure go with --display none|reinhard|aces")
+    if display["curve"] not in pbrs_amd.DisplayParams.CURVES or display.get("encode", "srgb") not in pbrs_amd.DisplayParams.ENCODES:
+        sys.exit("--display none|reinhard|aces [--encode sqrt|srgb]")
+    display["auto"] = auto_exposure
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -147,12 +166,15 @@ if frames:
         sys.exit("--spatial-variance goes with --frames N --temporal")
     if history_clip is not None and (not temporal or "gamma" not in history_clip):
         sys.exit("--history-clip GAMMA goes with --frames N --temporal, --history-clip-radius with --history-clip")
+    if display is not None and not temporal:
+        sys.exit("with --frames N, --display goes with --temporal")
     spatial = True if spatial_variance else None
     if spin or motion_vectors:
         sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
-                                        spatial=spatial, clip=history_clip, **denoise_var_params)
+                                        spatial=spatial, clip=history_clip, display=display, **denoise_var_params)
     elif temporal:
-        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, clip=history_clip, **denoise_var_params)
+        sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, clip=history_clip, display=display,
+                                       **denoise_var_params)
     else:
         sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
     for k, images in enumerate(sequence):
@@ -160,6 +182,8 @@ if frames:
         if temporal:
             pbrs_amd.write_image(f"{stem}.{k:04d}.accumulated{ext}", images[1])
             pbrs_amd.write_image(f"{stem}.{k:04d}.noisy{ext}", images[2])
+        if display is not None:
+            pbrs_amd.write_image_u8(f"{stem}.{k:04d}.display.png", images[3]["display"])
         if motion_vectors:
             pbrs_amd.write_image(f"{stem}.{k:04d}.motion.exr", images[4])
     print(f"{frames} frames of {hs.width}x{hs.height} at {msaa * msaa} spp, {orbit} degrees per frame"
@@ -192,6 +216,10 @@ if want_layers and (filtered or matte_key):  # like the AOVs beside a filtered i
     layers = ctx.render_passes(msaa, msaa, depth, 1, passes=want_layers, integrator=integrator)[1]
 pbrs_amd.write_image(out, img)
 stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
+if display is not None:
+    shown, e = ctx.display(img, return_exposure=True, **display)
+    pbrs_amd.write_image_u8(f"{stem}.display.png", shown)
+    print(f"-> {stem}.display.png ({display['curve']}, {display.get('encode', 'srgb')}, exposure {float(e) * display.get('exposure', 1.0):.4g})")
 if denoise:
     pbrs_amd.write_image(f"{stem}.denoised{ext}", ctx.denoise(img, **{n: buf[n] for n in guides}, **denoise_params))
     print(f"-> {stem}.denoised{ext}")
