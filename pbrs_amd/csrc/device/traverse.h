@@ -85,7 +85,9 @@ PD float qdiv(float nn, float d, float nr) {
     return __builtin_fmaf(e, nr, q0);
 }
 // geometry/src/bvh.rs:84-99 (same min/max/NaN conventions as dmath.h::slab_test)
-PD bool slab_rs(const pbrs_node& n, const RaySpace& R, float t_max) {
+// For a ray on the division-free test it also hands back the two numbers the split-plane cull of the closest-hit walk reads
+// (ClosestWalk::cull_children): t_low, and hi_el — where the ray leaves the box, whatever the extent.
+PD bool slab_rs(const pbrs_node& n, const RaySpace& R, float t_max, float& t_low, float& hi_el) {
     if (!R.fast) return slab_test(nmin(n), nmax(n), R.o, R.d, t_max);
     float t0x = qdiv(R.o.x - n.min[0], R.d.x, R.nr.x), t0y = qdiv(R.o.y - n.min[1], R.d.y, R.nr.y), t0z = qdiv(R.o.z - n.min[2], R.d.z, R.nr.z);
     float t1x = qdiv(R.o.x - n.max[0], R.d.x, R.nr.x), t1y = qdiv(R.o.y - n.max[1], R.d.y, R.nr.y), t1z = qdiv(R.o.z - n.max[2], R.d.z, R.nr.z);
@@ -93,11 +95,16 @@ PD bool slab_rs(const pbrs_node& n, const RaySpace& R, float t_max) {
     // to plain min/max (they differ only on NaN operands and on the sign of a zero, which no comparison sees):
     // v_min_f32 / v_max_f32 / v_min3 / v_max3 instead of compare+select chains.
     float lo_el = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t0x, t1x), __builtin_fminf(t0y, t1y)), __builtin_fminf(t0z, t1z));
-    float hi_el = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t0x, t1x), __builtin_fmaxf(t0y, t1y)), __builtin_fmaxf(t0z, t1z));
-    float t_low = __builtin_fmaxf(lo_el, 0.0f);
+    hi_el = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t0x, t1x), __builtin_fmaxf(t0y, t1y)), __builtin_fmaxf(t0z, t1z));
+    t_low = __builtin_fmaxf(lo_el, 0.0f);
     float t_high = __builtin_fminf(hi_el, t_max);  // minNum: a NaN extent is ignored, as f32::min does
     return t_low <= t_high;
 }
+PD bool slab_rs(const pbrs_node& n, const RaySpace& R, float t_max) {
+    float t_low = 0.0f, hi_el = 0.0f;
+    return slab_rs(n, R, t_max, t_low, hi_el);
+}
+#include "split_planes.h"
 #include "wide.h"
 
 // `self.transform.inverse().apply(*ray)` (tlas/src/instance.rs:51).  For an instance whose matrices are
@@ -167,6 +174,9 @@ PD uint32_t enter_instance(const DevScene& S, const pbrs_instance& in, uint32_t 
 // lanes of one wave that are in different phases of their walks still share the instruction stream (k_extend).
 #ifndef PBRS_EARLY_OUT  // a failed box test that leaves nothing pending below the instance goes to the boundary state at once
 #define PBRS_EARLY_OUT 1
+#endif
+#ifndef PBRS_SPLIT_PLANE_CULL  // BLAS children the node's split planes prove the ray misses are not pushed (ClosestWalk::cull_children); 0: every child is
+#define PBRS_SPLIT_PLANE_CULL 1
 #endif
 #define PBRS_WALK_IDLE 0u
 #define PBRS_WALK_NODE 1u
@@ -378,6 +388,59 @@ struct ClosestWalk {
         }
     }
 
+    // Split-plane cull: which children of inner BLAS node X, which has just passed its box test, are worth pushing.  X carries two
+    // planes on its split axis k (device/split_planes.h; the host chose them, host/scene_prepare.cpp): pd = down(qd) <= R.min[k] and
+    // pu = up(qu) >= L.max[k], L = the left child, R = the right one.  With e(p) = qdiv(o_k - p, d_k, nr_k), the box test's own
+    // correctly rounded quotient, T = min(hi_el(X), mt) and t_low(X) as slab_rs returned them:
+    //     d_k > 0  (near L, far R):   R is not pushed if e(pd) > T,   L is not pushed if e(pu) < t_low(X)
+    //     d_k < 0  (near R, far L):   L is not pushed if e(pu) > T,   R is not pushed if e(pd) < t_low(X)
+    // Why the walk's results keep their bits.  A child that is not pushed would have failed its own box test when popped, against
+    // whatever extent the walk had by then:
+    //   * RN subtraction and RN division are monotone, so the far child's entry quotient on k is >= e(its plane) (R.min[k] >= pd with
+    //     d_k > 0; L.max[k] <= pu with d_k < 0, where the quotient falls as the plane rises) and the near child's exit quotient on k is
+    //     <= e(its plane);
+    //   * a child's box lies inside X's (the host checks it, or stores planes that cull nothing), so by the same monotonicity
+    //     hi_el(child) <= hi_el(X) and t_low(child) >= t_low(X);
+    //   * children are tested against the mesh-local best mt, never against X's incoming extent (which differs from mt at the BLAS
+    //     root only), and the extent a lane tests with only falls while it stays in one BLAS: at the child's pop it is <= mt of now.
+    //   Far child:  t_low(child) >= its entry on k >= e(plane) > T >= min(hi_el(child), extent at its pop) = its t_high: fails.
+    //   Near child: hi_el(child) <= its exit on k <= e(plane) < t_low(X) <= t_low(child): fails.
+    // All comparisons are strict, so a child that grazes its plane is still pushed and decided by its own test.  A failed pop has no
+    // side effect (the early-out to the instance boundary is reached by the next step's first check all the same); the sequence of
+    // leaves whose triangles are tested, and the extent each sees, is the reference's.  Planes of zero (q = 0: X's own min / max) never
+    // cull: e(X.min[k]) and e(X.max[k]) are the bounds X has just passed with.  Rays on the literal divisions are never culled, nor are
+    // the counting instantiations (their node counts are the oracle's) and the walks that follow the extent (PBRS_FEAT_EXTENT).
+    // Per scene, at compile time: the kernels of scenes whose TLAS is too large to scan (PBRS_FEAT_LDS_TOP: C5's 128 instances over
+    // meshes three levels deep) do not carry the cull.  Their lanes spend their steps in the TLAS; with the cull compiled in C5 lost
+    // 1.6 % — and lost it just the same when a run-time flag kept every lane from executing it, so the price is the larger node step
+    // itself, not the test.
+    // Returns bit 0: push the near child, bit 1: push the far child.
+    static constexpr bool CULL = PBRS_SPLIT_PLANE_CULL != 0 && !STATS && !EXT && !(FEAT & PBRS_FEAT_LDS_TOP);
+    PD uint32_t cull_children(const pbrs_node& X, float dk, float t_low, float hi_el) const {
+        const int k = (int)(X.b & 3u);
+        const float lo = comp(nmin(X), k), hi = comp(nmax(X), k);
+        const float step = pbrs_plane_step(lo, hi);
+        const float pd = pbrs_plane_down(pbrs_plane_qd(X.b), step, lo), pu = pbrs_plane_up(pbrs_plane_qu(X.b), step, hi);
+        const bool pos = dk > 0.0f;
+        const float ok = comp(C.o, k), nrk = comp(C.nr, k);
+        const float e_near = qdiv(ok - (pos ? pu : pd), dk, nrk), e_far = qdiv(ok - (pos ? pd : pu), dk, nrk);
+        const float T = __builtin_fminf(hi_el, mt);
+        return (e_near < t_low ? 0u : 1u) | (e_far > T ? 0u : 2u);
+    }
+    // far child first, near child on top; a child that is not kept is overwritten or left above the top
+    PD void push_children(LaneStack stk, bool left_first, uint32_t left, uint32_t right, uint32_t keep) {
+        const uint32_t far = left_first ? right : left, near = left_first ? left : right;
+        if constexpr (!CULL) {
+            stk.put(sp++, far);
+            stk.put(sp++, near);
+        } else {
+            stk.put(sp, far);
+            sp += (int)(keep >> 1);
+            stk.put(sp, near);
+            sp += (int)(keep & 1u);
+        }
+    }
+
     // One node: pop, box test, then push the children / hold the leaf / stop at the instance boundary.
     PD void node_step(const DevScene& S, LaneStack stk, Cnt<STATS>& cnt) {
         PBRS_TP(0);
@@ -417,7 +480,8 @@ struct ClosestWalk {
         }
         const pbrs_node node = walk_node<FEAT>(S, ni);
         PBRS_TP(1);
-        if (!slab_rs(node, C, lt)) {
+        float t_low = 0.0f, hi_el = 0.0f;
+        if (!slab_rs(node, C, lt, t_low, hi_el)) {
             PBRS_TP(2);
             if (PBRS_EARLY_OUT && in_blas && sp == blas_base) mode = exit_mode();
             return;
@@ -425,7 +489,8 @@ struct ClosestWalk {
         if (!(node.b & PBRS_LEAF_FLAG)) {
             // TLAS: left (i+1) is popped first.  BLAS: the child the ray enters first along the split axis
             // (blas.rs:456-466), and the cloned ray's t_max follows outer_hit (blas.rs:468).
-            bool left_first = !in_blas || comp(C.d, (int)(node.b & 3u)) > 0.0f;
+            const float dk = comp(C.d, (int)(node.b & 3u));
+            bool left_first = !in_blas || dk > 0.0f;
             uint32_t left = ni + 1, right = node.a;
             if constexpr (EXT) {
                 if (!in_blas) {  // a new window opens for the left subtree; the one it interrupts waits with the right sibling
@@ -434,8 +499,11 @@ struct ClosestWalk {
                     win_has = false;
                 }
             }
-            stk.put(sp++, left_first ? right : left);
-            stk.put(sp++, left_first ? left : right);
+            uint32_t keep = 3u;
+            if constexpr (CULL) {
+                if (in_blas && C.fast) keep = cull_children(node, dk, t_low, hi_el);
+            }
+            push_children(stk, left_first, left, right, keep);
             lt = in_blas ? mt : lt;
         } else if (in_blas) {
             PBRS_TP(3);
@@ -469,15 +537,20 @@ struct ClosestWalk {
         PBRS_TP(1);
         RaySpace F = C;
         F.fast = true;  // known here: this copy of the box test carries no division path
-        if (!slab_rs(node, F, lt)) {
+        float t_low = 0.0f, hi_el = 0.0f;
+        if (!slab_rs(node, F, lt, t_low, hi_el)) {
             PBRS_TP(2);
             return;
         }
         if (!(node.b & PBRS_LEAF_FLAG)) {
-            bool left_first = !in_blas || comp(C.d, (int)(node.b & 3u)) > 0.0f;
+            const float dk = comp(C.d, (int)(node.b & 3u));
+            bool left_first = !in_blas || dk > 0.0f;
             uint32_t left = ni + 1, right = node.a;
-            stk.put(sp++, left_first ? right : left);
-            stk.put(sp++, left_first ? left : right);
+            uint32_t keep = 3u;
+            if constexpr (CULL) {
+                if (in_blas) keep = cull_children(node, dk, t_low, hi_el);  // (C.fast: this step's condition)
+            }
+            push_children(stk, left_first, left, right, keep);
             lt = in_blas ? mt : lt;
         } else if (in_blas) {
             PBRS_TP(3);

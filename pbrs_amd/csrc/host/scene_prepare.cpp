@@ -9,6 +9,7 @@
 
 #include "../../../include/pbrs_numeric.h"
 #include "../../../include/pbrs_scene_spec.h"
+#include "../device/split_planes.h"
 
 namespace pbrs {
 namespace {
@@ -97,6 +98,36 @@ uint32_t build_wide(const std::vector<pbrs_node>& nodes, uint32_t x, std::vector
     w.child[2] |= ((info >> 4) & 3u) << PBRS_WREF_AXIS_SHIFT;
     out[me] = w;
     return me;
+}
+
+// A coordinate inside the guarded range of the division-free box test (prepare_scene, DevScene::fast_slab)
+bool coord_ok(float b) {
+    const uint32_t u = pn_bits(b) & 0x7fffffffu, e = u >> 23;
+    return u == 0u || (e >= 127u - 60u && e <= 127u + 40u);
+}
+
+// The split planes of inner BLAS node x (device/split_planes.h), packed for its b word; 0 — planes that cull nothing — unless both
+// children's boxes lie inside x's (the cull's argument rests on that, device/traverse.h, and no check before this one asks it of a
+// description).  Each number is the largest whose plane, evaluated as the device evaluates it, stays on its side of the child; a plane
+// the walk's quotient is not exact for (non-zero below 2^-60: cancellation next to a coordinate of the other sign) gives way to q = 0.
+uint32_t split_planes(const std::vector<pbrs_node>& nodes, uint32_t x) {
+    const pbrs_node &X = nodes[x], &L = nodes[x + 1u], &R = nodes[X.a];
+    for (int a = 0; a < 3; ++a) {
+        const bool inside = X.min[a] <= L.min[a] && L.min[a] <= L.max[a] && L.max[a] <= X.max[a] && X.min[a] <= R.min[a] && R.min[a] <= R.max[a] && R.max[a] <= X.max[a];
+        if (!inside) return 0u;  // (a NaN coordinate fails every comparison)
+    }
+    const uint32_t k = X.b & 3u;
+    const float lo = X.min[k], hi = X.max[k], step = pbrs_plane_step(lo, hi);
+    if (!(step > 0.0f) || !pn_isfinite(step)) return 0u;
+    // both planes move monotonically with q (one correctly rounded operation of a monotone exact value) and q = 0 holds: bisection
+    uint32_t qd = 0u, qu = 0u;
+    for (uint32_t bit = 1u << (PBRS_PLANE_BITS - 1u); bit; bit >>= 1) {
+        if (pbrs_plane_down(qd | bit, step, lo) <= R.min[k]) qd |= bit;
+        if (pbrs_plane_up(qu | bit, step, hi) >= L.max[k]) qu |= bit;
+    }
+    if (!coord_ok(pbrs_plane_down(qd, step, lo))) qd = 0u;
+    if (!coord_ok(pbrs_plane_up(qu, step, hi))) qu = 0u;
+    return pbrs_plane_pack(qd, qu);
 }
 
 }  // namespace
@@ -212,10 +243,6 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
     // f64 route of rounds 1-2 that the f32 quotient inherited: c4xl's 8.4 M vertices hold three heights below it (1.6e-7, 7.4e-7,
     // -9.8e-8), and the WHOLE scene walked on the literal divisions, its lean node steps sitting idle (round 3's "-11 % out of cache").
     {
-        auto coord_ok = [](float b) {
-            uint32_t u = pn_bits(b) & 0x7fffffffu, e = u >> 23;
-            return u == 0u || (e >= 127u - 60u && e <= 127u + 40u);
-        };
         bool ok = true;
         for (uint32_t i = 0; i < d.n_tlas_nodes && ok; ++i)
             for (int a = 0; a < 3; ++a) ok = ok && coord_ok(d.tlas_nodes[i].min[a]) && coord_ok(d.tlas_nodes[i].max[a]);
@@ -239,6 +266,12 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
     nodes.insert(nodes.end(), d.blas_nodes, d.blas_nodes + d.n_blas_nodes);
     for (size_t i = blas_off; i < nodes.size(); ++i)
         if (!(nodes[i].b & PBRS_LEAF_FLAG)) nodes[i].a += (uint32_t)blas_off;  // right child; the left one is i + 1
+    // The split planes of the inner BLAS nodes (device/split_planes.h), one word per node of `nodes`: pbrs_upload_scene ORs them into
+    // the b words of the copy it uploads; `nodes` itself stays the description's.  Only rays on the division-free box test read them.
+    P.node_planes.assign(nodes.size(), 0u);
+    if (S.fast_slab != 0u)
+        for (size_t i = blas_off; i < nodes.size(); ++i)
+            if (!(nodes[i].b & PBRS_LEAF_FLAG)) P.node_planes[i] = split_planes(nodes, (uint32_t)i);
     P.walk_bytes = nodes.size() * sizeof(pbrs_node) + (uint64_t)d.n_triangles * sizeof(pbrs_tri_verts) + (uint64_t)d.n_instances * sizeof(pbrs_instance);
 
     std::vector<pbrs_instance>& inst = P.inst;

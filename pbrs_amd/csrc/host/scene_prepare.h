@@ -2,8 +2,8 @@
 // header, so that tests/scene_prepare_check.cpp runs it on a CPU under AddressSanitizer.
 //
 //   check_scene    every index the kernels dereference is in range, and the scene is within the limits of the device code
-//   prepare_scene  of a checked scene: the node array the walks read (TLAS, leaf copies, BLASes with absolute links), the device
-//                  copies of the instance records, the four-wide nodes, the DevScene scalars and the SceneFacts of choose_kernels
+//   prepare_scene  of a checked scene: the node array the walks read (TLAS, leaf copies, BLASes with absolute links), the split
+//                  planes of its inner BLAS nodes, the device copies of the instance records, the four-wide nodes, the DevScene scalars and the SceneFacts of choose_kernels
 // Neither copies the triangle, material, texture or light arrays: those go to the device straight from the descriptor.
 #pragma once
 #include <cstdint>
@@ -32,6 +32,7 @@ SceneCheck check_scene(const pbrs_scene_desc& d);
 struct PreparedScene {
     DevScene S{};  // every scalar but the lds_* of the kernel choice (pbrs_upload_scene); the pointers are null
     std::vector<pbrs_node> nodes;    // DevScene::nodes
+    std::vector<uint32_t> node_planes;  // per node of `nodes`: the split planes of an inner BLAS node, packed for its b word (device/split_planes.h); 0 for leaves and the TLAS
     std::vector<pbrs_instance> inst; // DevScene::inst: pad[0] the shading class, pad[1] the wide root, blas_root and flags as the walks read them
     std::vector<pbrs_wnode> wide;    // DevScene::wnodes; empty where the scene keeps the binary walks (S.wnodes stays null)
     uint32_t wide_levels = 0;        // wide nodes on the longest way down a BLAS (0: no wide nodes)

@@ -1127,6 +1127,8 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     c->plan = plan;
     DevScene S = P.S;
     int rc;
+    // the split planes ride in the spare bits of the inner BLAS nodes' b words (device/split_planes.h), on the uploaded copy only
+    for (size_t i = 0; i < P.nodes.size(); ++i) P.nodes[i].b |= P.node_planes[i];
     if ((rc = upload(c, P.nodes.data(), P.nodes.size(), &S.nodes))) return rc;
     if (!P.wide.empty() && (rc = upload(c, P.wide.data(), P.wide.size(), &S.wnodes))) return rc;
     if ((rc = upload(c, P.inst.data(), P.inst.size(), &S.inst))) return rc;
