@@ -7,7 +7,9 @@
 // State: planar words by pixel ORDER (order_of_pixel), 10 per pixel — albedo sum xyz, normal sum xyz, n_hit, best t, inst, prim.  It
 // starts as zeros (pbrs_gpu.hip, render_common): n_hit == 0 means "no hit yet", so best t / inst / prim need no other initial value.
 #pragma once
-#include "kernels.h"
+#include "lights.h"
+#include "path_state.h"
+#include "textures.h"
 
 #define PBRS_AOV_STATE_WORDS 10u
 

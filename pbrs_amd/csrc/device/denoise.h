@@ -19,7 +19,7 @@
 // filter's three differences and d2 cost) and not kept in LDS: a fifth word per record would break the 16-byte read, and a separate
 // plane adds 4 KB to the 36 KB of s = 4 (the fourth block per CU would no longer fit beside it) and a third ds_read per tap.
 #pragma once
-#include "kernels.h"
+#include "path_state.h"
 
 #define PBRS_DENOISE_CELL 16u  // a block owns a 16 x 16 cell of pixels, one thread each
 

@@ -132,3 +132,16 @@ PD f3 xf_normal(const float (*inv_rows)[4], f3 n) {
                inv_rows[0][1] * n.x + inv_rows[1][1] * n.y + inv_rows[2][1] * n.z,
                inv_rows[0][2] * n.x + inv_rows[1][2] * n.y + inv_rows[2][2] * n.z);
 }
+
+// RN(n / d) from the NEGATED numerator nn = -n, the denominator and nr = -RN(1 / d): the division-free box test of the walks, see the head of traverse.h; here because the
+// numeric probe (kernels.h, k_numeric_eval) evaluates it too
+PD float qdiv(float nn, float d, float nr) {
+    const float q0 = nn * nr;
+    const float e = __builtin_fmaf(d, q0, nn);
+    return __builtin_fmaf(e, nr, q0);
+}
+
+// Wave-level prefix: what the walks' triangle sharing (traverse.h), the compaction of k_shade and the class sort count with.
+PD uint32_t lane_prefix(uint64_t mask) {  // set bits of a wave mask below this lane
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}

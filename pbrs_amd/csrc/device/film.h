@@ -6,7 +6,7 @@
 // The pass traces the tile plus its halo (the "region", clipped to the film); its radiance sits in st.L by the region's
 // slot order.  State: planar f32 by row-major TILE pixel, 4 planes: S.rgb, W (zeroed by render_common).
 #pragma once
-#include "kernels.h"
+#include "path_state.h"
 #include "../../../include/pbrs_filter.h"
 
 #define PBRS_FILTER_CELL 16u  // a block owns a 16 x 16 cell of tile pixels, one thread each

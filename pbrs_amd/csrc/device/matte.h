@@ -13,7 +13,7 @@
 // The table lives in registers: every loop over it has a compile-time trip count (the kernels are instantiated on `slots`) and is
 // unrolled, and an entry is updated by compare-select, never by a runtime index (which would put the arrays into scratch).
 #pragma once
-#include "kernels.h"
+#include "path_state.h"
 
 #define PBRS_MATTE_STATE_WORDS(slots) (2u * (slots) + 1u)
 

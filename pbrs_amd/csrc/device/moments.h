@@ -7,7 +7,7 @@
 //
 // State: planar words by pixel ORDER (order_of_pixel), 3 per pixel — m1, m2, n.  It starts as zeros (pbrs_gpu.hip, render_common).
 #pragma once
-#include "kernels.h"
+#include "path_state.h"
 
 #define PBRS_MOMENT_STATE_WORDS 3u
 

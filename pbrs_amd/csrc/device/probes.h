@@ -1,6 +1,6 @@
-// device/probes.h — developer probes of the traversal and shading kernels.  Every macro below expands to nothing in the shipped
-// library; the instrumented builds are made by tools/trav_probe.py (-DPBRS_PROBE_TRAV), tools/trav_time.py (-DPBRS_PROBE_TIME),
-// tools/util_probe.py / util_probe2.py (-DPBRS_PROBE_UTIL[2]) and tools/shade_probe.py (-DPBRS_PROBE_SHADE).
+// device/probes.h — developer probes of the traversal kernels (k_shade's: device/shade.h, PBRS_SHADE_MARK).  Every macro below expands
+// to nothing in the shipped library; the instrumented builds are made by tools/trav_probe.py (-DPBRS_PROBE_TRAV), tools/trav_time.py
+// (-DPBRS_PROBE_TIME) and tools/util_probe.py / util_probe2.py (-DPBRS_PROBE_UTIL[2]).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,8 +25,12 @@
 // 11 rounds whose first node step had a lane; then the walks' own eight counters (traverse.h).  [0]: k_extend, [1]: k_shadow.
 // ... and where a wave's cycles go (-DPBRS_PROBE_TIME, tools/trav_time.py): s_memtime at the boundaries of the loop's regions —
 // 0 refill (retire, fetch, start, scan), 1 boundary step (with its ballots), 2 node steps, 3 leaf step — summed over the waves.
+// g_trav_time[2][8] and g_trav_probe[2][24] are defined by the unit that owns the traversal kernels and the probes' readers (traverse.hip),
+// before it includes this file: one definition in the library.
+#if (defined(PBRS_PROBE_TIME) || defined(PBRS_PROBE_TRAV)) && !defined(PBRS_TRAVERSAL_PROBES_DEFINED)
+#error "device/probes.h in a probe build: only the unit that defines g_trav_time / g_trav_probe may include the traversal headers, after defining them (traverse.hip)"
+#endif
 #ifdef PBRS_PROBE_TIME
-__device__ unsigned long long g_trav_time[2][8];
 #define PBRS_TT_DECL                                       \
     unsigned long long tt[4] = {0ull, 0ull, 0ull, 0ull};   \
     unsigned long long tprev = __builtin_amdgcn_s_memtime()
@@ -53,7 +57,6 @@ __device__ unsigned long long g_trav_time[2][8];
     } while (0)
 #endif
 #ifdef PBRS_PROBE_TRAV
-__device__ unsigned long long g_trav_probe[2][24];
 #define PBRS_KP_DECL(walk)      \
     uint32_t kp[16];            \
     for (int k_ = 0; k_ < 16; ++k_) kp[k_] = 0; \
@@ -139,20 +142,5 @@ PD void trav_probe_flush(int which, const uint32_t* kp, const uint32_t* pr) {
     } while (0)
 #define PBRS_PROBE_XFER_COUNT(cnt) \
     do {                           \
-    } while (0)
-#endif
-
-// Developer probe (tools/shade_probe.py; -DPBRS_PROBE_SHADE builds only): wall cycles of k_shade's regions, summed per wave.
-#ifdef PBRS_PROBE_SHADE
-__device__ unsigned long long g_shade_probe[16];
-#define PBRS_SHADE_MARK(k)                                          \
-    do {                                                            \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        probe_acc[k] += now_ - probe_t;                             \
-        probe_t = now_;                                             \
-    } while (0)
-#else
-#define PBRS_SHADE_MARK(k) \
-    do {                   \
     } while (0)
 #endif

@@ -7,7 +7,7 @@
 // On a 64-wide wave nested loops make every lane wait for the slowest, so a walk is a small state machine over ONE
 // pending-node stack (per lane, in LDS, lane-major) shared by the TLAS and the BLAS of the instance being visited, and it
 // advances by single steps: a node (pop + box test), the primitives of the held leaf (triangles: shared out over the
-// wave's lanes, TriShare), or an instance boundary (ray into / out of the instance's space).  The kernels (kernels.h, PBRS_STEP_WALK) run, each round, whichever steps their lanes are
+// wave's lanes, TriShare), or an instance boundary (ray into / out of the instance's space).  The kernels (extend.h, PBRS_STEP_WALK) run, each round, whichever steps their lanes are
 // waiting for — lanes in different phases of their walks share the instruction stream — and refill finished lanes.
 //
 // In this file: the box test (RaySpace, qdiv, slab_rs) and the instance boundary (enter_instance, leave_instance); the two ways a wave
@@ -78,12 +78,7 @@ PD void leave_instance(const DevScene& S, LaneStack stk, uint32_t moved, RaySpac
         C = reload_world(S, stk);
     }
 }
-// RN(n / d) from the NEGATED numerator nn = -n, the denominator and nr = -RN(1 / d): see the head of this file
-PD float qdiv(float nn, float d, float nr) {
-    const float q0 = nn * nr;
-    const float e = __builtin_fmaf(d, q0, nn);
-    return __builtin_fmaf(e, nr, q0);
-}
+// (qdiv, the quotient this test divides with: dmath.h)
 // geometry/src/bvh.rs:84-99 (same min/max/NaN conventions as dmath.h::slab_test)
 // For a ray on the division-free test it also hands back the two numbers the split-plane cull of the closest-hit walk reads
 // (ClosestWalk::cull_children): t_low, and hi_el — where the ray leaves the box, whatever the extent.
@@ -194,9 +189,7 @@ PD uint32_t enter_instance(const DevScene& S, const pbrs_instance& in, uint32_t 
 // (blas.rs:440-452).  Pair (owner, k) sits at helper lane (number of pairs with smaller k) + (owners with a k-th triangle
 // in lower lanes): wave-uniform ballots and mbcnt.  Lane 63 is never a helper (it takes the ds_permute writes of lanes
 // with nothing to send); pairs that would land on 63 or beyond wait for the next execution.
-PD uint32_t lane_prefix(uint64_t mask) {  // set bits of a wave mask below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+// (lane_prefix: dmath.h)
 struct TriShare {
     uint32_t tag;     // as a helper: 0x10000 | k << 8 | owner lane — whose triangle this lane tests; 0 = none
     uint32_t cnt;     // as an owner: triangles of this lane's leaf tested in this execution
@@ -519,7 +512,7 @@ struct ClosestWalk {
         }
     }
 
-    // A round's FURTHER node steps (kernels.h, PBRS_MORE_NODE_STEPS): the common case only — a pending entry of the tree the lane is
+    // A round's FURTHER node steps (extend.h, PBRS_MORE_NODE_STEPS): the common case only — a pending entry of the tree the lane is
     // in is popped and tested.  A lane whose stack is down to the floor of its tree (the instance used up, the next scanned TLAS
     // leaf, the end of the walk) sits the step out and lets the round's first step (node_step), which has the code for all that, take it: the
     // second and third copies of the step carry a third fewer scalar instructions (exec-mask bookkeeping of branches that nearly
@@ -1006,7 +999,7 @@ struct AnyWalk {
 // never changes, a leaf that passed the scan is entered without a second test); a BLAS leaf that comes up is held UNVERIFIED until
 // the leaf step gives it the reference's own box test.  A ray that leaves the guarded range (at its start or inside an instance) or
 // whose stack would exceed DevScene::wide_cap takes mode PBRS_WALK_SLOW: the kernel hands it, whole, to the binary-walk kernel
-// (kernels.h).
+// (extend.h).
 #define PBRS_WALK_SLOW 6u
 #define PBRS_LEAF_UNVERIFIED 0xffffffffu
 template <uint32_t FEAT>

@@ -1,6 +1,6 @@
 // pbrs_gpu.hip — implementation of include/pbrs_gpu.h for gfx950 (MI355X).
 //
-// Host-side driver of the wavefront pipeline in device/kernels.h: owns the HBM copies of the
+// Host-side driver of the wavefront pipeline (device/kernels.h names the stages; k_extend, k_shadow and k_shade through kernel_tables.h): owns the HBM copies of the
 // flattened scene, the SoA path state, the slot queues and the per-tile accumulator, and issues
 //     raygen -> [extend -> shade -> shadow] x max_depth -> accumulate
 // per pass of `samples_per_pass` sample indices, all on one HIP stream with no host round trip
@@ -20,7 +20,11 @@
 #include <vector>
 
 #include "../../include/pbrs_gpu.h"
-#include "device/kernels.h"
+#include "device/raygen.h"
+#include "device/class_sort.h"
+#include "device/accumulate.h"
+#include "device/dev_kernels.h"
+#include "kernel_tables.h"
 #include "host/scene_prepare.h"
 #include "host/arg_checks.h"
 #include "host/pass_plan.h"
@@ -80,11 +84,6 @@ DevOverrides read_dev_overrides() {
     return o;
 }
 #endif
-
-typedef void (*extend_fn_t)(DevScene, PathState, uint32_t, const uint32_t*, uint32_t, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
-typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*);
-typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*,
-                           const uint32_t*);
 
 // The kernels that render the uploaded scene, bound once per upload (bind_kernels): what choose_kernels names (host/kernel_choice.h: the
 // keys, the dynamic LDS and the class range of every launch), and the instantiations the keys name.
@@ -232,6 +231,26 @@ namespace {
             return PBRS_E_DEVICE;                                                                     \
         }                                                                                             \
     } while (0)
+
+// The device memory an entry point allocates for one call (the developer entry points: memory held between calls would change the
+// free memory that pass_size reads): freed when the call returns, whichever way it does.
+struct CallAllocs {
+    std::vector<void*> held;
+    CallAllocs() = default;
+    CallAllocs(const CallAllocs&) = delete;
+    CallAllocs& operator=(const CallAllocs&) = delete;
+    ~CallAllocs() {
+        for (void* p : held) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t alloc(T** p, size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes);
+        if (e == hipSuccess) held.push_back(q);
+        *p = static_cast<T*>(q);
+        return e;
+    }
+};
 
 int fail(pbrs_ctx* c, int code, const char* msg) {
     c->error = msg;
@@ -524,47 +543,7 @@ RenderConst make_const(const pbrs_ctx* c, const pbrs_camera* cam, const pbrs_ren
     return rc;
 }
 
-// The traversal kernels, one per valid key (host/kernel_choice.h: extend_key_ok, shadow_key_ok), in tables filled at compile time.
-template <uint32_t K>
-constexpr extend_fn_t extend_fn_of() {
-    if constexpr (extend_key_ok(K)) return &k_extend<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
-    else return nullptr;
-}
-template <uint32_t K>
-constexpr shadow_fn_t shadow_fn_of() {
-    if constexpr (shadow_key_ok(K)) return &k_shadow<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
-    else return nullptr;
-}
-template <uint32_t... K>
-const extend_fn_t* extend_table(std::integer_sequence<uint32_t, K...>) {
-    static const extend_fn_t t[sizeof...(K)] = {extend_fn_of<K>()...};
-    return t;
-}
-template <uint32_t... K>
-const shadow_fn_t* shadow_table(std::integer_sequence<uint32_t, K...>) {
-    static const shadow_fn_t t[sizeof...(K)] = {shadow_fn_of<K>()...};
-    return t;
-}
-const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
-const shadow_fn_t* shadow_fns() { return shadow_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
-
-// The k_shade instantiations (kernels.h: INTEG, TEX, SPEC) the choices name: host/kernel_choice.h, PBRS_SHADE_KERNELS.
-struct ShadeKernel {
-    uint32_t integ;
-    bool tex;
-    uint32_t spec;
-    shade_fn_t fn;
-};
-#define PBRS_SHADE_KERNEL_ENTRY(I, T, SP) ShadeKernel{I, T, SP, &k_shade<I, T, SP>},
-const ShadeKernel kShadeKernels[] = {PBRS_SHADE_KERNELS(PBRS_SHADE_KERNEL_ENTRY)};
-#undef PBRS_SHADE_KERNEL_ENTRY
-shade_fn_t shade_fn(const ShadeKey& key) {
-    for (const ShadeKernel& k : kShadeKernels)
-        if (k.integ == key.integ && k.tex == key.tex && k.spec == key.spec) return k.fn;
-    return nullptr;
-}
-
-// The kernels a choice names (choose_kernels), from the tables above.  False where a table lacks one.
+// The kernels a choice names (choose_kernels), from their owners' tables (kernel_tables.h).  False where a table lacks one.
 bool bind_kernels(const KernelChoice& ch, KernelPlan& p) {
     p = KernelPlan{};
     p.choice = ch;
@@ -874,7 +853,7 @@ int configure_kernels(pbrs_ctx* c) {
     std::lock_guard<std::mutex> lock(g_kernel_cfg_mutex);
     if (c->device < 64 && g_kernel_cfg_done[c->device]) return PBRS_OK;
     const int cap = (int)(kLdsBytesPerCU / 2);
-    std::vector<const void*> traversal_kernels = {reinterpret_cast<const void*>(&k_intersect_rays<false>), reinterpret_cast<const void*>(&k_intersect_rays<true>)};
+    std::vector<const void*> traversal_kernels = {reinterpret_cast<const void*>(intersect_fn(false)), reinterpret_cast<const void*>(intersect_fn(true))};
     for (uint32_t k = 0; k < kTraversalKeys; ++k) {
         if (extend_fns()[k]) traversal_kernels.push_back(reinterpret_cast<const void*>(extend_fns()[k]));
         if (shadow_fns()[k]) traversal_kernels.push_back(reinterpret_cast<const void*>(shadow_fns()[k]));
@@ -988,35 +967,6 @@ RenderTargets make_targets(float* rgb, const pbrs_aov_buffers* aovs, float* vari
 }  // namespace
 
 extern "C" {
-
-#ifdef PBRS_PROBE_SHADE
-// developer probe: reads and clears the k_shade region cycle sums
-int pbrs_debug_shade_probe(unsigned long long* out16) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_shade_probe), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long zero[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_shade_probe), zero, sizeof zero) == hipSuccess ? 0 : -1;
-}
-#endif
-
-#ifdef PBRS_PROBE_TIME
-// developer probe: reads and clears the traversal loops' cycle sums by region ([0]: k_extend, [1]: k_shadow; kernels.h)
-int pbrs_debug_trav_time(unsigned long long* out16) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_trav_time), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long zero[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_trav_time), zero, sizeof zero) == hipSuccess ? 0 : -1;
-}
-#endif
-#ifdef PBRS_PROBE_TRAV
-// developer probe: reads and clears the traversal loops' event counts ([0]: k_extend, [1]: k_shadow; kernels.h)
-int pbrs_debug_trav_probe(unsigned long long* out48) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out48, HIP_SYMBOL(g_trav_probe), 48 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long zero[48] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_trav_probe), zero, sizeof zero) == hipSuccess ? 0 : -1;
-}
-#endif
 
 int pbrs_create(int device_ordinal, pbrs_ctx** out) {
     if (!out) return PBRS_E_INVALID;
@@ -1764,36 +1714,23 @@ int pbrs_intersect_rays(pbrs_ctx* c, uint32_t n, const float* origins, const flo
     pbrs_hit_record* d_h = nullptr;
     uint8_t* d_occ = nullptr;
     uint32_t* d_info = nullptr;
-    int rc = PBRS_OK;
-    auto cleanup = [&]() {
-        (void)hipFree(d_o); (void)hipFree(d_d); (void)hipFree(d_t); (void)hipFree(d_h); (void)hipFree(d_occ); (void)hipFree(d_info);
-    };
-#define TRY(expr)                                                                  \
-    do {                                                                           \
-        hipError_t e_ = (expr);                                                    \
-        if (e_ != hipSuccess) {                                                    \
-            c->error = std::string(#expr) + ": " + hipGetErrorString(e_);          \
-            (void)hipGetLastError();                                               \
-            cleanup();                                                             \
-            return PBRS_E_DEVICE;                                                  \
-        }                                                                          \
-    } while (0)
+    CallAllocs mem;
     // rays travel as 16-byte records, the form the walks re-read their ray in (traverse.h, reload_world)
     std::vector<float4> h_o(n), h_d(n);
     for (uint32_t i = 0; i < n; ++i) {
         h_o[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], 0.0f);
         h_d[i] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], 0.0f);
     }
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_o), (size_t)n * 16));
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_d), (size_t)n * 16));
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_t), (size_t)n * 4));
-    if (hits_out) TRY(hipMalloc(reinterpret_cast<void**>(&d_h), (size_t)n * sizeof(pbrs_hit_record)));
-    if (occluded_out) TRY(hipMalloc(reinterpret_cast<void**>(&d_occ), (size_t)n));
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_info), 2 * sizeof(uint32_t)));
-    TRY(hipMemsetAsync(d_info, 0, 2 * sizeof(uint32_t), c->stream));
-    TRY(hipMemcpyAsync(d_o, h_o.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    TRY(hipMemcpyAsync(d_d, h_d.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    TRY(hipMemcpyAsync(d_t, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, mem.alloc(&d_o, (size_t)n * 16));
+    HIPCHK(c, mem.alloc(&d_d, (size_t)n * 16));
+    HIPCHK(c, mem.alloc(&d_t, (size_t)n * 4));
+    if (hits_out) HIPCHK(c, mem.alloc(&d_h, (size_t)n * sizeof(pbrs_hit_record)));
+    if (occluded_out) HIPCHK(c, mem.alloc(&d_occ, (size_t)n));
+    HIPCHK(c, mem.alloc(&d_info, 2 * sizeof(uint32_t)));
+    HIPCHK(c, hipMemsetAsync(d_info, 0, 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_o, h_o.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_d, h_d.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_t, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     {
         // the walks the pipeline runs for this scene: any-hit over four-wide nodes where k_shadow walks them (the binary walk takes
         // what that one refuses, as in the pipeline), else the binary walks
@@ -1804,19 +1741,17 @@ int pbrs_intersect_rays(pbrs_ctx* c, uint32_t n, const float* origins, const flo
         // k_shadow takes it, closest hits through the binary walk
         const bool wide = c->plan.choice.wide_shadow;
         c->last_intersect = pbrs_intersect_info{wide ? 1u : 0u, 0u, 0u, 0u};
-        const auto fn = wide ? &k_intersect_rays<true> : &k_intersect_rays<false>;
-        hipLaunchKernelGGL(fn, grid, dim3(kBlock), lds, c->stream, c->S, n, d_o, d_d, d_t, d_h, d_occ, d_info);
+        hipLaunchKernelGGL(intersect_fn(wide), grid, dim3(kBlock), lds, c->stream, c->S, n, d_o, d_d, d_t, d_h, d_occ, d_info);
     }
-    TRY(hipGetLastError());
-    if (hits_out) TRY(hipMemcpyAsync(hits_out, d_h, (size_t)n * sizeof(pbrs_hit_record), hipMemcpyDeviceToHost, c->stream));
-    if (occluded_out) TRY(hipMemcpyAsync(occluded_out, d_occ, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (hits_out) HIPCHK(c, hipMemcpyAsync(hits_out, d_h, (size_t)n * sizeof(pbrs_hit_record), hipMemcpyDeviceToHost, c->stream));
+    if (occluded_out) HIPCHK(c, hipMemcpyAsync(occluded_out, d_occ, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     uint32_t slow[2] = {0u, 0u};
-    TRY(hipMemcpyAsync(slow, d_info, sizeof slow, hipMemcpyDeviceToHost, c->stream));
-    TRY(hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(slow, d_info, sizeof slow, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->last_intersect.slow_any = slow[0];
     c->last_intersect.slow_closest = slow[1];
-    cleanup();
-    return rc;
+    return PBRS_OK;
 }
 
 int pbrs_last_intersect_info(const pbrs_ctx* c, pbrs_intersect_info* out) {
@@ -1842,15 +1777,14 @@ int pbrs_camera_rays(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_para
     k.n_slots = P;
     hipLaunchKernelGGL(k_raygen, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, k, cur(c).rng_hi0);  // (the rays are read back, nothing else)
     float *d_o = nullptr, *d_d = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_o); (void)hipFree(d_d); };
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_o), (size_t)P * 12));
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_d), (size_t)P * 12));
+    CallAllocs mem;
+    HIPCHK(c, mem.alloc(&d_o, (size_t)P * 12));
+    HIPCHK(c, mem.alloc(&d_d, (size_t)P * 12));
     hipLaunchKernelGGL(k_export_rays, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, P, d_o, d_d);
-    TRY(hipGetLastError());
-    TRY(hipMemcpyAsync(origins_out, d_o, (size_t)P * 12, hipMemcpyDeviceToHost, c->stream));
-    TRY(hipMemcpyAsync(dirs_out, d_d, (size_t)P * 12, hipMemcpyDeviceToHost, c->stream));
-    TRY(hipStreamSynchronize(c->stream));
-    cleanup();
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(origins_out, d_o, (size_t)P * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dirs_out, d_d, (size_t)P * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
 
@@ -1860,19 +1794,18 @@ int pbrs_numeric_eval(pbrs_ctx* c, uint32_t fn, uint32_t n, const float* x, cons
     if (!x || !out || fn > PN_PROBE_LAST) return fail(c, PBRS_E_INVALID, "bad numeric_eval arguments");
     HIPCHK(c, hipSetDevice(c->device));
     float *d_x = nullptr, *d_y = nullptr, *d_r = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_x); (void)hipFree(d_y); (void)hipFree(d_r); };
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_x), (size_t)n * 4));
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_r), (size_t)n * 4));
-    TRY(hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    CallAllocs mem;
+    HIPCHK(c, mem.alloc(&d_x, (size_t)n * 4));
+    HIPCHK(c, mem.alloc(&d_r, (size_t)n * 4));
+    HIPCHK(c, hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (y) {
-        TRY(hipMalloc(reinterpret_cast<void**>(&d_y), (size_t)n * 4));
-        TRY(hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, mem.alloc(&d_y, (size_t)n * 4));
+        HIPCHK(c, hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     }
     hipLaunchKernelGGL(k_numeric_eval, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, fn, n, d_x, d_y, d_r);
-    TRY(hipGetLastError());
-    TRY(hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    TRY(hipStreamSynchronize(c->stream));
-    cleanup();
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
 
@@ -1883,15 +1816,14 @@ int pbrs_numeric_eval_k(pbrs_ctx* c, uint32_t fn, uint32_t n, uint32_t k, const 
         return fail(c, PBRS_E_INVALID, "bad numeric_eval_k arguments");
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t *d_ops = nullptr, *d_r = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_ops); (void)hipFree(d_r); };
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_ops), (size_t)n * k * 4));
-    TRY(hipMalloc(reinterpret_cast<void**>(&d_r), (size_t)n * 4));
-    TRY(hipMemcpyAsync(d_ops, ops, (size_t)n * k * 4, hipMemcpyHostToDevice, c->stream));
+    CallAllocs mem;
+    HIPCHK(c, mem.alloc(&d_ops, (size_t)n * k * 4));
+    HIPCHK(c, mem.alloc(&d_r, (size_t)n * 4));
+    HIPCHK(c, hipMemcpyAsync(d_ops, ops, (size_t)n * k * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_numeric_eval_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, fn, n, k, d_ops, d_r);
-    TRY(hipGetLastError());
-    TRY(hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    TRY(hipStreamSynchronize(c->stream));
-    cleanup();
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }
 

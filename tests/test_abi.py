@@ -85,5 +85,39 @@ def test_the_shipped_hip_library_does_not_read_the_environment():
     from pbrs_amd import api
     syms = subprocess.run(["nm", "-D", "--undefined-only", api.lib_paths()[1]], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in syms
-    src = open(os.path.join(ROOT, "pbrs_amd", "csrc", "pbrs_gpu.hip")).read()
-    assert src.count("getenv(") == 1 and "#ifdef PBRS_DEV_OVERRIDES" in src  # the one call sits inside dev_env()
+    # every translation unit of the library: one call in all, inside dev_env(), which exists only under #ifdef PBRS_DEV_OVERRIDES
+    csrc = os.path.join(ROOT, "pbrs_amd", "csrc")
+    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert len(units) > 1, units
+    calls = {f: open(os.path.join(csrc, f)).read().count("getenv(") for f in units}
+    assert sum(calls.values()) == 1, calls
+    src = open(os.path.join(csrc, next(f for f, n in calls.items() if n))).read()
+    guarded = re.search(r"#ifdef PBRS_DEV_OVERRIDES\n(.*?)\n#endif", src, flags=re.S).group(1)
+    assert "const char* dev_env(const char* name) { return std::getenv(name); }" in guarded
+
+
+def defined_dynamic_symbols(path):
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return [line.split()[-1] for line in out.splitlines() if line.strip()]
+
+
+def test_gpu_library_exports_the_header_and_nothing_internal():
+    """What the library's translation units share (pbrs_amd/csrc/kernel_tables.h) is hidden: the defined dynamic symbols that begin
+    with pbrs_ are exactly the functions of include/pbrs_gpu.h, and of the project's C++ namespace only the host code's interface is
+    visible (pbrs_amd/csrc/host/*.h: plain C++ that the CPU tests also compile on its own) — none of the tables' accessors."""
+    import subprocess
+    syms = defined_dynamic_symbols(pbrs_amd.lib_paths()[1])
+    assert sorted(s for s in syms if s.startswith("pbrs_")) == declared_functions("pbrs_gpu.h")
+    ours = [s for s in syms if re.match(r"_ZNK?4pbrs", s)]
+    assert ours, "the host code's functions are part of the library"
+    plain = subprocess.run(["c++filt"], input="\n".join(ours), capture_output=True, text=True, check=True).stdout.splitlines()
+    host_dir = os.path.join(ROOT, "pbrs_amd", "csrc", "host")
+    host_text = "\n".join(open(os.path.join(host_dir, f)).read() for f in sorted(os.listdir(host_dir)) if f.endswith(".h"))
+    tables = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "pbrs_amd", "csrc", "kernel_tables.h")).read())
+    internal = set(re.findall(r"^[\w:\* ]+?\b(\w+)\([^()]*\);", tables, flags=re.M))  # the functions it declares
+    assert internal == {"extend_fns", "shadow_fns", "intersect_fn", "shade_fn"}, internal
+    for name in plain:
+        m = re.search(r"\bpbrs::(\w+)", name)
+        assert m and m.group(1) not in internal, name
+        assert re.search(r"\b%s\b" % m.group(1), host_text), name

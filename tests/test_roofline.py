@@ -179,6 +179,10 @@ def test_the_committed_counter_files_apply_to_the_sources_in_the_tree():
         with open(p) as f:
             doc = json.load(f)
         assert doc.get("source_hash") and isinstance(doc.get("same_isa_as_measured", []), list), p
+        for e in doc.get("same_isa_as_measured", []):  # the form counters_apply reads, and the comparison's log beside the file
+            assert isinstance(e.get("source_hash"), str) and len(e["source_hash"]) == 16, (p, e.get("source_hash"))
+            assert isinstance(e.get("differing_kernels"), list) and all(isinstance(k, str) for k in e["differing_kernels"]), (p, e["source_hash"])
+            assert os.path.exists(os.path.join(root, e.get("log", ""))) and e["log"].startswith("profiles/"), (p, e.get("log"))
         if not roofline.counters_apply(doc)[0]:
             stale.append(os.path.basename(p))
     if stale:  # a kernel source was edited since: bench.py leaves the counters out until tools/round_artifacts.sh has run again

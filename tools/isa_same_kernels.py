@@ -1,6 +1,11 @@
-"""Developer tool (CPU): which kernels of two device assemblies of pbrs_gpu.hip are the same instruction for instruction.
+"""Developer tool (CPU): which kernels of two device assemblies of the library are the same instruction for instruction.
 
-usage: python tools/isa_same_kernels.py [--mask-registers] OLD.s NEW.s        (hipcc <the Makefile's flags> --cuda-device-only -S -o X.s pbrs_gpu.hip)
+usage: python tools/isa_same_kernels.py [--mask-registers] OLD.s NEW.s
+
+An assembly of the library is the concatenation of its translation units' (a kernel is instantiated in one unit, so none appears twice):
+    make -C pbrs_amd/csrc asm ASMDIR=/tmp/new && cat /tmp/new/*.s > NEW.s
+and the same in a checkout of the other tree.  A tree from before the split has one unit: hipcc <the Makefile's flags>
+--cuda-device-only -S -o OLD.s pbrs_gpu.hip.
 
 A counter file (profiles/*traffic*.json) is stamped with a hash of ALL kernel sources; a change to one header moves the hash although
 most kernels compile to the same code.  This tool compares every kernel's body (label .. .Lfunc_end, local labels renumbered in order of

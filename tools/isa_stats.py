@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: static instruction mix and register use per kernel, from the device assembly of pbrs_gpu.hip.
+"""Developer tool: static instruction mix and register use per kernel, from the device assembly of the library's translation units
+(pbrs_amd/csrc/Makefile, `asm`: the Makefile's flags and units, nothing repeated here).
 
     python tools/isa_stats.py [--json PATH] [extra hipcc flags ...]     (CPU only; hipcc cross-compiles gfx950)
 
@@ -21,9 +22,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "pbrs_amd", "csrc", "pbrs_gpu.hip")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-         "-Wno-unused-function", "--cuda-device-only", "-S"]
+CSRC = os.path.join(ROOT, "pbrs_amd", "csrc")
 
 FAMILIES = [
     ("div", r"v_div_fixup_f32"), ("rcp", r"v_rcp_f32"), ("sqrt", r"v_sqrt_f32"), ("rsq", r"v_rsq_f32"), ("f64", r"v_\w+_f64"),
@@ -46,9 +45,9 @@ def main():
         json_path = argv[k + 1]
         del argv[k:k + 2]
     with tempfile.TemporaryDirectory() as td:
-        asm = os.path.join(td, "dev.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + argv + ["-o", asm, SRC], cwd=os.path.dirname(SRC))
-        text = open(asm).read()
+        subprocess.check_call(["make", "-C", CSRC, "-j%d" % min(os.cpu_count() or 1, 16), "asm", "ASMDIR=" + td, "HIPCC_EXTRA=" + " ".join(argv)],
+                              stdout=sys.stderr)
+        text = "".join(open(os.path.join(td, f)).read() for f in sorted(os.listdir(td)) if f.endswith(".s"))
     kernels = {}
     cur = None
     for line in text.split("\n"):
@@ -87,7 +86,7 @@ def main():
         import json
         sys.path.insert(0, ROOT)
         from pbrs_amd import roofline
-        doc = {"source_hash": roofline.source_hash(), "flags": " ".join(FLAGS + argv),
+        doc = {"source_hash": roofline.source_hash(), "flags": subprocess.check_output(["make", "-s", "-C", CSRC, "flags", "HIPCC_EXTRA=" + " ".join(argv)], text=True).strip(),
                "note": "static counts per kernel: valu = vector instructions, valu32 = those in a 32-bit encoding (no literal), salu = scalar instructions",
                "kernels": {names[k].split("(")[0].replace("void ", ""): {"valu": c["valu"], "valu32": c["valu32"], "salu": c["salu"], "vgpr": c["@NumVgprs"],
                                                                           "scratch": c["@ScratchSize"], "waves_per_simd": c["@Occupancy"]}
