@@ -1039,6 +1039,71 @@ int pbrs_display(pbrs_ctx*, const pbrs_display_params*, const float* rgb_host, c
 int pbrs_display_device(pbrs_ctx*, const pbrs_display_params*, const float* rgb_device, const pbrs_display_io* io_device,
                         uint32_t* rgba8_out_device);
 
+/* ---- guided upsampling ------------------------------------------------------------------------------------------ */
+/* Joint bilateral upsampling (Kopf, Cohen, Lischinski and Uyttendaele, SIGGRAPH 2007): an image traced and filtered at 1 / factor of the
+ * resolution per axis is rebuilt at full size with weights taken from first-hit guides rendered at full size, which cost one cast per
+ * pixel.  With albedo demodulation the texture detail comes back from the full-size albedo.  An image operation like pbrs_denoise: it
+ * needs a context (device, stream) and no uploaded scene.  All arithmetic is f32 without fused multiply-add, in the order written; pn_* is
+ * include/pbrs_numeric.h; c = r, g, b.
+ *   Sizes.  w x h is the full size, factor f in {2, 3, 4} applies to both axes, the low size is wl = (w + f - 1) / f, hl = (h + f - 1) / f.
+ *     rgb_lo and the planes of guides_lo are wl x hl, out, weight_out and the planes of guides_hi are w x h, all row-major.  Low pixel
+ *     Q = (X, Y) lies under the full pixels fX .. fX + f - 1, fY .. fY + f - 1.
+ *   Demodulation.  With PBRS_UPSAMPLE_DEMODULATE: d(.).c = albedo.c > albedo_floor ? albedo.c : 1.0f, exactly pbrs_denoise's, d_lo(Q)
+ *     from guides_lo->albedo and d_hi(p) from guides_hi->albedo; c(Q).c = rgb_lo(Q).c / d_lo(Q).c.  Without the flag c = rgb_lo, d = 1.
+ *   Footprint of full pixel p = (x, y).  X0 = floor_div(2x + 1 - f, 2f) in integer arithmetic (floor toward -inf), Y0 likewise.  The taps
+ *     are Y = Y0 - R + 1 .. Y0 + R (outer, ascending), X = X0 - R + 1 .. X0 + R (inner, ascending), R = radius in {1, 2}.  With
+ *     D = 2 * f * R: nx = |2f * X + f - (2x + 1)|, ny likewise (integers: twice the distance of the centres in full pixels).  A tap outside
+ *     the low image is skipped; a tap with nx >= D or ny >= D is skipped.  Otherwise
+ *       hw = ((float)(D - nx) / (float)D) * ((float)(D - ny) / (float)D),
+ *     a tent of half-width R low pixels around p's centre (R = 1: the bilinear footprint).  A tap with a channel of c(Q) that is not
+ *     finite (pn_isfinite) is skipped.
+ *   Sums.  From T = (+0, +0, +0), V = +0, S = (+0, +0, +0), W = +0, per counted tap:
+ *     T.c = T.c + hw * c(Q).c per channel, then V = V + hw: the unguided sums.
+ *     wn, wd are exactly pbrs_denoise's normal and depth stops between the low guide at Q and the full guide at p: the normal stop on
+ *     normal_lo(Q) - normal_hi(p); the depth stop with zp = depth_hi(p), zq = depth_lo(Q) and s = factor (r = ((zq - zp) / zp) /
+ *     (float)factor), the both-infinite case (1.0f) and the exactly-one-infinite case (+0) included.  A guide counts when both guides_lo
+ *     and guides_hi give it; a pair of NULLs gives 1.0f.
+ *     g = (hw * wn) * wd; with PBRS_UPSAMPLE_ID_STOP, instance_lo(Q) != instance_hi(p) makes g = +0 whatever the stops gave.
+ *     A tap whose g is NaN is left out of the guided sums only.  Otherwise S.c = S.c + g * c(Q).c per channel, then W = W + g.
+ *   Result.  W > min_weight: r.c = S.c * (1.0f / W).  Else V > 0: r.c = T.c * (1.0f / V), the plain tent: it covers a full-size feature the
+ *     low image does not hold, and a non-finite guide at p.  Else r = c(N), N = (x / f, y / f): a non-finite value stays visible, as
+ *     everywhere in this library, and by the tap rule contaminates no pixel that has another tap.
+ *     out(p).c = r.c * d_hi(p).c.  weight_out(p) = W where that plane is given (NULL: not wanted).
+ * Scale rule.  The weights depend on the guides alone: rgb_lo times 2^j gives out times 2^j bit for bit, with pbrs_denoise_var's proviso
+ * (no product or sum that depends on the scale overflows or is a nonzero value below the smallest normal f32 at either scale).
+ * The albedo and the instance planes are read only with their flag.  Pointers are host memory for pbrs_upsample, which stages what it
+ * copies on first use (up to 11 words per low pixel and 12 per full pixel) and synchronises before it returns; device memory for
+ * pbrs_upsample_device (the two guide structs themselves are host memory), which needs no scratch, runs on the context's stream
+ * (pbrs_set_stream honoured) and does not wait: queued behind pbrs_denoise_var_device and the guide render on the same context it needs
+ * no synchronisation.  A context that never calls it allocates nothing.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, rgb_lo, guides_lo, guides_hi or out; w or h 0; factor outside
+ * 2 .. 4; radius outside 1 .. 2; a sigma that is not finite or not > 0; an albedo_floor or a min_weight that is not finite or < 0; unknown
+ * flag bits; a guide given by only one of guides_lo and guides_hi; PBRS_UPSAMPLE_DEMODULATE without the albedo pair;
+ * PBRS_UPSAMPLE_ID_STOP without the instance pair; out equal to rgb_lo or to a guide plane; weight_out equal to out, to rgb_lo or to a
+ * guide plane.  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_UPSAMPLE_DEMODULATE 1u /* rebuild rgb / albedo, multiply by the full-size albedo afterwards */
+#define PBRS_UPSAMPLE_ID_STOP 2u    /* a tap on another instance id has weight 0 */
+#define PBRS_UPSAMPLE_MIN_FACTOR 2u
+#define PBRS_UPSAMPLE_MAX_FACTOR 4u
+#define PBRS_UPSAMPLE_MAX_RADIUS 2u
+typedef struct pbrs_upsample_params {
+    uint32_t w, h;                   /* the full size */
+    uint32_t factor;                 /* 2 .. 4 */
+    uint32_t radius;                 /* 1 .. 2: the tent's half-width in low pixels */
+    uint32_t flags;                  /* PBRS_UPSAMPLE_* */
+    float sigma_normal, sigma_depth; /* finite and > 0: pbrs_denoise's */
+    float albedo_floor;              /* finite and >= 0 */
+    float min_weight;                /* finite and >= 0: a guided sum W at or below it falls back on the plain tent */
+    uint32_t pad[3];
+} pbrs_upsample_params; /* 48 B */
+/* radius 1, no flag, sigma_normal 0.3, sigma_depth 0.2, albedo_floor 1e-3 (the denoiser's), min_weight 1e-3; `out` NULL does
+ * nothing.  Host code: needs no context. */
+void pbrs_upsample_params_default(uint32_t w, uint32_t h, uint32_t factor, pbrs_upsample_params* out);
+int pbrs_upsample(pbrs_ctx*, const pbrs_upsample_params*, const float* rgb_lo_host, const pbrs_denoise_guides* guides_lo_host,
+                  const pbrs_denoise_guides* guides_hi_host, float* out_host, float* weight_out_host);
+int pbrs_upsample_device(pbrs_ctx*, const pbrs_upsample_params*, const float* rgb_lo_device, const pbrs_denoise_guides* guides_lo_device,
+                         const pbrs_denoise_guides* guides_hi_device, float* out_device, float* weight_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -358,6 +358,77 @@ class DisplayParams(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
 
 
+class UpsampleParams(C.Structure):
+    """pbrs_upsample_params (include/pbrs_gpu.h, "guided upsampling"): the full size, the factor per axis, the tent's radius in low
+    pixels, flags, the two guide sigmas of the denoisers, the albedo floor and the guided weight below which a pixel takes the plain
+    tent."""
+    DEMODULATE, ID_STOP = 1, 2
+    FACTORS, RADII = (2, 3, 4), (1, 2)
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("factor", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float), ("min_weight", C.c_float),
+                ("pad", C.c_uint32 * 3)]
+
+    @classmethod
+    def make(cls, w, h, factor=2, radius=1, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, min_weight=1e-3, demodulate=False,
+             id_stop=False):
+        """The defaults are pbrs_upsample_params_default's."""
+        p = cls()
+        p.w, p.h, p.factor, p.radius = w, h, factor, radius
+        p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
+        p.sigma_normal, p.sigma_depth, p.albedo_floor, p.min_weight = sigma_normal, sigma_depth, albedo_floor, min_weight
+        return p
+
+    @classmethod
+    def for_guides(cls, w, h, factor, albedo=False, instance=False, **params):
+        """make() with the image demodulated when there is an albedo pair and taps stopped at id edges when there is an instance pair,
+        unless `params` says otherwise."""
+        params.setdefault("demodulate", bool(albedo))
+        params.setdefault("id_stop", bool(instance))
+        return cls.make(w, h, factor, **params)
+
+    @property
+    def low_size(self):
+        return (self.w + self.factor - 1) // self.factor, (self.h + self.factor - 1) // self.factor
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+def scaled_camera(camera, factor):
+    """`camera` for a film of 1 / factor of the resolution per axis -> a new Camera: width and height rounded up, the pixel steps a and b
+    multiplied in f32 by (float)factor, c and center kept.  A low pixel then sees exactly its factor x factor full pixels for factor 2
+    and 4; for factor 3 the products round, and that is the definition."""
+    factor = int(factor)
+    if factor < 1:
+        raise ValueError("the factor is a positive integer")
+    cam = Camera.from_buffer_copy(camera)
+    cam.width, cam.height = (camera.width + factor - 1) // factor, (camera.height + factor - 1) // factor
+    f = np.float32(factor)
+    for k in range(3):
+        cam.a[k] = np.float32(camera.a[k]) * f
+        cam.b[k] = np.float32(camera.b[k]) * f
+    return cam
+
+
+def _upscale_params(upscale, guides):
+    """render_temporal's / render_animation's `upscale` -> (factor, UpsampleParams.for_guides' keywords), or None: None is the sequence
+    at full resolution, an int the factor, a dict UpsampleParams.make's keywords plus "factor" (2 unless given).  Demodulation follows
+    the albedo guide and the id stop the instance guide unless the dict says otherwise.  An unknown keyword fails here."""
+    if upscale is None or upscale is False:
+        return None
+    if isinstance(upscale, dict):
+        up = dict(upscale)
+        factor = int(up.pop("factor", 2))
+    elif isinstance(upscale, (int, np.integer)) and not isinstance(upscale, bool):
+        up, factor = {}, int(upscale)
+    else:
+        raise ValueError("upscale is None, a factor or a dict of UpsampleParams.make's keywords plus \"factor\"")
+    if factor not in UpsampleParams.FACTORS:
+        raise ValueError(f"the upscale factor is one of {UpsampleParams.FACTORS}, not {factor}")
+    UpsampleParams.for_guides(1, 1, factor, "albedo" in guides, "instance" in guides, **up)
+    return factor, up
+
+
 class DisplayIO(C.Structure):
     """pbrs_display_io: the previous exposure (one float), where this call's goes, where the 512 histogram counts go; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("exposure_in", "exposure_out", "histogram_out")]
@@ -429,7 +500,8 @@ GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_strea
                "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device",
                "pbrs_temporal_accumulate_clip", "pbrs_temporal_accumulate_clip_device",
                "pbrs_spatial_variance", "pbrs_spatial_variance_device",
-               "pbrs_display_params_default", "pbrs_display", "pbrs_display_device"]
+               "pbrs_display_params_default", "pbrs_display", "pbrs_display_device",
+               "pbrs_upsample_params_default", "pbrs_upsample", "pbrs_upsample_device"]
 HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
                 "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
                 "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
@@ -531,6 +603,10 @@ def gpu_lib():
         L.pbrs_display_params_default.restype = None
         L.pbrs_display.argtypes = [C.c_void_p] * 5
         L.pbrs_display_device.argtypes = [C.c_void_p] * 5
+        L.pbrs_upsample_params_default.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.pbrs_upsample_params_default.restype = None
+        L.pbrs_upsample.argtypes = [C.c_void_p] * 7
+        L.pbrs_upsample_device.argtypes = [C.c_void_p] * 7
         _gpu = L
     return _gpu
 
@@ -1335,6 +1411,86 @@ class Context:
         self._check(self._L.pbrs_display_device(self._h, C.addressof(p), C.c_void_p(rgb_device_ptr), C.addressof(io), C.c_void_p(rgba8_device_ptr)),
                     "pbrs_display_device")
 
+    def upsample(self, rgb_lo, w, h, factor=2, lo=None, hi=None, return_weight=False, **params):
+        """Guided upsampling (include/pbrs_gpu.h, pbrs_upsample) of an (hl, wl, 3) f32 image to w x h, hl = ceil(h / factor) and wl
+        likewise -> (h, w, 3) f32; with return_weight also the (h, w) f32 guided weight sums: (out, weight).  `lo`, `hi`: dicts of the
+        guides at the low and at the full size (albedo / normal / depth / instance arrays as render_aovs returns them; a guide counts
+        when both give it).  params: UpsampleParams.make's keywords; by default the image is demodulated when there is an albedo pair and
+        taps stop at instance edges when there is an instance pair."""
+        rgb_lo = np.ascontiguousarray(rgb_lo, dtype=np.float32)
+        lo, hi = {n: a for n, a in dict(lo or {}).items() if a is not None}, {n: a for n, a in dict(hi or {}).items() if a is not None}
+        self._denoise_guide_names(list(lo) + list(hi))
+        p = UpsampleParams.for_guides(w, h, factor, "albedo" in lo and "albedo" in hi, "instance" in lo and "instance" in hi, **params)
+        wl, hl = p.low_size
+        if rgb_lo.shape != (hl, wl, 3):
+            raise ValueError(f"the low image is ({hl}, {wl}, 3) for {w} x {h} at factor {factor}, not {rgb_lo.shape}")
+        gl, gh = DenoiseGuides(), DenoiseGuides()
+        keep = self._host_guides(gl, rgb_lo, lo) + self._host_guides(gh, np.empty((h, w, 0), dtype=np.float32), hi)  # noqa: F841
+        out = np.empty((h, w, 3), dtype=np.float32)
+        weight = np.empty((h, w), dtype=np.float32) if return_weight else None
+        self._check(self._L.pbrs_upsample(self._h, C.addressof(p), rgb_lo.ctypes.data, C.addressof(gl), C.addressof(gh), out.ctypes.data,
+                                          weight.ctypes.data if return_weight else None), "pbrs_upsample")
+        return (out, weight) if return_weight else out
+
+    def upsample_device(self, rgb_lo_device_ptr, out_device_ptr, w, h, factor=2, lo_device_ptrs=None, hi_device_ptrs=None,
+                        weight_out_device_ptr=None, **params):
+        """upsample() on caller-owned device memory: `lo_device_ptrs`, `hi_device_ptrs` = {name: pointer} of albedo / normal / depth /
+        instance at the low and at the full size.  Runs on the context's stream behind whatever was queued there (the filter of the low
+        image and the render of the full-size guides need no synchronisation in between) and does not wait: valid after
+        `collect_stats()`."""
+        gl, gh = DenoiseGuides(), DenoiseGuides()
+        lo, hi = self._device_guides(gl, lo_device_ptrs), self._device_guides(gh, hi_device_ptrs)
+        p = UpsampleParams.for_guides(w, h, factor, bool(lo.get("albedo")) and bool(hi.get("albedo")),
+                                      bool(lo.get("instance")) and bool(hi.get("instance")), **params)
+        self._check(self._L.pbrs_upsample_device(self._h, C.addressof(p), C.c_void_p(rgb_lo_device_ptr), C.addressof(gl), C.addressof(gh),
+                                                 C.c_void_p(out_device_ptr), C.c_void_p(weight_out_device_ptr)), "pbrs_upsample_device")
+
+    def _render_guides_device(self, rgb_device_ptr, guide_device_ptrs, seed, camera=None):
+        """The full-size first-hit guides of guided upsampling: a one-sample render of `seed` through the path integrator at depth 1 (the
+        cheapest route whose first hits are the jittered ones the low-resolution AOVs average; the visualisers shoot through the
+        pixel's corner), its image into `rgb_device_ptr`."""
+        bufs, _ = self._aov_device(guide_device_ptrs)
+        self._render_device(self._params(1, 1, 1, seed, None), rgb_device_ptr, bufs, None, camera=camera)
+
+    def render_upscaled(self, strata_x, strata_y, depth, seed, factor=2, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
+                        upsample=None, **params):
+        """The frame traced and filtered at 1 / factor of the resolution per axis and rebuilt at full size: render_denoised_var's chain
+        through scaled_camera(camera, factor) on the low-resolution tile, the full-size guides as a one-sample render of the same seed
+        (the path integrator at depth 1), then upsample_device; one stream, no synchronisation in between, copied back once ->
+        (h, w, 3) f32 full-size image, (hl, wl, 3) f32 filtered low-resolution image, stats dict (the guide render's, plus "low_res":
+        (wl, hl)).  `upsample`: a dict of UpsampleParams.make's keywords; params: DenoiseVarParams.make's."""
+        self._denoise_guide_names(guides)
+        factor, up = _upscale_params(dict(upsample or {}, factor=factor), guides)
+        w, h = self.scene.width, self.scene.height
+        cam_lo = scaled_camera(self.scene.camera, factor)
+        wl, hl = cam_lo.width, cam_lo.height
+        hip = hip_runtime()
+        sizes = {"rgb": 3 * wl * hl * 4, "out": 3 * wl * hl * 4, VARIANCE: wl * hl * 4, "up": 3 * w * h * 4,
+                 **{f"{n}_lo": DENOISE_GUIDES[n][0] * wl * hl * 4 for n in guides}, **{f"{n}_hi": DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
+        dev = {}
+        try:
+            for n, nbytes in sizes.items():
+                ptr = C.c_void_p()
+                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
+                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_upscaled failed")
+                dev[n] = ptr
+            gl, gh = {n: dev[f"{n}_lo"].value for n in guides}, {n: dev[f"{n}_hi"].value for n in guides}
+            bufs, _ = self._aov_device(gl)
+            self._render_device(self._params(strata_x, strata_y, depth, seed, (0, 0, wl, hl), samples_per_pass), dev["rgb"].value, bufs,
+                                dev[VARIANCE].value, camera=cam_lo)
+            self.denoise_var_device(dev["rgb"].value, dev["out"].value, wl, hl, dev[VARIANCE].value, gl, **params)
+            self._render_guides_device(dev["up"].value, gh, seed)
+            self.upsample_device(dev["out"].value, dev["up"].value, w, h, factor, gl, gh, **up)
+            stats = self.collect_stats()  # waits for the stream
+            stats["low_res"] = (wl, hl)
+            full, low = np.empty((h, w, 3), dtype=np.float32), np.empty((hl, wl, 3), dtype=np.float32)
+            if hip.hipMemcpy(full.ctypes.data, dev["up"], full.nbytes, 2) != 0 or hip.hipMemcpy(low.ctypes.data, dev["out"], low.nbytes, 2) != 0:
+                raise PbrsError("hipMemcpy of the upscaled image failed")
+            return full, low, stats
+        finally:
+            for ptr in dev.values():
+                hip.hipFree(ptr)
+
     @staticmethod
     def _spatial_params(spatial, tparams, guides):
         """render_temporal's / render_animation's `spatial` -> SpatialVarianceParams.make's keywords, or None: min_temporal follows the
@@ -1348,7 +1504,7 @@ class Context:
         return sp
 
     def render_temporal(self, cameras, strata_x, strata_y, depth, seeds, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                        temporal=None, spatial=None, clip=None, display=None, **params):
+                        temporal=None, spatial=None, clip=None, display=None, upscale=None, **params):
         """A sequence of frames of the uploaded scene, one per Camera of `cameras` with the seed of `seeds` at the same place, each
         rendered with its guides and its variance, accumulated against the generator's own history (temporal_accumulate_device; the
         history and the guides it is tested against live in ping-pong device buffers) and filtered (denoise_var_device on the
@@ -1362,7 +1518,12 @@ class Context:
         HistoryClipParams makes every accumulation after the first the clipped one (temporal_accumulate's `clip`).  `display`: None is
         that chain; True, or a dict of DisplayParams.make's keywords (auto=True unless it says otherwise), queues display_device on each
         frame's filtered image on the same stream, the exposure carried from frame to frame in a device word: the frame's stats gain
-        "display", the (h, w, 4) uint8 image, and "exposure", the auto exposure applied to it."""
+        "display", the (h, w, 4) uint8 image, and "exposure", the auto exposure applied to it.  `upscale`: None is that chain; a factor
+        (2, 3 or 4), or a dict of UpsampleParams.make's keywords plus "factor", runs the chain unchanged at 1 / factor of the resolution
+        per axis through scaled_camera of each Camera (which are still given at full size) and queues two more calls per frame on the
+        same stream, the render of the full-size guides and upsample_device behind the filter: the first image of a frame is then the
+        full-size one, the accumulated and the noisy ones stay low, `display` acts on the full-size image, and the stats gain
+        "low_res", (wl, hl)."""
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -1370,11 +1531,12 @@ class Context:
         if len(cameras) != len(seeds):
             raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display,
+                                         upscale):
             yield out[:4]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
-                         temporal=None, motion_vectors=False, spatial=None, clip=None, display=None, **params):
+                         temporal=None, motion_vectors=False, spatial=None, clip=None, display=None, upscale=None, **params):
         """render_temporal for sequences in which instances move.  `frames` yields (HostScene, Camera or None, seed): every frame's scene
         is uploaded (the same instances in the same order as the frame before, moved: instance ids are stable), rendered through the
         Camera (None: the scene's own) with its guides and its variance, accumulated with the table of instance_motion(scene, previous
@@ -1383,31 +1545,35 @@ class Context:
         frame; motion_vectors="prev_depth": (h, w, 3), the depth the previous frame would have recorded as the third channel, +inf where
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
-        are `spatial` and `display`."""
+        are `spatial`, `display` and `upscale` (the motion vectors are then the low-resolution chain's)."""
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
-        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display):
+        for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display,
+                                         upscale):
             yield out if motion_vectors else out[:4]
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None, display=None):
+                         clip=None, display=None, upscale=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  `spatial`: None, or what queues the
         spatial variance estimate between the accumulation and the filter (_spatial_params).  `clip`: temporal_accumulate_device's.  `display`: None, or what queues the
-        display transform behind the filter (_display_params); only then are its two buffers allocated."""
+        display transform behind the filter (_display_params); only then are its two buffers allocated.  `upscale`: None, or what runs the
+        chain at low resolution and queues the guide render and the upsample behind the filter (_upscale_params); only then are the
+        full-size guides and the full-size image allocated, and w, h below are the low size (fw, fh the full one)."""
         tparams = dict(temporal or {})
         TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
         clip = _history_clip(clip)
         sparams = self._spatial_params(spatial, tparams, guides)
         dparams = _display_params(display)
+        uparams = _upscale_params(upscale, guides)
         hip = hip_runtime()
         kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
         dev = {}
         try:
             cam_prev = scene_prev = None
-            w = h = n_rgb = 0
+            w = h = fw = fh = n_rgb = 0
             for i, (scene, cam, seed) in enumerate(frames):
                 table = None
                 if scene is not None:
@@ -1416,8 +1582,13 @@ class Context:
                         table = instance_motion(scene, scene_prev)
                     scene_prev = scene
                 cam = Camera.from_buffer_copy(cam if cam is not None else self.scene.camera)  # (a scene's own camera lives in the scene)
+                cam_full, tile = cam, None
+                if uparams is not None:
+                    cam = scaled_camera(cam_full, uparams[0])
+                    tile = (0, 0, cam.width, cam.height)
                 if i == 0:
-                    w, h = self.scene.width, self.scene.height
+                    fw, fh = self.scene.width, self.scene.height
+                    w, h = (fw, fh) if uparams is None else (cam.width, cam.height)
                     n_rgb = 3 * w * h * 4
                     sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, "acc_variance": w * h * 4}
                     for k in (0, 1):
@@ -1426,19 +1597,22 @@ class Context:
                     sizes.update({n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides if n not in kept})
                     if motion_vectors:
                         sizes["motion"], sizes["prev_depth"] = 2 * w * h * 4, w * h * 4
+                    if uparams is not None:
+                        sizes["up"] = 3 * fw * fh * 4
+                        sizes.update({f"{n}_hi": DENOISE_GUIDES[n][0] * fw * fh * 4 for n in guides})
                     if dparams is not None:
-                        sizes["display"], sizes["exposure"] = w * h * 4, 4
+                        sizes["display"], sizes["exposure"] = fw * fh * 4, 4
                     for n, nbytes in sizes.items():
                         ptr = C.c_void_p()
                         if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
                             raise PbrsError(f"hipMalloc of {nbytes} bytes for a temporal sequence failed")
                         dev[n] = ptr
-                elif (self.scene.width, self.scene.height) != (w, h):
-                    raise ValueError(f"frame {i} has a film of {self.scene.width} x {self.scene.height}, the sequence {w} x {h}")
+                elif (self.scene.width, self.scene.height) != (fw, fh):
+                    raise ValueError(f"frame {i} has a film of {self.scene.width} x {self.scene.height}, the sequence {fw} x {fh}")
                 cur, old = i & 1, (i & 1) ^ 1
                 gp = {n: dev[f"{n}{cur}" if n in kept else n].value for n in guides}
                 bufs, _ = self._aov_device(gp)
-                self._render_device(self._params(strata_x, strata_y, depth, seed, None, samples_per_pass), dev["rgb"].value, bufs,
+                self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), dev["rgb"].value, bufs,
                                     dev[VARIANCE].value, camera=cam)
                 frame = {"rgb": dev["rgb"].value, "variance": dev[VARIANCE].value, **{n: gp[n] for n in kept}}
                 hist = [{n: dev[f"h_{n}{k}"].value for n in TEMPORAL_HISTORY} for k in (0, 1)]
@@ -1452,19 +1626,27 @@ class Context:
                     self.spatial_variance_device(hist[cur]["moments"], hist[cur]["length"], dev["acc_variance"].value, dev["acc_variance"].value,
                                                  w, h, {n: gp[n] for n in kept}, **sparams)
                 self.denoise_var_device(hist[cur]["rgb"], dev["out"].value, w, h, dev["acc_variance"].value, gp, **params)
+                shown_src = dev["out"]
+                if uparams is not None:
+                    gh = {n: dev[f"{n}_hi"].value for n in guides}
+                    self._render_guides_device(dev["up"].value, gh, seed, camera=cam_full)
+                    self.upsample_device(dev["out"].value, dev["up"].value, fw, fh, uparams[0], gp, gh, **uparams[1])
+                    shown_src = dev["up"]
                 if dparams is not None:  # the first frame has no previous exposure; later ones read the word the last one wrote
-                    self.display_device(dev["out"].value, dev["display"].value, w, h,
+                    self.display_device(shown_src.value, dev["display"].value, fw, fh,
                                         {"exposure_in": dev["exposure"].value if i else None, "exposure_out": dev["exposure"].value}, **dparams)
                 stats = self.collect_stats()  # waits for the stream
                 if dparams is not None:
-                    shown, e = np.empty((h, w, 4), dtype=np.uint8), np.zeros(1, dtype=np.float32)
+                    shown, e = np.empty((fh, fw, 4), dtype=np.uint8), np.zeros(1, dtype=np.float32)
                     if hip.hipMemcpy(shown.ctypes.data, dev["display"], shown.nbytes, 2) != 0 or hip.hipMemcpy(e.ctypes.data, dev["exposure"], 4, 2) != 0:
                         raise PbrsError("hipMemcpy of a temporal sequence's display image failed")
                     stats["display"], stats["exposure"] = shown, e[0]
+                if uparams is not None:
+                    stats["low_res"] = (w, h)
                 images = []
-                for src in (dev["out"], dev[f"h_rgb{cur}"], dev["rgb"]):
-                    img = np.empty((h, w, 3), dtype=np.float32)
-                    if hip.hipMemcpy(img.ctypes.data, src, n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
+                for src in (shown_src, dev[f"h_rgb{cur}"], dev["rgb"]):
+                    img = np.empty((fh, fw, 3) if src is dev.get("up") else (h, w, 3), dtype=np.float32)
+                    if hip.hipMemcpy(img.ctypes.data, src, img.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
                         raise PbrsError("hipMemcpy of a temporal sequence's image failed")
                     images.append(img)
                 mv = None

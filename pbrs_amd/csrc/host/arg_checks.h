@@ -67,5 +67,9 @@ Refusal check_spatial_variance(const pbrs_spatial_variance_params* p, const floa
 // pbrs_display* (host/arg_checks_display.cpp, beside the filler pbrs_display_params_default).  `io` and its pointers may be NULL; the
 // fields only the auto exposure reads are checked only with PBRS_DISPLAY_AUTO_EXPOSURE.
 Refusal check_display(const pbrs_display_params* p, const float* rgb, const pbrs_display_io* io, const uint32_t* rgba8_out);
+// pbrs_upsample* (host/arg_checks_upsample.cpp, beside the filler pbrs_upsample_params_default).  `weight_out` may be NULL; a guide of
+// `lo` and `hi` counts when both give it.
+Refusal check_upsample(const pbrs_upsample_params* p, const float* rgb_lo, const pbrs_denoise_guides* lo, const pbrs_denoise_guides* hi,
+                       const float* out, const float* weight_out);
 
 }  // namespace pbrs

@@ -37,6 +37,7 @@
 #include "device/temporal.h"
 #include "device/spatial_variance.h"
 #include "device/display.h"
+#include "device/upsample.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -144,6 +145,9 @@ enum BufferId {
     // display transform (pbrs_display, device/display.h): the 512-word histogram, the scale word and the host variant's two exposure
     // words (kDisplayScratchWords), and the host variant's staging (the image, the 8-bit result)
     BUF_DISPLAY, BUF_DISPLAY_STAGE,
+    // guided upsampling (pbrs_upsample, device/upsample.h): the host variant's staging (the low image and its four guides at the low
+    // size, the four full-size guides, the result and its weights, one after the other); the device variant needs nothing
+    BUF_UPSAMPLE_STAGE,
     N_BUFFERS
 };
 
@@ -409,12 +413,15 @@ int ensure_direct(pbrs_ctx* c, int k, size_t n_slots, bool wanted) {
 
 // One plane of a host variant's device staging: the host memory copied up into it before the launches (`up`; null: not given), its
 // words per pixel, the host memory it is copied back to after them (`down`; null: not wanted), and where `stage` put it on the device
-// (null where neither is given).  A result that lands in an input's place is one row with both.
+// (null where neither is given).  A result that lands in an input's place is one row with both.  A row of another size than the
+// call's P pixels says so in `pixels` (pbrs_upsample's low-resolution planes); 0 is P.
 struct Staged {
     const void* up;
     size_t words;
     void* down = nullptr;
     void* dev = nullptr;
+    size_t pixels = 0;
+    size_t count(size_t P) const { return words * (pixels ? pixels : P); }
     template <class T>
     T* as() const { return static_cast<T*>(dev); }
 };
@@ -425,14 +432,14 @@ struct Staged {
 template <size_t N>
 int stage(pbrs_ctx* c, BufferId id, const char* what, Staged (&s)[N], size_t P) {
     size_t words = 0;
-    for (const Staged& r : s) words += r.words;
+    for (const Staged& r : s) words += r.count(P);
     DeviceBuffer& buf = c->buf[id];
-    int rc = buf.grow(c, words * P * sizeof(uint32_t), what);
+    int rc = buf.grow(c, words * sizeof(uint32_t), what);
     if (rc) return rc;
     uint32_t* at = buf.as<uint32_t>();
     for (Staged& r : s) {
         r.dev = (r.up || r.down) ? at : nullptr;
-        at += r.words * P;
+        at += r.count(P);
     }
     return PBRS_OK;
 }
@@ -444,7 +451,7 @@ int copy_staged(pbrs_ctx* c, const Staged (&s)[N], size_t P, hipMemcpyKind kind)
     for (const Staged& r : s) {
         const bool up = kind == hipMemcpyHostToDevice;
         if (!(up ? r.up != nullptr : r.down != nullptr)) continue;
-        HIPCHK(c, hipMemcpyAsync(up ? r.dev : r.down, up ? r.up : r.dev, r.words * P * sizeof(uint32_t), kind, c->stream));
+        HIPCHK(c, hipMemcpyAsync(up ? r.dev : r.down, up ? r.up : r.dev, r.count(P) * sizeof(uint32_t), kind, c->stream));
     }
     return PBRS_OK;
 }
@@ -1694,6 +1701,63 @@ int pbrs_display(pbrs_ctx* c, const pbrs_display_params* p, const float* rgb_hos
         if (io.exposure_out) HIPCHK(c, hipMemcpyAsync(io.exposure_out, scratch + kDisplayExposureWord, sizeof(float), hipMemcpyDeviceToHost, c->stream));
         if (io.histogram_out) HIPCHK(c, hipMemcpyAsync(io.histogram_out, scratch, PBRS_DISPLAY_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         return (int)PBRS_OK;
+    });
+}
+
+// ---- guided upsampling (include/pbrs_gpu.h, device/upsample.h) ----
+static_assert(sizeof(pbrs_upsample_params) == 48, "pbrs_upsample_params is 48 B");
+static_assert(PBRS_UPSAMPLE_MIN_FACTOR == 2u && PBRS_UPSAMPLE_MAX_FACTOR == 4u && PBRS_UPSAMPLE_MAX_RADIUS == 2u, "kUpsample holds every factor and radius");
+
+namespace {
+
+using UpsampleKernel = void (*)(UpsampleIn, float*, float*, UpsampleConst);
+// [factor - 2][radius - 1][id stop]
+#define PBRS_UPSAMPLE_ROW(F) {{k_upsample<F, 1u, false>, k_upsample<F, 1u, true>}, {k_upsample<F, 2u, false>, k_upsample<F, 2u, true>}}
+constexpr UpsampleKernel kUpsample[3][2][2] = {PBRS_UPSAMPLE_ROW(2u), PBRS_UPSAMPLE_ROW(3u), PBRS_UPSAMPLE_ROW(4u)};
+#undef PBRS_UPSAMPLE_ROW
+
+// The one launch on the context's stream (arguments checked; device pointers).  A plane the call's flags and pairs leave unread goes to
+// the kernel as null.
+int upsample_launch(pbrs_ctx* c, const pbrs_upsample_params& p, const float* rgb_lo, const pbrs_denoise_guides& lo, const pbrs_denoise_guides& hi,
+                    float* out, float* weight_out) {
+    UpsampleConst k{};
+    k.w = p.w, k.h = p.h;
+    k.wl = (p.w + p.factor - 1) / p.factor, k.hl = (p.h + p.factor - 1) / p.factor;
+    k.in = 1.0f / (p.sigma_normal * p.sigma_normal);
+    k.id = 1.0f / (p.sigma_depth * p.sigma_depth);
+    k.albedo_floor = p.albedo_floor, k.min_weight = p.min_weight;
+    const bool demodulate = (p.flags & PBRS_UPSAMPLE_DEMODULATE) != 0, ids = (p.flags & PBRS_UPSAMPLE_ID_STOP) != 0;
+    const UpsampleIn in{rgb_lo, demodulate ? lo.albedo : nullptr, lo.normal, lo.depth, ids ? lo.instance : nullptr,
+                        demodulate ? hi.albedo : nullptr, hi.normal, hi.depth, ids ? hi.instance : nullptr};
+    const dim3 grid((p.w + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL, (p.h + PBRS_DENOISE_CELL - 1) / PBRS_DENOISE_CELL);
+    hipLaunchKernelGGL(kUpsample[p.factor - 2u][p.radius - 1u][ids], grid, dim3(kBlock), 0, c->stream, in, out, weight_out, k);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrs_upsample_device(pbrs_ctx* c, const pbrs_upsample_params* p, const float* rgb_lo_device, const pbrs_denoise_guides* guides_lo_device,
+                         const pbrs_denoise_guides* guides_hi_device, float* out_device, float* weight_out_device) {
+    const int rc = enter(c, check_upsample(p, rgb_lo_device, guides_lo_device, guides_hi_device, out_device, weight_out_device));
+    if (rc) return rc;
+    return upsample_launch(c, *p, rgb_lo_device, *guides_lo_device, *guides_hi_device, out_device, weight_out_device);
+}
+
+int pbrs_upsample(pbrs_ctx* c, const pbrs_upsample_params* p, const float* rgb_lo_host, const pbrs_denoise_guides* guides_lo_host,
+                  const pbrs_denoise_guides* guides_hi_host, float* out_host, float* weight_out_host) {
+    const int rc = enter(c, check_upsample(p, rgb_lo_host, guides_lo_host, guides_hi_host, out_host, weight_out_host));
+    if (rc) return rc;
+    const size_t P = (size_t)p->w * p->h;
+    const size_t Pl = (size_t)((p->w + p->factor - 1) / p->factor) * ((p->h + p->factor - 1) / p->factor);
+    const pbrs_denoise_guides &lo = *guides_lo_host, &hi = *guides_hi_host;
+    Staged s[] = {{rgb_lo_host, 3, nullptr, nullptr, Pl}, {lo.albedo, 3, nullptr, nullptr, Pl}, {lo.normal, 3, nullptr, nullptr, Pl},
+                  {lo.depth, 1, nullptr, nullptr, Pl},    {lo.instance, 1, nullptr, nullptr, Pl},
+                  {hi.albedo, 3}, {hi.normal, 3}, {hi.depth, 1}, {hi.instance, 1}, {nullptr, 3, out_host}, {nullptr, 1, weight_out_host}};
+    return run_staged(c, BUF_UPSAMPLE_STAGE, "the guided upsampling's staging", s, P, [&] {
+        const pbrs_denoise_guides lod{s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
+        const pbrs_denoise_guides hid{s[5].as<float>(), s[6].as<float>(), s[7].as<float>(), s[8].as<uint32_t>()};
+        return upsample_launch(c, *p, s[0].as<float>(), lod, hid, s[9].as<float>(), s[10].as<float>());
     });
 }
 

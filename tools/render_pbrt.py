@@ -40,7 +40,12 @@ and lights that change do not lag (include/pbrs_gpu.h, pbrs_temporal_accumulate_
 exposure (--exposure X, default 1; with --auto-exposure the trimmed log-average luminance is mapped to 0.18 and X is a compensation on
 top), the tone curve, the transfer function (--encode, default srgb) and rounding to 8 bits; the file holds the GPU's bytes.  With
 --frames N --temporal every frame's filtered image goes through it on the frame's stream (render_temporal's display=) and
-<out>.NNNN.display.png is written; the auto exposure then eases from frame to frame."""
+<out>.NNNN.display.png is written; the auto exposure then eases from frame to frame.
+--upscale F [--upscale-radius R]: the frame traced and filtered at 1 / F of the resolution per axis (F 2 .. 4) and rebuilt at full size by
+guided upsampling (include/pbrs_gpu.h, pbrs_upsample; R 1 .. 2, default 1: the tent's half-width in low pixels) with full-size guides of one
+sample per pixel: also writes <out>.upscaled.<ext> and <out>.upscaled_low.<ext> (Context.render_upscaled; --denoise-var's parameters apply
+to the low-resolution filter).  With --frames N --temporal the sequence itself runs at low resolution (render_temporal's upscale=) and
+<out>.NNNN.<ext> is the full-size image.  --msaa counts samples per traced, low-resolution pixel."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -51,6 +56,7 @@ motion_vectors = "--motion-vectors" in sys.argv
 spatial_variance = "--spatial-variance" in sys.argv
 history_clip = None  # HistoryClipParams.make's keywords
 display = None  # DisplayParams.make's keywords
+upscale = None  # UpsampleParams.make's keywords plus "factor"
 auto_exposure = "--auto-exposure" in sys.argv
 spin, spin_deg = [], 0.0
 aovs = "--aovs" in sys.argv
@@ -62,7 +68,7 @@ denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 frames, orbit = 0, 0.0
-for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -85,6 +91,10 @@ for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "-
             display = dict(display or {}, encode=value)
         elif flag == "--exposure":
             display = dict(display or {}, exposure=float(value))
+        elif flag == "--upscale":
+            upscale = dict(upscale or {}, factor=int(value))
+        elif flag == "--upscale-radius":
+            upscale = dict(upscale or {}, radius=int(value))
         elif flag == "--denoise-iterations":
             denoise_params["iterations"] = denoise_var_params["iterations"] = int(value)
         elif flag == "--matte":
@@ -99,6 +109,8 @@ for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "-
             denoise_params.update(zip(("sigma_color", "sigma_normal", "sigma_depth"), (float(v) for v in value.split(","))))
             denoise_var_params.update({k: v for k, v in denoise_params.items() if k in ("sigma_normal", "sigma_depth")})
 sys.argv = [a for a in sys.argv if a not in ("--aovs", "--pixel-filter", "--denoise", "--denoise-var", "--passes", "--denoise-passes", "--temporal", "--motion-vectors", "--spatial-variance", "--auto-exposure")]
+if upscale is not None and (upscale.get("factor") not in pbrs_amd.UpsampleParams.FACTORS or upscale.get("radius", 1) not in pbrs_amd.UpsampleParams.RADII):
+    sys.exit("--upscale 2|3|4 [--upscale-radius 1|2]")
 if display is not None or auto_exposure:
     if "curve" not in (display or {}):
         sys.exit("--encode, --exposure and --auto-exposure go with --display none|reinhard|aces")
@@ -168,13 +180,15 @@ if frames:
         sys.exit("--history-clip GAMMA goes with --frames N --temporal, --history-clip-radius with --history-clip")
     if display is not None and not temporal:
         sys.exit("with --frames N, --display goes with --temporal")
+    if upscale is not None and not temporal:
+        sys.exit("with --frames N, --upscale goes with --temporal")
     spatial = True if spatial_variance else None
     if spin or motion_vectors:
         sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
-                                        spatial=spatial, clip=history_clip, display=display, **denoise_var_params)
+                                        spatial=spatial, clip=history_clip, display=display, upscale=upscale, **denoise_var_params)
     elif temporal:
         sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, clip=history_clip, display=display,
-                                       **denoise_var_params)
+                                       upscale=upscale, **denoise_var_params)
     else:
         sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
     for k, images in enumerate(sequence):
@@ -220,6 +234,12 @@ if display is not None:
     shown, e = ctx.display(img, return_exposure=True, **display)
     pbrs_amd.write_image_u8(f"{stem}.display.png", shown)
     print(f"-> {stem}.display.png ({display['curve']}, {display.get('encode', 'srgb')}, exposure {float(e) * display.get('exposure', 1.0):.4g})")
+if upscale is not None:
+    up = {k: v for k, v in upscale.items() if k != "factor"}
+    full, low, _ = ctx.render_upscaled(msaa, msaa, depth, 1, factor=upscale["factor"], upsample=up, **denoise_var_params)
+    pbrs_amd.write_image(f"{stem}.upscaled{ext}", full)
+    pbrs_amd.write_image(f"{stem}.upscaled_low{ext}", low)
+    print(f"-> {stem}.upscaled{ext} ({low.shape[1]}x{low.shape[0]} traced and filtered, factor {upscale['factor']}, radius {upscale.get('radius', 1)})")
 if denoise:
     pbrs_amd.write_image(f"{stem}.denoised{ext}", ctx.denoise(img, **{n: buf[n] for n in guides}, **denoise_params))
     print(f"-> {stem}.denoised{ext}")
