@@ -2,7 +2,8 @@
 
 Only the path-integrator hot path of plumer/pbrs: the HIP kernels + C ABI
 (csrc/, include/pbrs_gpu.h), the host-side scene flattener (csrc/host, include/pbrs_host.h),
-their ctypes bindings (api.py) and the synthetic scene generators (scenes.py).
+their ctypes mirrors (abi.py), loaders (libs.py) and driver (api.py, device buffers in devmem.py),
+and the synthetic scene generators (scenes.py).
 """
-from .api import Context, DenoiseGuides, DenoiseParams, DenoiseVarGuides, DenoiseVarParams, DisplayParams, HistoryClipParams, HostScene, LoadedScene, MatteBuffers, MatteParams, PassBuffers, PbrsError, PixelFilter, SpatialVarianceParams, UpsampleParams, gpu_lib, host_lib, lib_paths, load_pbrt, scaled_camera, write_image, write_image_u8  # noqa: F401
+from .api import Context, DenoiseGuides, DenoiseParams, DenoiseVarGuides, DenoiseVarParams, DeviceBuffers, DisplayParams, HistoryClipParams, HostScene, LoadedScene, MatteBuffers, MatteParams, PassBuffers, PbrsError, PixelFilter, SpatialVarianceParams, UpsampleParams, gpu_lib, host_lib, lib_paths, load_pbrt, scaled_camera, write_image, write_image_u8  # noqa: F401
 from . import scenes, spec  # noqa: F401

@@ -8,624 +8,19 @@ device call fails, these raise.
 """
 import ctypes as C
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
-from .spec import SceneSpec
-
-from . import spec as _spec
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIBDIR = os.path.join(_HERE, "lib")
-
-
-class PbrsError(RuntimeError):
-    pass
-
-
-class Node(C.Structure):
-    _fields_ = [("min", C.c_float * 3), ("a", C.c_uint32), ("max", C.c_float * 3), ("b", C.c_uint32)]
-
-
-class SceneDesc(C.Structure):
-    _fields_ = [("n_tlas_nodes", C.c_uint32), ("tlas_nodes", C.c_void_p), ("tlas_height", C.c_uint32),
-                ("n_instances", C.c_uint32), ("instances", C.c_void_p),
-                ("n_shapes", C.c_uint32), ("shapes", C.c_void_p),
-                ("n_meshes", C.c_uint32), ("meshes", C.c_void_p),
-                ("n_blas_nodes", C.c_uint32), ("blas_nodes", C.c_void_p),
-                ("n_triangles", C.c_uint32), ("tri_verts", C.c_void_p), ("tri_shade", C.c_void_p),
-                ("n_materials", C.c_uint32), ("materials", C.c_void_p),
-                ("n_bxdfs", C.c_uint32), ("bxdfs", C.c_void_p),
-                ("n_area_lights", C.c_uint32), ("area_lights", C.c_void_p),
-                ("n_delta_lights", C.c_uint32), ("delta_lights", C.c_void_p),
-                ("env_constant", C.c_float * 3), ("env_kind", C.c_uint32),
-                ("n_textures", C.c_uint32), ("textures", C.c_void_p),
-                ("n_tex_floats", C.c_uint32), ("tex_floats", C.c_void_p),
-                ("n_tex_words", C.c_uint32), ("tex_words", C.c_void_p),
-                ("env_texture", C.c_uint32), ("env_scale", C.c_float * 3),
-                ("n_fourier_tables", C.c_uint32), ("fourier_tables", C.c_void_p)]
-
-
-class Camera(C.Structure):
-    _fields_ = [("center", C.c_float * 3), ("width", C.c_uint32), ("c", C.c_float * 3), ("height", C.c_uint32),
-                ("a", C.c_float * 3), ("pad0", C.c_float), ("b", C.c_float * 3), ("pad1", C.c_float)]
-
-
-class Stats(C.Structure):
-    _fields_ = ([(n, C.c_uint64) for n in (
-        "samples", "closest_rays", "shadow_rays", "shade_events", "tlas_nodes", "blas_nodes", "instances", "instance_hits",
-        "triangles", "tri_shading", "spheres", "quads", "cuboids", "disks", "shadow_tlas_nodes", "shadow_blas_nodes",
-        "shadow_instances", "shadow_triangles", "shadow_prims", "invalid_samples")] +
-                [(n, C.c_float) for n in ("ms_raygen", "ms_extend", "ms_shade", "ms_shadow", "ms_accumulate", "ms_total")] +
-                [(n, C.c_uint32) for n in ("launches_extend", "launches_shadow", "launches_shade", "passes", "kernel_features_extend", "kernel_features_shadow")] +
-                [("paths_at_bounce", C.c_uint64 * 16), ("shadow_rays_at_bounce", C.c_uint64 * 16)])
-
-    def as_dict(self):
-        return {n: (list(getattr(self, n)) if n.endswith("_at_bounce") else getattr(self, n)) for n, _ in self._fields_}
-
-
-class RenderParams(C.Structure):
-    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("strata_x", C.c_uint32),
-                ("strata_y", C.c_uint32), ("max_depth", C.c_uint32), ("samples_per_pass", C.c_uint32), ("seed", C.c_uint64),
-                ("collect_counters", C.c_uint32), ("time_stages", C.c_uint32),
-                ("band_rows", C.c_uint32), ("band_count", C.c_uint32), ("band_index", C.c_uint32), ("integrator", C.c_uint32)]
-
-
-class AovBuffers(C.Structure):
-    """pbrs_aov_buffers: one pointer per first-hit AOV, NULL = not wanted (include/pbrs_gpu.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "coverage", "depth", "instance", "material", "prim")]
-
-
-# name -> (channels, dtype) of each AOV, in the order of pbrs_aov_buffers
-AOVS = {"albedo": (3, np.float32), "normal": (3, np.float32), "coverage": (1, np.float32), "depth": (1, np.float32),
-        "instance": (1, np.uint32), "material": (1, np.uint32), "prim": (1, np.uint32)}
-AOV_NAMES = ("albedo", "normal", "depth", "instance", "material", "prim", "coverage")
-
-
-VARIANCE = "variance"  # the variance AOV (pbrs_render_tile_aovs_var): (h, w) f32, a pointer of its own beside pbrs_aov_buffers
-
-
-def _aov_names(aovs):
-    names = tuple(aovs)
-    unknown = [n for n in names if n not in AOVS and n != VARIANCE]
-    if unknown:
-        raise ValueError(f"unknown AOV name(s) {unknown}; known: {sorted(AOVS) + [VARIANCE]}")
-    return names
-
-
-class PixelFilter(C.Structure):
-    """pbrs_pixel_filter (include/pbrs_gpu.h): kind, radius (x, y), a, b.  The constructors carry pbrt-v3's defaults."""
-    BOX, TRIANGLE, GAUSSIAN, MITCHELL, LANCZOS = range(5)
-    _fields_ = [("kind", C.c_uint32), ("radius", C.c_float * 2), ("a", C.c_float), ("b", C.c_float), ("pad", C.c_uint32)]
-
-    @classmethod
-    def make(cls, kind, rx, ry=None, a=0.0, b=0.0):
-        f = cls()
-        f.kind, f.radius[0], f.radius[1], f.a, f.b = kind, rx, rx if ry is None else ry, a, b
-        return f
-
-    @classmethod
-    def box(cls, rx=0.5, ry=None):
-        return cls.make(cls.BOX, rx, ry)
-
-    @classmethod
-    def triangle(cls, rx=2.0, ry=None):
-        return cls.make(cls.TRIANGLE, rx, ry)
-
-    @classmethod
-    def gaussian(cls, rx=2.0, ry=None, alpha=2.0):
-        return cls.make(cls.GAUSSIAN, rx, ry, alpha)
-
-    @classmethod
-    def mitchell(cls, rx=2.0, ry=None, B=1.0 / 3.0, C=1.0 / 3.0):
-        return cls.make(cls.MITCHELL, rx, ry, B, C)
-
-    @classmethod
-    def lanczos(cls, rx=4.0, ry=None, tau=3.0):
-        return cls.make(cls.LANCZOS, rx, ry, tau)
-
-    def as_tuple(self):
-        return (int(self.kind), float(self.radius[0]), float(self.radius[1]), float(self.a), float(self.b))
-
-    def __repr__(self):
-        names = ("box", "triangle", "gaussian", "mitchell", "lanczos")
-        k = names[self.kind] if self.kind < len(names) else self.kind
-        return f"PixelFilter({k}, radius=({self.radius[0]}, {self.radius[1]}), a={self.a}, b={self.b})"
-
-
-class _DenoiseParamsMixin:
-    """What DenoiseParams and DenoiseVarParams share: the flag bits, the defaults that follow the guides, as_dict."""
-    DEMODULATE, ID_STOP = 1, 2
-    MAX_ITERATIONS = 6
-
-    @classmethod
-    def _make(cls, w, h, iterations, sigmas, albedo_floor, demodulate, id_stop):
-        p = cls()
-        p.w, p.h, p.iterations = w, h, iterations
-        p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
-        for (n, _), v in zip(cls._fields_[4:7], sigmas):
-            setattr(p, n, v)
-        p.albedo_floor = albedo_floor
-        return p
-
-    @classmethod
-    def for_guides(cls, w, h, albedo=False, instance=False, **params):
-        """The defaults for the guides at hand: demodulate when there is an albedo, stop at instance edges when there are ids."""
-        params.setdefault("demodulate", bool(albedo))
-        params.setdefault("id_stop", bool(instance))
-        return cls.make(w, h, **params)
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
-
-
-class DenoiseParams(_DenoiseParamsMixin, C.Structure):
-    """pbrs_denoise_params (include/pbrs_gpu.h): image size, iterations, flags, the three sigmas and the albedo floor.  `make` carries
-    the defaults ("Denoiser": chosen from the measured error ratios)."""
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float),
-                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
-
-    @classmethod
-    def make(cls, w, h, iterations=5, sigma_color=16.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
-             id_stop=False):
-        return cls._make(w, h, iterations, (sigma_color, sigma_normal, sigma_depth), albedo_floor, demodulate, id_stop)
-
-
-class DenoiseGuides(C.Structure):
-    """pbrs_denoise_guides: the AOV layouts, NULL = that stop is off."""
-    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance")]
-
-
-class DenoiseVarParams(_DenoiseParamsMixin, C.Structure):
-    """pbrs_denoise_var_params (include/pbrs_gpu.h): DenoiseParams with sigma_luminance, a count of standard deviations (SVGF's 4),
-    in the place of sigma_color."""
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_luminance", C.c_float),
-                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float)]
-
-    @classmethod
-    def make(cls, w, h, iterations=5, sigma_luminance=4.0, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, demodulate=False,
-             id_stop=False):
-        return cls._make(w, h, iterations, (sigma_luminance, sigma_normal, sigma_depth), albedo_floor, demodulate, id_stop)
-
-
-class DenoiseVarGuides(C.Structure):
-    """pbrs_denoise_var_guides: the four guides of DenoiseGuides and the variance, which is required."""
-    _fields_ = [(n, C.c_void_p) for n in ("albedo", "normal", "depth", "instance", "variance")]
-
-
-class MatteParams(C.Structure):
-    """pbrs_matte_params (include/pbrs_gpu.h): what a hit is keyed by and how many (id, count) entries a pixel keeps."""
-    INSTANCE, MATERIAL = 0, 1
-    KEYS = {"instance": INSTANCE, "material": MATERIAL}
-    MAX_SLOTS = 8
-    MAX_SELECT = 4096
-    _fields_ = [("key", C.c_uint32), ("slots", C.c_uint32)]
-
-    @classmethod
-    def make(cls, key="instance", slots=6):
-        if key not in cls.KEYS:
-            raise ValueError(f"unknown matte key {key!r}; known: {sorted(cls.KEYS)}")
-        p = cls()
-        p.key, p.slots = cls.KEYS[key], slots
-        return p
-
-
-class MatteBuffers(C.Structure):
-    """pbrs_matte_buffers: ids and coverage, (h, w, slots) u32 / f32, ranked per pixel; residual (h, w) f32, NULL = not wanted."""
-    _fields_ = [(n, C.c_void_p) for n in ("ids", "coverage", "residual")]
-
-
-MATTE_LAYERS = ("ids", "coverage", "residual")
-
-
-class PassBuffers(C.Structure):
-    """pbrs_pass_buffers: direct and indirect light, (h, w, 3) f32, and the variance of each one's pixel mean, (h, w) f32; NULL = not
-    wanted (include/pbrs_gpu.h, "light passes")."""
-    _fields_ = [(n, C.c_void_p) for n in ("direct", "indirect", "direct_variance", "indirect_variance")]
-
-
-# name -> channels of each light pass, in the order of pbrs_pass_buffers
-PASSES = ("direct", "indirect", "direct_variance", "indirect_variance")
-PASS_CHANNELS = {"direct": 3, "indirect": 3, "direct_variance": 1, "indirect_variance": 1}
-
-
-def _pass_names(passes):
-    names = tuple(passes)
-    unknown = [n for n in names if n not in PASS_CHANNELS]
-    if unknown:
-        raise ValueError(f"unknown light pass(es) {unknown}; known: {list(PASSES)}")
-    return names
-
-
-class TemporalParams(C.Structure):
-    """pbrs_temporal_params (include/pbrs_gpu.h, "temporal accumulation"): image size, flags, where the history length saturates, the
-    two reprojection tolerances and the length from which the variance comes from the temporal moments."""
-    ID_TEST = 1
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("flags", C.c_uint32), ("max_history", C.c_float), ("depth_tolerance", C.c_float),
-                ("normal_tolerance", C.c_float), ("min_temporal", C.c_float), ("pad", C.c_uint32)]
-
-    @classmethod
-    def make(cls, w, h, max_history=32.0, depth_tolerance=0.05, normal_tolerance=0.3, min_temporal=4.0, id_test=False):
-        p = cls()
-        p.w, p.h, p.flags = w, h, cls.ID_TEST if id_test else 0
-        p.max_history, p.depth_tolerance, p.normal_tolerance, p.min_temporal = max_history, depth_tolerance, normal_tolerance, min_temporal
-        return p
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
-
-
-class TemporalFrame(C.Structure):
-    """pbrs_temporal_frame: this frame's image, its variance AOV and its guides; rgb and depth are required."""
-    _fields_ = [(n, C.c_void_p) for n in ("rgb", "variance", "depth", "normal", "instance")]
-
-
-class TemporalGuides(C.Structure):
-    """pbrs_temporal_guides: the previous frame's depth, normal and instance."""
-    _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]
-
-
-class TemporalHistory(C.Structure):
-    """pbrs_temporal_history: accumulated colour (h, w, 3), luminance moments (h, w, 2) and history length (h, w), all f32."""
-    _fields_ = [(n, C.c_void_p) for n in ("rgb", "moments", "length")]
-
-
-class InstanceMotion(C.Structure):
-    """pbrs_instance_motion (include/pbrs_gpu.h, "moving instances and motion vectors"): where a point of one instance was one frame
-    ago (m, rows of an affine map), what that does to a normal (n) and IDENTITY = the record is not applied.  96 bytes."""
-    IDENTITY = 1
-    _fields_ = [("m", (C.c_float * 4) * 3), ("n", (C.c_float * 3) * 3), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
-
-
-class HistoryClipParams(C.Structure):
-    """pbrs_history_clip_params (include/pbrs_gpu.h, "history clipping"): the radius of the window whose colour box the reprojected
-    history is clipped to, the box's half width in standard deviations, and the most history a clipped pixel keeps (+inf: all of it)."""
-    MAX_RADIUS = 3
-    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float), ("clip_history", C.c_float), ("flags", C.c_uint32)]
-
-    @classmethod
-    def make(cls, radius=1, gamma=1.0, clip_history=None):
-        p = cls()
-        p.radius, p.gamma, p.clip_history = radius, gamma, float("inf") if clip_history is None else clip_history
-        return p
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
-
-
-def _history_clip(clip):
-    """temporal_accumulate's `clip` -> a HistoryClipParams or None: None or False is the call without a clip, True the defaults, a dict
-    HistoryClipParams.make's keywords (an unknown one fails here)."""
-    if clip is None or clip is False:
-        return None
-    if isinstance(clip, HistoryClipParams):
-        return clip
-    if clip is True:
-        return HistoryClipParams.make()
-    if isinstance(clip, dict):
-        return HistoryClipParams.make(**clip)
-    raise ValueError("clip is None, True, a dict of HistoryClipParams.make's keywords or a HistoryClipParams")
-
-
-class SpatialVarianceParams(C.Structure):
-    """pbrs_spatial_variance_params (include/pbrs_gpu.h, "spatial variance estimate for short histories"): image size, the window's
-    radius, flags, the two guide sigmas of the denoisers and the history length below which a pixel's variance is estimated."""
-    ID_STOP, ONLY_UNKNOWN = 1, 2
-    MAX_RADIUS = 3
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("sigma_normal", C.c_float),
-                ("sigma_depth", C.c_float), ("min_temporal", C.c_float), ("pad", C.c_uint32)]
-
-    @classmethod
-    def make(cls, w, h, radius=3, sigma_normal=0.3, sigma_depth=0.2, min_temporal=4.0, id_stop=False, only_unknown=False):
-        p = cls()
-        p.w, p.h, p.radius = w, h, radius
-        p.flags = (cls.ID_STOP if id_stop else 0) | (cls.ONLY_UNKNOWN if only_unknown else 0)
-        p.sigma_normal, p.sigma_depth, p.min_temporal = sigma_normal, sigma_depth, min_temporal
-        return p
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
-
-
-class DisplayParams(C.Structure):
-    """pbrs_display_params (include/pbrs_gpu.h, "display transform"): image size, tone curve, transfer function, quantiser, flags, the
-    exposure, and what the auto exposure reads (key, exposure limits, adapt, the ranks kept); white is the Reinhard curve's."""
-    CURVES = {"none": 0, "reinhard": 1, "aces": 2}
-    ENCODES = {"sqrt": 0, "srgb": 1}
-    QUANTIZERS = {"trunc": 0, "round": 1, "dither": 2}
-    AUTO_EXPOSURE = 1
-    BINS = 512
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("curve", C.c_uint32), ("encode", C.c_uint32), ("quantize", C.c_uint32),
-                ("flags", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("white", C.c_float), ("min_exposure", C.c_float),
-                ("max_exposure", C.c_float), ("adapt", C.c_float), ("low_q16", C.c_uint32), ("high_q16", C.c_uint32), ("pad", C.c_uint32 * 2)]
-
-    @classmethod
-    def make(cls, w, h, curve="aces", encode="srgb", quantize="round", auto=False, exposure=1.0, key=0.18, white=None, min_exposure=2.0 ** -20,
-             max_exposure=2.0 ** 20, adapt=1.0, low_q16=6554, high_q16=62259):
-        """The defaults are pbrs_display_params_default's; curve, encode and quantize by name (or by their number); white None = +inf."""
-        p = cls()
-        p.w, p.h = w, h
-        p.curve = cls.CURVES[curve] if isinstance(curve, str) else curve
-        p.encode = cls.ENCODES[encode] if isinstance(encode, str) else encode
-        p.quantize = cls.QUANTIZERS[quantize] if isinstance(quantize, str) else quantize
-        p.flags = cls.AUTO_EXPOSURE if auto else 0
-        p.exposure, p.key, p.white = exposure, key, float("inf") if white is None else white
-        p.min_exposure, p.max_exposure, p.adapt = min_exposure, max_exposure, adapt
-        p.low_q16, p.high_q16 = low_q16, high_q16
-        return p
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
-
-
-class UpsampleParams(C.Structure):
-    """pbrs_upsample_params (include/pbrs_gpu.h, "guided upsampling"): the full size, the factor per axis, the tent's radius in low
-    pixels, flags, the two guide sigmas of the denoisers, the albedo floor and the guided weight below which a pixel takes the plain
-    tent."""
-    DEMODULATE, ID_STOP = 1, 2
-    FACTORS, RADII = (2, 3, 4), (1, 2)
-    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("factor", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32),
-                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float), ("min_weight", C.c_float),
-                ("pad", C.c_uint32 * 3)]
-
-    @classmethod
-    def make(cls, w, h, factor=2, radius=1, sigma_normal=0.3, sigma_depth=0.2, albedo_floor=1e-3, min_weight=1e-3, demodulate=False,
-             id_stop=False):
-        """The defaults are pbrs_upsample_params_default's."""
-        p = cls()
-        p.w, p.h, p.factor, p.radius = w, h, factor, radius
-        p.flags = (cls.DEMODULATE if demodulate else 0) | (cls.ID_STOP if id_stop else 0)
-        p.sigma_normal, p.sigma_depth, p.albedo_floor, p.min_weight = sigma_normal, sigma_depth, albedo_floor, min_weight
-        return p
-
-    @classmethod
-    def for_guides(cls, w, h, factor, albedo=False, instance=False, **params):
-        """make() with the image demodulated when there is an albedo pair and taps stopped at id edges when there is an instance pair,
-        unless `params` says otherwise."""
-        params.setdefault("demodulate", bool(albedo))
-        params.setdefault("id_stop", bool(instance))
-        return cls.make(w, h, factor, **params)
-
-    @property
-    def low_size(self):
-        return (self.w + self.factor - 1) // self.factor, (self.h + self.factor - 1) // self.factor
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
-
-
-def scaled_camera(camera, factor):
-    """`camera` for a film of 1 / factor of the resolution per axis -> a new Camera: width and height rounded up, the pixel steps a and b
-    multiplied in f32 by (float)factor, c and center kept.  A low pixel then sees exactly its factor x factor full pixels for factor 2
-    and 4; for factor 3 the products round, and that is the definition."""
-    factor = int(factor)
-    if factor < 1:
-        raise ValueError("the factor is a positive integer")
-    cam = Camera.from_buffer_copy(camera)
-    cam.width, cam.height = (camera.width + factor - 1) // factor, (camera.height + factor - 1) // factor
-    f = np.float32(factor)
-    for k in range(3):
-        cam.a[k] = np.float32(camera.a[k]) * f
-        cam.b[k] = np.float32(camera.b[k]) * f
-    return cam
-
-
-def _upscale_params(upscale, guides):
-    """render_temporal's / render_animation's `upscale` -> (factor, UpsampleParams.for_guides' keywords), or None: None is the sequence
-    at full resolution, an int the factor, a dict UpsampleParams.make's keywords plus "factor" (2 unless given).  Demodulation follows
-    the albedo guide and the id stop the instance guide unless the dict says otherwise.  An unknown keyword fails here."""
-    if upscale is None or upscale is False:
-        return None
-    if isinstance(upscale, dict):
-        up = dict(upscale)
-        factor = int(up.pop("factor", 2))
-    elif isinstance(upscale, (int, np.integer)) and not isinstance(upscale, bool):
-        up, factor = {}, int(upscale)
-    else:
-        raise ValueError("upscale is None, a factor or a dict of UpsampleParams.make's keywords plus \"factor\"")
-    if factor not in UpsampleParams.FACTORS:
-        raise ValueError(f"the upscale factor is one of {UpsampleParams.FACTORS}, not {factor}")
-    UpsampleParams.for_guides(1, 1, factor, "albedo" in guides, "instance" in guides, **up)
-    return factor, up
-
-
-class DisplayIO(C.Structure):
-    """pbrs_display_io: the previous exposure (one float), where this call's goes, where the 512 histogram counts go; each may be NULL."""
-    _fields_ = [(n, C.c_void_p) for n in ("exposure_in", "exposure_out", "histogram_out")]
-
-
-def _display_params(display):
-    """render_temporal's / render_animation's `display` -> DisplayParams.make's keywords, or None: None or False is the sequence
-    without a display transform, True the defaults with the auto exposure, a dict the keywords (auto=True unless it says otherwise).  An
-    unknown keyword fails here."""
-    if display is None or display is False:
-        return None
-    if display is not True and not isinstance(display, dict):
-        raise ValueError("display is None, True or a dict of DisplayParams.make's keywords")
-    dp = {} if display is True else dict(display)
-    dp.setdefault("auto", True)
-    DisplayParams.make(1, 1, **dp)
-    return dp
-
-
-class SpatialVarianceGuides(C.Structure):
-    """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
-    _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]
-
-
-# name -> (channels, dtype) of the planes of each struct above
-TEMPORAL_FRAME = {"rgb": (3, np.float32), "variance": (1, np.float32), "depth": (1, np.float32), "normal": (3, np.float32),
-                  "instance": (1, np.uint32)}
-TEMPORAL_GUIDES = {n: TEMPORAL_FRAME[n] for n in ("depth", "normal", "instance")}
-TEMPORAL_HISTORY = {"rgb": (3, np.float32), "moments": (2, np.float32), "length": (1, np.float32)}
-SPATIAL_VARIANCE_PLANES = {"moments": (2, np.float32), "length": (1, np.float32), "variance": (1, np.float32)}
-
-
-def _temporal_struct(cls, layout, ptrs, what):
-    """The ctypes struct `cls` from {name: pointer} (None entries: NULL)."""
-    s = cls()
-    for n, ptr in dict(ptrs).items():
-        if n not in layout:
-            raise ValueError(f"unknown {what} plane {n!r}; known: {list(layout)}")
-        setattr(s, n, ptr)
-    return s
-
-
-def _matte_select(select):
-    """The selected ids as pbrs_matte_mask wants them: u32, strictly ascending (sorted and deduplicated here)."""
-    sel = np.unique(np.asarray(select, dtype=np.int64).reshape(-1))
-    if sel.size and (sel[0] < 0 or sel[-1] > 0xFFFFFFFF):
-        raise ValueError("a selected id is not a u32")
-    return np.ascontiguousarray(sel, dtype=np.uint32)
-
-
-DENOISE_GUIDES = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "instance": (1, np.uint32)}
-
-HIT_DTYPE = np.dtype([("t", np.float32), ("inst", np.uint32), ("prim", np.uint32), ("b1", np.float32), ("b2", np.float32)])
-NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "exp": 6, "ln": 7, "hypot": 8, "div": 9,
-               "sqrt": 10, "asin": 11, "powi": 12, "fract": 13, "floor": 14, "box_quotient": 15, "trunc": 16, "f32_to_i32": 17, "ldexp": 18, "max": 19,
-               "min": 20, "signum": 21, "weak_recip": 22, "sincos64_sin_hi": 23, "sincos64_sin_lo": 24, "sincos64_cos_hi": 25,
-               "sincos64_cos_lo": 26, "rng_u32": 27, "rng_f32": 28}
-# include/pbrs_numeric_probe.h: ids from 16 on return raw 32-bit words (view the result as uint32 where it is no f32)
-NUMERIC_K_FNS = {"mul_add": 0, "clamp": 1, "slab_filter": 2, "rng_init_lo": 3, "rng_init_hi": 4, "rng_stream_u32": 5, "rng_stream_f32": 6}
-
-GPU_SYMBOLS = ["pbrs_create", "pbrs_destroy", "pbrs_last_error", "pbrs_set_stream", "pbrs_set_pass_overlap", "pbrs_upload_scene", "pbrs_render_tile",
-               "pbrs_render_tile_device", "pbrs_collect_stats", "pbrs_intersect_rays", "pbrs_last_intersect_info", "pbrs_camera_rays",
-               "pbrs_numeric_eval", "pbrs_numeric_eval_k", "pbrs_render_sample_radiance", "pbrs_render_tile_aovs", "pbrs_render_tile_aovs_device",
-               "pbrs_render_tile_filtered", "pbrs_render_tile_filtered_device", "pbrs_denoise", "pbrs_denoise_device",
-               "pbrs_render_tile_aovs_var", "pbrs_render_tile_aovs_var_device", "pbrs_denoise_var", "pbrs_denoise_var_device",
-               "pbrs_render_tile_matte", "pbrs_render_tile_matte_device", "pbrs_matte_mask", "pbrs_matte_mask_device",
-               "pbrs_render_tile_passes", "pbrs_render_tile_passes_device", "pbrs_combine_passes", "pbrs_combine_passes_device",
-               "pbrs_temporal_accumulate", "pbrs_temporal_accumulate_device", "pbrs_temporal_accumulate_motion",
-               "pbrs_temporal_accumulate_motion_device", "pbrs_motion_vectors", "pbrs_motion_vectors_device",
-               "pbrs_temporal_accumulate_clip", "pbrs_temporal_accumulate_clip_device",
-               "pbrs_spatial_variance", "pbrs_spatial_variance_device",
-               "pbrs_display_params_default", "pbrs_display", "pbrs_display_device",
-               "pbrs_upsample_params_default", "pbrs_upsample", "pbrs_upsample_device"]
-HOST_SYMBOLS = ["pbrs_host_scene_build", "pbrs_host_scene_free", "pbrs_host_scene_desc", "pbrs_host_scene_camera",
-                "pbrs_host_scene_stack_depth", "pbrs_host_last_error",
-                "pbrs_host_load_pbrt", "pbrs_loaded_scene_spec", "pbrs_loaded_scene_free", "pbrs_host_load_error", "pbrs_loaded_scene_filter",
-                "pbrs_host_write_exr", "pbrs_host_write_png", "pbrs_host_write_png_rgba8", "pbrs_host_io_error"]
-
-_host = None
-_gpu = None
-
-
-def lib_paths():
-    return os.path.join(_LIBDIR, "libpbrs_host.so"), os.path.join(_LIBDIR, "libpbrs_gpu.so")
-
-
-def host_lib():
-    global _host
-    if _host is None:
-        # PBRS_HOST_LIB: the sanitizer build of the host library (tools/cpu_asan.sh: make -C pbrs_amd/csrc host-asan)
-        path = os.environ.get("PBRS_HOST_LIB") or lib_paths()[0]
-        if not os.path.exists(path):
-            raise PbrsError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (make -C pbrs_amd/csrc)")
-        L = C.CDLL(path)
-        L.pbrs_host_scene_build.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.pbrs_host_scene_free.argtypes = [C.c_void_p]
-        L.pbrs_host_scene_desc.restype = C.POINTER(SceneDesc)
-        L.pbrs_host_scene_desc.argtypes = [C.c_void_p]
-        L.pbrs_host_scene_camera.restype = C.POINTER(Camera)
-        L.pbrs_host_scene_camera.argtypes = [C.c_void_p]
-        L.pbrs_host_scene_stack_depth.restype = C.c_uint32
-        L.pbrs_host_scene_stack_depth.argtypes = [C.c_void_p]
-        L.pbrs_host_last_error.restype = C.c_char_p
-        L.pbrs_host_load_pbrt.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        L.pbrs_loaded_scene_spec.restype = C.POINTER(SceneSpec)
-        L.pbrs_loaded_scene_spec.argtypes = [C.c_void_p]
-        L.pbrs_loaded_scene_free.argtypes = [C.c_void_p]
-        L.pbrs_loaded_scene_filter.argtypes = [C.c_void_p, C.c_void_p]
-        L.pbrs_host_load_error.restype = C.c_char_p
-        L.pbrs_host_write_exr.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
-        L.pbrs_host_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
-        L.pbrs_host_write_png_rgba8.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
-        L.pbrs_host_io_error.restype = C.c_char_p
-        _host = L
-    return _host
-
-
-def gpu_lib():
-    """Loads the HIP library. Raises (never falls back) when it is absent or cannot be loaded."""
-    global _gpu
-    if _gpu is None:
-        # PBRS_GPU_LIB: developer override to A/B two builds of the HIP library in one session (tools/ablate.sh)
-        path = os.environ.get("PBRS_GPU_LIB") or lib_paths()[1]
-        if not os.path.exists(path):
-            raise PbrsError(f"{path} is missing: the HIP extension must be built (make -C pbrs_amd/csrc); there is no CPU fallback")
-        L = C.CDLL(path)
-        L.pbrs_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.pbrs_destroy.argtypes = [C.c_void_p]
-        L.pbrs_last_error.restype = C.c_char_p
-        L.pbrs_last_error.argtypes = [C.c_void_p]
-        L.pbrs_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.pbrs_set_pass_overlap.argtypes = [C.c_void_p, C.c_int]
-        L.pbrs_upload_scene.argtypes = [C.c_void_p, C.c_void_p]
-        L.pbrs_render_tile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pbrs_render_tile_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pbrs_collect_stats.argtypes = [C.c_void_p, C.c_void_p]
-        L.pbrs_intersect_rays.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
-        L.pbrs_last_intersect_info.argtypes = [C.c_void_p, C.c_void_p]
-        L.pbrs_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.pbrs_numeric_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pbrs_numeric_eval_k.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.pbrs_render_sample_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.pbrs_render_tile_aovs.argtypes = [C.c_void_p] * 6
-        L.pbrs_render_tile_aovs_device.argtypes = [C.c_void_p] * 6
-        L.pbrs_render_tile_filtered.argtypes = [C.c_void_p] * 6
-        L.pbrs_render_tile_filtered_device.argtypes = [C.c_void_p] * 6
-        L.pbrs_denoise.argtypes = [C.c_void_p] * 5
-        L.pbrs_denoise_device.argtypes = [C.c_void_p] * 5
-        L.pbrs_render_tile_aovs_var.argtypes = [C.c_void_p] * 7
-        L.pbrs_render_tile_aovs_var_device.argtypes = [C.c_void_p] * 7
-        L.pbrs_denoise_var.argtypes = [C.c_void_p] * 6
-        L.pbrs_denoise_var_device.argtypes = [C.c_void_p] * 6
-        L.pbrs_render_tile_matte.argtypes = [C.c_void_p] * 9
-        L.pbrs_render_tile_matte_device.argtypes = [C.c_void_p] * 9
-        L.pbrs_matte_mask.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.pbrs_matte_mask_device.argtypes = L.pbrs_matte_mask.argtypes
-        L.pbrs_render_tile_passes.argtypes = [C.c_void_p] * 10
-        L.pbrs_render_tile_passes_device.argtypes = [C.c_void_p] * 10
-        L.pbrs_combine_passes.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.pbrs_combine_passes_device.argtypes = L.pbrs_combine_passes.argtypes
-        L.pbrs_temporal_accumulate.argtypes = [C.c_void_p] * 9
-        L.pbrs_temporal_accumulate_device.argtypes = [C.c_void_p] * 9
-        L.pbrs_temporal_accumulate_motion.argtypes = [C.c_void_p] * 10 + [C.c_uint32]
-        L.pbrs_temporal_accumulate_motion_device.argtypes = L.pbrs_temporal_accumulate_motion.argtypes
-        L.pbrs_temporal_accumulate_clip.argtypes = L.pbrs_temporal_accumulate_motion.argtypes + [C.c_void_p]
-        L.pbrs_temporal_accumulate_clip_device.argtypes = L.pbrs_temporal_accumulate_clip.argtypes
-        L.pbrs_motion_vectors.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_void_p]
-        L.pbrs_motion_vectors_device.argtypes = L.pbrs_motion_vectors.argtypes
-        L.pbrs_spatial_variance.argtypes = [C.c_void_p] * 7
-        L.pbrs_spatial_variance_device.argtypes = [C.c_void_p] * 7
-        L.pbrs_display_params_default.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
-        L.pbrs_display_params_default.restype = None
-        L.pbrs_display.argtypes = [C.c_void_p] * 5
-        L.pbrs_display_device.argtypes = [C.c_void_p] * 5
-        L.pbrs_upsample_params_default.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-        L.pbrs_upsample_params_default.restype = None
-        L.pbrs_upsample.argtypes = [C.c_void_p] * 7
-        L.pbrs_upsample_device.argtypes = [C.c_void_p] * 7
-        _gpu = L
-    return _gpu
-
-
-_hip = None
-
-
-def hip_runtime():
-    """The HIP runtime libpbrs_gpu.so is linked against (already loaded with it), for the device buffers of Context.render_denoised."""
-    global _hip
-    if _hip is None:
-        gpu_lib()
-        path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-        L = C.CDLL(path)
-        L.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        L.hipFree.argtypes = [C.c_void_p]
-        _hip = L
-    return _hip
+from .abi import (AOV_NAMES, AOVS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
+                  SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, Camera, DenoiseGuides, DenoiseParams,
+                  DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
+                  PixelFilter, RenderParams, SceneDesc, SpatialVarianceGuides, SpatialVarianceParams, Stats, TemporalFrame, TemporalGuides, TemporalHistory,
+                  TemporalParams, UpsampleParams, _aov_names, _DenoiseParamsMixin, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
+                  _temporal_struct, _upscale_params, scaled_camera)
+from .devmem import DeviceBuffers
+from .libs import GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .spec import SceneSpec  # noqa: F401
 
 
 def orbited(camera, about, axis, degrees):
@@ -670,16 +65,29 @@ def instance_motion(scene, scene_prev):
     return table
 
 
-def _motion_args(motion):
-    """(pointer, record count) of a motion table: a ctypes array of InstanceMotion, or None."""
-    if motion is None:
-        return None, 0
-    if not isinstance(motion, C.Array) or motion._type_ is not InstanceMotion:
-        raise ValueError("a motion table is a ctypes array of InstanceMotion (api.instance_motion)")
-    return C.addressof(motion), len(motion)
+def _guide_bytes(guides, w, h, suffix=""):
+    """{guide + suffix: bytes of its w x h plane}."""
+    return {n + suffix: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}
 
 
-INTEGRATORS = {"path": 0, "direct": 1, "materials": 2, "normals": 3}  # PBRS_INTEGRATOR_*
+def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display):
+    """{name: bytes} of the device buffers of a frame sequence (Context._temporal_frames) that runs at w x h and shows fw x fh: the
+    frame's image, the filtered one, the two variances; two ping-pong halves ("0", "1") of the guides the next frame is tested against
+    and of the history; the other guides once; and what each option that is on adds."""
+    kept = [n for n in TEMPORAL_GUIDES if n in guides]
+    sizes = {"rgb": 3 * w * h * 4, "out": 3 * w * h * 4, VARIANCE: w * h * 4, "acc_variance": w * h * 4}
+    for k in ("0", "1"):
+        sizes.update(_guide_bytes(kept, w, h, k))
+        sizes.update({f"h_{n}{k}": ch * w * h * 4 for n, (ch, _) in TEMPORAL_HISTORY.items()})
+    sizes.update(_guide_bytes([n for n in guides if n not in kept], w, h))
+    if motion_vectors:
+        sizes["motion"], sizes["prev_depth"] = 2 * w * h * 4, w * h * 4
+    if upscale:
+        sizes["up"] = 3 * fw * fh * 4
+        sizes.update(_guide_bytes(guides, fw, fh, "_hi"))
+    if display:
+        sizes["display"], sizes["exposure"] = fw * fh * 4, 4
+    return sizes
 
 
 class LoadedScene:
@@ -1106,39 +514,27 @@ class Context:
         guides, the denoise behind it on the same stream, one copy back."""
         self._denoise_guide_names(guides)
         w, h = self.scene.width, self.scene.height
-        hip = hip_runtime()
         n_rgb = 3 * w * h * 4
-        sizes = {"rgb": n_rgb, "out": n_rgb, **({VARIANCE: w * h * 4} if with_variance else {}),
-                 **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
-        dev = {}
-        try:
-            for n, nbytes in sizes.items():
-                ptr = C.c_void_p()
-                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                    raise PbrsError(f"hipMalloc of {nbytes} bytes for {name} failed")
-                dev[n] = ptr
-            gp = {n: dev[n].value for n in guides}
+        sizes = {"rgb": n_rgb, "out": n_rgb, **({VARIANCE: w * h * 4} if with_variance else {}), **_guide_bytes(guides, w, h)}
+        with DeviceBuffers(sizes, name) as dev:
+            gp = dev.ptrs(guides)
             if with_variance:
-                self.render_aovs_var_device(dev["rgb"].value, gp, dev[VARIANCE].value, strata_x, strata_y, depth, seed,
+                self.render_aovs_var_device(dev.ptr("rgb"), gp, dev.ptr(VARIANCE), strata_x, strata_y, depth, seed,
                                             samples_per_pass=samples_per_pass, integrator=integrator)
-                self.denoise_var_device(dev["rgb"].value, dev["out"].value, w, h, dev[VARIANCE].value, gp, **params)
+                self.denoise_var_device(dev.ptr("rgb"), dev.ptr("out"), w, h, dev.ptr(VARIANCE), gp, **params)
             else:
-                self.render_aovs_device(dev["rgb"].value, gp, strata_x, strata_y, depth, seed, samples_per_pass=samples_per_pass,
+                self.render_aovs_device(dev.ptr("rgb"), gp, strata_x, strata_y, depth, seed, samples_per_pass=samples_per_pass,
                                         integrator=integrator)
-                self.denoise_device(dev["rgb"].value, dev["out"].value, w, h, gp, **params)
-            stats = self.collect_stats()  # waits for the stream
-            out = np.empty((h, w, 3), dtype=np.float32)
-            if hip.hipMemcpy(out.ctypes.data, dev["out"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
-                raise PbrsError("hipMemcpy of the denoised image failed")
-            if not keep_noisy:
-                return out, stats
-            noisy = np.empty_like(out)
-            if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
-                raise PbrsError("hipMemcpy of the plain image failed")
-            return out, noisy, stats
-        finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+                self.denoise_device(dev.ptr("rgb"), dev.ptr("out"), w, h, gp, **params)
+            return self._denoised_frame(dev, "out", (h, w, 3), keep_noisy, self.collect_stats())  # (which waits for the stream)
+
+    @staticmethod
+    def _denoised_frame(dev, denoised, shape, keep_noisy, stats):
+        """The one copy back of the render_denoised family -> (denoised, stats) or (denoised, noisy, stats)."""
+        out = dev.download(denoised, shape, np.float32, "the denoised image")
+        if not keep_noisy:
+            return out, stats
+        return out, dev.download("rgb", shape, np.float32, "the plain image"), stats
 
     def render_denoised(self, strata_x, strata_y, depth, seed, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
                         integrator="path", keep_noisy=False, **params):
@@ -1191,35 +587,15 @@ class Context:
         stats).  params: DenoiseVarParams.make's keywords, for both layers."""
         self._denoise_guide_names(guides)
         w, h = self.scene.width, self.scene.height
-        hip = hip_runtime()
-        n_rgb = 3 * w * h * 4
-        sizes = {"rgb": n_rgb, **{n: PASS_CHANNELS[n] * w * h * 4 for n in PASSES}, **{n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
-        dev = {}
-        try:
-            for n, nbytes in sizes.items():
-                ptr = C.c_void_p()
-                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_denoised_passes failed")
-                dev[n] = ptr
-            gp = {n: dev[n].value for n in guides}
-            self.render_passes_device(dev["rgb"].value, {n: dev[n].value for n in PASSES}, strata_x, strata_y, depth, seed, aov_device_ptrs=gp,
+        sizes = {"rgb": 3 * w * h * 4, **{n: PASS_CHANNELS[n] * w * h * 4 for n in PASSES}, **_guide_bytes(guides, w, h)}
+        with DeviceBuffers(sizes, "render_denoised_passes") as dev:
+            gp = dev.ptrs(guides)
+            self.render_passes_device(dev.ptr("rgb"), dev.ptrs(PASSES), strata_x, strata_y, depth, seed, aov_device_ptrs=gp,
                                       samples_per_pass=samples_per_pass)
             for layer in ("direct", "indirect"):  # each in place
-                self.denoise_var_device(dev[layer].value, dev[layer].value, w, h, dev[layer + "_variance"].value, gp, **params)
-            self.combine_passes_device(dev["direct"].value, dev["indirect"].value, dev["direct"].value, w, h)
-            stats = self.collect_stats()  # waits for the stream
-            out = np.empty((h, w, 3), dtype=np.float32)
-            if hip.hipMemcpy(out.ctypes.data, dev["direct"], n_rgb, 2) != 0:  # hipMemcpyDeviceToHost
-                raise PbrsError("hipMemcpy of the denoised image failed")
-            if not keep_noisy:
-                return out, stats
-            noisy = np.empty_like(out)
-            if hip.hipMemcpy(noisy.ctypes.data, dev["rgb"], n_rgb, 2) != 0:
-                raise PbrsError("hipMemcpy of the plain image failed")
-            return out, noisy, stats
-        finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+                self.denoise_var_device(dev.ptr(layer), dev.ptr(layer), w, h, dev.ptr(layer + "_variance"), gp, **params)
+            self.combine_passes_device(dev.ptr("direct"), dev.ptr("indirect"), dev.ptr("direct"), w, h)
+            return self._denoised_frame(dev, "direct", (h, w, 3), keep_noisy, self.collect_stats())  # (which waits for the stream)
 
     @staticmethod
     def _temporal_host(layout, arrays, shape, what):
@@ -1464,32 +840,30 @@ class Context:
         w, h = self.scene.width, self.scene.height
         cam_lo = scaled_camera(self.scene.camera, factor)
         wl, hl = cam_lo.width, cam_lo.height
-        hip = hip_runtime()
-        sizes = {"rgb": 3 * wl * hl * 4, "out": 3 * wl * hl * 4, VARIANCE: wl * hl * 4, "up": 3 * w * h * 4,
-                 **{f"{n}_lo": DENOISE_GUIDES[n][0] * wl * hl * 4 for n in guides}, **{f"{n}_hi": DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}}
-        dev = {}
-        try:
-            for n, nbytes in sizes.items():
-                ptr = C.c_void_p()
-                if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                    raise PbrsError(f"hipMalloc of {nbytes} bytes for render_upscaled failed")
-                dev[n] = ptr
-            gl, gh = {n: dev[f"{n}_lo"].value for n in guides}, {n: dev[f"{n}_hi"].value for n in guides}
-            bufs, _ = self._aov_device(gl)
-            self._render_device(self._params(strata_x, strata_y, depth, seed, (0, 0, wl, hl), samples_per_pass), dev["rgb"].value, bufs,
-                                dev[VARIANCE].value, camera=cam_lo)
-            self.denoise_var_device(dev["rgb"].value, dev["out"].value, wl, hl, dev[VARIANCE].value, gl, **params)
-            self._render_guides_device(dev["up"].value, gh, seed)
-            self.upsample_device(dev["out"].value, dev["up"].value, w, h, factor, gl, gh, **up)
+        sizes = {"rgb": 3 * wl * hl * 4, "out": 3 * wl * hl * 4, VARIANCE: wl * hl * 4, "up": 3 * w * h * 4, **_guide_bytes(guides, wl, hl, "_lo"),
+                 **_guide_bytes(guides, w, h, "_hi")}
+        with DeviceBuffers(sizes, "render_upscaled") as dev:
+            gl = {n: dev.ptr(f"{n}_lo") for n in guides}
+            self._render_var_device(dev, gl, self._params(strata_x, strata_y, depth, seed, (0, 0, wl, hl), samples_per_pass), cam_lo)
+            self.denoise_var_device(dev.ptr("rgb"), dev.ptr("out"), wl, hl, dev.ptr(VARIANCE), gl, **params)
+            self._upsample_out_device(dev, gl, guides, seed, w, h, factor, up)
             stats = self.collect_stats()  # waits for the stream
             stats["low_res"] = (wl, hl)
-            full, low = np.empty((h, w, 3), dtype=np.float32), np.empty((hl, wl, 3), dtype=np.float32)
-            if hip.hipMemcpy(full.ctypes.data, dev["up"], full.nbytes, 2) != 0 or hip.hipMemcpy(low.ctypes.data, dev["out"], low.nbytes, 2) != 0:
-                raise PbrsError("hipMemcpy of the upscaled image failed")
-            return full, low, stats
-        finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+            full = dev.download("up", (h, w, 3), np.float32, "the upscaled image")
+            return full, dev.download("out", (hl, wl, 3), np.float32, "the upscaled image"), stats
+
+    def _render_var_device(self, dev, guide_device_ptrs, p, camera):
+        """What render_upscaled and a frame sequence both begin with: the render of `p` through `camera` into dev's "rgb", its variance
+        into dev's "variance", its guides where `guide_device_ptrs` says."""
+        bufs, _ = self._aov_device(guide_device_ptrs)
+        self._render_device(p, dev.ptr("rgb"), bufs, dev.ptr(VARIANCE), camera=camera)
+
+    def _upsample_out_device(self, dev, lo_device_ptrs, guides, seed, w, h, factor, up, camera=None):
+        """What both end with: the full-size guides rendered into dev's "*_hi" (the image of that render into "up"), then dev's filtered
+        low image "out" upsampled over it into "up"."""
+        gh = {n: dev.ptr(f"{n}_hi") for n in guides}
+        self._render_guides_device(dev.ptr("up"), gh, seed, camera=camera)
+        self.upsample_device(dev.ptr("out"), dev.ptr("up"), w, h, factor, lo_device_ptrs, gh, **up)
 
     @staticmethod
     def _spatial_params(spatial, tparams, guides):
@@ -1557,23 +931,20 @@ class Context:
                          clip=None, display=None, upscale=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
-        brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  `spatial`: None, or what queues the
-        spatial variance estimate between the accumulation and the filter (_spatial_params).  `clip`: temporal_accumulate_device's.  `display`: None, or what queues the
-        display transform behind the filter (_display_params); only then are its two buffers allocated.  `upscale`: None, or what runs the
-        chain at low resolution and queues the guide render and the upsample behind the filter (_upscale_params); only then are the
-        full-size guides and the full-size image allocated, and w, h below are the low size (fw, fh the full one)."""
-        tparams = dict(temporal or {})
-        TemporalParams.make(1, 1, **tparams)  # an unknown keyword fails here, before anything is allocated
-        clip = _history_clip(clip)
-        sparams = self._spatial_params(spatial, tparams, guides)
-        dparams = _display_params(display)
-        uparams = _upscale_params(upscale, guides)
-        hip = hip_runtime()
-        kept = [n for n in ("depth", "normal", "instance") if n in guides]  # what the next frame is tested against
-        dev = {}
+        brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  The options are checked here, before
+        anything is allocated; the first frame fixes the sizes (_sequence_buffers: with `upscale` the chain runs at the low size w x h,
+        fw x fh is the full one); every frame is queued (_queue_frame), waited for once and read back (_read_frame)."""
+        s = SimpleNamespace(guides=guides, kept=[n for n in TEMPORAL_GUIDES if n in guides], motion_vectors=motion_vectors, params=params,
+                            tparams=dict(temporal or {}))
+        TemporalParams.make(1, 1, **s.tparams)  # an unknown keyword fails here
+        s.clip = _history_clip(clip)
+        s.sparams = self._spatial_params(spatial, s.tparams, guides)
+        s.dparams = _display_params(display)
+        s.uparams = _upscale_params(upscale, guides)
+        s.shown = "out" if s.uparams is None else "up"  # the buffer of a frame's first image
+        dev = None
         try:
             cam_prev = scene_prev = None
-            w = h = fw = fh = n_rgb = 0
             for i, (scene, cam, seed) in enumerate(frames):
                 table = None
                 if scene is not None:
@@ -1583,85 +954,71 @@ class Context:
                     scene_prev = scene
                 cam = Camera.from_buffer_copy(cam if cam is not None else self.scene.camera)  # (a scene's own camera lives in the scene)
                 cam_full, tile = cam, None
-                if uparams is not None:
-                    cam = scaled_camera(cam_full, uparams[0])
+                if s.uparams is not None:
+                    cam = scaled_camera(cam_full, s.uparams[0])
                     tile = (0, 0, cam.width, cam.height)
-                if i == 0:
-                    fw, fh = self.scene.width, self.scene.height
-                    w, h = (fw, fh) if uparams is None else (cam.width, cam.height)
-                    n_rgb = 3 * w * h * 4
-                    sizes = {"rgb": n_rgb, "out": n_rgb, VARIANCE: w * h * 4, "acc_variance": w * h * 4}
-                    for k in (0, 1):
-                        sizes.update({f"{n}{k}": DENOISE_GUIDES[n][0] * w * h * 4 for n in kept})
-                        sizes.update({f"h_{n}{k}": ch * w * h * 4 for n, (ch, _) in TEMPORAL_HISTORY.items()})
-                    sizes.update({n: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides if n not in kept})
-                    if motion_vectors:
-                        sizes["motion"], sizes["prev_depth"] = 2 * w * h * 4, w * h * 4
-                    if uparams is not None:
-                        sizes["up"] = 3 * fw * fh * 4
-                        sizes.update({f"{n}_hi": DENOISE_GUIDES[n][0] * fw * fh * 4 for n in guides})
-                    if dparams is not None:
-                        sizes["display"], sizes["exposure"] = fw * fh * 4, 4
-                    for n, nbytes in sizes.items():
-                        ptr = C.c_void_p()
-                        if hip.hipMalloc(C.byref(ptr), nbytes) != 0:
-                            raise PbrsError(f"hipMalloc of {nbytes} bytes for a temporal sequence failed")
-                        dev[n] = ptr
-                elif (self.scene.width, self.scene.height) != (fw, fh):
-                    raise ValueError(f"frame {i} has a film of {self.scene.width} x {self.scene.height}, the sequence {fw} x {fh}")
-                cur, old = i & 1, (i & 1) ^ 1
-                gp = {n: dev[f"{n}{cur}" if n in kept else n].value for n in guides}
-                bufs, _ = self._aov_device(gp)
-                self._render_device(self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), dev["rgb"].value, bufs,
-                                    dev[VARIANCE].value, camera=cam)
-                frame = {"rgb": dev["rgb"].value, "variance": dev[VARIANCE].value, **{n: gp[n] for n in kept}}
-                hist = [{n: dev[f"h_{n}{k}"].value for n in TEMPORAL_HISTORY} for k in (0, 1)]
-                self.temporal_accumulate_device(frame, hist[cur], w, h, cam, hist[old] if i else None,
-                                                {n: dev[f"{n}{old}"].value for n in kept} if i else None, cam_prev,
-                                                dev["acc_variance"].value, motion=table if i else None, clip=clip, **tparams)
-                if motion_vectors and i:
-                    self.motion_vectors_device(gp["depth"], dev["motion"].value, w, h, cam, cam_prev, gp.get("instance") if table else None, table,
-                                               dev["prev_depth"].value)
-                if sparams is not None:
-                    self.spatial_variance_device(hist[cur]["moments"], hist[cur]["length"], dev["acc_variance"].value, dev["acc_variance"].value,
-                                                 w, h, {n: gp[n] for n in kept}, **sparams)
-                self.denoise_var_device(hist[cur]["rgb"], dev["out"].value, w, h, dev["acc_variance"].value, gp, **params)
-                shown_src = dev["out"]
-                if uparams is not None:
-                    gh = {n: dev[f"{n}_hi"].value for n in guides}
-                    self._render_guides_device(dev["up"].value, gh, seed, camera=cam_full)
-                    self.upsample_device(dev["out"].value, dev["up"].value, fw, fh, uparams[0], gp, gh, **uparams[1])
-                    shown_src = dev["up"]
-                if dparams is not None:  # the first frame has no previous exposure; later ones read the word the last one wrote
-                    self.display_device(shown_src.value, dev["display"].value, fw, fh,
-                                        {"exposure_in": dev["exposure"].value if i else None, "exposure_out": dev["exposure"].value}, **dparams)
+                if dev is None:
+                    s.fw, s.fh = self.scene.width, self.scene.height
+                    s.w, s.h = (s.fw, s.fh) if s.uparams is None else (cam.width, cam.height)
+                    dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None),
+                                        "a temporal sequence")
+                elif (self.scene.width, self.scene.height) != (s.fw, s.fh):
+                    raise ValueError(f"frame {i} has a film of {self.scene.width} x {self.scene.height}, the sequence {s.fw} x {s.fh}")
+                self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table)
                 stats = self.collect_stats()  # waits for the stream
-                if dparams is not None:
-                    shown, e = np.empty((fh, fw, 4), dtype=np.uint8), np.zeros(1, dtype=np.float32)
-                    if hip.hipMemcpy(shown.ctypes.data, dev["display"], shown.nbytes, 2) != 0 or hip.hipMemcpy(e.ctypes.data, dev["exposure"], 4, 2) != 0:
-                        raise PbrsError("hipMemcpy of a temporal sequence's display image failed")
-                    stats["display"], stats["exposure"] = shown, e[0]
-                if uparams is not None:
-                    stats["low_res"] = (w, h)
-                images = []
-                for src in (shown_src, dev[f"h_rgb{cur}"], dev["rgb"]):
-                    img = np.empty((fh, fw, 3) if src is dev.get("up") else (h, w, 3), dtype=np.float32)
-                    if hip.hipMemcpy(img.ctypes.data, src, img.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
-                        raise PbrsError("hipMemcpy of a temporal sequence's image failed")
-                    images.append(img)
-                mv = None
-                if motion_vectors:
-                    mv, wq = np.zeros((h, w, 2), dtype=np.float32), np.full((h, w), np.inf, dtype=np.float32)
-                    if i and (hip.hipMemcpy(mv.ctypes.data, dev["motion"], mv.nbytes, 2) != 0 or
-                              hip.hipMemcpy(wq.ctypes.data, dev["prev_depth"], wq.nbytes, 2) != 0):
-                        raise PbrsError("hipMemcpy of the motion vectors failed")
-                    if motion_vectors == "prev_depth":
-                        mv = np.concatenate([mv, wq[:, :, None]], axis=2)
                 cam_prev = cam
-                yield images[0], images[1], images[2], stats, mv
+                yield self._read_frame(s, dev, i, stats)
         finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+            if dev is not None:
+                dev.free()
+
+    def _queue_frame(self, s, dev, i, p, cam, cam_full, cam_prev, table):
+        """Frame i of the sequence `s` on the context's stream, nothing waits: the render of `p` with its guides and its variance; the
+        accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
+        on the accumulated variance; the filter; the full-size guides and the upsample; the display transform, whose exposure word is
+        read from the second frame on and written by every one."""
+        w, h, cur, old = s.w, s.h, i & 1, (i & 1) ^ 1
+        gp = {n: dev.ptr(f"{n}{cur}" if n in s.kept else n) for n in s.guides}
+        kept = {n: gp[n] for n in s.kept}  # what the next frame is tested against
+        hist = [{n: dev.ptr(f"h_{n}{k}") for n in TEMPORAL_HISTORY} for k in (0, 1)]
+        acc_variance = dev.ptr("acc_variance")
+        self._render_var_device(dev, gp, p, cam)
+        self.temporal_accumulate_device({"rgb": dev.ptr("rgb"), "variance": dev.ptr(VARIANCE), **kept}, hist[cur], w, h, cam, hist[old] if i else None,
+                                        {n: dev.ptr(f"{n}{old}") for n in s.kept} if i else None, cam_prev, acc_variance,
+                                        motion=table if i else None, clip=s.clip, **s.tparams)
+        if s.motion_vectors and i:
+            self.motion_vectors_device(gp["depth"], dev.ptr("motion"), w, h, cam, cam_prev, gp.get("instance") if table else None, table,
+                                       dev.ptr("prev_depth"))
+        if s.sparams is not None:
+            self.spatial_variance_device(hist[cur]["moments"], hist[cur]["length"], acc_variance, acc_variance, w, h, kept, **s.sparams)
+        self.denoise_var_device(hist[cur]["rgb"], dev.ptr("out"), w, h, acc_variance, gp, **s.params)
+        if s.uparams is not None:
+            self._upsample_out_device(dev, gp, s.guides, p.seed, s.fw, s.fh, *s.uparams, camera=cam_full)
+        if s.dparams is not None:
+            self.display_device(dev.ptr(s.shown), dev.ptr("display"), s.fw, s.fh,
+                                {"exposure_in": dev.ptr("exposure") if i else None, "exposure_out": dev.ptr("exposure")}, **s.dparams)
+
+    @staticmethod
+    def _read_frame(s, dev, i, stats):
+        """Frame i copied back, behind the wait -> (first image, accumulated, noisy, stats, motion vectors or None); the display image,
+        its exposure and the low size go into `stats`."""
+        w, h = s.w, s.h
+        if s.dparams is not None:
+            stats["display"] = dev.download("display", (s.fh, s.fw, 4), np.uint8, "a temporal sequence's display image")
+            stats["exposure"] = dev.download("exposure", 1, np.float32, "a temporal sequence's display image")[0]
+        if s.uparams is not None:
+            stats["low_res"] = (w, h)
+        shapes = {s.shown: (h, w, 3) if s.uparams is None else (s.fh, s.fw, 3), f"h_rgb{i & 1}": (h, w, 3), "rgb": (h, w, 3)}
+        shown, accumulated, noisy = (dev.download(n, shape, np.float32, "a temporal sequence's image") for n, shape in shapes.items())
+        mv = None
+        if s.motion_vectors:
+            mv, wq = np.zeros((h, w, 2), dtype=np.float32), np.full((h, w), np.inf, dtype=np.float32)  # the first frame has no previous one
+            if i:
+                mv = dev.download("motion", mv.shape, np.float32, "the motion vectors")
+                wq = dev.download("prev_depth", wq.shape, np.float32, "the motion vectors")
+            if s.motion_vectors == "prev_depth":
+                mv = np.concatenate([mv, wq[:, :, None]], axis=2)
+        return shown, accumulated, noisy, stats, mv
 
     def collect_stats(self):
         st = Stats()

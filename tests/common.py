@@ -21,3 +21,8 @@ def golden_case(name):
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def all_ones(arrays):
+    """{name: bytes of the array's size with every bit set}: what a device call is given to write its planes over."""
+    return {n: np.full(a.nbytes, 0xFF, dtype=np.uint8) for n, a in arrays.items()}

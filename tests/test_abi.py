@@ -61,9 +61,9 @@ int main(void) {
 
 def test_product_path_fails_loudly_without_the_hip_library(monkeypatch, tmp_path):
     """No CPU fallback: a missing libpbrs_gpu.so is an error, not a silent detour."""
-    from pbrs_amd import api
-    monkeypatch.setattr(api, "_gpu", None)
-    monkeypatch.setattr(api, "_LIBDIR", str(tmp_path))
+    from pbrs_amd import api, libs  # (the loaders' state lives in libs.py)
+    monkeypatch.setattr(libs, "_gpu", None)
+    monkeypatch.setattr(libs, "_LIBDIR", str(tmp_path))
     with pytest.raises(api.PbrsError, match="no CPU fallback"):
         api.gpu_lib()
 

@@ -7,8 +7,8 @@ import pytest
 
 import pbrs_amd
 from oracle.binding import OracleScene
-from pbrs_amd import scenes
-from common import GOLDEN_NAMES, SEED, bits, golden_case
+from pbrs_amd import DeviceBuffers, scenes
+from common import GOLDEN_NAMES, SEED, all_ones, bits, golden_case
 
 pytestmark = pytest.mark.gpu
 
@@ -213,18 +213,6 @@ def test_aovs_do_not_depend_on_how_the_render_is_cut(gpu_ctx, name):
         gpu_ctx.set_pass_overlap(True)
 
 
-def _hip_runtime():
-    """The HIP runtime libpbrs_gpu.so is linked against (already loaded with it): device buffers for the _device variant."""
-    pbrs_amd.gpu_lib()
-    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-    L = C.CDLL(path)
-    L.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    L.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    L.hipFree.argtypes = [C.c_void_p]
-    return L
-
-
 def test_api_errors_and_the_device_variant(gpu_ctx):
     _upload(gpu_ctx, "c2")
     for integrator in ("path", "direct"):
@@ -236,21 +224,9 @@ def test_api_errors_and_the_device_variant(gpu_ctx):
     assert (bits(img) == bits(gpu_ctx.render(2, 2, 4, 9)[0])).all()
     # the device variant: valid after collect_stats()
     img, aov, _ = gpu_ctx.render_aovs(2, 2, 4, 9)
-    hip = _hip_runtime()
     host = {"rgb": img, **aov}
-    dev = {}
-    try:
-        for n, a in host.items():
-            ptr = C.c_void_p()
-            assert hip.hipMalloc(C.byref(ptr), a.nbytes) == 0
-            dev[n] = ptr
-            assert hip.hipMemset(ptr, 0xFF, a.nbytes) == 0
-        gpu_ctx.render_aovs_device(dev["rgb"].value, {n: dev[n].value for n in aov}, 2, 2, 4, 9)
+    with DeviceBuffers(all_ones(host)) as dev:
+        gpu_ctx.render_aovs_device(dev.ptr("rgb"), dev.ptrs(aov), 2, 2, 4, 9)
         gpu_ctx.collect_stats()
         for n, a in host.items():
-            got = np.empty_like(a)
-            assert hip.hipMemcpy(got.ctypes.data, dev[n], a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            assert (got.view(np.uint32) == a.view(np.uint32)).all(), n
-    finally:
-        for ptr in dev.values():
-            hip.hipFree(ptr)
+            assert (dev.download_like(n, a).view(np.uint32) == a.view(np.uint32)).all(), n

@@ -12,6 +12,7 @@ import pbrs_amd
 from common import bits
 from oracle.binding import OracleScene
 from pbrs_amd import scenes, tiling
+from pbrs_amd.devmem import DEVICE_TO_HOST
 
 pytestmark = pytest.mark.gpu
 
@@ -46,8 +47,8 @@ def test_two_contexts_with_different_stack_depths_interleaved():
             a.collect_stats()  # waits for the context's own stream: the output is valid from here on
             b.collect_stats()
             h4, h2 = np.empty((8, 64, 3), dtype=np.float32), np.empty((8, 64, 3), dtype=np.float32)
-            assert hip.hipMemcpy(ctypes.c_void_p(h4.ctypes.data), o4, ctypes.c_size_t(nbytes), 2) == 0  # hipMemcpyDeviceToHost
-            assert hip.hipMemcpy(ctypes.c_void_p(h2.ctypes.data), o2, ctypes.c_size_t(nbytes), 2) == 0
+            assert hip.hipMemcpy(ctypes.c_void_p(h4.ctypes.data), o4, ctypes.c_size_t(nbytes), DEVICE_TO_HOST) == 0
+            assert hip.hipMemcpy(ctypes.c_void_p(h2.ctypes.data), o2, ctypes.c_size_t(nbytes), DEVICE_TO_HOST) == 0
             assert (bits(h4) == bits(ref4)).all() and (bits(h2) == bits(ref2)).all()
         finally:
             hip.hipFree(o4)

@@ -10,7 +10,7 @@ import pytest
 import denoise_model as dm
 import pbrs_amd
 from common import bits
-from pbrs_amd import api, scenes
+from pbrs_amd import DeviceBuffers, api, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -135,22 +135,6 @@ def test_matches_the_cpu_model_bit_for_bit_on_rendered_inputs(gpu_ctx, name, dep
         assert (np.isfinite(got).all(axis=2) == np.isfinite(img).all(axis=2)).all()
 
 
-def _device_buffers(hip, arrays):
-    dev = {}
-    for n, a in arrays.items():
-        ptr = C.c_void_p()
-        assert hip.hipMalloc(C.byref(ptr), a.nbytes) == 0
-        dev[n] = ptr
-        assert hip.hipMemcpy(ptr, a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
-    return dev
-
-
-def _download(hip, ptr, like):
-    got = np.empty_like(like)
-    assert hip.hipMemcpy(got.ctypes.data, ptr, like.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-    return got
-
-
 def test_render_denoised_is_render_aovs_then_denoise(gpu_ctx):
     img, aov, _ = rendered(gpu_ctx, "cornell", (2, 2), 5, 9)
     want = gpu_ctx.denoise(img, **aov)
@@ -162,19 +146,14 @@ def test_render_denoised_is_render_aovs_then_denoise(gpu_ctx):
     got, _ = gpu_ctx.render_denoised(2, 2, 5, 9, guides=("normal", "depth"), iterations=3)
     assert same(got, gpu_ctx.denoise(img, normal=aov["normal"], depth=aov["depth"], iterations=3)).all()
     # in place on the device, and on a caller's buffers
-    hip = api.hip_runtime()
     h, w, _ = img.shape
-    dev = _device_buffers(hip, {"rgb": img, "out": np.zeros_like(img), **aov})
-    try:
-        gp = {n: dev[n].value for n in aov}
-        gpu_ctx.denoise_device(dev["rgb"].value, dev["out"].value, w, h, gp)
-        gpu_ctx.denoise_device(dev["rgb"].value, dev["rgb"].value, w, h, gp)
+    with DeviceBuffers({"rgb": img, "out": np.zeros_like(img), **aov}) as dev:
+        gp = dev.ptrs(aov)
+        gpu_ctx.denoise_device(dev.ptr("rgb"), dev.ptr("out"), w, h, gp)
+        gpu_ctx.denoise_device(dev.ptr("rgb"), dev.ptr("rgb"), w, h, gp)
         gpu_ctx.collect_stats()
-        assert same(_download(hip, dev["out"], img), want).all()
-        assert same(_download(hip, dev["rgb"], img), want).all()
-    finally:
-        for ptr in dev.values():
-            hip.hipFree(ptr)
+        assert same(dev.download_like("out", img), want).all()
+        assert same(dev.download_like("rgb", img), want).all()
 
 
 def test_the_default_parameters_remove_error_on_the_cornell_box(gpu_ctx):

@@ -10,8 +10,8 @@ import denoise_model as dm
 import denoise_var_model as vm
 import pbrs_amd
 from common import bits
-from pbrs_amd import api, scenes
-from test_gpu_denoise import FLOOR, GUIDES, SIZES, _configs, _device_buffers, _download, same, synthetic
+from pbrs_amd import DeviceBuffers, api, scenes
+from test_gpu_denoise import FLOOR, GUIDES, SIZES, _configs, same, synthetic
 
 pytestmark = pytest.mark.gpu
 
@@ -124,22 +124,17 @@ def test_render_denoised_var_is_render_aovs_then_denoise_var(gpu_ctx):
     got, _ = gpu_ctx.render_denoised_var(2, 2, 5, 9, guides=("normal", "depth"), iterations=3)
     assert same(got, gpu_ctx.denoise_var(img, var, normal=aov["normal"], depth=aov["depth"], iterations=3)).all()
     # in place on the device (image and variance), and on a caller's buffers
-    hip = api.hip_runtime()
     h, w, _ = img.shape
-    dev = _device_buffers(hip, {"rgb": img, "out": np.zeros_like(img), "variance": var, "vout": np.zeros_like(var), **aov})
-    try:
-        gp = {n: dev[n].value for n in aov}
-        gpu_ctx.denoise_var_device(dev["rgb"].value, dev["out"].value, w, h, dev["variance"].value, gp, dev["vout"].value)
+    with DeviceBuffers({"rgb": img, "out": np.zeros_like(img), "variance": var, "vout": np.zeros_like(var), **aov}) as dev:
+        gp = dev.ptrs(aov)
+        gpu_ctx.denoise_var_device(dev.ptr("rgb"), dev.ptr("out"), w, h, dev.ptr("variance"), gp, dev.ptr("vout"))
         gpu_ctx.collect_stats()
-        assert same(_download(hip, dev["out"], img), want).all()
-        assert same(_download(hip, dev["vout"], var), vwant).all()
-        gpu_ctx.denoise_var_device(dev["rgb"].value, dev["rgb"].value, w, h, dev["variance"].value, gp, dev["variance"].value)
+        assert same(dev.download_like("out", img), want).all()
+        assert same(dev.download_like("vout", var), vwant).all()
+        gpu_ctx.denoise_var_device(dev.ptr("rgb"), dev.ptr("rgb"), w, h, dev.ptr("variance"), gp, dev.ptr("variance"))
         gpu_ctx.collect_stats()
-        assert same(_download(hip, dev["rgb"], img), want).all()
-        assert same(_download(hip, dev["variance"], var), vwant).all()
-    finally:
-        for ptr in dev.values():
-            hip.hipFree(ptr)
+        assert same(dev.download_like("rgb", img), want).all()
+        assert same(dev.download_like("variance", var), vwant).all()
 
 
 def _mse(img, ref, ok):

@@ -11,9 +11,8 @@ import pytest
 import display_model as dm
 import pbrs_amd
 from common import bits
-from pbrs_amd import api, scenes
+from pbrs_amd import DeviceBuffers, api, scenes
 from test_display_model import lognormal, specials
-from test_gpu_denoise import _device_buffers, _download
 
 pytestmark = pytest.mark.gpu
 
@@ -101,19 +100,15 @@ def test_the_reference_settings_are_the_host_png(gpu_ctx, tmp_path):
     assert (read_png(tmp_path / "b.png") == out[:, :, :3]).all()
 
 
-def _device_display(ctx, hip, img, offset_words=0, io=None, **kw):
+def _device_display(ctx, img, offset_words=0, io=None, **kw):
     """display_device on fresh caller buffers; the rgb plane starts `offset_words` floats into its allocation."""
     h, w, _ = img.shape
     pad = np.zeros(offset_words + img.size, dtype=f32)
     pad[offset_words:] = img.reshape(-1)
-    dev = _device_buffers(hip, {"rgb": pad, "out": np.zeros((h, w), np.uint32)})
-    try:
-        ctx.display_device(dev["rgb"].value + 4 * offset_words, dev["out"].value, w, h, io, **kw)
+    with DeviceBuffers({"rgb": pad, "out": np.zeros((h, w), np.uint32)}) as dev:
+        ctx.display_device(dev.ptr("rgb") + 4 * offset_words, dev.ptr("out"), w, h, io, **kw)
         ctx.collect_stats()
-        return _download(hip, dev["out"], np.zeros((h, w), np.uint32)).view(np.uint8).reshape(h, w, 4)
-    finally:
-        for p in dev.values():
-            hip.hipFree(p)
+        return dev.download("out", (h, w), np.uint32).view(np.uint8).reshape(h, w, 4)
 
 
 @pytest.mark.parametrize("size", ((37, 29), (129, 67), (130, 70), (7, 5), (64, 1)), ids=lambda s: f"{s[0]}x{s[1]}")
@@ -121,42 +116,36 @@ def test_the_device_variant_on_caller_buffers_gives_the_host_variants_bytes(gpu_
     """Aligned planes (the 16-byte path with its tail of w * h mod 4 pixels) and an rgb plane 4 bytes off (the scalar path), no io."""
     w, h = size
     img = image(w, h, seed=8)
-    hip = api.hip_runtime()
     for kw in (dict(curve="aces", encode="srgb", quantize="dither", exposure=0.5), dict(curve="reinhard", encode="sqrt", quantize="round", auto=True, white=2.0)):
         want = gpu_ctx.display(img, **kw)
         assert (want == dm.display(img, **kw)[0]).all()
         for offset in (0, 1):
-            assert (_device_display(gpu_ctx, hip, img, offset, **kw) == want).all(), (size, offset, kw)
+            assert (_device_display(gpu_ctx, img, offset, **kw) == want).all(), (size, offset, kw)
 
 
 def test_the_exposure_word_carries_a_sequence_on_the_device(gpu_ctx):
     """Three calls, exposure_out fed back as exposure_in through one device word (the host only looks at it), against the model's three;
     the histogram comes back too."""
     w, h = 37, 29
-    hip = api.hip_runtime()
     imgs = [(lognormal(h, w, 20 + k, sigma=1.0) * f32(4.0 ** k)).astype(f32) for k in range(3)]
     kw = dict(auto=True, adapt=0.25, curve="aces", encode="srgb", quantize="round")
-    word = _device_buffers(hip, {"e": np.zeros(1, f32), "hist": np.zeros(dm.BINS, np.uint32)})
-    try:
+    with DeviceBuffers({"e": np.zeros(1, f32), "hist": np.zeros(dm.BINS, np.uint32)}) as word:
         # without the auto exposure the word receives 1 (from the apply kernel: nothing else is launched) and exposure_in is not read
-        out = _device_display(gpu_ctx, hip, imgs[0], io={"exposure_in": word["e"].value, "exposure_out": word["e"].value}, curve="none", exposure=2.0)
+        out = _device_display(gpu_ctx, imgs[0], io={"exposure_in": word.ptr("e"), "exposure_out": word.ptr("e")}, curve="none", exposure=2.0)
         assert (out == dm.display(imgs[0], curve="none", exposure=2.0)[0]).all()
-        assert _download(hip, word["e"], np.zeros(1, f32))[0].tobytes() == f32(1.0).tobytes()
+        assert word.download("e", 1, f32)[0].tobytes() == f32(1.0).tobytes()
         e = None
         for k, img in enumerate(imgs):
             prev = e
-            io = {"exposure_in": word["e"].value if k else None, "exposure_out": word["e"].value, "histogram_out": word["hist"].value}
-            out = _device_display(gpu_ctx, hip, img, io=io, **kw)
+            io = {"exposure_in": word.ptr("e") if k else None, "exposure_out": word.ptr("e"), "histogram_out": word.ptr("hist")}
+            out = _device_display(gpu_ctx, img, io=io, **kw)
             want, e, hist = dm.display(img, exposure_in=prev, **kw)
             assert (out == want).all(), k
-            assert _download(hip, word["e"], np.zeros(1, f32))[0].tobytes() == e.tobytes(), k
-            assert (_download(hip, word["hist"], np.zeros(dm.BINS, np.uint32)) == hist).all(), k
+            assert word.download("e", 1, f32)[0].tobytes() == e.tobytes(), k
+            assert (word.download("hist", dm.BINS, np.uint32) == hist).all(), k
             agree(gpu(gpu_ctx, img, exposure_in=prev, **kw), (want, e, hist), k)  # the host variant, the same chain
         assert len({float(dm.display(img, **kw)[1]) for img in imgs}) == 3  # the three targets differ: the easing is visible
         assert float(e) != float(dm.display(imgs[2], **kw)[1])
-    finally:
-        for p in word.values():
-            hip.hipFree(p)
 
 
 def test_an_image_that_sends_the_grid_stride_loops_round_again(gpu_ctx):

@@ -8,8 +8,8 @@ import pytest
 
 import matte_model
 import pbrs_amd
-from pbrs_amd import api, scenes
-from common import SEED, bits
+from pbrs_amd import DeviceBuffers, api, scenes
+from common import SEED, all_ones, bits
 from matte_common import MISS, SCENES, first_hits, scene
 
 pytestmark = pytest.mark.gpu
@@ -141,12 +141,6 @@ def test_mask_with_the_largest_selection(gpu_ctx):
     assert (_u32(gpu_ctx.matte_mask(ids, coverage, select)) == _u32(got)).all()
 
 
-def _hip_runtime():
-    L = api.hip_runtime()
-    L.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    return L
-
-
 def test_the_device_variants_give_the_host_variants_bits(gpu_ctx):
     """render_matte_device, then matte_mask_device on the context's stream with nothing in between, read after collect_stats()."""
     gpu_ctx.upload(pbrs_amd.HostScene(scenes.build_config("c5", width=48, height=32)[0]))
@@ -155,26 +149,13 @@ def test_the_device_variants_give_the_host_variants_bits(gpu_ctx):
     select = np.unique(matte["ids"])[::2]
     host = {"rgb": img, **matte, **aov, "mask": gpu_ctx.matte_mask(matte["ids"], matte["coverage"], select)}
     assert host["mask"].any() and matte["residual"].any()
-    hip = _hip_runtime()
-    dev = {}
-    try:
-        for n, a in host.items():
-            ptr = C.c_void_p()
-            assert hip.hipMalloc(C.byref(ptr), a.nbytes) == 0
-            dev[n] = ptr
-            assert hip.hipMemset(ptr, 0xFF, a.nbytes) == 0
+    with DeviceBuffers(all_ones(host)) as dev:
         H, W = host["mask"].shape
-        gpu_ctx.render_matte_device(dev["rgb"].value, {n: dev[n].value for n in matte}, 4, 4, 4, 9, slots=slots,
-                                    aov_device_ptrs={n: dev[n].value for n in names})
-        gpu_ctx.matte_mask_device(dev["ids"].value, dev["coverage"].value, dev["mask"].value, W, H, slots, select)
+        gpu_ctx.render_matte_device(dev.ptr("rgb"), dev.ptrs(matte), 4, 4, 4, 9, slots=slots, aov_device_ptrs=dev.ptrs(names))
+        gpu_ctx.matte_mask_device(dev.ptr("ids"), dev.ptr("coverage"), dev.ptr("mask"), W, H, slots, select)
         gpu_ctx.collect_stats()
         for n, a in host.items():
-            got = np.empty_like(a)
-            assert hip.hipMemcpy(got.ctypes.data, dev[n], a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            assert (_u32(got) == _u32(a)).all(), n
-    finally:
-        for ptr in dev.values():
-            hip.hipFree(ptr)
+            assert (_u32(dev.download_like(n, a)) == _u32(a)).all(), n
 
 
 def test_refusals_leave_the_context_usable(gpu_ctx):

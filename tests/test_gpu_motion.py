@@ -2,6 +2,7 @@
 device/temporal.h): bit for bit against the CPU model of tests/motion_model.py on synthetic and rendered sequences, against the kernels
 without a table where the table says nothing, the device variants and the ordering of the table's copy, Context.render_animation, the
 error a table removes on a sliding box, and what the header refuses."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -11,8 +12,8 @@ import motion_model as mm
 import pbrs_amd
 import temporal_model as tm
 from common import bits
-from pbrs_amd import api, scenes
-from test_gpu_denoise import _device_buffers, _download, same
+from pbrs_amd import DeviceBuffers, api, scenes
+from test_gpu_denoise import same
 from test_gpu_temporal import PLANES, agree, api_camera, model_camera, sequence_bits
 from test_motion_model import SLIDE_FRAMES, sliding_box_scene
 
@@ -105,27 +106,21 @@ def test_the_device_variants_equal_the_host_ones_and_the_tables_copy_is_ordered(
                                         history=hist0, prev=prev, camera_prev=c0, id_test=True, motion=mm.to_ctypes(t)) for t in (ta, tb)]
     host_mv = [gpu_ctx.motion_vectors(f1["depth"], c1, c0, instance=f1["instance"], motion=mm.to_ctypes(t), return_prev_depth=True) for t in (ta, tb)]
     assert sequence_bits([host[0]]) != sequence_bits([host[1]]) and (bits(host_mv[0][0]) != bits(host_mv[1][0])).any()
-    hip = api.hip_runtime()
     like = {"rgb": np.zeros((h, w, 3), f32), "moments": np.zeros((h, w, 2), f32), "length": np.zeros((h, w), f32), "v": np.zeros((h, w), f32),
             "mv": np.zeros((h, w, 2), f32), "wq": np.zeros((h, w), f32)}
-    held = [_device_buffers(hip, f1), _device_buffers(hip, prev), _device_buffers(hip, hist0), _device_buffers(hip, like), _device_buffers(hip, like)]
-    frame, guides, hin, outs = held[0], held[1], held[2], held[3:]
-    try:
+    with contextlib.ExitStack() as held:
+        frame, guides, hin, *outs = (held.enter_context(DeviceBuffers(arrays)) for arrays in (f1, prev, hist0, like, like))
         for t, out in zip((ta, tb), outs):
             table = mm.to_ctypes(t)
-            gpu_ctx.temporal_accumulate_device({n: p.value for n, p in frame.items()}, {n: out[n].value for n in PLANES}, w, h, c1,
-                                               {n: p.value for n, p in hin.items()}, {n: p.value for n, p in guides.items()}, c0, out["v"].value,
-                                               id_test=True, motion=table)
-            gpu_ctx.motion_vectors_device(frame["depth"].value, out["mv"].value, w, h, c1, c0, frame["instance"].value, table, out["wq"].value)
+            gpu_ctx.temporal_accumulate_device(frame.ptrs(), out.ptrs(PLANES), w, h, c1, hin.ptrs(), guides.ptrs(), c0, out.ptr("v"), id_test=True,
+                                               motion=table)
+            gpu_ctx.motion_vectors_device(frame.ptr("depth"), out.ptr("mv"), w, h, c1, c0, frame.ptr("instance"), table, out.ptr("wq"))
             del table  # the library has read it
         gpu_ctx.collect_stats()
         for k, out in enumerate(outs):
-            got = {n: _download(hip, out[n], like[n]) for n in like}
+            got = {n: out.download_like(n, like[n]) for n in like}
             agree(({n: got[n] for n in PLANES}, got["v"]), host[k], k)
             assert same(got["mv"], host_mv[k][0]).all() and same(got["wq"], host_mv[k][1]).all(), k
-    finally:
-        for ptr in [p for d in held for p in d.values()]:
-            hip.hipFree(ptr)
 
 
 AOVS = ("normal", "depth", "instance", "variance")

@@ -2,16 +2,14 @@
 the numpy model of the header's text (tests/passes_model.py) fed with the oracle's per-sample radiances at depth 1 (D_i) and at the
 render's depth (L_i), against the same render without passes, and against themselves however the render is cut into passes, tiles
 and bands."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import passes_model as pm
 import pbrs_amd
-from common import bits
+from common import all_ones, bits
 from passes_common import SEED, builder, oracle_samples
-from pbrs_amd import api
+from pbrs_amd import DeviceBuffers, api
 
 pytestmark = pytest.mark.gpu
 
@@ -209,12 +207,6 @@ def test_refusals_name_the_reason_and_leave_the_context_usable(gpu_ctx):
     assert L.pbrs_combine_passes(h, 2, 2, a.ctypes.data, a.ctypes.data, a.ctypes.data) == 0
 
 
-def _hip_runtime():
-    L = api.hip_runtime()
-    L.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    return L
-
-
 def test_the_device_variants_give_the_host_variants_bits(gpu_ctx):
     """Case 11, first half: render_passes_device, then combine_passes_device on the context's stream with nothing in between, read after
     collect_stats(); the sum written over the direct layer's copy."""
@@ -222,31 +214,16 @@ def test_the_device_variants_give_the_host_variants_bits(gpu_ctx):
     names = ("depth", "variance")
     rgb, layers, aov, _ = gpu_ctx.render_passes(2, 2, 8, SEED, aovs=names, samples_per_pass=1)
     host = {"rgb": rgb, **layers, **aov, "sum": gpu_ctx.combine_passes(layers["direct"], layers["indirect"])}
-    hip = _hip_runtime()
-    dev = {}
-    try:
-        for n, a in host.items():
-            ptr = C.c_void_p()
-            assert hip.hipMalloc(C.byref(ptr), a.nbytes) == 0
-            dev[n] = ptr
-            assert hip.hipMemset(ptr, 0xFF, a.nbytes) == 0
-        gpu_ctx.render_passes_device(dev["rgb"].value, {n: dev[n].value for n in layers}, 2, 2, 8, SEED,
-                                     aov_device_ptrs={n: dev[n].value for n in names}, samples_per_pass=1)
-        gpu_ctx.combine_passes_device(dev["direct"].value, dev["indirect"].value, dev["sum"].value, 16, 16)
+    with DeviceBuffers(all_ones(host)) as dev:
+        gpu_ctx.render_passes_device(dev.ptr("rgb"), dev.ptrs(layers), 2, 2, 8, SEED, aov_device_ptrs=dev.ptrs(names), samples_per_pass=1)
+        gpu_ctx.combine_passes_device(dev.ptr("direct"), dev.ptr("indirect"), dev.ptr("sum"), 16, 16)
         gpu_ctx.collect_stats()
         for n, a in host.items():
-            got = np.empty_like(a)
-            assert hip.hipMemcpy(got.ctypes.data, dev[n], a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            assert (_u32(got) == _u32(a)).all(), n
+            assert (_u32(dev.download_like(n, a)) == _u32(a)).all(), n
         # in place: the sum over the direct layer
-        gpu_ctx.combine_passes_device(dev["direct"].value, dev["indirect"].value, dev["direct"].value, 16, 16)
+        gpu_ctx.combine_passes_device(dev.ptr("direct"), dev.ptr("indirect"), dev.ptr("direct"), 16, 16)
         gpu_ctx.collect_stats()
-        got = np.empty_like(host["sum"])
-        assert hip.hipMemcpy(got.ctypes.data, dev["direct"], got.nbytes, 2) == 0
-        assert (_u32(got) == _u32(host["sum"])).all()
-    finally:
-        for ptr in dev.values():
-            hip.hipFree(ptr)
+        assert (_u32(dev.download_like("direct", host["sum"])) == _u32(host["sum"])).all()
 
 
 def test_render_denoised_passes_is_the_chain_of_its_host_steps(gpu_ctx):

@@ -8,9 +8,9 @@ import pytest
 
 import filter_model as fm
 import pbrs_amd
-from common import bits
+from common import all_ones, bits
 from oracle.binding import OracleScene
-from pbrs_amd import PixelFilter, scenes
+from pbrs_amd import DeviceBuffers, PixelFilter, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -138,19 +138,10 @@ def test_passes_overlap_and_the_device_variant_give_the_same_bits(gpu_ctx):
                     assert st["passes"] == 6
     finally:
         gpu_ctx.set_pass_overlap(True)
-    from test_gpu_aov import _hip_runtime
-    hip = _hip_runtime()
-    ptr = C.c_void_p()
-    assert hip.hipMalloc(C.byref(ptr), ref.nbytes) == 0
-    try:
-        assert hip.hipMemset(ptr, 0xFF, ref.nbytes) == 0
-        gpu_ctx.render_filtered_device(ptr.value, pf, 4, 4, 5, 5, samples_per_pass=3)
+    with DeviceBuffers(all_ones({"rgb": ref})) as dev:
+        gpu_ctx.render_filtered_device(dev.ptr("rgb"), pf, 4, 4, 5, 5, samples_per_pass=3)
         gpu_ctx.collect_stats()
-        got = np.empty_like(ref)
-        assert hip.hipMemcpy(got.ctypes.data, ptr, ref.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-        assert (bits(got) == bits(ref)).all()
-    finally:
-        hip.hipFree(ptr)
+        assert (bits(dev.download_like("rgb", ref)) == bits(ref)).all()
 
 
 def test_invalid_samples_count_the_tile_only_and_plain_renders_are_untouched(gpu_ctx):

@@ -13,8 +13,8 @@ import pbrs_amd
 import spatial_variance_model as sv
 import temporal_model as tm
 from common import bits
-from pbrs_amd import api, scenes
-from test_gpu_denoise import _device_buffers, _download, same
+from pbrs_amd import DeviceBuffers, api, scenes
+from test_gpu_denoise import same
 from test_gpu_temporal import _yawed
 
 pytestmark = pytest.mark.gpu
@@ -153,23 +153,18 @@ def test_blocks_without_a_short_pixel_pass_through_beside_blocks_with_one(gpu_ct
 
 
 def test_the_device_variant_on_caller_buffers_equals_the_host_variant(gpu_ctx):
-    hip = api.hip_runtime()
     for (w, h), kw in (((37, 29), dict(min_temporal=2.5, radius=2)), ((130, 70), dict(only_unknown=True))):
         inp = inputs(w, h, "yaw")
         host = gpu_ctx.spatial_variance(**inp, **kw)
-        dev = _device_buffers(hip, dict(inp, out=np.zeros((h, w), f32)))
-        try:
-            guides = {n: dev[n].value for n in tm.GUIDE_NAMES}
-            gpu_ctx.spatial_variance_device(dev["moments"].value, dev["length"].value, dev["variance"].value, dev["out"].value, w, h, guides, **kw)
+        with DeviceBuffers(dict(inp, out=np.zeros((h, w), f32))) as dev:
+            guides = dev.ptrs(tm.GUIDE_NAMES)
+            gpu_ctx.spatial_variance_device(dev.ptr("moments"), dev.ptr("length"), dev.ptr("variance"), dev.ptr("out"), w, h, guides, **kw)
             gpu_ctx.collect_stats()
-            agree(_download(hip, dev["out"], host), host, (w, h, "out of place"))
-            agree(_download(hip, dev["variance"], host), inp["variance"], (w, h, "the input is left alone"))
-            gpu_ctx.spatial_variance_device(dev["moments"].value, dev["length"].value, dev["variance"].value, dev["variance"].value, w, h, guides, **kw)
+            agree(dev.download_like("out", host), host, (w, h, "out of place"))
+            agree(dev.download_like("variance", host), inp["variance"], (w, h, "the input is left alone"))
+            gpu_ctx.spatial_variance_device(dev.ptr("moments"), dev.ptr("length"), dev.ptr("variance"), dev.ptr("variance"), w, h, guides, **kw)
             gpu_ctx.collect_stats()
-            agree(_download(hip, dev["variance"], host), host, (w, h, "in place"))
-        finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+            agree(dev.download_like("variance", host), host, (w, h, "in place"))
 
 
 def test_render_temporal_with_the_estimate_is_the_hand_made_chain(gpu_ctx):

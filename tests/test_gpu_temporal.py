@@ -1,6 +1,7 @@
 """Temporal accumulation on the GPU (include/pbrs_gpu.h, pbrs_temporal_accumulate[_device]; device/temporal.h): bit for bit against the
 CPU model of tests/temporal_model.py on synthetic sequences and on rendered ones, every guide present or absent, the device variant and
 the device chain of Context.render_temporal, the error the accumulation removes, and what the header refuses."""
+import contextlib
 import ctypes as C
 import itertools
 
@@ -10,8 +11,8 @@ import pytest
 import pbrs_amd
 import temporal_model as tm
 from common import bits
-from pbrs_amd import api, scenes
-from test_gpu_denoise import _device_buffers, _download, same
+from pbrs_amd import DeviceBuffers, api, scenes
+from test_gpu_denoise import same
 
 pytestmark = pytest.mark.gpu
 
@@ -137,27 +138,22 @@ def test_matches_the_cpu_model_bit_for_bit_on_rendered_sequences(gpu_ctx, name):
 def test_the_device_variant_on_caller_buffers_equals_the_host_sequence(gpu_ctx):
     w, h = 37, 29
     host = tm.run_sequence(gpu_step(gpu_ctx), w, h, 5, "yaw", id_test=True)
-    hip = api.hip_runtime()
     like = {"rgb": np.zeros((h, w, 3), f32), "moments": np.zeros((h, w, 2), f32), "length": np.zeros((h, w), f32)}
-    hist = [_device_buffers(hip, like) for _ in (0, 1)]
-    vout = _device_buffers(hip, {"v": like["length"]})["v"]
-    held, cam_prev, prev_dev = [], None, None
-    try:
+    cam_prev = prev_dev = None
+    with contextlib.ExitStack() as held:
+        hist = [held.enter_context(DeviceBuffers(like)) for _ in (0, 1)]
+        vout = held.enter_context(DeviceBuffers({"v": like["length"]}))
         for k, (cam, frame, plant) in enumerate(tm.synthetic_sequence(w, h, 5, "yaw")):
-            dev = _device_buffers(hip, frame)
-            held.append(dev)
+            dev = held.enter_context(DeviceBuffers(frame))
             cur, old = hist[k & 1], hist[(k & 1) ^ 1]
-            gpu_ctx.temporal_accumulate_device({n: p.value for n, p in dev.items()}, {n: p.value for n, p in cur.items()}, w, h, api_camera(cam),
-                                               {n: p.value for n, p in old.items()} if k else None, prev_dev, cam_prev, vout.value, id_test=True)
+            gpu_ctx.temporal_accumulate_device(dev.ptrs(), cur.ptrs(), w, h, api_camera(cam), old.ptrs() if k else None, prev_dev, cam_prev, vout.ptr("v"),
+                                               id_test=True)
             gpu_ctx.collect_stats()
-            got = {n: _download(hip, cur[n], like[n]) for n in PLANES}
-            agree((got, _download(hip, vout, like["length"])), host[k], k)
+            got = {n: cur.download_like(n, like[n]) for n in PLANES}
+            agree((got, vout.download_like("v", like["length"])), host[k], k)
             for n, a in tm.plant_history(got, plant).items():  # what the host sequence fed back
-                assert hip.hipMemcpy(cur[n], a.ctypes.data, a.nbytes, 1) == 0
-            prev_dev, cam_prev = {n: dev[n].value for n in tm.GUIDE_NAMES}, api_camera(cam)
-    finally:
-        for ptr in [p for d in held + hist for p in d.values()] + [vout]:
-            hip.hipFree(ptr)
+                cur.upload(n, a)
+            prev_dev, cam_prev = dev.ptrs(tm.GUIDE_NAMES), api_camera(cam)
 
 
 def test_render_temporal_is_the_hand_made_chain(gpu_ctx):

@@ -13,8 +13,8 @@ import pytest
 import pbrs_amd
 import upsample_model as um
 from common import bits
-from pbrs_amd import api, scenes
-from test_gpu_denoise import _device_buffers, _download, same
+from pbrs_amd import DeviceBuffers, api, scenes
+from test_gpu_denoise import same
 from test_gpu_temporal import _yawed
 
 pytestmark = pytest.mark.gpu
@@ -90,27 +90,22 @@ def test_every_guide_subset_min_weight_and_weight_out(gpu_ctx, size, f, R):
 
 def test_the_device_variant_on_caller_buffers_equals_the_host_variant(gpu_ctx):
     """On planes at 16-byte alignment and 4 bytes off it (the kernel loads words: both must give the host variant's bits)."""
-    hip = api.hip_runtime()
     for (w, h, f, R), off in zip(((33, 31, 2, 2), (130, 97, 3, 1), (17, 15, 4, 2)), (0, 1, 1)):
         rgb_lo, lo, hi = inputs(w, h, f)
         host, hw_ = gpu_ctx.upsample(rgb_lo, w, h, f, lo=lo, hi=hi, radius=R, return_weight=True)
         pad = lambda a: np.concatenate([np.zeros(off, a.dtype), a.reshape(-1)])  # noqa: E731
         arrays = {"rgb_lo": rgb_lo, "out": np.zeros((h, w, 3), f32), "weight": np.zeros((h, w), f32),
                   **{f"{n}_lo": lo[n] for n in GUIDES}, **{f"{n}_hi": hi[n] for n in GUIDES}}
-        dev = _device_buffers(hip, {n: pad(a) for n, a in arrays.items()})
-        try:
-            at = lambda n: dev[n].value + 4 * off  # noqa: E731
+        with DeviceBuffers({n: pad(a) for n, a in arrays.items()}) as dev:
+            at = lambda n: dev.ptr(n) + 4 * off  # noqa: E731
             gpu_ctx.upsample_device(at("rgb_lo"), at("out"), w, h, f, {n: at(f"{n}_lo") for n in GUIDES}, {n: at(f"{n}_hi") for n in GUIDES},
                                     at("weight"), radius=R)
             gpu_ctx.collect_stats()
-            agree(_download(hip, dev["out"], pad(host))[off:].reshape(host.shape), host, (w, h, f, R, off))
-            agree(_download(hip, dev["weight"], pad(hw_))[off:].reshape(hw_.shape), hw_, (w, h, f, R, off, "weight_out"))
+            agree(dev.download_like("out", pad(host))[off:].reshape(host.shape), host, (w, h, f, R, off))
+            agree(dev.download_like("weight", pad(hw_))[off:].reshape(hw_.shape), hw_, (w, h, f, R, off, "weight_out"))
             gpu_ctx.upsample_device(at("rgb_lo"), at("out"), w, h, f, radius=R)  # no guides, no weights
             gpu_ctx.collect_stats()
-            agree(_download(hip, dev["out"], pad(host))[off:].reshape(host.shape), gpu_ctx.upsample(rgb_lo, w, h, f, radius=R), (w, h, f, R, off, "tent"))
-        finally:
-            for ptr in dev.values():
-                hip.hipFree(ptr)
+            agree(dev.download_like("out", pad(host))[off:].reshape(host.shape), gpu_ctx.upsample(rgb_lo, w, h, f, radius=R), (w, h, f, R, off, "tent"))
 
 
 def test_refusals_leave_the_context_usable(gpu_ctx):
