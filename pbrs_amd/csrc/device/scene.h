@@ -66,6 +66,12 @@ struct DevScene {
     const pbrs_node* nodes_top;
     // element counts of the arrays k_shade may stage in LDS (kernels.h, stage_shade_scene); n_area / n_delta above
     uint32_t n_inst, n_shapes, n_tris, n_mats, n_bxdfs;
+    // tri_leaf: one word per triangle record of `tv`, the index in `nodes` of the BLAS leaf that holds it.  A packed leaf reference
+    // (PBRS_WREF_PACKED) names its triangles, not its node; the any-hit walk finds the node — the leaf's box — through this table, and only
+    // once a triangle of the leaf has passed (traverse.h, AnyWalkW::verify_leaf).  The table lies in the wide nodes' allocation, right behind
+    // the n_wnodes wide nodes (device/wide.h, tri_leaf); 0 without wide nodes.  (This word fills what was the structure's padding: a kernel
+    // that takes the scene and does not read the table keeps its argument layout.)
+    uint32_t n_wnodes;
 };
 
 // Scene features the traversal kernels are specialised on (prepare_scene derives them from the arrays check_scene has checked).
@@ -103,7 +109,8 @@ struct DevScene {
 struct pbrs_wnode {
     float lo[3][4];     // [axis][slot]: min planes   (bytes   0 ..  47)
     float hi[3][4];     // [axis][slot]: max planes   (bytes  48 ..  95)
-    uint32_t child[4];  // PBRS_WREF_LEAF | index of the reference's leaf node in DevScene::nodes; else index of a wide node; PBRS_WREF_NONE
+    uint32_t child[4];  // PBRS_WREF_LEAF | index of the reference's leaf node in DevScene::nodes, or, as uploaded, PBRS_WREF_LEAF | PBRS_WREF_PACKED |
+                        // count - 1 | first triangle (below); else index of a wide node; PBRS_WREF_NONE
                         // in a slot not in use (its box is inverted — lo = 2^60, hi = -2^60 — and fails the filter for every ray of the
                         // guarded range, without an overflow).  Slots 0 and 2 are always in use and carry the three split axes above
                         // the index (PBRS_WREF_AXIS_SHIFT): child[0] bits 27-28 X's, bits 29-30 its left child's; child[2] bits 27-28 its
@@ -121,6 +128,22 @@ struct pbrs_wnode {
 #define PBRS_WREF_NONE 0xffffffffu
 #define PBRS_WREF_INDEX 0x07ffffffu  // a leaf's index in DevScene::nodes (below 2^27: the node array is addressed with 32-bit byte offsets); a wide
 #define PBRS_WREF_AXIS_SHIFT 27      // node's index loses the bits above it in `index * sizeof(pbrs_wnode)` (below 2^25 for the same reason)
+// A leaf reference that carries its triangles (host/scene_prepare.cpp, pack_wide_leaves): inside the 27 index bits, bit 26 set, bits 24-25
+// the triangle count - 1, bits 0-23 the first triangle's index in DevScene::tv.  For a leaf of one to four triangles that start below 2^24
+// (a terrain of 2^24 triangles packs whole); a leaf of more (coincident centroids), an empty leaf and a leaf further up the triangle array
+// keep the node form, which never has bit 26 set: prepare_scene builds wide nodes only where every node index is below 2^26.
+#define PBRS_WREF_PACKED 0x04000000u
+#define PBRS_WREF_TRI_BITS 24
+#define PBRS_WREF_TRI 0x00ffffffu
+#define PBRS_WREF_COUNT_SHIFT 24
+#define PBRS_WREF_COUNT_MAX 4u
+static_assert((PBRS_WREF_PACKED & PBRS_WREF_INDEX) == PBRS_WREF_PACKED && PBRS_WREF_PACKED < (1u << PBRS_WREF_AXIS_SHIFT), "the packed flag lies inside the index bits, below the axes");
+static_assert(PBRS_WREF_TRI == (1u << PBRS_WREF_TRI_BITS) - 1u && PBRS_WREF_COUNT_SHIFT == PBRS_WREF_TRI_BITS, "first triangle: the low bits, the count above them");
+static_assert(((PBRS_WREF_COUNT_MAX - 1u) << PBRS_WREF_COUNT_SHIFT) < PBRS_WREF_PACKED && (PBRS_WREF_PACKED >> PBRS_WREF_COUNT_SHIFT) == PBRS_WREF_COUNT_MAX,
+              "two bits of count - 1 between the triangle index and the flag");
+static_assert((PBRS_WREF_PACKED | ((PBRS_WREF_COUNT_MAX - 1u) << PBRS_WREF_COUNT_SHIFT) | PBRS_WREF_TRI) == PBRS_WREF_INDEX, "flag, count and triangle fill the 27 bits exactly");
+static_assert(PBRS_WREF_TRI_BITS >= 24, "a mesh of 2^24 triangles (indices 0 .. 2^24 - 1) packs");
+static_assert((PBRS_WREF_LEAF | PBRS_WREF_INDEX | (15u << PBRS_WREF_AXIS_SHIFT)) == 0xffffffffu && PBRS_WREF_LEAF == (1u << 31), "leaf bit, four axis bits, 27 index bits");
 #define PBRS_WIDE_UNUSED_PLANE 1152921504606846976.0f /* 2^60 */
 // slots 0, 1: the children of X's left child (or that child itself in slot 0, where it is a leaf); slots 2, 3: of its right child
 

@@ -31,6 +31,8 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_WIDE) ? PBR
             if constexpr (WIDE) {
                 wave_append_slow(walk.mode == PBRS_WALK_SLOW, rec, slow_list, slow_count);
                 if (walk.mode == PBRS_WALK_SLOW) walk.mode = PBRS_WALK_IDLE;
+                walk.settle(S);  // the leaf boxes the finished walks still owe; a lane whose box fails walks on
+                live = __ballot(walk.mode == PBRS_WALK_NODE || walk.mode == PBRS_WALK_LEAF || walk.mode == PBRS_WALK_XFER);
             }
             if (walk.mode == PBRS_WALK_DONE) {
                 const bool occluded = walk.occluded;

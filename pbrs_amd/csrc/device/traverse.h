@@ -13,7 +13,8 @@
 // In this file: the box test (RaySpace, qdiv, slab_rs) and the instance boundary (enter_instance, leave_instance); the two ways a wave
 // shares work among its lanes — TriShare (triangle tests) and FlatScan (the leaf boxes of a small TLAS: one scaffold, FlatScan::scan,
 // behind the exact test of the any-hit walks and the f32 filter of the closest-hit walk); the walks ClosestWalk, AnyWalk and, derived
-// from it for four-wide BLAS nodes (wide.h), AnyWalkW, whose leaf step is AnyWalk::share_leaf behind a prologue of its own; and the
+// from it for four-wide BLAS nodes (wide.h), AnyWalkW, whose leaf step is AnyWalk::share_leaf (behind a prologue for the leaves that do
+// not carry their triangles) and which settles the leaf boxes it owes when its walks are retired; and the
 // run-to-completion drivers of the parity harness (tlas_closest, tlas_any, tlas_any_wide).
 //
 // Box test.  geometry/src/bvh.rs:84-99 divides six times per node; IEEE f32 division costs ~11 instructions on gfx950.  With
@@ -996,12 +997,14 @@ struct AnyWalk {
 // and leaf steps as the binary any-hit walk above — AnyWalkW inherits them, and its leaf step is AnyWalk::share_leaf behind a prologue
 // of its own — but: inside a mesh a node step takes a WIDE node (four boxes through the conservative filter, the survivors pushed near
 // side first, the first one kept in a register), from an empty stack (the TLAS level is the scan's mask alone: any hit, the extent
-// never changes, a leaf that passed the scan is entered without a second test); a BLAS leaf that comes up is held UNVERIFIED until
-// the leaf step gives it the reference's own box test.  A ray that leaves the guarded range (at its start or inside an instance) or
+// never changes, a leaf that passed the scan is entered without a second test); a BLAS leaf that comes up through a reference that
+// carries its triangles is held at once and its triangles are tested first (hold_leaf, settle: the argument is at settle); one that
+// comes up as a node is held UNVERIFIED until the leaf step gives it the reference's own box test.  A ray that leaves the guarded range (at its start or inside an instance) or
 // whose stack would exceed DevScene::wide_cap takes mode PBRS_WALK_SLOW: the kernel hands it, whole, to the binary-walk kernel
 // (extend.h).
 #define PBRS_WALK_SLOW 6u
 #define PBRS_LEAF_UNVERIFIED 0xffffffffu
+#define PBRS_KIND_BOX_OWED 0x200u  // AnyWalk::inst_kind: the held leaf came from a reference that carries its triangles and its own box is untested
 template <uint32_t FEAT>
 struct AnyWalkW : AnyWalk<false, FEAT> {
     using B = AnyWalk<false, FEAT>;
@@ -1027,10 +1030,22 @@ struct AnyWalkW : AnyWalk<false, FEAT> {
         B::scan_wave(S, cnt);
     }
     PD uint32_t after_leaf() const { return sp == 0 ? B::exit_mode() : PBRS_WALK_NODE; }
+    // A reference that carries its triangles (PBRS_WREF_PACKED, device/scene.h) is a held leaf at once; its box is still owed
+    // (PBRS_KIND_BOX_OWED in inst_kind, beside the 0x100 of xfer_step) and is paid by settle, if a triangle ever passes.
+    // The node form waits for leaf_wave's prologue, as before.
     PD void hold_leaf(uint32_t ref) {
-        leaf_a = ref & PBRS_WREF_INDEX;
-        leaf_end = PBRS_LEAF_UNVERIFIED;
+        const bool packed = (ref & PBRS_WREF_PACKED) != 0u;
+        leaf_a = ref & (packed ? PBRS_WREF_TRI : PBRS_WREF_INDEX);
+        leaf_end = packed ? leaf_a + ((ref >> PBRS_WREF_COUNT_SHIFT) & (PBRS_WREF_COUNT_MAX - 1u)) + 1u : PBRS_LEAF_UNVERIFIED;
+        inst_kind = packed ? inst_kind | PBRS_KIND_BOX_OWED : inst_kind & ~PBRS_KIND_BOX_OWED;
+        if (packed) PBRS_TP(3);  // a leaf has come up (the node form: counted by the prologue)
         mode = PBRS_WALK_LEAF;
+    }
+    // The reference's test of the box of the leaf that holds triangle `tri` (tri_leaf, device/wide.h, leads to its node)
+    PD bool verify_leaf(const DevScene& S, uint32_t tri) {
+        const bool pass = slab_rs(load_node(S.nodes + tri_leaf(S, tri)), exact_w(), t_max);
+        if (pass) PBRS_TP(4);
+        return pass;
     }
     PD void forget_reciprocals() { C.nr = gray(0.0f); }
     // a round's further node steps: a lane with nothing to take from its register or its stack (the next scanned TLAS leaf, the end
@@ -1140,6 +1155,27 @@ struct AnyWalkW : AnyWalk<false, FEAT> {
         }
         B::share_leaf(S, cnt, [&]() __attribute__((always_inline)) { return after_leaf(); });
     }
+    // The box a walk still owes when it ends on a passing triangle of a leaf that carried its triangles (hold_leaf): every lane whose walk
+    // is DONE calls this before its answer is read — the kernel at retire time, with the other lanes the refill retires, not in the leaf
+    // step, where some lane or other of nearly every execution has a triangle that passes and the test would run for one or two lanes
+    // (measured on C4: run in the leaf step it gave back everything the missing prologue had saved).
+    // Why no answer changes (device/wide.h has the long form): occluded = OR over the leaves reached of (the leaf's own box passes AND one
+    // of its triangles passes).  Inner tests only prune and the filter never rejects what the exact test accepts, so the leaves reached
+    // include every leaf whose box passes; the triangle predicate (mesh_tri_pred) is pure arithmetic on a ray inside the guarded range
+    // with a fixed extent, so evaluating it before the box, or for a leaf whose box fails, has no effect beyond its value; AND commutes.
+    // The box passes: the ray is occluded.  It fails: the leaf contributes nothing, its other triangles are not wanted either, and the lane
+    // walks on as after_leaf() says (its stack, register entry and pending TLAS leaves are as the leaf step left them: a DONE lane takes no
+    // step).  share_leaf has moved leaf_a past the triangles of its execution: leaf_a - 1 is a triangle of the leaf.  A leaf is settled once:
+    // either way the lane has left it.
+    PD void settle(const DevScene& S) {
+        if (mode == PBRS_WALK_DONE && occluded && (inst_kind & PBRS_KIND_BOX_OWED)) {
+            inst_kind &= ~PBRS_KIND_BOX_OWED;
+            if (!verify_leaf(S, leaf_a - 1u)) {
+                occluded = false;
+                mode = after_leaf();
+            }
+        }
+    }
 };
 
 // One ray per lane start to finish (parity harness; the pipeline kernels interleave walks and refill lanes instead).
@@ -1179,11 +1215,14 @@ PD bool tlas_any_wide(const DevScene& S, bool active, f3 o, f3 d, float t_max, L
     w.start(S, o, d, t_max, stk);
     if (!active) w.mode = PBRS_WALK_DONE;
     w.scan_wave(S, stk);
-    while (__ballot(w.mode == PBRS_WALK_NODE || w.mode == PBRS_WALK_LEAF || w.mode == PBRS_WALK_XFER)) {
-        if (w.mode == PBRS_WALK_XFER) w.xfer_step(S, stk, cnt);
-        if (w.mode == PBRS_WALK_NODE) w.node_step(S, stk, cnt);
-        if (__ballot(w.mode == PBRS_WALK_LEAF)) w.leaf_wave(S, cnt);
-    }
+    do {
+        while (__ballot(w.mode == PBRS_WALK_NODE || w.mode == PBRS_WALK_LEAF || w.mode == PBRS_WALK_XFER)) {
+            if (w.mode == PBRS_WALK_XFER) w.xfer_step(S, stk, cnt);
+            if (w.mode == PBRS_WALK_NODE) w.node_step(S, stk, cnt);
+            if (__ballot(w.mode == PBRS_WALK_LEAF)) w.leaf_wave(S, cnt);
+        }
+        w.settle(S);  // (a lane whose leaf's box fails walks on)
+    } while (__ballot(w.mode == PBRS_WALK_NODE || w.mode == PBRS_WALK_LEAF || w.mode == PBRS_WALK_XFER));
     slow = w.mode == PBRS_WALK_SLOW;  // refused (outside the guarded range, or the stack would not fit): the binary walk's ray, as in the pipeline
     bool occ = w.occluded;
     if (__ballot(slow)) {

@@ -13,10 +13,17 @@
 // child, where it is a leaf) of an inner node X, in left-first order, tested together with pn_slab_filter (include/pbrs_numeric.h:
 // f32 products by the rounded reciprocals, bounds widened by 2^-21 — proved and tested never to reject what the reference
 // accepts); the children that pass are visited in the reference's order (three split axes per wide node: X's and its two
-// children's).  A leaf that comes up gets the reference's exact test (slab_rs) at ITS turn, with the best hit
-// of that moment, before its triangles are tested (closest hit), or once one of its triangles has passed (any hit).  The
-// sequence of (leaf, extent) pairs whose triangles are tested — hence every hit, every tie-break and the final result — is the
-// reference's.  Measured on C4's terrain (tools/trav_stats): 54 box tests in 54 dependent steps per bounce ray become 54
+// children's).  A leaf that comes up gets the reference's exact test (slab_rs): in a closest-hit walk at ITS turn, with the best hit
+// of that moment, before its triangles are tested — the sequence of (leaf, extent) pairs whose triangles are tested, hence every hit,
+// every tie-break and the final result, is the reference's.  In the any-hit walk (AnyWalkW, traverse.h) a leaf of one to four triangles
+// is named by a reference that carries the triangles themselves (PBRS_WREF_PACKED, device/scene.h) and the order is the other way
+// round: the triangles first, the leaf's box — found through tri_leaf below — only for a leaf one of whose triangles has passed, and
+// only when the lane's walk is retired (AnyWalkW::settle).  The answer is the OR, over the leaves reached, of (box passes AND some
+// triangle passes); the conjunction commutes, the triangle predicate is pure arithmetic on a ray inside the guarded range (no side
+// effect, no state carried from leaf to leaf, a fixed extent), and reaching MORE leaves than the reference does is harmless because
+// each still has to pass its own box: no bit of the answer changes.  A ray that leaves every leaf without a passing triangle — most
+// shadow rays of an open scene — never pays for a leaf's box.  Leaves of more than four triangles (coincident centroids), empty leaves
+// and leaves beyond the reference's triangle field keep the node form and are verified first, as before.  Measured on C4's terrain (tools/trav_stats): 54 box tests in 54 dependent steps per bounce ray become 54
 // tests in 14 steps + 2.4 exact leaf tests; shadow rays 61 -> 16 steps.
 //
 // Rays outside the guarded range (a zero / denormal / huge direction or origin component, in the world or inside an instance)
@@ -26,6 +33,9 @@
 #include "shapes.h"  // included by traverse.h once RaySpace exists
 
 // pbrs_wnode, PBRS_WREF_* and the PBRS_WIDE_* constants: device/scene.h (the host builds the nodes: host/scene_prepare.cpp)
+
+// DevScene::tri_leaf: the leaf node of triangle record `t` (behind the wide nodes, in their allocation)
+PD uint32_t tri_leaf(const DevScene& S, uint32_t t) { return reinterpret_cast<const uint32_t*>(S.wnodes + S.n_wnodes)[t]; }
 
 struct WideRay {
     f3 r32;       // RN(1 / d) per component: the correctly rounded reciprocals of the direction (-RaySpace::nr)

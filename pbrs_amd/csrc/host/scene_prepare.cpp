@@ -320,7 +320,8 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
     // the wide node of its root, PBRS_WREF_NONE where the mesh is a single leaf.  Built and uploaded only for scenes whose
     // k_shadow can walk them: a scanned TLAS and coordinates inside the guarded range of the division-free box test (the
     // deciding PBRS_WIDE_MIN_LEVELS is known once they are built).  A wide array of 4 GiB or more (32-bit byte offsets) is not
-    // an error: the scene keeps the binary walks.
+    // an error: the scene keeps the binary walks.  Nor is a node array of more than 2^26 nodes, in which a leaf's index would reach the
+    // bit that marks a reference carrying its triangles (PBRS_WREF_PACKED, pack_wide_leaves).
     for (pbrs_instance& in : inst) in.pad[1] = PBRS_WREF_NONE;
     S.wide_cap = 4u;
     if (scan && S.fast_slab != 0u) {
@@ -333,14 +334,21 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
             if (it == wide_of_root.end()) it = wide_of_root.emplace(in.blas_root, build_wide(nodes, in.blas_root, wide, 0u, levels)).first;
             in.pad[1] = it->second;
         }
-        if (levels >= PBRS_WIDE_MIN_LEVELS && wide.size() * sizeof(pbrs_wnode) < (1ull << 32)) {
+        if (levels >= PBRS_WIDE_MIN_LEVELS && wide.size() * sizeof(pbrs_wnode) < (1ull << 32) && nodes.size() <= PBRS_WREF_PACKED) {
             P.walk_bytes += wide.size() * sizeof(pbrs_wnode);
+            // DevScene::tri_leaf: the BLAS leaf that holds each triangle record (0xffffffff: none — an IsolatedTriangle's record)
+            P.tri_leaf.assign(d.n_triangles, 0xffffffffu);
+            for (size_t i = blas_off; i < nodes.size(); ++i)
+                if (nodes[i].b & PBRS_LEAF_FLAG)
+                    for (uint32_t t = nodes[i].a, end = t + (nodes[i].b & ~PBRS_LEAF_FLAG); t < end; ++t) P.tri_leaf[t] = (uint32_t)i;  // (in range: check_scene)
+            P.walk_bytes += P.tri_leaf.size() * sizeof(uint32_t);
+            S.n_wnodes = (uint32_t)wide.size();
             // a node step pushes up to three survivors per level; deeper stacks than PBRS_WIDE_STACK_MAX entries are not given LDS:
             // a ray that would need one (none on the BASELINE scenes) is traced by the binary-walk kernel instead
             S.wide_cap = std::max(4u, std::min(3u * levels + 1u, (uint32_t)PBRS_WIDE_STACK_MAX));
             P.wide_levels = levels;
         } else {
-            wide.clear();
+            wide.clear();  // (and no tri_leaf)
             for (pbrs_instance& in : inst) in.pad[1] = PBRS_WREF_NONE;
         }
     }
@@ -420,6 +428,29 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
     const size_t budget = 16u << 10;
     f.shade_lds = f.shade_rec_bytes + f.shade_tri_bytes <= budget ? PBRS_SHADE_LDS_ALL : f.shade_rec_bytes <= budget ? PBRS_SHADE_LDS_RECORDS : 0u;
     return P;
+}
+
+// Leaf references that carry their triangles (device/scene.h, PBRS_WREF_PACKED), on the wide nodes as they are uploaded — like the split
+// planes, which ride on the uploaded copy of the nodes.  A leaf keeps the node form unless it has one to four triangles, the first of them
+// below 2^24, and tri_leaf leads from each of them back to it (a description whose leaves share a triangle record: the table names one leaf
+// only).  No reference of the node form has the flag bit set: prepare_scene builds wide nodes only over node arrays of at most 2^26 nodes.
+uint32_t pack_wide_leaves(PreparedScene& P) {
+    uint32_t packed = 0;
+    for (pbrs_wnode& w : P.wide)
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t ref = w.child[k];
+            if (ref == PBRS_WREF_NONE || !(ref & PBRS_WREF_LEAF)) continue;
+            const uint32_t ni = ref & PBRS_WREF_INDEX;
+            const pbrs_node& n = P.nodes[ni];
+            const uint32_t cnt = n.b & ~PBRS_LEAF_FLAG;
+            if (cnt == 0u || cnt > PBRS_WREF_COUNT_MAX || n.a > PBRS_WREF_TRI) continue;
+            bool own = true;
+            for (uint32_t j = 0; j < cnt; ++j) own = own && P.tri_leaf[n.a + j] == ni;
+            if (!own) continue;
+            w.child[k] = (ref & ~PBRS_WREF_INDEX) | PBRS_WREF_PACKED | (cnt - 1u) << PBRS_WREF_COUNT_SHIFT | n.a;
+            ++packed;
+        }
+    return packed;
 }
 
 }  // namespace pbrs

@@ -35,13 +35,17 @@ struct PreparedScene {
     std::vector<uint32_t> node_planes;  // per node of `nodes`: the split planes of an inner BLAS node, packed for its b word (device/split_planes.h); 0 for leaves and the TLAS
     std::vector<pbrs_instance> inst; // DevScene::inst: pad[0] the shading class, pad[1] the wide root, blas_root and flags as the walks read them
     std::vector<pbrs_wnode> wide;    // DevScene::wnodes; empty where the scene keeps the binary walks (S.wnodes stays null)
+    std::vector<uint32_t> tri_leaf;  // DevScene::tri_leaf: per triangle record, the BLAS leaf of `nodes` that holds it; built with the wide nodes, empty without them
     uint32_t wide_levels = 0;        // wide nodes on the longest way down a BLAS (0: no wide nodes)
     SceneFacts facts;
     uint32_t stack_depth = 0;      // entries of a lane's traversal stack
     bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
-    uint64_t walk_bytes = 0;       // what the walks read: nodes, wide nodes, triangle vertices, instance records (pbrs_ctx::overlap_from)
+    uint64_t walk_bytes = 0;       // what the walks read: nodes, wide nodes, tri_leaf, triangle vertices, instance records (pbrs_ctx::overlap_from)
 };
 // `d` has passed check_scene, which returned `levels`.  Of `dev`, refill_below alone is read (DevScene::refill_below).
 PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& levels, const DevOverrides& dev);
+// What pbrs_upload_scene does to `P.wide` before it uploads it: the references to leaves of one to four triangles take the form that names
+// the triangles themselves (device/scene.h, PBRS_WREF_PACKED).  Returns how many it rewrote.
+uint32_t pack_wide_leaves(PreparedScene& P);
 
 }  // namespace pbrs

@@ -284,6 +284,19 @@ int upload(pbrs_ctx* c, const T* src, size_t n, const T** dst) {
     return PBRS_OK;
 }
 
+// The wide nodes and, right behind them in one allocation, the tri_leaf table (DevScene::n_wnodes)
+int upload_wide(pbrs_ctx* c, const PreparedScene& P, const pbrs_wnode** dst) {
+    *dst = nullptr;
+    const size_t wide_bytes = P.wide.size() * sizeof(pbrs_wnode), table_bytes = P.tri_leaf.size() * sizeof(uint32_t);
+    void* p = nullptr;
+    HIPCHK(c, hipMalloc(&p, wide_bytes + table_bytes));
+    c->scene_allocs.push_back(p);
+    HIPCHK(c, hipMemcpy(p, P.wide.data(), wide_bytes, hipMemcpyHostToDevice));
+    if (table_bytes) HIPCHK(c, hipMemcpy(static_cast<char*>(p) + wide_bytes, P.tri_leaf.data(), table_bytes, hipMemcpyHostToDevice));
+    *dst = static_cast<const pbrs_wnode*>(p);
+    return PBRS_OK;
+}
+
 void free_scene(pbrs_ctx* c) {
     for (void* p : c->scene_allocs) (void)hipFree(p);
     c->scene_allocs.clear();
@@ -1087,7 +1100,9 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     // the split planes ride in the spare bits of the inner BLAS nodes' b words (device/split_planes.h), on the uploaded copy only
     for (size_t i = 0; i < P.nodes.size(); ++i) P.nodes[i].b |= P.node_planes[i];
     if ((rc = upload(c, P.nodes.data(), P.nodes.size(), &S.nodes))) return rc;
-    if (!P.wide.empty() && (rc = upload(c, P.wide.data(), P.wide.size(), &S.wnodes))) return rc;
+    // ... and the leaves' triangles in the wide nodes' references to them (device/scene.h, PBRS_WREF_PACKED), with the table that leads back to the leaf
+    pack_wide_leaves(P);
+    if (!P.wide.empty() && (rc = upload_wide(c, P, &S.wnodes))) return rc;
     if ((rc = upload(c, P.inst.data(), P.inst.size(), &S.inst))) return rc;
     if ((rc = upload(c, d->shapes, d->n_shapes, &S.shapes))) return rc;
     if ((rc = upload(c, d->meshes, d->n_meshes, &S.meshes))) return rc;
