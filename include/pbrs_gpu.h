@@ -1104,6 +1104,95 @@ int pbrs_upsample(pbrs_ctx*, const pbrs_upsample_params*, const float* rgb_lo_ho
 int pbrs_upsample_device(pbrs_ctx*, const pbrs_upsample_params*, const float* rgb_lo_device, const pbrs_denoise_guides* guides_lo_device,
                          const pbrs_denoise_guides* guides_hi_device, float* out_device, float* weight_out_device);
 
+/* ---- image comparison -------------------------------------------------------------------------------------------- */
+/* What a step of the image chain buys: an image `a` under test is compared with a reference `b` on the device — mean squared error,
+ * relative squared error, mean absolute error, the largest difference, the structural similarity index (SSIM; Wang, Bovik, Sheikh and
+ * Simoncelli 2004) and, where asked for, per-pixel maps of the error and of the SSIM.  a and b are w * h pixels, row-major, 3 floats
+ * each; the maps are w * h floats.  An image operation like pbrs_denoise: it needs a context (device, stream) and no uploaded scene.
+ * Per-pixel image arithmetic is f32 without fused multiply-add, in the order written; error terms and sums are f64 without fused
+ * multiply-add; pn_* is include/pbrs_numeric.h.  Every sum has one stated order, so the result does not depend on the launch shape or on
+ * the order in which blocks finish, and a CPU model of this text gives the same 64 bytes.
+ *   Validity.  A pixel p is valid when all six values a(p).c, b(p).c, c = r, g, b, pass pn_isfinite.  n_valid and n_invalid count the two
+ *     kinds.  An invalid pixel contributes +0.0 to every sum and weight 0 to every window.
+ *   Transform.  PBRS_COMPARE_LINEAR: t(x) = x.  PBRS_COMPARE_REINHARD: x' = x < 0 ? +0 : x, t(x) = x' / (1.0f + x'), a correctly rounded
+ *     division and no libm: negative radiance counts as black, the rest lands in [0, 1).
+ *   Terms.  At a valid pixel A.c = (double)t(a(p).c), B.c = (double)t(b(p).c), D.c = A.c - B.c, eps = (double)rel_epsilon:
+ *       se(p) = (D.r * D.r + D.g * D.g) + D.b * D.b
+ *       ae(p) = (|D.r| + |D.g|) + |D.b|
+ *       re(p) = (D.r * D.r / (B.r * B.r + eps) + D.g * D.g / (B.g * B.g + eps)) + D.b * D.b / (B.b * B.b + eps)
+ *   Order of every sum T(v) of a per-pixel f64 value v.  The image is cut into PBRS_COMPARE_TILE x PBRS_COMPARE_TILE tiles from pixel
+ *     (0, 0).  The 256 entries of a tile are taken row-major, positions outside the image (and invalid pixels) as +0.0, and reduced by the
+ *     adjacent-pair tree: v'[j] = v[2j] + v[2j + 1], until one value is left.  The tile sums, row-major over tiles and padded with +0.0
+ *     to the next power of two, are reduced by the same tree.  (Adding +0.0 to a sum that is not -0.0 is exact: an implementation
+ *     need not materialise padding beyond a value's first partner.)  PBRS_COMPARE_TILE is part of the contract because it fixes this order.
+ *   Result.  mse = T(se) / (double)(3 * n_valid), mae = T(ae) / (double)(3 * n_valid), rel_mse = T(re) / (double)(3 * n_valid); with
+ *     n_valid == 0 the three are what 0.0 / 0.0 gives (NaN).  max_abs is the largest |D.c| over valid pixels and channels, +0.0 when there
+ *     are none.  The pads are written as 0.
+ *   SSIM (only with PBRS_COMPARE_SSIM), on luminance through an 11 x 11 Gaussian window, sigma 1.5.
+ *     lum(c) = (0.21267127f * c.r + 0.71515972f * c.g) + 0.07216883f * c.b, the variance AOV's.  Fields: x(p) = lum(t(a(p))),
+ *     y(p) = lum(t(b(p))), both +0 at invalid pixels; m(p) = 1.0f at valid pixels, +0 elsewhere.  Six fields are filtered: m, x, y, x * x,
+ *     y * y, x * y (the products are f32, formed per pixel before the filter).
+ *     g[k] = PBRS_COMPARE_G0 .. PBRS_COMPARE_G5 below: the f32 nearest to exp(-k * k / 4.5), k = 0 .. 5.  Not normalised: W does that.
+ *     The filter is separable, first along the row, then along the column of the row pass' result.  Each pass starts from A = +0 and
+ *     does A = A + g[|k|] * v(q) for k = -5 .. 5 ascending, q the position k further along the axis; a tap outside the image is skipped.
+ *     The six window sums of p are W, Sx, Sy, Sxx, Syy, Sxy.  At a valid pixel (W >= 1 there):
+ *       iw = 1.0f / W;  mx = Sx * iw;  my = Sy * iw;
+ *       sxx = Sxx * iw - mx * mx;  syy = Syy * iw - my * my;  sxy = Sxy * iw - mx * my;
+ *       C1 = (0.01f * peak) * (0.01f * peak);  C2 = (0.03f * peak) * (0.03f * peak);
+ *       ssim(p) = ((2.0f * (mx * my) + C1) * (2.0f * sxy + C2)) / (((mx * mx + my * my) + C1) * ((sxx + syy) + C2))
+ *     The variances are not clamped at 0: that keeps ssim(a, a) == 1.0f exactly and the formula symmetric in a and b.  A valid pixel
+ *     whose ssim(p) is not finite (pn_isfinite) is left out; that can only happen on linear values far above peak, where the one-pass
+ *     variances cancel.  n_ssim counts the pixels that are kept, and ssim = T((double)ssim(p)) / (double)n_ssim over them (0.0 / 0.0
+ *     with none).  Without the flag ssim is written as 0.0 and n_ssim as 0.
+ *   Maps (maps NULL, or a pointer of it NULL: not wanted).  error_out(p) = (float)se(p).  ssim_out(p) = ssim(p): the computed value,
+ *     finite or not, at valid pixels.  Both hold the quiet NaN 0x7fc00000 at invalid pixels.
+ * Scale rule.  With PBRS_COMPARE_LINEAR, a and b times 2^j give mse and se times 4^j and mae and max_abs times 2^j, bit for bit, while
+ * nothing overflows or goes subnormal.
+ * SSIM is meant for display-referred values in [0, peak]; with PBRS_COMPARE_REINHARD peak = 1 is exact.  PSNR is left to the caller:
+ * 10 * log10(peak^2 / mse).
+ * Pointers are host memory for pbrsx_compare, which stages the two images, the maps and the record on first use (32 B per pixel) and
+ * synchronises before it returns; device memory for pbrsx_compare_device (the maps struct itself is host memory, its pointers and
+ * result_device device memory), which runs on the context's stream (pbrs_set_stream honoured), writes the 64-byte record from its last
+ * kernel and does not wait: a sequence scores its frames without leaving the stream.  Its only scratch is the per-tile partial sums
+ * (80 B per tile), allocated on first use; a context that never calls it allocates nothing.  a == b is allowed.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, a, b or result; w or h 0; an unknown transform; unknown flag bits;
+ * rel_epsilon or peak not finite or not > 0; ssim_out without PBRS_COMPARE_SSIM; a map equal to a, to b or to the other map.  w * h
+ * above 2^28: PBRS_E_LIMIT. */
+#define PBRS_COMPARE_TILE 16u
+#define PBRS_COMPARE_LINEAR 0u
+#define PBRS_COMPARE_REINHARD 1u
+#define PBRS_COMPARE_SSIM 1u
+#define PBRS_COMPARE_G0 0x1p+0f
+#define PBRS_COMPARE_G1 0x1.99fa4p-1f
+#define PBRS_COMPARE_G2 0x1.a4fa9ep-2f
+#define PBRS_COMPARE_G3 0x1.152aaap-3f
+#define PBRS_COMPARE_G4 0x1.d40464p-6f
+#define PBRS_COMPARE_G5 0x1.fab6c2p-9f
+typedef struct pbrs_compare_params {
+    uint32_t w, h;      /* image size */
+    uint32_t transform; /* PBRS_COMPARE_LINEAR, PBRS_COMPARE_REINHARD */
+    uint32_t flags;     /* PBRS_COMPARE_SSIM */
+    float rel_epsilon;  /* finite, > 0: the relative error's floor under B * B */
+    float peak;         /* finite, > 0: SSIM's dynamic range L */
+    uint32_t pad[2];
+} pbrs_compare_params; /* 32 B */
+typedef struct pbrs_compare_maps { /* each pointer may be NULL */
+    float* error_out; /* w * h f32: se(p) */
+    float* ssim_out;  /* w * h f32: ssim(p); needs PBRS_COMPARE_SSIM */
+} pbrs_compare_maps;
+typedef struct pbrs_compare_result {
+    double mse, rel_mse, mae, ssim, max_abs;
+    uint32_t n_valid, n_invalid, n_ssim;
+    uint32_t pad[3]; /* 0 */
+} pbrs_compare_result; /* 64 B */
+/* (The three functions' prefix is pbrsx_; the structs and constants above carry pbrs_.)
+ * Filler: PBRS_COMPARE_REINHARD, PBRS_COMPARE_SSIM, rel_epsilon 1e-2, peak 1; `out` NULL does nothing.  Host code: needs no context. */
+void pbrsx_compare_params_default(uint32_t w, uint32_t h, pbrs_compare_params* out);
+int pbrsx_compare(pbrs_ctx*, const pbrs_compare_params*, const float* a_host, const float* b_host, const pbrs_compare_maps* maps_host,
+                 pbrs_compare_result* result_host);
+int pbrsx_compare_device(pbrs_ctx*, const pbrs_compare_params*, const float* a_device, const float* b_device,
+                        const pbrs_compare_maps* maps_device, pbrs_compare_result* result_device);
+
 #ifdef __cplusplus
 }
 #endif

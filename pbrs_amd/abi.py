@@ -1,6 +1,8 @@
 """ctypes mirrors of the C ABI (include/pbrs_gpu.h, include/pbrs_host.h): the structures with their constructors, the name tables
 of their planes, and the helpers that turn an option of the driver (api.py) into one of them.  Nothing here loads a library."""
 import ctypes as C
+import itertools
+import math
 
 import numpy as np
 
@@ -428,6 +430,72 @@ def _display_params(display):
     dp.setdefault("auto", True)
     DisplayParams.make(1, 1, **dp)
     return dp
+
+
+class CompareParams(C.Structure):
+    """pbrs_compare_params (include/pbrs_gpu.h, "image comparison"): image size, the transform both images go through, flags, the floor
+    of the relative error and SSIM's peak."""
+    TRANSFORMS = {"linear": 0, "reinhard": 1}
+    SSIM = 1
+    TILE = 16
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("transform", C.c_uint32), ("flags", C.c_uint32), ("rel_epsilon", C.c_float),
+                ("peak", C.c_float), ("pad", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, w, h, transform="reinhard", ssim=True, rel_epsilon=1e-2, peak=1.0):
+        """The defaults are pbrsx_compare_params_default's; transform by name (or by its number)."""
+        p = cls()
+        p.w, p.h = w, h
+        p.transform = cls.TRANSFORMS[transform] if isinstance(transform, str) else transform
+        p.flags = cls.SSIM if ssim else 0
+        p.rel_epsilon, p.peak = rel_epsilon, peak
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+class CompareMaps(C.Structure):
+    """pbrs_compare_maps: where the per-pixel squared error and the per-pixel SSIM go ((h, w) f32 each); each may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("error_out", "ssim_out")]
+
+
+class CompareResult(C.Structure):
+    """pbrs_compare_result: the means over the valid pixels, the largest difference, and the counts."""
+    _fields_ = [("mse", C.c_double), ("rel_mse", C.c_double), ("mae", C.c_double), ("ssim", C.c_double), ("max_abs", C.c_double),
+                ("n_valid", C.c_uint32), ("n_invalid", C.c_uint32), ("n_ssim", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+    def psnr(self, peak=1.0):
+        """10 log10(peak^2 / mse) in dB: +inf for identical images, NaN where there was no valid pixel."""
+        if not self.mse > 0.0:
+            return float("inf") if self.mse == 0.0 else float("nan")
+        return 10.0 * math.log10(peak * peak / self.mse)
+
+
+def _reference_frames(reference):
+    """render_temporal's / render_animation's `reference` -> an iterator of one image per frame, or None: a single (h, w, 3) array
+    stands for every frame, anything else is iterated.  A single array of another rank or channel count fails here."""
+    if reference is None:
+        return None
+    if isinstance(reference, np.ndarray):
+        if reference.ndim != 3 or reference.shape[2] != 3:
+            raise ValueError(f"the reference is (h, w, 3), not {reference.shape}")
+        return itertools.repeat(reference)
+    return iter(reference)
+
+
+def _reference_frame(frames, i, w, h):
+    """Frame i's reference out of _reference_frames' iterator, as a contiguous (h, w, 3) f32 array."""
+    try:
+        ref = np.ascontiguousarray(next(frames), dtype=np.float32)
+    except StopIteration:
+        raise ValueError(f"the reference ends before frame {i}") from None
+    if ref.shape != (h, w, 3):
+        raise ValueError(f"frame {i}'s reference is ({h}, {w}, 3), not {ref.shape}")
+    return ref
 
 
 class SpatialVarianceGuides(C.Structure):

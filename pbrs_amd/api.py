@@ -13,13 +13,14 @@ from types import SimpleNamespace
 import numpy as np
 
 from .abi import (AOV_NAMES, AOVS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
-                  SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, Camera, DenoiseGuides, DenoiseParams,
+                  SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, Camera, CompareMaps, CompareParams, CompareResult,
+                  DenoiseGuides, DenoiseParams,
                   DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
                   PixelFilter, RenderParams, SceneDesc, SpatialVarianceGuides, SpatialVarianceParams, Stats, TemporalFrame, TemporalGuides, TemporalHistory,
                   TemporalParams, UpsampleParams, _aov_names, _DenoiseParamsMixin, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
-                  _temporal_struct, _upscale_params, scaled_camera)
+                  _reference_frame, _reference_frames, _temporal_struct, _upscale_params, scaled_camera)
 from .devmem import DeviceBuffers
-from .libs import GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .libs import GPU_COMPARE_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
 from .spec import SceneSpec  # noqa: F401
 
 
@@ -70,7 +71,7 @@ def _guide_bytes(guides, w, h, suffix=""):
     return {n + suffix: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}
 
 
-def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display):
+def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False):
     """{name: bytes} of the device buffers of a frame sequence (Context._temporal_frames) that runs at w x h and shows fw x fh: the
     frame's image, the filtered one, the two variances; two ping-pong halves ("0", "1") of the guides the next frame is tested against
     and of the history; the other guides once; and what each option that is on adds."""
@@ -87,6 +88,8 @@ def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display):
         sizes.update(_guide_bytes(guides, fw, fh, "_hi"))
     if display:
         sizes["display"], sizes["exposure"] = fw * fh * 4, 4
+    if reference:
+        sizes["reference"], sizes["compare"] = 3 * fw * fh * 4, C.sizeof(CompareResult)
     return sizes
 
 
@@ -821,6 +824,37 @@ class Context:
         self._check(self._L.pbrs_upsample_device(self._h, C.addressof(p), C.c_void_p(rgb_lo_device_ptr), C.addressof(gl), C.addressof(gh),
                                                  C.c_void_p(out_device_ptr), C.c_void_p(weight_out_device_ptr)), "pbrs_upsample_device")
 
+    def compare(self, a, b, maps=False, **params):
+        """The comparison (include/pbrs_gpu.h, pbrsx_compare) of the (h, w, 3) f32 image `a` with the reference `b` -> CompareResult: mse,
+        rel_mse, mae, ssim, max_abs over the valid pixels and the counts.  With maps=True a tuple: the result, the (h, w) f32 squared
+        error of every pixel and, where SSIM is on, its (h, w) f32 SSIM (None where it is off); NaN at invalid pixels.  params:
+        CompareParams.make's keywords."""
+        a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 3 or b.shape != a.shape:
+            raise ValueError(f"the image and the reference are (h, w, 3) and alike, not {a.shape} and {b.shape}")
+        h, w, _ = a.shape
+        p = CompareParams.make(w, h, **params)
+        result = CompareResult()
+        error = np.empty((h, w), dtype=np.float32) if maps else None
+        ssim = np.empty((h, w), dtype=np.float32) if maps and p.flags & CompareParams.SSIM else None
+        m = CompareMaps(*(x.ctypes.data if x is not None else None for x in (error, ssim)))
+        self._check(self._L.pbrsx_compare(self._h, C.addressof(p), a.ctypes.data, b.ctypes.data, C.addressof(m) if maps else None, C.addressof(result)),
+                    "pbrsx_compare")
+        return (result, error, ssim) if maps else result
+
+    def compare_device(self, a_ptr, b_ptr, w, h, result_ptr, map_ptrs=None, **params):
+        """compare() on caller-owned device memory: `result_ptr` receives the 64 bytes of CompareResult, `map_ptrs` = {name: pointer} of
+        error_out / ssim_out.  Runs on the context's stream behind whatever was queued there and does not wait: valid after
+        `collect_stats()`."""
+        p = CompareParams.make(w, h, **params)
+        m = CompareMaps()
+        for n, ptr in dict(map_ptrs or {}).items():
+            if n not in ("error_out", "ssim_out"):
+                raise ValueError(f"unknown compare map pointer {n!r}; known: error_out, ssim_out")
+            setattr(m, n, ptr)
+        self._check(self._L.pbrsx_compare_device(self._h, C.addressof(p), C.c_void_p(a_ptr), C.c_void_p(b_ptr), C.addressof(m), C.c_void_p(result_ptr)),
+                    "pbrsx_compare_device")
+
     def _render_guides_device(self, rgb_device_ptr, guide_device_ptrs, seed, camera=None):
         """The full-size first-hit guides of guided upsampling: a one-sample render of `seed` through the path integrator at depth 1 (the
         cheapest route whose first hits are the jittered ones the low-resolution AOVs average; the visualisers shoot through the
@@ -897,17 +931,22 @@ class Context:
         per axis through scaled_camera of each Camera (which are still given at full size) and queues two more calls per frame on the
         same stream, the render of the full-size guides and upsample_device behind the filter: the first image of a frame is then the
         full-size one, the accumulated and the noisy ones stay low, `display` acts on the full-size image, and the stats gain
-        "low_res", (wl, hl)."""
+        "low_res", (wl, hl).  `reference` (a keyword taken out of `params`; the signature is the one callers know): None is that chain; an iterable of one (h, w, 3) image per frame at full size, or a single such
+        array for every frame, queues compare_device of each frame's first image against it on the same stream (CompareParams' defaults)
+        and yields the CompareResult, read back behind the frame's one wait, as a fifth entry."""
+        reference = params.pop("reference", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
         cameras, seeds = list(cameras), list(seeds)
         if len(cameras) != len(seeds):
             raise ValueError(f"{len(cameras)} cameras beside {len(seeds)} seeds")
+        if isinstance(reference, np.ndarray) and self.scene is not None:  # the scene is uploaded: its film is the size every frame has
+            _reference_frame(_reference_frames(reference), 0, self.scene.width, self.scene.height)
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display,
-                                         upscale):
-            yield out[:4]
+                                         upscale, reference):
+            yield out[:4] if reference is None else out[:4] + out[5:]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
                          temporal=None, motion_vectors=False, spatial=None, clip=None, display=None, upscale=None, **params):
@@ -919,18 +958,20 @@ class Context:
         frame; motion_vectors="prev_depth": (h, w, 3), the depth the previous frame would have recorded as the third channel, +inf where
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
-        are `spatial`, `display` and `upscale` (the motion vectors are then the low-resolution chain's)."""
+        are `spatial`, `display`, `upscale` (the motion vectors are then the low-resolution chain's) and the keyword `reference`, whose
+        CompareResult is the last entry."""
+        reference = params.pop("reference", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display,
-                                         upscale):
-            yield out if motion_vectors else out[:4]
+                                         upscale, reference):
+            yield (out[:5] if motion_vectors else out[:4]) + (() if reference is None else out[5:])
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None, display=None, upscale=None):
+                         clip=None, display=None, upscale=None, reference=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
-        accumulated, noisy, stats, motion vectors or None) per frame.  A scene that is given is uploaded and, from the second one on,
+        accumulated, noisy, stats, motion vectors or None, CompareResult or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  The options are checked here, before
         anything is allocated; the first frame fixes the sizes (_sequence_buffers: with `upscale` the chain runs at the low size w x h,
         fw x fh is the full one); every frame is queued (_queue_frame), waited for once and read back (_read_frame)."""
@@ -942,6 +983,7 @@ class Context:
         s.dparams = _display_params(display)
         s.uparams = _upscale_params(upscale, guides)
         s.shown = "out" if s.uparams is None else "up"  # the buffer of a frame's first image
+        s.reference, s.one_reference = _reference_frames(reference), isinstance(reference, np.ndarray)
         dev = None
         try:
             cam_prev = scene_prev = None
@@ -960,10 +1002,16 @@ class Context:
                 if dev is None:
                     s.fw, s.fh = self.scene.width, self.scene.height
                     s.w, s.h = (s.fw, s.fh) if s.uparams is None else (cam.width, cam.height)
-                    dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None),
-                                        "a temporal sequence")
                 elif (self.scene.width, self.scene.height) != (s.fw, s.fh):
                     raise ValueError(f"frame {i} has a film of {self.scene.width} x {self.scene.height}, the sequence {s.fw} x {s.fh}")
+                ref = None
+                if s.reference is not None and not (s.one_reference and i):  # checked before anything is allocated or queued
+                    ref = _reference_frame(s.reference, i, s.fw, s.fh)
+                if dev is None:
+                    dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None,
+                                                          s.reference is not None), "a temporal sequence")
+                if ref is not None:
+                    dev.upload("reference", ref)  # the frame before has been waited for: nothing reads the buffer
                 self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table)
                 stats = self.collect_stats()  # waits for the stream
                 cam_prev = cam
@@ -976,7 +1024,7 @@ class Context:
         """Frame i of the sequence `s` on the context's stream, nothing waits: the render of `p` with its guides and its variance; the
         accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
         on the accumulated variance; the filter; the full-size guides and the upsample; the display transform, whose exposure word is
-        read from the second frame on and written by every one."""
+        read from the second frame on and written by every one; the comparison of the frame's first image with its reference."""
         w, h, cur, old = s.w, s.h, i & 1, (i & 1) ^ 1
         gp = {n: dev.ptr(f"{n}{cur}" if n in s.kept else n) for n in s.guides}
         kept = {n: gp[n] for n in s.kept}  # what the next frame is tested against
@@ -997,11 +1045,13 @@ class Context:
         if s.dparams is not None:
             self.display_device(dev.ptr(s.shown), dev.ptr("display"), s.fw, s.fh,
                                 {"exposure_in": dev.ptr("exposure") if i else None, "exposure_out": dev.ptr("exposure")}, **s.dparams)
+        if s.reference is not None:
+            self.compare_device(dev.ptr(s.shown), dev.ptr("reference"), s.fw, s.fh, dev.ptr("compare"))
 
     @staticmethod
     def _read_frame(s, dev, i, stats):
-        """Frame i copied back, behind the wait -> (first image, accumulated, noisy, stats, motion vectors or None); the display image,
-        its exposure and the low size go into `stats`."""
+        """Frame i copied back, behind the wait -> (first image, accumulated, noisy, stats, motion vectors or None, CompareResult or
+        None); the display image, its exposure and the low size go into `stats`."""
         w, h = s.w, s.h
         if s.dparams is not None:
             stats["display"] = dev.download("display", (s.fh, s.fw, 4), np.uint8, "a temporal sequence's display image")
@@ -1018,7 +1068,10 @@ class Context:
                 wq = dev.download("prev_depth", wq.shape, np.float32, "the motion vectors")
             if s.motion_vectors == "prev_depth":
                 mv = np.concatenate([mv, wq[:, :, None]], axis=2)
-        return shown, accumulated, noisy, stats, mv
+        record = None
+        if s.reference is not None:
+            record = CompareResult.from_buffer_copy(dev.download("compare", C.sizeof(CompareResult), np.uint8, "a temporal sequence's comparison"))
+        return shown, accumulated, noisy, stats, mv, record
 
     def collect_stats(self):
         st = Stats()

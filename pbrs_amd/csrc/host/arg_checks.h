@@ -71,5 +71,8 @@ Refusal check_display(const pbrs_display_params* p, const float* rgb, const pbrs
 // `lo` and `hi` counts when both give it.
 Refusal check_upsample(const pbrs_upsample_params* p, const float* rgb_lo, const pbrs_denoise_guides* lo, const pbrs_denoise_guides* hi,
                        const float* out, const float* weight_out);
+// pbrsx_compare* (host/arg_checks_compare.cpp, beside the filler pbrsx_compare_params_default).  `maps` and its pointers may be NULL;
+// `a` may be `b`.
+Refusal check_compare(const pbrs_compare_params* p, const float* a, const float* b, const pbrs_compare_maps* maps, const pbrs_compare_result* result);
 
 }  // namespace pbrs

@@ -38,6 +38,7 @@
 #include "device/spatial_variance.h"
 #include "device/display.h"
 #include "device/upsample.h"
+#include "device/compare.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -148,6 +149,9 @@ enum BufferId {
     // guided upsampling (pbrs_upsample, device/upsample.h): the host variant's staging (the low image and its four guides at the low
     // size, the four full-size guides, the result and its weights, one after the other); the device variant needs nothing
     BUF_UPSAMPLE_STAGE,
+    // image comparison (pbrsx_compare, device/compare.h): the per-tile partial sums and the room k_compare_finish quarters them into (64 +
+    // 16 B per tile), and the host variant's staging (the two images, the two maps, the 64-byte record, one after the other)
+    BUF_COMPARE, BUF_COMPARE_STAGE,
     N_BUFFERS
 };
 
@@ -1773,6 +1777,72 @@ int pbrs_upsample(pbrs_ctx* c, const pbrs_upsample_params* p, const float* rgb_l
         const pbrs_denoise_guides lod{s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<uint32_t>()};
         const pbrs_denoise_guides hid{s[5].as<float>(), s[6].as<float>(), s[7].as<float>(), s[8].as<uint32_t>()};
         return upsample_launch(c, *p, s[0].as<float>(), lod, hid, s[9].as<float>(), s[10].as<float>());
+    });
+}
+
+// ---- image comparison (include/pbrs_gpu.h, device/compare.h) ----
+static_assert(sizeof(pbrs_compare_params) == 32, "pbrs_compare_params is 32 B");
+static_assert(sizeof(pbrs_compare_result) == 64 && offsetof(pbrs_compare_result, n_valid) == 40, "pbrs_compare_result is 64 B");
+
+namespace {
+
+using CompareKernel = void (*)(const float*, const float*, CompareRecords, CompareConst);
+// [transform][ssim]
+constexpr CompareKernel kCompare[2][2] = {{k_compare_tile<PBRS_COMPARE_LINEAR, false>, k_compare_tile<PBRS_COMPARE_LINEAR, true>},
+                                          {k_compare_tile<PBRS_COMPARE_REINHARD, false>, k_compare_tile<PBRS_COMPARE_REINHARD, true>}};
+
+uint32_t compare_tiles(uint32_t extent) { return (extent + PBRS_COMPARE_TILE - 1u) / PBRS_COMPARE_TILE; }
+
+// The scratch of a call with n tiles: n records, then the (n + 3) / 4 of k_compare_finish's second buffer.  A planar record is 52 B (five
+// f64 sums, three u32 counts); each buffer gets 64 B per record, which keeps the second one's f64 planes aligned.
+constexpr size_t kCompareRecordBytes = 64;
+uint32_t compare_quarter(uint32_t n) { return (n + 3u) / 4u; }
+size_t compare_scratch_bytes(uint32_t n) { return kCompareRecordBytes * ((size_t)n + compare_quarter(n)); }
+
+int compare_scratch(pbrs_ctx* c, const pbrs_compare_params& p) {
+    return c->buf[BUF_COMPARE].grow(c, compare_scratch_bytes(compare_tiles(p.w) * compare_tiles(p.h)), "the comparison's tile sums");
+}
+
+// The two launches on the context's stream (arguments checked, the scratch grown; device pointers, `maps` by value with NULL for what is
+// not wanted).
+int compare_launch(pbrs_ctx* c, const pbrs_compare_params& p, const float* a, const float* b, const pbrs_compare_maps& maps, pbrs_compare_result* result) {
+    const bool ssim = (p.flags & PBRS_COMPARE_SSIM) != 0;
+    const uint32_t tiles_x = compare_tiles(p.w), n = tiles_x * compare_tiles(p.h);  // at most 2^28 pixels: at most 2^28 tiles
+    // the layout compare_scratch_bytes sizes: in each buffer the five f64 planes, then the three u32 planes
+    char* base = c->buf[BUF_COMPARE].as<char>();
+    const uint32_t n2 = compare_quarter(n);
+    const CompareRecords tiles{reinterpret_cast<double*>(base), reinterpret_cast<uint32_t*>(base + 40 * (size_t)n), n};
+    char* base2 = base + kCompareRecordBytes * (size_t)n;
+    const CompareRecords halved{reinterpret_cast<double*>(base2), reinterpret_cast<uint32_t*>(base2 + 40 * (size_t)n2), n2};
+    const CompareConst k{p.w, p.h, tiles_x, p.peak, (double)p.rel_epsilon, maps.error_out, ssim ? maps.ssim_out : nullptr};
+    hipLaunchKernelGGL(kCompare[p.transform][ssim], dim3(n), dim3(kCompareBlock), 0, c->stream, a, b, tiles, k);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_compare_finish, dim3(1), dim3(kCompareFinishBlock), 0, c->stream, tiles, halved, n, ssim ? 1u : 0u, result);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrsx_compare_device(pbrs_ctx* c, const pbrs_compare_params* p, const float* a_device, const float* b_device, const pbrs_compare_maps* maps_device,
+                        pbrs_compare_result* result_device) {
+    int rc = enter(c, check_compare(p, a_device, b_device, maps_device, result_device));
+    if (rc) return rc;
+    if ((rc = compare_scratch(c, *p))) return rc;
+    return compare_launch(c, *p, a_device, b_device, maps_device ? *maps_device : pbrs_compare_maps{}, result_device);
+}
+
+int pbrsx_compare(pbrs_ctx* c, const pbrs_compare_params* p, const float* a_host, const float* b_host, const pbrs_compare_maps* maps_host,
+                 pbrs_compare_result* result_host) {
+    int rc = enter(c, check_compare(p, a_host, b_host, maps_host, result_host));
+    if (rc) return rc;
+    if ((rc = compare_scratch(c, *p))) return rc;
+    const pbrs_compare_maps maps = maps_host ? *maps_host : pbrs_compare_maps{};
+    const size_t P = (size_t)p->w * p->h;
+    Staged s[] = {{a_host, 3}, {b_host, 3}, {nullptr, 1, maps.error_out}, {nullptr, 1, maps.ssim_out},
+                  {nullptr, sizeof(pbrs_compare_result) / sizeof(uint32_t), result_host, nullptr, 1}};
+    return run_staged(c, BUF_COMPARE_STAGE, "the comparison's staging", s, P, [&] {
+        return compare_launch(c, *p, s[0].as<float>(), s[1].as<float>(), pbrs_compare_maps{s[2].as<float>(), s[3].as<float>()}, s[4].as<pbrs_compare_result>());
     });
 }
 

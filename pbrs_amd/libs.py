@@ -59,6 +59,13 @@ GPU_FUNCTIONS = _table({
     "pbrs_display": [P] * 5,
     "pbrs_upsample": [P] * 7,
 })
+# The image comparison's entry points (include/pbrs_gpu.h, "image comparison"), in a table of their own: GPU_FUNCTIONS and GPU_SYMBOLS are
+# the surface tests/golden/api_surface.json pins name for name.  gpu_lib() loads both tables, so a missing symbol fails at load here too.
+GPU_COMPARE_FUNCTIONS = _table({
+    "pbrsx_compare_params_default": ([U32, U32, P], None),
+}, with_device={
+    "pbrsx_compare": [P] * 6,
+})
 HOST_FUNCTIONS = _table({
     "pbrs_host_scene_build": [P, C.POINTER(P)],
     "pbrs_host_scene_free": [P],
@@ -77,6 +84,7 @@ HOST_FUNCTIONS = _table({
     "pbrs_host_io_error": ([], STR),
 })
 GPU_SYMBOLS, HOST_SYMBOLS = list(GPU_FUNCTIONS), list(HOST_FUNCTIONS)
+GPU_COMPARE_SYMBOLS = list(GPU_COMPARE_FUNCTIONS)
 _host = _gpu = _hip = None
 
 
@@ -111,7 +119,7 @@ def gpu_lib():
         path = os.environ.get("PBRS_GPU_LIB") or lib_paths()[1]
         if not os.path.exists(path):
             raise PbrsError(f"{path} is missing: the HIP extension must be built (make -C pbrs_amd/csrc); there is no CPU fallback")
-        _gpu = _load(path, GPU_FUNCTIONS)
+        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS})
     return _gpu
 
 

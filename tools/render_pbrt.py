@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]] [--display none|reinhard|aces [--encode sqrt|srgb] [--auto-exposure] [--exposure X]]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]] [--display none|reinhard|aces [--encode sqrt|srgb] [--auto-exposure] [--exposure X]] [--compare-strata N]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -45,7 +45,11 @@ top), the tone curve, the transfer function (--encode, default srgb) and roundin
 guided upsampling (include/pbrs_gpu.h, pbrs_upsample; R 1 .. 2, default 1: the tent's half-width in low pixels) with full-size guides of one
 sample per pixel: also writes <out>.upscaled.<ext> and <out>.upscaled_low.<ext> (Context.render_upscaled; --denoise-var's parameters apply
 to the low-resolution filter).  With --frames N --temporal the sequence itself runs at low resolution (render_temporal's upscale=) and
-<out>.NNNN.<ext> is the full-size image.  --msaa counts samples per traced, low-resolution pixel."""
+<out>.NNNN.<ext> is the full-size image.  --msaa counts samples per traced, low-resolution pixel.
+--compare-strata N (one image, not --frames): also renders a reference at N x N strata (seed 4242) and prints, as one JSON line, what the
+library's comparison (include/pbrs_gpu.h, pbrsx_compare; Context.compare's defaults) says of the produced image against it: mse, rel_mse,
+mae, ssim, max_abs, psnr_db and the counts, under "image", and likewise under "upscaled", "denoised" and "denoised_var" where those are
+produced."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -68,13 +72,16 @@ denoise_passes = "--denoise-passes" in sys.argv
 denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 frames, orbit = 0, 0.0
-for flag in ("--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+compare_strata = 0
+for flag in ("--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
         del sys.argv[k:k + 2]
         if flag == "--frames":
             frames = int(value)
+        elif flag == "--compare-strata":
+            compare_strata = int(value)
         elif flag == "--orbit":
             orbit = float(value)
         elif flag == "--spin":
@@ -168,6 +175,8 @@ ls = pbrs_amd.load_pbrt(scene)
 ctx = pbrs_amd.Context(0)
 hs = pbrs_amd.HostScene(ls)
 ctx.upload(hs)
+if compare_strata and (frames or compare_strata < 1):
+    sys.exit("--compare-strata N (N >= 1) goes with one image, not with --frames")
 if frames:
     spec = ls.build().camera
     cams = [pbrs_amd.api.orbited(hs.camera, list(spec.target), list(spec.up), orbit * k) for k in range(frames)]
@@ -229,6 +238,7 @@ else:
 if want_layers and (filtered or matte_key):  # like the AOVs beside a filtered image: from a separate render of the same samples
     layers = ctx.render_passes(msaa, msaa, depth, 1, passes=want_layers, integrator=integrator)[1]
 pbrs_amd.write_image(out, img)
+scored = {"image": img}  # what --compare-strata scores
 stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
 if display is not None:
     shown, e = ctx.display(img, return_exposure=True, **display)
@@ -238,13 +248,16 @@ if upscale is not None:
     up = {k: v for k, v in upscale.items() if k != "factor"}
     full, low, _ = ctx.render_upscaled(msaa, msaa, depth, 1, factor=upscale["factor"], upsample=up, **denoise_var_params)
     pbrs_amd.write_image(f"{stem}.upscaled{ext}", full)
+    scored["upscaled"] = full
     pbrs_amd.write_image(f"{stem}.upscaled_low{ext}", low)
     print(f"-> {stem}.upscaled{ext} ({low.shape[1]}x{low.shape[0]} traced and filtered, factor {upscale['factor']}, radius {upscale.get('radius', 1)})")
 if denoise:
-    pbrs_amd.write_image(f"{stem}.denoised{ext}", ctx.denoise(img, **{n: buf[n] for n in guides}, **denoise_params))
+    scored["denoised"] = ctx.denoise(img, **{n: buf[n] for n in guides}, **denoise_params)
+    pbrs_amd.write_image(f"{stem}.denoised{ext}", scored["denoised"])
     print(f"-> {stem}.denoised{ext}")
 if denoise_var:
-    pbrs_amd.write_image(f"{stem}.denoised_var{ext}", ctx.denoise_var(img, buf["variance"], **{n: buf[n] for n in guides}, **denoise_var_params))
+    scored["denoised_var"] = ctx.denoise_var(img, buf["variance"], **{n: buf[n] for n in guides}, **denoise_var_params)
+    pbrs_amd.write_image(f"{stem}.denoised_var{ext}", scored["denoised_var"])
     print(f"-> {stem}.denoised_var{ext}")
 if passes:
     for name in ("direct", "indirect"):
@@ -267,3 +280,11 @@ if matte_key:
         pbrs_amd.write_image(f"{stem}.mask.png", np.repeat(m[:, :, None], 3, axis=2))
         print(f"-> {stem}.mask.png")
 print(f"{img.shape[1]}x{img.shape[0]} at {msaa * msaa} spp in {st['ms_total']:.1f} ms -> {out}")
+if compare_strata:
+    import json
+    reference = ctx.render(compare_strata, compare_strata, depth, 4242, integrator=integrator)[0]
+    metrics = {"reference_strata": compare_strata}
+    for name, image in scored.items():
+        r = ctx.compare(image, reference)
+        metrics[name] = dict(r.as_dict(), psnr_db=r.psnr())
+    print(json.dumps({"compare": metrics}))
