@@ -1193,6 +1193,80 @@ int pbrsx_compare(pbrs_ctx*, const pbrs_compare_params*, const float* a_host, co
 int pbrsx_compare_device(pbrs_ctx*, const pbrs_compare_params*, const float* a_device, const float* b_device,
                         const pbrs_compare_maps* maps_device, pbrs_compare_result* result_device);
 
+/* ---- despeckle --------------------------------------------------------------------------------------------------- */
+/* Fireflies and non-finite pixels, the artefact of a path tracer at a few samples per pixel, taken out of an image before the steps
+ * that would spread them (the a-trous filters) or keep them (the temporal accumulation): a pixel that is brighter than `gain` times
+ * the rank-th brightest of its neighbours is scaled down to that limit, and a pixel that is not finite is rebuilt from its neighbours.
+ * An image operation like pbrs_denoise: it needs a context (device, stream) and no uploaded scene.  rgb_in and rgb_out are w * h pixels,
+ * row-major, 3 floats each; the variance planes (the variance AOV: of the pixel's luminance, +inf = "unknown"), mask_out (u32) and
+ * removed_out (3 floats per pixel) follow the same order.  The filter is biased: it removes energy, and removed_out says how much.
+ * All arithmetic is f32 without fused multiply-add, in the order written; divisions are correctly rounded; pn_* is
+ * include/pbrs_numeric.h.  No sum here depends on the launch shape or on arrival order: a CPU model of this text gives the same bytes.
+ *   1. Luminance.  lum(c) = (0.21267127f * c.r + 0.71515972f * c.g) + 0.07216883f * c.b, the variance AOV's.
+ *   2. Good pixels.  A pixel q is good when c(q).r, c(q).g, c(q).b and lum(c(q)) all pass pn_isfinite: a finite colour whose luminance
+ *      overflows is not good.  (These weights sum to less than 1, so no finite f32 colour has such a luminance today: 3e38 in every
+ *      channel is a good, very bright pixel.  The clause keeps "good" meaning "has a usable luminance" whatever the weights.)
+ *   3. Window.  G(p) is the set of good pixels q != p inside the image with |dx| <= radius and |dy| <= radius; n = |G(p)|.
+ *   4. Repair, only where p is not good.  With n == 0: c' = (+0, +0, +0).  Otherwise per channel a sum that starts from +0 and adds
+ *      c(q).ch over G(p) in row-major order (dy outer, dx inner, ascending), then / (float)n.  If that c' is not good (the sum
+ *      overflowed), c' = (+0, +0, +0).  Where p is good, c' = c(p).
+ *   5. Limit, only with n > 0.  S is the k-th largest of { lum(c(q)) : q in G(p) }, counted with multiplicity, k = min(rank, n).
+ *      limit = gain * S + floor; a limit that is < 0, or -0, is replaced by +0 (S may be negative where channels are).
+ *   6. Clamp.  With n > 0 and l' = lum(c') > limit:  s = limit / l',  out.ch = c'.ch * s  (p is "clamped"; l' > limit >= 0, so s is in
+ *      [0, 1)).  Otherwise out = c': a good pixel that is not clamped keeps its bits.
+ *   7. Variance (when the pair is given).  A repaired pixel (p not good): +inf.  A clamped good pixel whose variance v passes
+ *      pn_isfinite: (v * s) * s.  Every other pixel: the input word, a NaN's payload included.
+ *   8. mask_out(p) = PBRS_DESPECKLE_CLAMPED where p is clamped | PBRS_DESPECKLE_REPAIRED where p is not good.
+ *   9. removed_out(p).ch = c'.ch - out.ch at clamped pixels, +0 elsewhere.
+ *  10. n_clamped and n_repaired count the pixels with each bit over the image; the result's pads are written as 0.
+ * Scale rule.  With floor == 0, an input times 2^j gives an output and a removed_out times 2^j, a variance times 4^j and the same mask and
+ * counts, bit for bit, while nothing overflows or goes subnormal.
+ * Pass-through rule.  An image of good pixels none of which exceeds its limit comes back bit for bit; with gain >= 1 every constant
+ * image does (S is then the pixel's own luminance).
+ * rank stops at 4 because the kernel holds the four largest taps in four registers.  With radius 1 and rank 2 a single bright pixel is
+ * clamped and two bright neighbours are too, each seeing the other as the largest and the background as the second.
+ * Pointers of pbrs_despeckle_io (the struct itself is host memory) and `result` are host memory for pbrsi_despeckle, which stages its
+ * planes on first use (44 B per pixel) and synchronises before it returns; device memory for pbrsi_despeckle_device, which runs on the
+ * context's stream (pbrs_set_stream honoured) and does not wait.  `result` may be NULL; where it is given, the blocks store their two
+ * integer counts in a scratch of 16 KiB, which the first such call of a context allocates, and a last kernel sums them and writes the
+ * 16-byte record: no atomics, and a context that never asks for the record allocates nothing.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, io, rgb_in or rgb_out; w or h 0; radius outside 1 .. 2; rank
+ * outside 1 .. 4; gain not finite or < 1; floor not finite or < 0; flag bits (none is defined); one variance pointer without the
+ * other; rgb_out == rgb_in (neighbours are read); any output plane (rgb_out, variance_out, mask_out, removed_out) equal to another
+ * plane of the call, except variance_out == variance_in, which is allowed because the variance is pixel-local.  w * h above 2^28:
+ * PBRS_E_LIMIT. */
+#define PBRS_DESPECKLE_TILE 16u
+#define PBRS_DESPECKLE_MAX_RADIUS 2u
+#define PBRS_DESPECKLE_MAX_RANK 4u
+#define PBRS_DESPECKLE_CLAMPED 1u
+#define PBRS_DESPECKLE_REPAIRED 2u
+typedef struct pbrs_despeckle_params {
+    uint32_t w, h;   /* image size */
+    uint32_t radius; /* 1 .. PBRS_DESPECKLE_MAX_RADIUS: the window is (2 radius + 1)^2 pixels less the centre */
+    uint32_t rank;   /* 1 .. PBRS_DESPECKLE_MAX_RANK: the order statistic of the neighbours' luminances, 1 = the largest */
+    float gain;      /* finite, >= 1: the factor on that statistic */
+    float floor;     /* finite, >= 0: the additive floor of the limit */
+    uint32_t flags;  /* none defined: 0 */
+    uint32_t pad;
+} pbrs_despeckle_params; /* 32 B */
+typedef struct pbrs_despeckle_io {
+    const float* rgb_in;      /* w * h * 3 f32 */
+    float* rgb_out;           /* w * h * 3 f32 */
+    const float* variance_in; /* w * h f32, or NULL: both variance pointers or neither */
+    float* variance_out;      /* w * h f32, or NULL; may be variance_in */
+    uint32_t* mask_out;       /* w * h u32, or NULL */
+    float* removed_out;       /* w * h * 3 f32, or NULL */
+} pbrs_despeckle_io;
+typedef struct pbrs_despeckle_result {
+    uint32_t n_clamped, n_repaired;
+    uint32_t pad[2]; /* 0 */
+} pbrs_despeckle_result; /* 16 B */
+/* (The three functions' prefix is pbrsi_; the structs and constants above carry pbrs_.)
+ * Filler: radius 1, rank 2, gain 2, floor 0, flags 0; `out` NULL does nothing.  Host code: needs no context. */
+void pbrsi_despeckle_params_default(uint32_t w, uint32_t h, pbrs_despeckle_params* out);
+int pbrsi_despeckle(pbrs_ctx*, const pbrs_despeckle_params*, const pbrs_despeckle_io* io_host, pbrs_despeckle_result* result_host);
+int pbrsi_despeckle_device(pbrs_ctx*, const pbrs_despeckle_params*, const pbrs_despeckle_io* io_device, pbrs_despeckle_result* result_device);
+
 #ifdef __cplusplus
 }
 #endif

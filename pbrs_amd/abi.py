@@ -498,6 +498,55 @@ def _reference_frame(frames, i, w, h):
     return ref
 
 
+class DespeckleParams(C.Structure):
+    """pbrs_despeckle_params (include/pbrs_gpu.h, "despeckle"): image size, the window's radius, the order statistic of the neighbours'
+    luminances, the factor on it and the additive floor of the limit."""
+    CLAMPED, REPAIRED = 1, 2  # mask_out's bits
+    TILE = 16
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("radius", C.c_uint32), ("rank", C.c_uint32), ("gain", C.c_float), ("floor", C.c_float),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+    @classmethod
+    def make(cls, w, h, radius=1, rank=2, gain=2.0, floor=0.0):
+        """The defaults are pbrsi_despeckle_params_default's."""
+        p = cls()
+        p.w, p.h = w, h
+        p.radius, p.rank, p.gain, p.floor = radius, rank, gain, floor
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+DESPECKLE_PLANES = ("rgb_in", "rgb_out", "variance_in", "variance_out", "mask_out", "removed_out")
+
+
+class DespeckleIO(C.Structure):
+    """pbrs_despeckle_io: the image in and out ((h, w, 3) f32), the variance pair ((h, w) f32, both or neither), the mask ((h, w) u32) and
+    the removed energy ((h, w, 3) f32); the last four may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in DESPECKLE_PLANES]
+
+
+class DespeckleResult(C.Structure):
+    """pbrs_despeckle_result: how many pixels were clamped and how many repaired."""
+    _fields_ = [("n_clamped", C.c_uint32), ("n_repaired", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+def _despeckle_params(despeckle):
+    """render_temporal's / render_animation's `despeckle` -> DespeckleParams.make's keywords, or None: None or False is the sequence
+    without the step, True the defaults, a dict the keywords.  An unknown keyword fails here."""
+    if despeckle is None or despeckle is False:
+        return None
+    if despeckle is not True and not isinstance(despeckle, dict):
+        raise ValueError("despeckle is None, True or a dict of DespeckleParams.make's keywords")
+    dp = {} if despeckle is True else dict(despeckle)
+    DespeckleParams.make(1, 1, **dp)
+    return dp
+
+
 class SpatialVarianceGuides(C.Structure):
     """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]

@@ -14,13 +14,13 @@ import numpy as np
 
 from .abi import (AOV_NAMES, AOVS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
                   SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, Camera, CompareMaps, CompareParams, CompareResult,
-                  DenoiseGuides, DenoiseParams,
+                  DenoiseGuides, DenoiseParams, DespeckleIO, DespeckleParams, DespeckleResult,
                   DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
                   PixelFilter, RenderParams, SceneDesc, SpatialVarianceGuides, SpatialVarianceParams, Stats, TemporalFrame, TemporalGuides, TemporalHistory,
-                  TemporalParams, UpsampleParams, _aov_names, _DenoiseParamsMixin, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
+                  TemporalParams, UpsampleParams, _aov_names, _DenoiseParamsMixin, _despeckle_params, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
                   _reference_frame, _reference_frames, _temporal_struct, _upscale_params, scaled_camera)
 from .devmem import DeviceBuffers
-from .libs import GPU_COMPARE_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .libs import GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
 from .spec import SceneSpec  # noqa: F401
 
 
@@ -71,7 +71,7 @@ def _guide_bytes(guides, w, h, suffix=""):
     return {n + suffix: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}
 
 
-def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False):
+def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False):
     """{name: bytes} of the device buffers of a frame sequence (Context._temporal_frames) that runs at w x h and shows fw x fh: the
     frame's image, the filtered one, the two variances; two ping-pong halves ("0", "1") of the guides the next frame is tested against
     and of the history; the other guides once; and what each option that is on adds."""
@@ -90,6 +90,8 @@ def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, re
         sizes["display"], sizes["exposure"] = fw * fh * 4, 4
     if reference:
         sizes["reference"], sizes["compare"] = 3 * fw * fh * 4, C.sizeof(CompareResult)
+    if despeckle:
+        sizes["despeckled"], sizes["despeckle"] = 3 * w * h * 4, C.sizeof(DespeckleResult)
     return sizes
 
 
@@ -855,6 +857,41 @@ class Context:
         self._check(self._L.pbrsx_compare_device(self._h, C.addressof(p), C.c_void_p(a_ptr), C.c_void_p(b_ptr), C.addressof(m), C.c_void_p(result_ptr)),
                     "pbrsx_compare_device")
 
+    def despeckle(self, rgb, variance=None, mask=False, removed=False, **params):
+        """The (h, w, 3) f32 image `rgb` despeckled (include/pbrs_gpu.h, pbrsi_despeckle): fireflies scaled down to gain times the rank-th
+        brightest neighbour, non-finite pixels rebuilt from their neighbours -> a tuple: the image; with `variance`, the (h, w) f32 variance
+        AOV, what becomes of it; with mask=True the (h, w) u32 mask (DespeckleParams.CLAMPED | REPAIRED); with removed=True the (h, w, 3)
+        f32 energy taken out; and, last, the DespeckleResult with the two counts.  params: DespeckleParams.make's keywords."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"the image is (h, w, 3), not {rgb.shape}")
+        h, w, _ = rgb.shape
+        p = DespeckleParams.make(w, h, **params)
+        if variance is not None:
+            variance = np.ascontiguousarray(variance, dtype=np.float32)
+            if variance.shape != (h, w):
+                raise ValueError(f"the variance is ({h}, {w}), not {variance.shape}")
+        out = np.empty((h, w, 3), dtype=np.float32)
+        vout = np.empty((h, w), dtype=np.float32) if variance is not None else None
+        m = np.empty((h, w), dtype=np.uint32) if mask else None
+        rm = np.empty((h, w, 3), dtype=np.float32) if removed else None
+        io = DespeckleIO(*(x.ctypes.data if x is not None else None for x in (rgb, out, variance, vout, m, rm)))
+        result = DespeckleResult()
+        self._check(self._L.pbrsi_despeckle(self._h, C.addressof(p), C.addressof(io), C.addressof(result)), "pbrsi_despeckle")
+        return tuple(x for x in (out, vout, m, rm) if x is not None) + (result,)
+
+    def despeckle_device(self, rgb_in_ptr, rgb_out_ptr, w, h, result_ptr=None, plane_ptrs=None, **params):
+        """despeckle() on caller-owned device memory: `plane_ptrs` = {name: pointer} of variance_in / variance_out (both or neither; they
+        may be one plane) / mask_out / removed_out, `result_ptr` receives the 16 bytes of DespeckleResult (None: not wanted).  Runs on the
+        context's stream behind whatever was queued there and does not wait: valid after `collect_stats()`."""
+        p = DespeckleParams.make(w, h, **params)
+        io = DespeckleIO(rgb_in_ptr, rgb_out_ptr)
+        for n, ptr in dict(plane_ptrs or {}).items():
+            if n not in ("variance_in", "variance_out", "mask_out", "removed_out"):
+                raise ValueError(f"unknown despeckle plane pointer {n!r}; known: variance_in, variance_out, mask_out, removed_out")
+            setattr(io, n, ptr)
+        self._check(self._L.pbrsi_despeckle_device(self._h, C.addressof(p), C.addressof(io), C.c_void_p(result_ptr)), "pbrsi_despeckle_device")
+
     def _render_guides_device(self, rgb_device_ptr, guide_device_ptrs, seed, camera=None):
         """The full-size first-hit guides of guided upsampling: a one-sample render of `seed` through the path integrator at depth 1 (the
         cheapest route whose first hits are the jittered ones the low-resolution AOVs average; the visualisers shoot through the
@@ -933,8 +970,12 @@ class Context:
         full-size one, the accumulated and the noisy ones stay low, `display` acts on the full-size image, and the stats gain
         "low_res", (wl, hl).  `reference` (a keyword taken out of `params`; the signature is the one callers know): None is that chain; an iterable of one (h, w, 3) image per frame at full size, or a single such
         array for every frame, queues compare_device of each frame's first image against it on the same stream (CompareParams' defaults)
-        and yields the CompareResult, read back behind the frame's one wait, as a fifth entry."""
-        reference = params.pop("reference", None)
+        and yields the CompareResult, read back behind the frame's one wait, as a fifth entry.  `despeckle` (a keyword taken out of
+        `params` likewise): None is that chain, with its allocations and tuples; True, or a dict of DespeckleParams.make's keywords, queues
+        despeckle_device on the frame's rendered image and its variance between the render and the accumulation, on the same stream, into
+        one more colour buffer and the variance in place: the accumulation then reads the despeckled colour, the stats gain "despeckle",
+        the DespeckleResult read back behind the frame's one wait, and the "noisy" image stays the render's own."""
+        reference, despeckle = params.pop("reference", None), params.pop("despeckle", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -945,7 +986,7 @@ class Context:
             _reference_frame(_reference_frames(reference), 0, self.scene.width, self.scene.height)
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display,
-                                         upscale, reference):
+                                         upscale, reference, despeckle):
             yield out[:4] if reference is None else out[:4] + out[5:]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
@@ -959,17 +1000,17 @@ class Context:
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
         are `spatial`, `display`, `upscale` (the motion vectors are then the low-resolution chain's) and the keyword `reference`, whose
-        CompareResult is the last entry."""
-        reference = params.pop("reference", None)
+        CompareResult is the last entry, and the keyword `despeckle`."""
+        reference, despeckle = params.pop("reference", None), params.pop("despeckle", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display,
-                                         upscale, reference):
+                                         upscale, reference, despeckle):
             yield (out[:5] if motion_vectors else out[:4]) + (() if reference is None else out[5:])
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None, display=None, upscale=None, reference=None):
+                         clip=None, display=None, upscale=None, reference=None, despeckle=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None, CompareResult or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  The options are checked here, before
@@ -984,6 +1025,7 @@ class Context:
         s.uparams = _upscale_params(upscale, guides)
         s.shown = "out" if s.uparams is None else "up"  # the buffer of a frame's first image
         s.reference, s.one_reference = _reference_frames(reference), isinstance(reference, np.ndarray)
+        s.despeckle = _despeckle_params(despeckle)
         dev = None
         try:
             cam_prev = scene_prev = None
@@ -1009,7 +1051,7 @@ class Context:
                     ref = _reference_frame(s.reference, i, s.fw, s.fh)
                 if dev is None:
                     dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None,
-                                                          s.reference is not None), "a temporal sequence")
+                                                          s.reference is not None, s.despeckle is not None), "a temporal sequence")
                 if ref is not None:
                     dev.upload("reference", ref)  # the frame before has been waited for: nothing reads the buffer
                 self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table)
@@ -1022,7 +1064,7 @@ class Context:
 
     def _queue_frame(self, s, dev, i, p, cam, cam_full, cam_prev, table):
         """Frame i of the sequence `s` on the context's stream, nothing waits: the render of `p` with its guides and its variance; the
-        accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
+        despeckle step, into a colour buffer of its own and in place on the variance; the accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
         on the accumulated variance; the filter; the full-size guides and the upsample; the display transform, whose exposure word is
         read from the second frame on and written by every one; the comparison of the frame's first image with its reference."""
         w, h, cur, old = s.w, s.h, i & 1, (i & 1) ^ 1
@@ -1031,7 +1073,12 @@ class Context:
         hist = [{n: dev.ptr(f"h_{n}{k}") for n in TEMPORAL_HISTORY} for k in (0, 1)]
         acc_variance = dev.ptr("acc_variance")
         self._render_var_device(dev, gp, p, cam)
-        self.temporal_accumulate_device({"rgb": dev.ptr("rgb"), "variance": dev.ptr(VARIANCE), **kept}, hist[cur], w, h, cam, hist[old] if i else None,
+        rgb = dev.ptr("rgb")
+        if s.despeckle is not None:
+            rgb = dev.ptr("despeckled")
+            self.despeckle_device(dev.ptr("rgb"), rgb, w, h, dev.ptr("despeckle"), {"variance_in": dev.ptr(VARIANCE), "variance_out": dev.ptr(VARIANCE)},
+                                  **s.despeckle)
+        self.temporal_accumulate_device({"rgb": rgb, "variance": dev.ptr(VARIANCE), **kept}, hist[cur], w, h, cam, hist[old] if i else None,
                                         {n: dev.ptr(f"{n}{old}") for n in s.kept} if i else None, cam_prev, acc_variance,
                                         motion=table if i else None, clip=s.clip, **s.tparams)
         if s.motion_vectors and i:
@@ -1058,6 +1105,8 @@ class Context:
             stats["exposure"] = dev.download("exposure", 1, np.float32, "a temporal sequence's display image")[0]
         if s.uparams is not None:
             stats["low_res"] = (w, h)
+        if s.despeckle is not None:
+            stats["despeckle"] = DespeckleResult.from_buffer_copy(dev.download("despeckle", C.sizeof(DespeckleResult), np.uint8, "a temporal sequence's despeckle record"))
         shapes = {s.shown: (h, w, 3) if s.uparams is None else (s.fh, s.fw, 3), f"h_rgb{i & 1}": (h, w, 3), "rgb": (h, w, 3)}
         shown, accumulated, noisy = (dev.download(n, shape, np.float32, "a temporal sequence's image") for n, shape in shapes.items())
         mv = None

@@ -74,5 +74,8 @@ Refusal check_upsample(const pbrs_upsample_params* p, const float* rgb_lo, const
 // pbrsx_compare* (host/arg_checks_compare.cpp, beside the filler pbrsx_compare_params_default).  `maps` and its pointers may be NULL;
 // `a` may be `b`.
 Refusal check_compare(const pbrs_compare_params* p, const float* a, const float* b, const pbrs_compare_maps* maps, const pbrs_compare_result* result);
+// pbrsi_despeckle* (host/arg_checks_despeckle.cpp, beside the filler pbrsi_despeckle_params_default).  The optional planes of `io`
+// may be NULL; the result, which may be NULL too, is not a plane and is not looked at.
+Refusal check_despeckle(const pbrs_despeckle_params* p, const pbrs_despeckle_io* io);
 
 }  // namespace pbrs

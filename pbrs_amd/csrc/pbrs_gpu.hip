@@ -39,6 +39,7 @@
 #include "device/display.h"
 #include "device/upsample.h"
 #include "device/compare.h"
+#include "device/despeckle.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -152,6 +153,12 @@ enum BufferId {
     // image comparison (pbrsx_compare, device/compare.h): the per-tile partial sums and the room k_compare_finish quarters them into (64 +
     // 16 B per tile), and the host variant's staging (the two images, the two maps, the 64-byte record, one after the other)
     BUF_COMPARE, BUF_COMPARE_STAGE,
+    // despeckle (pbrsi_despeckle, device/despeckle.h): the host variant's staging (the image, the variance, which is treated in place,
+    // the result, the mask, the removed energy and the 16-byte record, one after the other); the device variant needs nothing
+    BUF_DESPECKLE_STAGE,
+    // ... and the per-block counts k_despeckle_finish sums (8 B for each of kDespeckleMaxBlocks blocks), held only by a context that has
+    // asked a despeckle call for its record
+    BUF_DESPECKLE,
     N_BUFFERS
 };
 
@@ -1843,6 +1850,62 @@ int pbrsx_compare(pbrs_ctx* c, const pbrs_compare_params* p, const float* a_host
                   {nullptr, sizeof(pbrs_compare_result) / sizeof(uint32_t), result_host, nullptr, 1}};
     return run_staged(c, BUF_COMPARE_STAGE, "the comparison's staging", s, P, [&] {
         return compare_launch(c, *p, s[0].as<float>(), s[1].as<float>(), pbrs_compare_maps{s[2].as<float>(), s[3].as<float>()}, s[4].as<pbrs_compare_result>());
+    });
+}
+
+// ---- despeckle (include/pbrs_gpu.h, device/despeckle.h) ----
+static_assert(sizeof(pbrs_despeckle_params) == 32, "pbrs_despeckle_params is 32 B");
+static_assert(sizeof(pbrs_despeckle_result) == 16 && offsetof(pbrs_despeckle_result, n_repaired) == 4, "pbrs_despeckle_result is 16 B");
+static_assert(PBRS_DESPECKLE_MAX_RADIUS == 2u && PBRS_DESPECKLE_MAX_RANK == 4u, "kDespeckle holds every radius; k_despeckle keeps four taps");
+
+namespace {
+
+using DespeckleKernel = void (*)(DespeckleConst);
+// [radius - 1]
+constexpr DespeckleKernel kDespeckle[2] = {k_despeckle<1u>, k_despeckle<2u>};
+
+uint32_t despeckle_tiles(uint32_t extent) { return (extent + PBRS_DESPECKLE_TILE - 1u) / PBRS_DESPECKLE_TILE; }
+
+// The launches on the context's stream (arguments checked; device pointers, NULL for what is not wanted): the image kernel and, where
+// the record is wanted, the finish over the blocks' counts, whose scratch the first such call allocates.
+int despeckle_launch(pbrs_ctx* c, const pbrs_despeckle_params& p, const pbrs_despeckle_io& io, pbrs_despeckle_result* result) {
+    const uint32_t tiles_x = despeckle_tiles(p.w), n = tiles_x * despeckle_tiles(p.h);  // at most 2^28 pixels: at most 2^28 tiles
+    const uint32_t blocks = std::min(n, kDespeckleMaxBlocks);
+    uint32_t* block_counts = nullptr;
+    if (result) {
+        const int rc = c->buf[BUF_DESPECKLE].grow(c, 2 * sizeof(uint32_t) * kDespeckleMaxBlocks, "the despeckle blocks' counts");
+        if (rc) return rc;
+        block_counts = c->buf[BUF_DESPECKLE].as<uint32_t>();
+    }
+    const DespeckleConst k{p.w, p.h, tiles_x, n, p.rank, p.gain, p.floor, io.rgb_in, io.rgb_out, reinterpret_cast<const uint32_t*>(io.variance_in),
+                           reinterpret_cast<uint32_t*>(io.variance_out), io.mask_out, io.removed_out, block_counts};
+    hipLaunchKernelGGL(kDespeckle[p.radius - 1u], dim3(blocks), dim3(kDespeckleBlock), 0, c->stream, k);
+    HIPCHK(c, hipGetLastError());
+    if (result) {
+        hipLaunchKernelGGL(k_despeckle_finish, dim3(1), dim3(256), 0, c->stream, block_counts, blocks, result);
+        HIPCHK(c, hipGetLastError());
+    }
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrsi_despeckle_device(pbrs_ctx* c, const pbrs_despeckle_params* p, const pbrs_despeckle_io* io_device, pbrs_despeckle_result* result_device) {
+    const int rc = enter(c, check_despeckle(p, io_device));
+    if (rc) return rc;
+    return despeckle_launch(c, *p, *io_device, result_device);
+}
+
+int pbrsi_despeckle(pbrs_ctx* c, const pbrs_despeckle_params* p, const pbrs_despeckle_io* io_host, pbrs_despeckle_result* result_host) {
+    const int rc = enter(c, check_despeckle(p, io_host));
+    if (rc) return rc;
+    const pbrs_despeckle_io& io = *io_host;
+    const size_t P = (size_t)p->w * p->h;
+    Staged s[] = {{io.rgb_in, 3}, {io.variance_in, 1, io.variance_out}, {nullptr, 3, io.rgb_out}, {nullptr, 1, io.mask_out}, {nullptr, 3, io.removed_out},
+                  {nullptr, sizeof(pbrs_despeckle_result) / sizeof(uint32_t), result_host, nullptr, 1}};
+    return run_staged(c, BUF_DESPECKLE_STAGE, "the despeckle staging", s, P, [&] {
+        return despeckle_launch(c, *p, pbrs_despeckle_io{s[0].as<float>(), s[2].as<float>(), s[1].as<float>(), s[1].as<float>(), s[3].as<uint32_t>(), s[4].as<float>()},
+                                s[5].as<pbrs_despeckle_result>());
     });
 }
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]] [--display none|reinhard|aces [--encode sqrt|srgb] [--auto-exposure] [--exposure X]] [--compare-strata N]
+"""Renders a pbrt-v3 scene file on the GPU and writes an EXR (or PNG):  tools/render_pbrt.py scene.pbrt out.exr [msaa] [depth] [path|direct|materials|normals] [--aovs] [--pixel-filter] [--denoise [--denoise-iterations N] [--denoise-sigma c,n,d]] [--denoise-var [--denoise-sigma-luminance X]] [--matte instance|material [--matte-slots N] [--matte-select i,j,...]] [--passes] [--denoise-passes] [--frames N [--orbit DEG] [--temporal] [--spatial-variance] [--spin ID[,ID...] --spin-deg DEG] [--motion-vectors]] [--display none|reinhard|aces [--encode sqrt|srgb] [--auto-exposure] [--exposure X]] [--compare-strata N] [--despeckle [--despeckle-gain X] [--despeckle-rank K] [--despeckle-radius R]]
 
 --aovs: also writes the first-hit AOVs of the same samples (include/pbrs_gpu.h, pbrs_aov_buffers) beside the image, for a denoiser:
 <out>.albedo.exr, <out>.normal.exr and <out>.depth.exr (depth in all three channels; +inf where no sample hits).
@@ -49,7 +49,13 @@ to the low-resolution filter).  With --frames N --temporal the sequence itself r
 --compare-strata N (one image, not --frames): also renders a reference at N x N strata (seed 4242) and prints, as one JSON line, what the
 library's comparison (include/pbrs_gpu.h, pbrsx_compare; Context.compare's defaults) says of the produced image against it: mse, rel_mse,
 mae, ssim, max_abs, psnr_db and the counts, under "image", and likewise under "upscaled", "denoised" and "denoised_var" where those are
-produced."""
+produced.
+--despeckle [--despeckle-gain X] [--despeckle-rank K] [--despeckle-radius R]: fireflies clamped to X (>= 1, default 2) times the K-th
+brightest (1 .. 4, default 2) of the neighbours within R pixels (1 .. 2, default 1) and non-finite pixels rebuilt from their neighbours
+(include/pbrs_gpu.h, pbrsi_despeckle; the flag itself takes no value): also writes <out>.despeckled.<ext> and prints how many pixels were clamped and
+repaired and the mean energy removed; with --denoise-var also <out>.despeckled_denoised_var.<ext>, the filter behind the step on the
+despeckled image and variance.  With --frames N --temporal every frame is despeckled between its render and the accumulation
+(render_temporal's despeckle=).  --compare-strata scores "despeckled" and "despeckled_denoised_var" as well."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -73,7 +79,11 @@ denoise_params, denoise_var_params = {}, {}
 matte_key, matte_slots, matte_select = None, 6, None
 frames, orbit = 0, 0.0
 compare_strata = 0
-for flag in ("--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+despeckle = None  # DespeckleParams.make's keywords
+if "--despeckle" in sys.argv:  # takes no value: a number behind it would be indistinguishable from msaa and depth
+    sys.argv.remove("--despeckle")
+    despeckle = {}
+for flag in ("--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -82,6 +92,10 @@ for flag in ("--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", 
             frames = int(value)
         elif flag == "--compare-strata":
             compare_strata = int(value)
+        elif flag in ("--despeckle-gain", "--despeckle-rank", "--despeckle-radius"):
+            if despeckle is None:
+                sys.exit("--despeckle-gain, --despeckle-rank and --despeckle-radius go with --despeckle")
+            despeckle[flag[len("--despeckle-"):]] = float(value) if flag == "--despeckle-gain" else int(value)
         elif flag == "--orbit":
             orbit = float(value)
         elif flag == "--spin":
@@ -191,13 +205,16 @@ if frames:
         sys.exit("with --frames N, --display goes with --temporal")
     if upscale is not None and not temporal:
         sys.exit("with --frames N, --upscale goes with --temporal")
+    if despeckle is not None and not temporal:
+        sys.exit("with --frames N, --despeckle goes with --temporal")
+    extra = {} if despeckle is None else {"despeckle": despeckle}  # (a keyword of the sequences only when asked for)
     spatial = True if spatial_variance else None
     if spin or motion_vectors:
         sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
-                                        spatial=spatial, clip=history_clip, display=display, upscale=upscale, **denoise_var_params)
+                                        spatial=spatial, clip=history_clip, display=display, upscale=upscale, **extra, **denoise_var_params)
     elif temporal:
         sequence = ctx.render_temporal(cams, msaa, msaa, depth, range(1, frames + 1), spatial=spatial, clip=history_clip, display=display,
-                                       upscale=upscale, **denoise_var_params)
+                                       upscale=upscale, **extra, **denoise_var_params)
     else:
         sequence = ((ctx.render_aovs(msaa, msaa, depth, 1 + k, aovs=(), camera=cam)[0],) for k, cam in enumerate(cams))
     for k, images in enumerate(sequence):
@@ -259,6 +276,16 @@ if denoise_var:
     scored["denoised_var"] = ctx.denoise_var(img, buf["variance"], **{n: buf[n] for n in guides}, **denoise_var_params)
     pbrs_amd.write_image(f"{stem}.denoised_var{ext}", scored["denoised_var"])
     print(f"-> {stem}.denoised_var{ext}")
+if despeckle is not None:
+    variance = buf["variance"] if denoise_var else None
+    clean = ctx.despeckle(img, variance, removed=True, **despeckle)
+    scored["despeckled"] = clean[0]
+    pbrs_amd.write_image(f"{stem}.despeckled{ext}", clean[0])
+    print(f"-> {stem}.despeckled{ext} ({clean[-1].n_clamped} pixels clamped, {clean[-1].n_repaired} repaired, mean energy removed {float(clean[-2].mean()):.4g})")
+    if denoise_var:
+        scored["despeckled_denoised_var"] = ctx.denoise_var(clean[0], clean[1], **{n: buf[n] for n in guides}, **denoise_var_params)
+        pbrs_amd.write_image(f"{stem}.despeckled_denoised_var{ext}", scored["despeckled_denoised_var"])
+        print(f"-> {stem}.despeckled_denoised_var{ext}")
 if passes:
     for name in ("direct", "indirect"):
         pbrs_amd.write_image(f"{stem}.{name}.exr", layers[name])
