@@ -133,6 +133,11 @@ def test_random_scene_matches_oracle(gpu_ctx, seed):
         nan = np.isnan(ref)
         assert (nan == np.isnan(img)).all(), (seed, integrator)
         assert (img.view(np.uint32)[~nan] == ref.view(np.uint32)[~nan]).all(), (seed, integrator)
+        # ... and through the shipped kernels (counters=True runs the instrumented ones), the scenes with a ParallelQuad included
+        img, st = gpu_ctx.render(2, 2, depth, 11 + seed, integrator=integrator, counters=False)
+        assert st["invalid_samples"] == ost["nonfinite_samples"], (seed, integrator, "shipped")
+        assert (nan == np.isnan(img)).all(), (seed, integrator, "shipped")
+        assert (img.view(np.uint32)[~nan] == ref.view(np.uint32)[~nan]).all(), (seed, integrator, "shipped")
 
 
 def takes_the_exact_extent_walk(sb):
@@ -295,6 +300,10 @@ def test_random_scene_with_fourier_materials_matches_oracle(gpu_ctx, seed):
         nan = np.isnan(ref)
         assert (nan == np.isnan(img)).all(), (seed, integrator)
         assert (img.view(np.uint32)[~nan] == ref.view(np.uint32)[~nan]).all(), (seed, integrator)
+        img, st = gpu_ctx.render(2, 2, depth, 3 + seed, integrator=integrator, counters=False)  # the shipped kernels
+        assert st["invalid_samples"] == ost["nonfinite_samples"], (seed, integrator, "shipped")
+        assert (nan == np.isnan(img)).all(), (seed, integrator, "shipped")
+        assert (img.view(np.uint32)[~nan] == ref.view(np.uint32)[~nan]).all(), (seed, integrator, "shipped")
 
 
 def test_no_random_scene_was_skipped():
