@@ -1267,6 +1267,65 @@ void pbrsi_despeckle_params_default(uint32_t w, uint32_t h, pbrs_despeckle_param
 int pbrsi_despeckle(pbrs_ctx*, const pbrs_despeckle_params*, const pbrs_despeckle_io* io_host, pbrs_despeckle_result* result_host);
 int pbrsi_despeckle_device(pbrs_ctx*, const pbrs_despeckle_params*, const pbrs_despeckle_io* io_device, pbrs_despeckle_result* result_device);
 
+/* ---- bloom ------------------------------------------------------------------------------------------------------- */
+/* Glare, the step between the filter and the display transform: part of a bright pixel's energy is spread over its surround, on linear
+ * radiance, before the tone curve clamps it to white.  The bright part of the image goes down a pyramid of half-size levels, comes back
+ * up with each coarser level mixed into the finer one, and is added to (or mixed into) the image.  An image operation like
+ * pbrs_denoise: it needs a context (device, stream) and no uploaded scene.  rgb and rgb_out are w * h pixels, row-major, 3 floats each.
+ * All arithmetic is f32 without fused multiply-add, in the order written; divisions are correctly rounded; pn_* is
+ * include/pbrs_numeric.h; lum(c) = (0.21267127f * c.r + 0.71515972f * c.g) + 0.07216883f * c.b, the variance AOV's.  No sum here
+ * depends on the launch shape or on arrival order: a CPU model of this text gives the same bytes.
+ *   1. Level sizes.  w_0 = (w + 1) / 2, h_0 = (h + 1) / 2; w_{l+1} = (w_l + 1) / 2 and likewise h (integer divisions).  The effective level
+ *      count N is `levels`, cut at the first level that is 1 x 1: that level is the last one.
+ *   2. Bright pass, applied to a pixel of rgb as the first downsample reads it.  A pixel with a channel that does not pass pn_isfinite
+ *      gives (+0, +0, +0).  Otherwise, per channel, c = c > 0 ? c : +0; then Y = lum(c), t = threshold, k = threshold * knee:
+ *      Y <= t - k gives f = +0; otherwise Y >= t + k gives f = (Y - t) / Y; otherwise s = (Y - t) + k and
+ *      f = ((s * s) * (1.0f / (4.0f * k))) / Y.  bright.c = c.c * f.  With threshold 0, f is exactly 1 for every Y > 0.
+ *   3. Downsample: rgb to level 0 through the bright pass, then level l to level l + 1.  Destination (X, Y) sums the source at
+ *      (2X + dx, 2Y + dy) for dy = -1 .. 2 (outer) and dx = -1 .. 2 (inner), coordinates clamped to the source's edge, with the weight
+ *      K[dx + 1] * K[dy + 1], K = {0.125f, 0.375f, 0.375f, 0.125f} (every product is exact).  Per channel acc = acc + weight * c, in
+ *      that order, from +0.  There is no division.  This gives d_l.
+ *   4. Upsample and merge, from the coarsest level down: u_{N-1} = d_{N-1}; for l = N-2 .. 0,
+ *      u_l(p).c = d_l(p).c + spread * (up(u_{l+1})(p).c - d_l(p).c).  up(v)(x, y) reads v at X0 = x >> 1 and
+ *      X1 = X0 + ((x & 1) ? 1 : -1) clamped to v's edge, with the weights 0.75f and 0.25f, and y likewise; the four products wx * wy
+ *      are exact, and acc = acc + (wx * wy) * v(X, Y).c over (X0, Y0), (X1, Y0), (X0, Y1), (X1, Y1), from +0.
+ *   5. Composite, at full size: B(p) = up(u_0)(p).  Without PBRS_BLOOM_MIX out.c = rgb.c + strength * B.c; with it
+ *      out.c = rgb.c + strength * (B.c - rgb.c), the energy-conserving glare (use it with threshold 0; strength is then <= 1).  A
+ *      pixel of rgb with a channel that does not pass pn_isfinite passes through with its bits; it has entered the pyramid as +0, so
+ *      no neighbour becomes non-finite by it.  strength == 0 returns rgb's bits: a copy, or nothing where rgb_out == rgb.
+ * Scale rule.  With rgb and threshold both times 2^j the output is 2^j times the output, bit for bit, while nothing that depends on
+ * the scale overflows or becomes a nonzero value below the smallest normal f32.
+ * Fixed point.  A constant image of the finite value v > 0 in every channel is its own bloom under PBRS_BLOOM_MIX with threshold 0
+ * wherever 0.375f * v and every partial sum of steps 3 and 4 are exact.  The partial sums are multiples k / 64 of v, k <= 64 (seven
+ * bits), so a v with at most 17 significant bits, away from the ends of the exponent range, qualifies (0.75f is one).  Every level is
+ * then v, B is v, and v + strength * (v - v) is v.
+ * Pointers are host memory for pbrsb_bloom, which stages the image on first use (12 B per pixel; the result lands in the staged
+ * input's place) and synchronises before it returns; device memory for pbrsb_bloom_device, which runs on the context's stream
+ * (pbrs_set_stream honoured) and does not wait.  rgb_out may equal rgb: the one kernel that writes out(p) reads rgb only at p, after
+ * the pyramid has been built.  The first call allocates the pyramid, one chain of levels of 16 B per level pixel (r, g, b and a pad):
+ * the levels hold a third of the image's pixels (a little more where a size is odd), 5.4 B per image pixel.  A larger image grows it,
+ * pbrs_destroy frees it, and a context that never calls this (or only with strength 0) allocates nothing.
+ * Refused with PBRS_E_INVALID (the context stays usable): NULL params, rgb or rgb_out; w or h 0; levels 0 or above
+ * PBRS_BLOOM_MAX_LEVELS; unknown flag bits; threshold not finite or < 0; knee not finite or outside [0, 1]; strength not finite or
+ * < 0; spread not finite or outside [0, 1]; PBRS_BLOOM_MIX with strength > 1.  w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_BLOOM_MAX_LEVELS 8u
+#define PBRS_BLOOM_MIX 1u
+typedef struct pbrs_bloom_params {
+    uint32_t w, h;   /* image size */
+    uint32_t levels; /* 1 .. PBRS_BLOOM_MAX_LEVELS */
+    uint32_t flags;  /* PBRS_BLOOM_MIX */
+    float threshold; /* finite, >= 0: luminance above which a pixel blooms; 0 = the whole image */
+    float knee;      /* finite, in [0, 1]: soft knee as a fraction of threshold */
+    float strength;  /* finite, >= 0 (<= 1 with PBRS_BLOOM_MIX) */
+    float spread;    /* finite, in [0, 1]: how much of each coarser level reaches the finer one */
+} pbrs_bloom_params; /* 32 B */
+/* (The three functions' prefix is pbrsb_; the struct and the constants above carry pbrs_.)
+ * Filler: levels 6, flags 0, threshold 1, knee 0.5, strength 0.05, spread 0.6 (choices, not measurements); `out` NULL does nothing.
+ * Host code: needs no context. */
+void pbrsb_bloom_params_default(uint32_t w, uint32_t h, pbrs_bloom_params* out);
+int pbrsb_bloom(pbrs_ctx*, const pbrs_bloom_params*, const float* rgb_host, float* rgb_out_host);
+int pbrsb_bloom_device(pbrs_ctx*, const pbrs_bloom_params*, const float* rgb_device, float* rgb_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -547,6 +547,39 @@ def _despeckle_params(despeckle):
     return dp
 
 
+class BloomParams(C.Structure):
+    """pbrs_bloom_params (include/pbrs_gpu.h, "bloom"): image size, the pyramid's levels, the bright pass's threshold and soft knee, the
+    strength of the composite and how much of each coarser level reaches the finer one."""
+    MIX = 1  # flags: out = rgb + strength * (B - rgb)
+    MAX_LEVELS = 8
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("levels", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_float), ("knee", C.c_float),
+                ("strength", C.c_float), ("spread", C.c_float)]
+
+    @classmethod
+    def make(cls, w, h, levels=6, threshold=1.0, knee=0.5, strength=0.05, spread=0.6, mix=False):
+        """The defaults are pbrsb_bloom_params_default's."""
+        p = cls()
+        p.w, p.h = w, h
+        p.levels, p.flags = levels, cls.MIX if mix else 0
+        p.threshold, p.knee, p.strength, p.spread = threshold, knee, strength, spread
+        return p
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _bloom_params(bloom):
+    """render_temporal's / render_animation's `bloom` -> BloomParams.make's keywords, or None: None or False is the sequence without the
+    step, True the defaults, a dict the keywords.  An unknown keyword fails here."""
+    if bloom is None or bloom is False:
+        return None
+    if bloom is not True and not isinstance(bloom, dict):
+        raise ValueError("bloom is None, True or a dict of BloomParams.make's keywords")
+    bp = {} if bloom is True else dict(bloom)
+    BloomParams.make(1, 1, **bp)
+    return bp
+
+
 class SpatialVarianceGuides(C.Structure):
     """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]

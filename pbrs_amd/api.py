@@ -13,14 +13,14 @@ from types import SimpleNamespace
 import numpy as np
 
 from .abi import (AOV_NAMES, AOVS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
-                  SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, Camera, CompareMaps, CompareParams, CompareResult,
+                  SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, BloomParams, Camera, CompareMaps, CompareParams, CompareResult,
                   DenoiseGuides, DenoiseParams, DespeckleIO, DespeckleParams, DespeckleResult,
                   DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
                   PixelFilter, RenderParams, SceneDesc, SpatialVarianceGuides, SpatialVarianceParams, Stats, TemporalFrame, TemporalGuides, TemporalHistory,
-                  TemporalParams, UpsampleParams, _aov_names, _DenoiseParamsMixin, _despeckle_params, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
+                  TemporalParams, UpsampleParams, _aov_names, _bloom_params, _DenoiseParamsMixin, _despeckle_params, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
                   _reference_frame, _reference_frames, _temporal_struct, _upscale_params, scaled_camera)
 from .devmem import DeviceBuffers
-from .libs import GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
 from .spec import SceneSpec  # noqa: F401
 
 
@@ -71,7 +71,7 @@ def _guide_bytes(guides, w, h, suffix=""):
     return {n + suffix: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}
 
 
-def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False):
+def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False, bloom=False):
     """{name: bytes} of the device buffers of a frame sequence (Context._temporal_frames) that runs at w x h and shows fw x fh: the
     frame's image, the filtered one, the two variances; two ping-pong halves ("0", "1") of the guides the next frame is tested against
     and of the history; the other guides once; and what each option that is on adds."""
@@ -92,6 +92,8 @@ def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, re
         sizes["reference"], sizes["compare"] = 3 * fw * fh * 4, C.sizeof(CompareResult)
     if despeckle:
         sizes["despeckled"], sizes["despeckle"] = 3 * w * h * 4, C.sizeof(DespeckleResult)
+    if bloom:
+        sizes["bloom"] = 3 * fw * fh * 4
     return sizes
 
 
@@ -892,6 +894,25 @@ class Context:
             setattr(io, n, ptr)
         self._check(self._L.pbrsi_despeckle_device(self._h, C.addressof(p), C.addressof(io), C.c_void_p(result_ptr)), "pbrsi_despeckle_device")
 
+    def bloom(self, rgb, **params):
+        """The (h, w, 3) f32 image `rgb` with its glare (include/pbrs_gpu.h, pbrsb_bloom): the bright part of the image down a pyramid
+        of half-size levels, back up, and added to (mix=True: mixed into) the image -> the (h, w, 3) f32 image.  params: BloomParams.make's
+        keywords."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"the image is (h, w, 3), not {rgb.shape}")
+        h, w, _ = rgb.shape
+        p = BloomParams.make(w, h, **params)
+        out = np.empty((h, w, 3), dtype=np.float32)
+        self._check(self._L.pbrsb_bloom(self._h, C.addressof(p), rgb.ctypes.data, out.ctypes.data), "pbrsb_bloom")
+        return out
+
+    def bloom_device(self, src_ptr, dst_ptr, w, h, **params):
+        """bloom() on caller-owned device memory, (h, w, 3) f32 each; `dst_ptr` may be `src_ptr`.  Runs on the context's stream behind
+        whatever was queued there and does not wait: valid after `collect_stats()`."""
+        p = BloomParams.make(w, h, **params)
+        self._check(self._L.pbrsb_bloom_device(self._h, C.addressof(p), C.c_void_p(src_ptr), C.c_void_p(dst_ptr)), "pbrsb_bloom_device")
+
     def _render_guides_device(self, rgb_device_ptr, guide_device_ptrs, seed, camera=None):
         """The full-size first-hit guides of guided upsampling: a one-sample render of `seed` through the path integrator at depth 1 (the
         cheapest route whose first hits are the jittered ones the low-resolution AOVs average; the visualisers shoot through the
@@ -974,8 +995,12 @@ class Context:
         `params` likewise): None is that chain, with its allocations and tuples; True, or a dict of DespeckleParams.make's keywords, queues
         despeckle_device on the frame's rendered image and its variance between the render and the accumulation, on the same stream, into
         one more colour buffer and the variance in place: the accumulation then reads the despeckled colour, the stats gain "despeckle",
-        the DespeckleResult read back behind the frame's one wait, and the "noisy" image stays the render's own."""
-        reference, despeckle = params.pop("reference", None), params.pop("despeckle", None)
+        the DespeckleResult read back behind the frame's one wait, and the "noisy" image stays the render's own.  `bloom` (a keyword
+        taken out of `params` likewise): None is that chain, with its allocations and tuples; True, or a dict of BloomParams.make's
+        keywords, queues bloom_device on the frame's first image (the full-size one with `upscale`) behind the filter, on the same stream,
+        into one more colour buffer: `display` then reads the bloomed image, `reference` keeps scoring the first image as it was, and
+        the stats gain "bloom", the (h, w, 3) f32 bloomed image."""
+        reference, despeckle, bloom = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -986,7 +1011,7 @@ class Context:
             _reference_frame(_reference_frames(reference), 0, self.scene.width, self.scene.height)
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display,
-                                         upscale, reference, despeckle):
+                                         upscale, reference, despeckle, bloom):
             yield out[:4] if reference is None else out[:4] + out[5:]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
@@ -1000,17 +1025,17 @@ class Context:
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
         are `spatial`, `display`, `upscale` (the motion vectors are then the low-resolution chain's) and the keyword `reference`, whose
-        CompareResult is the last entry, and the keyword `despeckle`."""
-        reference, despeckle = params.pop("reference", None), params.pop("despeckle", None)
+        CompareResult is the last entry, and the keywords `despeckle` and `bloom`."""
+        reference, despeckle, bloom = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display,
-                                         upscale, reference, despeckle):
+                                         upscale, reference, despeckle, bloom):
             yield (out[:5] if motion_vectors else out[:4]) + (() if reference is None else out[5:])
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None, display=None, upscale=None, reference=None, despeckle=None):
+                         clip=None, display=None, upscale=None, reference=None, despeckle=None, bloom=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None, CompareResult or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  The options are checked here, before
@@ -1026,6 +1051,7 @@ class Context:
         s.shown = "out" if s.uparams is None else "up"  # the buffer of a frame's first image
         s.reference, s.one_reference = _reference_frames(reference), isinstance(reference, np.ndarray)
         s.despeckle = _despeckle_params(despeckle)
+        s.bloom = _bloom_params(bloom)
         dev = None
         try:
             cam_prev = scene_prev = None
@@ -1051,7 +1077,7 @@ class Context:
                     ref = _reference_frame(s.reference, i, s.fw, s.fh)
                 if dev is None:
                     dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None,
-                                                          s.reference is not None, s.despeckle is not None), "a temporal sequence")
+                                                          s.reference is not None, s.despeckle is not None, s.bloom is not None), "a temporal sequence")
                 if ref is not None:
                     dev.upload("reference", ref)  # the frame before has been waited for: nothing reads the buffer
                 self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table)
@@ -1065,7 +1091,8 @@ class Context:
     def _queue_frame(self, s, dev, i, p, cam, cam_full, cam_prev, table):
         """Frame i of the sequence `s` on the context's stream, nothing waits: the render of `p` with its guides and its variance; the
         despeckle step, into a colour buffer of its own and in place on the variance; the accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
-        on the accumulated variance; the filter; the full-size guides and the upsample; the display transform, whose exposure word is
+        on the accumulated variance; the filter; the full-size guides and the upsample; the bloom of the frame's first image, into a colour
+        buffer of its own, which the display transform then reads; the display transform, whose exposure word is
         read from the second frame on and written by every one; the comparison of the frame's first image with its reference."""
         w, h, cur, old = s.w, s.h, i & 1, (i & 1) ^ 1
         gp = {n: dev.ptr(f"{n}{cur}" if n in s.kept else n) for n in s.guides}
@@ -1089,8 +1116,10 @@ class Context:
         self.denoise_var_device(hist[cur]["rgb"], dev.ptr("out"), w, h, acc_variance, gp, **s.params)
         if s.uparams is not None:
             self._upsample_out_device(dev, gp, s.guides, p.seed, s.fw, s.fh, *s.uparams, camera=cam_full)
+        if s.bloom is not None:
+            self.bloom_device(dev.ptr(s.shown), dev.ptr("bloom"), s.fw, s.fh, **s.bloom)
         if s.dparams is not None:
-            self.display_device(dev.ptr(s.shown), dev.ptr("display"), s.fw, s.fh,
+            self.display_device(dev.ptr(s.shown if s.bloom is None else "bloom"), dev.ptr("display"), s.fw, s.fh,
                                 {"exposure_in": dev.ptr("exposure") if i else None, "exposure_out": dev.ptr("exposure")}, **s.dparams)
         if s.reference is not None:
             self.compare_device(dev.ptr(s.shown), dev.ptr("reference"), s.fw, s.fh, dev.ptr("compare"))
@@ -1107,6 +1136,8 @@ class Context:
             stats["low_res"] = (w, h)
         if s.despeckle is not None:
             stats["despeckle"] = DespeckleResult.from_buffer_copy(dev.download("despeckle", C.sizeof(DespeckleResult), np.uint8, "a temporal sequence's despeckle record"))
+        if s.bloom is not None:
+            stats["bloom"] = dev.download("bloom", (s.fh, s.fw, 3), np.float32, "a temporal sequence's bloomed image")
         shapes = {s.shown: (h, w, 3) if s.uparams is None else (s.fh, s.fw, 3), f"h_rgb{i & 1}": (h, w, 3), "rgb": (h, w, 3)}
         shown, accumulated, noisy = (dev.download(n, shape, np.float32, "a temporal sequence's image") for n, shape in shapes.items())
         mv = None

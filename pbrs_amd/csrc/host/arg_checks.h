@@ -77,5 +77,7 @@ Refusal check_compare(const pbrs_compare_params* p, const float* a, const float*
 // pbrsi_despeckle* (host/arg_checks_despeckle.cpp, beside the filler pbrsi_despeckle_params_default).  The optional planes of `io`
 // may be NULL; the result, which may be NULL too, is not a plane and is not looked at.
 Refusal check_despeckle(const pbrs_despeckle_params* p, const pbrs_despeckle_io* io);
+// pbrsb_bloom* (host/arg_checks_bloom.cpp, beside the filler pbrsb_bloom_params_default).  `rgb_out` may be `rgb`.
+Refusal check_bloom(const pbrs_bloom_params* p, const float* rgb, const float* rgb_out);
 
 }  // namespace pbrs

@@ -40,6 +40,7 @@
 #include "device/upsample.h"
 #include "device/compare.h"
 #include "device/despeckle.h"
+#include "device/bloom.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -159,6 +160,9 @@ enum BufferId {
     // ... and the per-block counts k_despeckle_finish sums (8 B for each of kDespeckleMaxBlocks blocks), held only by a context that has
     // asked a despeckle call for its record
     BUF_DESPECKLE,
+    // bloom (pbrsb_bloom, device/bloom.h): the pyramid, one chain of levels of a float4 per level pixel, held only by a context that has
+    // called it with a strength above 0; and the host variant's staging (the image, which the result replaces)
+    BUF_BLOOM, BUF_BLOOM_STAGE,
     N_BUFFERS
 };
 
@@ -1907,6 +1911,95 @@ int pbrsi_despeckle(pbrs_ctx* c, const pbrs_despeckle_params* p, const pbrs_desp
         return despeckle_launch(c, *p, pbrs_despeckle_io{s[0].as<float>(), s[2].as<float>(), s[1].as<float>(), s[1].as<float>(), s[3].as<uint32_t>(), s[4].as<float>()},
                                 s[5].as<pbrs_despeckle_result>());
     });
+}
+
+// ---- bloom (include/pbrs_gpu.h, device/bloom.h) ----
+static_assert(sizeof(pbrs_bloom_params) == 32 && offsetof(pbrs_bloom_params, threshold) == 16, "pbrs_bloom_params is 32 B");
+
+namespace {
+
+using BloomDownKernel = void (*)(BloomDown);
+using BloomCompositeKernel = void (*)(BloomComposite);
+// a level's source; the image through a scalar path; the image through 16-byte loads
+constexpr BloomDownKernel kBloomDown[3] = {k_bloom_down<false, false>, k_bloom_down<true, false>, k_bloom_down<true, true>};
+// [PBRS_BLOOM_MIX][both planes 16-byte aligned]
+constexpr BloomCompositeKernel kBloomComposite[2][2] = {{k_bloom_composite<false, false>, k_bloom_composite<false, true>},
+                                                        {k_bloom_composite<true, false>, k_bloom_composite<true, true>}};
+
+// The launches on the context's stream (arguments checked; device pointers).  PBRS_BLOOM_NO_TAIL (a developer build's define, for
+// tools/bloom_cost.py) takes every level through k_bloom_down and k_bloom_up; the bits are the same.
+int bloom_launch(pbrs_ctx* c, const pbrs_bloom_params& p, const float* rgb, float* out) {
+    const size_t P = (size_t)p.w * p.h;
+    if (p.strength == 0.0f) {  // the input's bits
+        if (out != rgb) HIPCHK(c, hipMemcpyAsync(out, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        return PBRS_OK;
+    }
+    uint32_t lw[PBRS_BLOOM_MAX_LEVELS], lh[PBRS_BLOOM_MAX_LEVELS];
+    size_t first[PBRS_BLOOM_MAX_LEVELS + 1];  // a level's first pixel in the chain; [N]: the chain's pixels
+    uint32_t N = 0;
+    first[0] = 0;
+    for (uint32_t w = p.w, h = p.h; N < p.levels;) {
+        w = (w + 1u) / 2u, h = (h + 1u) / 2u;
+        lw[N] = w, lh[N] = h;
+        first[N + 1] = first[N] + (size_t)w * h;
+        ++N;
+        if (w == 1u && h == 1u) break;
+    }
+    const int rc = c->buf[BUF_BLOOM].grow(c, first[N] * sizeof(float4), "the bloom pyramid");
+    if (rc) return rc;
+    float4* const chain = c->buf[BUF_BLOOM].as<float4>();
+    // the level at which k_bloom_tail takes over: the first one that fits its LDS with every level below it; N - 1 where it would have
+    // nothing to do (the last level is its own u)
+    uint32_t T = 0;
+#ifdef PBRS_BLOOM_NO_TAIL
+    T = N - 1u;
+#else
+    while (T < N - 1u && first[N] - first[T] > kBloomTailPixels) ++T;
+#endif
+    const float k = p.threshold * p.knee;
+    BloomDown d{};
+    d.bright = BloomBright{p.threshold, k, p.threshold - k, p.threshold + k, 1.0f / (4.0f * k)};
+    for (uint32_t l = 0; l <= T; ++l) {
+        d.rgb = l ? nullptr : rgb, d.src = l ? chain + first[l - 1] : nullptr, d.dst = chain + first[l];
+        d.sw = l ? lw[l - 1] : p.w, d.sh = l ? lh[l - 1] : p.h, d.dw = lw[l], d.dh = lh[l];
+        d.tiles_x = (d.dw + kBloomTile - 1u) / kBloomTile;
+        const uint32_t tiles = d.tiles_x * ((d.dh + kBloomTile - 1u) / kBloomTile);  // at most 2^26 pixels: at most 2^26 tiles
+        const bool aligned = (reinterpret_cast<uintptr_t>(rgb) & 15u) == 0;
+        hipLaunchKernelGGL(kBloomDown[l ? 0 : (aligned ? 2 : 1)], dim3(tiles), dim3(kBloomBlock), 0, c->stream, d);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (T < N - 1u) {
+        hipLaunchKernelGGL(k_bloom_tail, dim3(1), dim3(kBloomTailBlock), 0, c->stream, BloomTail{chain + first[T], lw[T], lh[T], N - T, p.spread});
+        HIPCHK(c, hipGetLastError());
+    }
+    for (uint32_t l = T; l-- > 0;) {
+        const uint32_t n = lw[l] * lh[l];
+        hipLaunchKernelGGL(k_bloom_up, dim3((n + kBloomBlock - 1u) / kBloomBlock), dim3(kBloomBlock), 0, c->stream,
+                           BloomUp{chain + first[l + 1], chain + first[l], lw[l + 1], lh[l + 1], lw[l], lh[l], p.spread});
+        HIPCHK(c, hipGetLastError());
+    }
+    const BloomComposite b{rgb, out, chain, p.w, (uint32_t)P, lw[0], lh[0], p.strength};
+    const bool aligned = ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+    const bool mix = (p.flags & PBRS_BLOOM_MIX) != 0;
+    const uint32_t groups = (uint32_t)((P + 3u) / 4u);
+    hipLaunchKernelGGL(kBloomComposite[mix][aligned], dim3((groups + kBloomBlock - 1u) / kBloomBlock), dim3(kBloomBlock), 0, c->stream, b);
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrsb_bloom_device(pbrs_ctx* c, const pbrs_bloom_params* p, const float* rgb_device, float* rgb_out_device) {
+    const int rc = enter(c, check_bloom(p, rgb_device, rgb_out_device));
+    if (rc) return rc;
+    return bloom_launch(c, *p, rgb_device, rgb_out_device);
+}
+
+int pbrsb_bloom(pbrs_ctx* c, const pbrs_bloom_params* p, const float* rgb_host, float* rgb_out_host) {
+    const int rc = enter(c, check_bloom(p, rgb_host, rgb_out_host));
+    if (rc) return rc;
+    Staged s[] = {{rgb_host, 3, rgb_out_host}};  // in place on the staged image
+    return run_staged(c, BUF_BLOOM_STAGE, "the bloom staging", s, (size_t)p->w * p->h, [&] { return bloom_launch(c, *p, s[0].as<float>(), s[0].as<float>()); });
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {

@@ -72,6 +72,12 @@ GPU_DESPECKLE_FUNCTIONS = _table({
 }, with_device={
     "pbrsi_despeckle": [P] * 4,
 })
+# The bloom call's entry points (include/pbrs_gpu.h, "bloom"), likewise, under the prefix pbrsb_.
+GPU_BLOOM_FUNCTIONS = _table({
+    "pbrsb_bloom_params_default": ([U32, U32, P], None),
+}, with_device={
+    "pbrsb_bloom": [P] * 4,
+})
 HOST_FUNCTIONS = _table({
     "pbrs_host_scene_build": [P, C.POINTER(P)],
     "pbrs_host_scene_free": [P],
@@ -92,6 +98,7 @@ HOST_FUNCTIONS = _table({
 GPU_SYMBOLS, HOST_SYMBOLS = list(GPU_FUNCTIONS), list(HOST_FUNCTIONS)
 GPU_COMPARE_SYMBOLS = list(GPU_COMPARE_FUNCTIONS)
 GPU_DESPECKLE_SYMBOLS = list(GPU_DESPECKLE_FUNCTIONS)
+GPU_BLOOM_SYMBOLS = list(GPU_BLOOM_FUNCTIONS)
 _host = _gpu = _hip = None
 
 
@@ -126,7 +133,7 @@ def gpu_lib():
         path = os.environ.get("PBRS_GPU_LIB") or lib_paths()[1]
         if not os.path.exists(path):
             raise PbrsError(f"{path} is missing: the HIP extension must be built (make -C pbrs_amd/csrc); there is no CPU fallback")
-        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS})
+        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS, **GPU_BLOOM_FUNCTIONS})
     return _gpu
 
 

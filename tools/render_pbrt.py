@@ -55,7 +55,12 @@ brightest (1 .. 4, default 2) of the neighbours within R pixels (1 .. 2, default
 (include/pbrs_gpu.h, pbrsi_despeckle; the flag itself takes no value): also writes <out>.despeckled.<ext> and prints how many pixels were clamped and
 repaired and the mean energy removed; with --denoise-var also <out>.despeckled_denoised_var.<ext>, the filter behind the step on the
 despeckled image and variance.  With --frames N --temporal every frame is despeckled between its render and the accumulation
-(render_temporal's despeckle=).  --compare-strata scores "despeckled" and "despeckled_denoised_var" as well."""
+(render_temporal's despeckle=).  --compare-strata scores "despeckled" and "despeckled_denoised_var" as well.
+--bloom [--bloom-threshold T] [--bloom-strength S] [--bloom-levels N] [--bloom-mix]: glare on linear radiance (include/pbrs_gpu.h,
+pbrsb_bloom; the flag itself takes no value): the part of the image above the luminance T (default 1; 0 = the whole image) goes down a
+pyramid of N levels (1 .. 8, default 6), comes back up and is added to the image S times (default 0.05), or mixed into it
+(--bloom-mix: out = rgb + S (B - rgb), for T = 0 and S <= 1): also writes <out>.bloom.<ext>, and --display then shows the bloomed image.
+With --frames N --temporal every frame's first image is bloomed behind the filter (render_temporal's bloom=), <out>.NNNN.bloom.<ext>."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -83,7 +88,16 @@ despeckle = None  # DespeckleParams.make's keywords
 if "--despeckle" in sys.argv:  # takes no value: a number behind it would be indistinguishable from msaa and depth
     sys.argv.remove("--despeckle")
     despeckle = {}
-for flag in ("--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+bloom = None  # BloomParams.make's keywords
+if "--bloom" in sys.argv:  # takes no value, like --despeckle
+    sys.argv.remove("--bloom")
+    bloom = {}
+if "--bloom-mix" in sys.argv:
+    sys.argv.remove("--bloom-mix")
+    if bloom is None:
+        sys.exit("--bloom-mix goes with --bloom")
+    bloom["mix"] = True
+for flag in ("--bloom-threshold", "--bloom-strength", "--bloom-levels", "--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -96,6 +110,10 @@ for flag in ("--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--co
             if despeckle is None:
                 sys.exit("--despeckle-gain, --despeckle-rank and --despeckle-radius go with --despeckle")
             despeckle[flag[len("--despeckle-"):]] = float(value) if flag == "--despeckle-gain" else int(value)
+        elif flag in ("--bloom-threshold", "--bloom-strength", "--bloom-levels"):
+            if bloom is None:
+                sys.exit("--bloom-threshold, --bloom-strength and --bloom-levels go with --bloom")
+            bloom[flag[len("--bloom-"):]] = int(value) if flag == "--bloom-levels" else float(value)
         elif flag == "--orbit":
             orbit = float(value)
         elif flag == "--spin":
@@ -207,7 +225,11 @@ if frames:
         sys.exit("with --frames N, --upscale goes with --temporal")
     if despeckle is not None and not temporal:
         sys.exit("with --frames N, --despeckle goes with --temporal")
+    if bloom is not None and not temporal:
+        sys.exit("with --frames N, --bloom goes with --temporal")
     extra = {} if despeckle is None else {"despeckle": despeckle}  # (a keyword of the sequences only when asked for)
+    if bloom is not None:
+        extra["bloom"] = bloom
     spatial = True if spatial_variance else None
     if spin or motion_vectors:
         sequence = ctx.render_animation(spun_scenes(ls.build(), spin, spin_deg, cams), msaa, msaa, depth, motion_vectors="prev_depth" if motion_vectors else False,
@@ -222,6 +244,8 @@ if frames:
         if temporal:
             pbrs_amd.write_image(f"{stem}.{k:04d}.accumulated{ext}", images[1])
             pbrs_amd.write_image(f"{stem}.{k:04d}.noisy{ext}", images[2])
+        if bloom is not None:
+            pbrs_amd.write_image(f"{stem}.{k:04d}.bloom{ext}", images[3]["bloom"])
         if display is not None:
             pbrs_amd.write_image_u8(f"{stem}.{k:04d}.display.png", images[3]["display"])
         if motion_vectors:
@@ -257,8 +281,13 @@ if want_layers and (filtered or matte_key):  # like the AOVs beside a filtered i
 pbrs_amd.write_image(out, img)
 scored = {"image": img}  # what --compare-strata scores
 stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
+glare = img  # what --display shows
+if bloom is not None:
+    glare = ctx.bloom(img, **bloom)
+    pbrs_amd.write_image(f"{stem}.bloom{ext}", glare)
+    print(f"-> {stem}.bloom{ext} ({pbrs_amd.BloomParams.make(img.shape[1], img.shape[0], **bloom).as_dict()})")
 if display is not None:
-    shown, e = ctx.display(img, return_exposure=True, **display)
+    shown, e = ctx.display(glare, return_exposure=True, **display)
     pbrs_amd.write_image_u8(f"{stem}.display.png", shown)
     print(f"-> {stem}.display.png ({display['curve']}, {display.get('encode', 'srgb')}, exposure {float(e) * display.get('exposure', 1.0):.4g})")
 if upscale is not None:
