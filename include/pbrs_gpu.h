@@ -505,6 +505,31 @@ int pbrs_numeric_eval(pbrs_ctx*, uint32_t fn, uint32_t n, const float* x, const 
 /* Its functions of more than two operands (include/pbrs_numeric_probe.h: pn_probe_eval_k): `ops` is an n x k matrix of 32-bit
  * words, row-major, k <= 16; out[i] is the result word of row i. */
 int pbrs_numeric_eval_k(pbrs_ctx*, uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out);
+/* src/bsdf.rs evaluated on the device for n queries against a material of the uploaded scene, through the code k_shade runs
+ * (device/bsdf.h): the frame of bsdf_new_frame over the query's normal and tangent, the material's lobes, then one of
+ *   PBRS_BSDF_EVAL             f = BSDF::eval(wo, wi)
+ *   PBRS_BSDF_PDF              pr = BSDF::pdf(wo, wi)
+ *   PBRS_BSDF_SAMPLE           (f, wi_out, pr) = BSDF::sample(wo, u, v)
+ *   PBRS_BSDF_SAMPLE_SPECULAR  BSDF::sample_specular(wo): flag bit 1 and (f, wi_out, pr) where the material has a Specular lobe
+ * A query is 16 words: material index (u32), then f32 normal[3], tangent[3], wo[3], wi[3] (world space), u, v, and a spare word
+ * that is ignored.  PBRS_BSDF_SAMPLE asks for 0 <= u < 1: BSDF::sample picks lobe `(u * n) as usize`.  A result is 8 words:
+ * f32 f[3], wi_out[3], pr, then a u32 of flags (PBRS_BSDF_IS_MASS: pr is a mass; PBRS_BSDF_FOUND); what an op does not return is 0.
+ * `lambert` != 0 runs the kernel specialised as k_shade's PBRS_SHADE_LAMBERT variants are, and is accepted only for a scene whose
+ * every lobe is an untextured Lambertian DiffuseReflect (the scenes those variants render).  Scenes with a Fourier material run
+ * the lobe in its generic form (no LDS series column).
+ * Refused with PBRS_E_INVALID (the context stays usable): no scene uploaded; NULL queries or results; an unknown op; a material index
+ * out of range; a material with PBRS_MATERIAL_TEXTURED (its lobes depend on the hit's uv and position, which a query does not
+ * carry); `lambert` on another scene; for PBRS_BSDF_SAMPLE a u that is not in [0, 1), NaN included.  n == 0 returns PBRS_OK and
+ * touches nothing. */
+#define PBRS_BSDF_EVAL 0u
+#define PBRS_BSDF_PDF 1u
+#define PBRS_BSDF_SAMPLE 2u
+#define PBRS_BSDF_SAMPLE_SPECULAR 3u
+#define PBRS_BSDF_QUERY_WORDS 16u
+#define PBRS_BSDF_RESULT_WORDS 8u
+#define PBRS_BSDF_IS_MASS 1u
+#define PBRS_BSDF_FOUND 2u
+int pbrs_bsdf_eval(pbrs_ctx*, uint32_t op, uint32_t lambert, uint32_t n, const uint32_t* queries, uint32_t* results);
 /* Per-sample radiance of one sample index for a tile (before the sum over samples), for bisecting. */
 int pbrs_render_sample_radiance(pbrs_ctx*, const pbrs_camera*, const pbrs_render_params*, uint32_t sample_index, float* rgb_out_host);
 

@@ -61,6 +61,7 @@ def lib():
         L.oracle_intersect_rays.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
         L.oracle_camera_rays.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_uint64, C.c_void_p, C.c_void_p]
         L.oracle_numeric_eval.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_bsdf_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_numeric_eval_k.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.oracle_rng_stream.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.oracle_temperature_to_color.argtypes = [C.c_float, C.c_void_p]
@@ -79,6 +80,7 @@ NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "
                "sincos64_cos_lo": 26, "rng_u32": 27, "rng_f32": 28}
 # include/pbrs_numeric_probe.h: ids from 16 on return raw 32-bit words (view the result as uint32 where it is no f32)
 NUMERIC_K_FNS = {"mul_add": 0, "clamp": 1, "slab_filter": 2, "rng_init_lo": 3, "rng_init_hi": 4, "rng_stream_u32": 5, "rng_stream_f32": 6}
+BSDF_OPS = {"eval": 0, "pdf": 1, "sample": 2, "sample_specular": 3}
 
 
 def numeric_eval(fn, x, y=None):
@@ -163,6 +165,17 @@ class OracleScene:
         out = np.empty_like(dirs)
         lib().oracle_env_eval(self._h, len(dirs), dirs.ctypes.data, out.ctypes.data)
         return out
+
+    def bsdf_eval(self, op, queries):
+        """BSDF::eval / pdf / sample / sample_specular for the rows of `queries` (n x 16 words, oracle_api.h) -> (n x 8 uint32 words,
+        per-query counts of the panic sites reached)."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.ndim == 2 and queries.shape[1] == 16 and queries.dtype.itemsize == 4
+        out = np.zeros((len(queries), 8), dtype=np.uint32)
+        panics = np.zeros(len(queries), dtype=np.uint32)
+        rc = lib().oracle_bsdf_eval(self._h, BSDF_OPS[op], len(queries), queries.ctypes.data, out.ctypes.data, panics.ctypes.data)
+        assert rc == 0
+        return out, panics
 
     def trace_sample(self, row, col, sample, strata_x, strata_y, depth, seed):
         tr = PathTrace()

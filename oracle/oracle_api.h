@@ -68,6 +68,12 @@ int oracle_camera_rays(const oracle_scene*, uint32_t x0, uint32_t y0, uint32_t w
 /* texture/src/lib.rs `Texture::value(uv, p)` for n (uv, p) pairs; scene/src/lib.rs:105-117 for n ray directions. */
 int oracle_texture_value(const pbrs_texture_spec* tex, uint32_t n, const float* uv, const float* pos, float* rgb_out);
 int oracle_env_eval(const oracle_scene*, uint32_t n, const float* dirs, float* rgb_out);
+/* src/bsdf.rs (BSDF::eval / pdf / sample / sample_specular: op 0 .. 3) over `mtl.bxdfs_at(hit)` of material queries[16 i] for n queries of
+ * 16 words (material index, normal[3], tangent[3], wo[3], wi[3], u, v, spare) -> n results of 8 words (f[3], wi[3], pr, flags: bit 0
+ * pr is a mass, bit 1 a specular lobe was found): the words of the device's pbrs_bsdf_eval.  panics_out (may be NULL): per query, the
+ * reference assert!/panic! sites reached.  Returns -1 for an unknown op, a material index out of range, or, for op 2, a u that is not
+ * in [0, 1) (NaN included): BSDF::sample's `bxdfs.swap_remove((u * n) as usize)` panics there, and a std::vector would not. */
+int oracle_bsdf_eval(const oracle_scene*, uint32_t op, uint32_t n, const uint32_t* queries, uint32_t* results, uint32_t* panics_out);
 int oracle_numeric_eval(uint32_t fn, uint32_t n, const float* x, const float* y, float* out);
 /* functions of more than two operands (include/pbrs_numeric_probe.h): n x k words, row-major -> n words */
 int oracle_numeric_eval_k(uint32_t fn, uint32_t n, uint32_t k, const uint32_t* ops, uint32_t* out);

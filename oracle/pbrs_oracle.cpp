@@ -12,6 +12,7 @@
 // reference holds for them (oracle/selftest.cpp); at integrator level (radiance per pixel, BVH
 // traversal, NEE) the reference has no tests and no golden images, so that level is
 // "parity unpinned": it rests on this restatement following the cited lines.
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <thread>
@@ -73,6 +74,7 @@ std::unique_ptr<Scene> scene_from_spec(const pbrs_scene_spec& spec) {
         instances.push_back(std::move(inst));
     }
     scene->tlas = build_bvh(std::move(instances));
+    scene->materials = mtls;
     for (uint32_t l = 0; l < spec.n_area_lights; ++l) {
         const pbrs_area_light_spec& a = spec.area_lights[l];
         DiffuseAreaLight light{};
@@ -686,6 +688,65 @@ int oracle_env_eval(const oracle_scene* os, uint32_t n, const float* dirs, float
         rgb_out[3 * i + 1] = c.g;
         rgb_out[3 * i + 2] = c.b;
     }
+    return 0;
+}
+
+// src/bsdf.rs for caller-supplied frames, directions and random numbers: the parity harness of the device's pbrs_bsdf_eval, same words.
+// A query: material index, normal[3], tangent[3] (the Interaction's tbn column 0, as bsdf_new_frame reads it), wo[3], wi[3], u, v, a
+// spare word.  A result: f[3], wi[3], pr, flags (bit 0: pr is a mass; bit 1: sample_specular found a lobe).  op: 0 eval, 1 pdf,
+// 2 sample, 3 sample_specular.  panics_out (may be null): per query, the assert / panic sites reached.
+static void bsdf_query(const Scene& scene, uint32_t op, const uint32_t* q, uint32_t* r, uint32_t* panics) {
+    float w[16];
+    for (int k = 1; k < 16; ++k) w[k] = pn_from_bits(q[k]);
+    Diag d;
+    g_diag = &d;
+    Interaction hit{};
+    hit.pos = Point3{0.0f, 0.0f, 0.0f};
+    hit.normal = Vec3{w[1], w[2], w[3]};
+    hit.tbn.cols[0] = Vec3{w[4], w[5], w[6]};
+    hit.wo = Vec3{w[7], w[8], w[9]};
+    const Vec3 wi_w{w[10], w[11], w[12]};
+    std::vector<BXDF> bxdfs = scene.materials[q[0]]->bxdfs_at(hit);
+    BSDF bsdf = bsdf_new_frame(hit);
+    bsdf.bxdfs = &bxdfs;
+    Color f = black();
+    Vec3 wi{0.0f, 0.0f, 0.0f};
+    Prob pr = Prob::Density(0.0f);
+    uint32_t flags = 0u;
+    switch (op) {
+        case 0: f = bsdf.eval(hit.wo, wi_w); break;
+        case 1: pr = Prob::Density(bsdf.pdf(hit.wo, wi_w)); break;
+        case 2: bsdf.sample(hit.wo, w[13], w[14], &f, &wi, &pr); break;
+        default:
+            if (bsdf.sample_specular(hit.wo, &f, &wi, &pr)) flags |= 2u;
+            break;
+    }
+    g_diag = nullptr;
+    if (pr.is_mass) flags |= 1u;
+    const float out[7] = {f.r, f.g, f.b, wi.x, wi.y, wi.z, pr.v};
+    for (int k = 0; k < 7; ++k) r[k] = pn_bits(out[k]);
+    r[7] = flags;
+    if (panics) *panics = (uint32_t)d.panics;
+}
+int oracle_bsdf_eval(const oracle_scene* os, uint32_t op, uint32_t n, const uint32_t* queries, uint32_t* results, uint32_t* panics_out) {
+    if (!os || op > 3u || (n && (!queries || !results))) return -1;
+    const Scene& scene = *os->scene;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (queries[(size_t)i * 16] >= scene.materials.size()) return -1;
+        const float u = pn_from_bits(queries[(size_t)i * 16 + 13]);
+        if (op == 2u && !(u >= 0.0f && u < 1.0f)) return -1;  // BSDF::sample indexes its lobe list with (u * n) as usize
+    }
+    // the queries are independent: a large batch is cut into one range per thread (g_diag, the panic count, is per thread)
+    auto run = [&](uint32_t first, uint32_t last) {
+        for (uint32_t i = first; i < last; ++i)
+            bsdf_query(scene, op, queries + (size_t)i * 16, results + (size_t)i * 8, panics_out ? panics_out + i : nullptr);
+    };
+    const uint32_t workers = n < 4096u ? 1u : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < workers; ++t)
+        pool.emplace_back(run, (uint32_t)((uint64_t)n * t / workers), (uint32_t)((uint64_t)n * (t + 1u) / workers));
+    run(0u, (uint32_t)((uint64_t)n / workers));
+    for (std::thread& th : pool) th.join();
     return 0;
 }
 

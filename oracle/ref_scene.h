@@ -291,6 +291,7 @@ struct Scene {
     std::shared_ptr<Texture> env_map;  // Image
     Color env_scale;
     Camera camera;
+    std::vector<std::shared_ptr<Material>> materials;  // not in the reference: the spec's materials by index (oracle_bsdf_eval)
     bool has_env_light() const { return env_kind != PBRS_ENV_CONSTANT || !is_black(env_constant); }  // :96-103
     Color eval_env_light(const Ray& ray) const;                                                      // :105-117
 };

@@ -620,6 +620,9 @@ NUMERIC_FNS = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "acos": 5, "
                "sincos64_cos_lo": 26, "rng_u32": 27, "rng_f32": 28}
 # include/pbrs_numeric_probe.h: ids from 16 on return raw 32-bit words (view the result as uint32 where it is no f32)
 NUMERIC_K_FNS = {"mul_add": 0, "clamp": 1, "slab_filter": 2, "rng_init_lo": 3, "rng_init_hi": 4, "rng_stream_u32": 5, "rng_stream_f32": 6}
+# include/pbrs_gpu.h: PBRS_BSDF_EVAL .. _SAMPLE_SPECULAR; a query is 16 words, a result 8
+BSDF_OPS = {"eval": 0, "pdf": 1, "sample": 2, "sample_specular": 3}
+BSDF_QUERY_WORDS, BSDF_RESULT_WORDS = 16, 8
 
 
 def _motion_args(motion):

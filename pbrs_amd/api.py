@@ -12,7 +12,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from .abi import (AOV_NAMES, AOVS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
+from .abi import (AOV_NAMES, AOVS, BSDF_OPS, BSDF_QUERY_WORDS, BSDF_RESULT_WORDS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
                   SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, BloomParams, Camera, CompareMaps, CompareParams, CompareResult,
                   DenoiseGuides, DenoiseParams, DespeckleIO, DespeckleParams, DespeckleResult,
                   DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
@@ -1208,4 +1208,15 @@ class Context:
         out = np.empty(len(ops), dtype=np.uint32)
         self._check(self._L.pbrs_numeric_eval_k(self._h, NUMERIC_K_FNS[fn], ops.shape[0], ops.shape[1], ops.ctypes.data, out.ctypes.data),
                     "pbrs_numeric_eval_k")
+        return out
+
+    def bsdf_eval(self, op, queries, lambert=False):
+        """src/bsdf.rs on the device for the rows of `queries` (n x 16 words: material index as uint32, then float32 normal, tangent, wo,
+        wi, u, v and a spare word) against the uploaded scene -> n x 8 uint32 words (f, wi_out, pr, flags).  `lambert`: through the kernel
+        specialised as k_shade's Lambert variants are (Lambert-only scenes)."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.ndim == 2 and queries.shape[1] == BSDF_QUERY_WORDS and queries.dtype.itemsize == 4
+        out = np.zeros((len(queries), BSDF_RESULT_WORDS), dtype=np.uint32)
+        self._check(self._L.pbrs_bsdf_eval(self._h, BSDF_OPS[op], 1 if lambert else 0, len(queries), queries.ctypes.data, out.ctypes.data),
+                    "pbrs_bsdf_eval")
         return out

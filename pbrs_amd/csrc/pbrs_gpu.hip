@@ -234,6 +234,9 @@ struct pbrs_ctx {
     hipEvent_t split_ev = nullptr;
     bool split_probe_in_flight = false;
     bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
+    // pbrs_bsdf_eval: what prepare_scene found out about the scene's lobes (SceneFacts::lambert, ::fourier), and each material's flags
+    bool lambert_scene = false, fourier_scene = false;
+    std::vector<uint32_t> material_flags;
     uint64_t pending_closest = 0;
     pbrs_intersect_info last_intersect{};  // which walks the last pbrs_intersect_rays went through
     DeviceBuffer buf[N_BUFFERS];  // the features' first-use buffers (BufferId)
@@ -1141,6 +1144,10 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     c->S = S;
     c->overlap_from = c->dev.overlap_from.value_or(P.walk_bytes <= (4ull << 20) ? 2u : 4u);  // one XCD's L2 holds the arrays the walks read, or not (pbrs_ctx::overlap_from)
     c->has_vis_records = P.has_vis_records;
+    c->lambert_scene = P.facts.lambert;
+    c->fourier_scene = P.facts.fourier;
+    c->material_flags.resize(d->n_materials);
+    for (uint32_t i = 0; i < d->n_materials; ++i) c->material_flags[i] = d->materials[i].flags;
     c->stack_depth = P.stack_depth;
     c->has_scene = true;
     c->split_decision = 0;  // (the streams were synchronised above: no probe of the previous scene is in flight)
@@ -2128,6 +2135,40 @@ int pbrs_numeric_eval_k(pbrs_ctx* c, uint32_t fn, uint32_t n, uint32_t k, const 
     hipLaunchKernelGGL(k_numeric_eval_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, fn, n, k, d_ops, d_r);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_r, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRS_OK;
+}
+
+int pbrs_bsdf_eval(pbrs_ctx* c, uint32_t op, uint32_t lambert, uint32_t n, const uint32_t* queries, uint32_t* results) {
+    if (!c) return PBRS_E_INVALID;
+    if (n == 0) return PBRS_OK;
+    if (!c->has_scene) return fail(c, PBRS_E_INVALID, "bsdf_eval: no scene uploaded");
+    if (!queries || !results) return fail(c, PBRS_E_INVALID, "bsdf_eval: null queries or results");
+    if (op > PBRS_BSDF_SAMPLE_SPECULAR) return fail(c, PBRS_E_INVALID, "bsdf_eval: unknown op");
+    if (lambert && !c->lambert_scene) return fail(c, PBRS_E_INVALID, "bsdf_eval: the Lambert variant needs a scene whose every lobe is an untextured Lambertian");
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t m = queries[(size_t)i * PBRS_BSDF_QUERY_WORDS];
+        if (m >= c->material_flags.size()) return fail(c, PBRS_E_INVALID, "bsdf_eval: material index out of range");
+        if (c->material_flags[m] & PBRS_MATERIAL_TEXTURED)
+            return fail(c, PBRS_E_INVALID, "bsdf_eval: textured materials are out of scope (a query carries no uv or position)");
+        if (op == PBRS_BSDF_SAMPLE) {  // bsdf_sample_l picks lobe (uint32_t)(u * n): k_shade's u comes from the RNG, below 1; this one from the caller
+            float u;
+            std::memcpy(&u, queries + (size_t)i * PBRS_BSDF_QUERY_WORDS + 13, sizeof u);
+            if (!(u >= 0.0f && u < 1.0f)) return fail(c, PBRS_E_INVALID, "bsdf_eval: u outside [0, 1) would pick a lobe the material does not have");
+        }
+    }
+    const bsdf_eval_fn_t fn = bsdf_eval_fn(lambert != 0, c->fourier_scene);
+    if (!fn) return fail(c, PBRS_E_DEVICE, "bsdf_eval: no kernel instantiation for this scene");
+    HIPCHK(c, hipSetDevice(c->device));
+    uint32_t *d_q = nullptr, *d_r = nullptr;
+    CallAllocs mem;
+    const size_t q_bytes = (size_t)n * PBRS_BSDF_QUERY_WORDS * 4, r_bytes = (size_t)n * PBRS_BSDF_RESULT_WORDS * 4;
+    HIPCHK(c, mem.alloc(&d_q, q_bytes));
+    HIPCHK(c, mem.alloc(&d_r, r_bytes));
+    HIPCHK(c, hipMemcpyAsync(d_q, queries, q_bytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(fn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, op, n, d_q, d_r);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(results, d_r, r_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PBRS_OK;
 }

@@ -1,4 +1,5 @@
-// shade.hip — the shade kernels: every k_shade a scene's plan can name.  (The units of the library: kernel_tables.h.)
+// shade.hip — the shade kernels: every k_shade a scene's plan can name, and the BSDF probe's k_bsdf_eval, which makes k_shade's calls
+// into device/bsdf.h.  (The units of the library: kernel_tables.h.)
 #include <hip/hip_runtime.h>
 
 #include "kernel_tables.h"
@@ -9,6 +10,7 @@ __device__ unsigned long long g_shade_probe[16];
 #define PBRS_SHADE_PROBE_DEFINED
 #endif
 #include "device/shade.h"
+#include "device/bsdf_probe.h"
 
 using namespace pbrs;
 
@@ -31,6 +33,11 @@ shade_fn_t pbrs::shade_fn(const ShadeKey& key) {
     for (const ShadeKernel& k : kShadeKernels)
         if (k.integ == key.integ && k.tex == key.tex && k.spec == key.spec) return k.fn;
     return nullptr;
+}
+
+bsdf_eval_fn_t pbrs::bsdf_eval_fn(bool lambert, bool fourier) {
+    if (lambert) return fourier ? nullptr : &k_bsdf_eval<true, false>;
+    return fourier ? &k_bsdf_eval<false, true> : &k_bsdf_eval<false, false>;
 }
 
 #ifdef PBRS_PROBE_SHADE

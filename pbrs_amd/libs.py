@@ -37,6 +37,7 @@ GPU_FUNCTIONS = _table({
     "pbrs_camera_rays": [P, P, P, U32, P, P],
     "pbrs_numeric_eval": [P, U32, U32, P, P, P],
     "pbrs_numeric_eval_k": [P, U32, U32, U32, P, P],
+    "pbrs_bsdf_eval": [P, U32, U32, U32, P, P],
     "pbrs_render_sample_radiance": [P, P, P, U32, P],
     "pbrs_display_params_default": ([U32, U32, P], None),
     "pbrs_upsample_params_default": ([U32, U32, U32, P], None),

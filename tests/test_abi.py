@@ -116,7 +116,7 @@ def test_gpu_library_exports_the_header_and_nothing_internal():
     host_text = "\n".join(open(os.path.join(host_dir, f)).read() for f in sorted(os.listdir(host_dir)) if f.endswith(".h"))
     tables = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "pbrs_amd", "csrc", "kernel_tables.h")).read())
     internal = set(re.findall(r"^[\w:\* ]+?\b(\w+)\([^()]*\);", tables, flags=re.M))  # the functions it declares
-    assert internal == {"extend_fns", "shadow_fns", "intersect_fn", "shade_fn"}, internal
+    assert internal == {"extend_fns", "shadow_fns", "intersect_fn", "shade_fn", "bsdf_eval_fn"}, internal
     for name in plain:
         m = re.search(r"\bpbrs::(\w+)", name)
         assert m and m.group(1) not in internal, name
