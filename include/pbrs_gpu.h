@@ -1351,6 +1351,61 @@ void pbrsb_bloom_params_default(uint32_t w, uint32_t h, pbrs_bloom_params* out);
 int pbrsb_bloom(pbrs_ctx*, const pbrs_bloom_params*, const float* rgb_host, float* rgb_out_host);
 int pbrsb_bloom_device(pbrs_ctx*, const pbrs_bloom_params*, const float* rgb_device, float* rgb_out_device);
 
+/* ---- depth of field ---------------------------------------------------------------------------------------------- */
+/* A thin-lens blur as an image operation: the camera of this library is a pinhole, and this call defocuses its image afterwards from the
+ * depth AOV.  That depth (pbrs_aov_buffers.depth) is the ray parameter t of the unnormalised direction c + a x + b y; a and b span the
+ * image plane, so t is the planar depth along the view axis in units of one constant, and the thin-lens circle of confusion depends on
+ * depth only through |z - F| / z, a ratio that t gives exactly.  Each pixel gets a blur radius from its depth (step 1); the image is
+ * rebuilt from its neighbours' circles in one gather (step 2), under two occlusion rules: a near, blurred object spreads over what is
+ * behind it, and a sharp object keeps its edge against a blurred background.  An image operation like pbrs_denoise: it needs a context
+ * (device, stream) and no uploaded scene.  rgb and rgb_out are w * h pixels, row-major, 3 floats each; depth is w * h floats as
+ * pbrs_aov_buffers writes it, +inf where nothing was hit.  All arithmetic is f32 without fused multiply-add, in the order written;
+ * divisions and square roots are correctly rounded; pn_* is include/pbrs_numeric.h.  No sum here depends on the launch shape or on
+ * arrival order: a CPU model of this text gives the same bytes.  R = max_radius, F = focus, K = scale.
+ *   0. K == 0 comes before everything else: rgb_out gets rgb's bits (a copy) and coc_out, where given, +0.  So 0 * inf never forms.
+ *   1. Circle of confusion r(p) from z = depth(p).  !(z > 0) (zero, negative, NaN: the depth is unknown) gives r = +0.  Otherwise
+ *      q = 1.0f where z is +inf and q = pn_abs(z - F) / z elsewhere; r = K * q; r = r < (float)R ? r : (float)R.
+ *   2. Gather.  A pixel p of rgb with a channel that does not pass pn_isfinite passes through with its bits.  Otherwise start from
+ *      acc = (+0, +0, +0), W = +0, n = 0, and for dy = -R .. R (outer) and dx = -R .. R (inner), q = p + (dx, dy):
+ *        q outside the image: left out.  rgb(q) has a channel that does not pass pn_isfinite: left out.
+ *        dist = sqrt((float)(dx * dx + dy * dy)).
+ *        e = depth(q) < depth(p) ? r(q) : (r(q) < r(p) ? r(q) : r(p)).  A tap in front spreads by its own circle; a tap at or
+ *            behind p never spreads further than p's own circle.  An unordered comparison is false.
+ *        cov = (e - dist) + 0.5f; cov <= 0: left out; then cov = cov < 1.0f ? cov : 1.0f.
+ *        rr = e > 0.5f ? e : 0.5f; wgt = cov / (rr * rr).
+ *        acc.c = acc.c + wgt * rgb(q).c per channel; W = W + wgt; n = n + 1.
+ *      The centre always counts: dist = 0, e = r(p) >= 0, cov >= 0.5.  n == 1 gives rgb(p)'s bits; otherwise out.c = acc.c / W.
+ *      A tap that is left out is not added at all, so an implementation may shorten its loops wherever it can prove cov <= 0, and
+ *      nothing changes.
+ *   3. coc_out, optional (NULL: not wanted), w * h floats: r(p), with the sign bit set where depth(p) < F (an unordered comparison is
+ *      false): the near field is negative, and a depth of zero or below gives -0.
+ * Rules.  (a) With rgb times 2^j the output is 2^j times the output, bit for bit, while nothing overflows or becomes a nonzero value
+ * below the smallest normal f32.  (b) With depth and focus both times 2^j, likewise, the output and coc_out keep their bits.  (c) Where
+ * every r is <= 0.5 the output is rgb, bit for bit.  (d) A pixel with r = 0 takes nothing from any pixel at or behind its own depth.
+ * What a gather cannot know is the background hidden behind a blurred foreground: where a near object is spread thin, what shows through
+ * it is the neighbouring visible background, not what a lens would see past the object's edge.  The bokeh is a disk.
+ * Pointers are host memory for pbrsf_dof, which stages the planes on first use (32 B per pixel) and synchronises before it returns;
+ * device memory for pbrsf_dof_device, which runs on the context's stream (pbrs_set_stream honoured) and does not wait: one launch, no
+ * scratch, no allocation.  rgb_out must not be rgb: a gather reads its neighbours.  Any other overlap is the caller's error.
+ * Refused, in this order, with PBRS_E_INVALID (the context stays usable): NULL params, rgb, depth or rgb_out; rgb_out == rgb; w or h 0;
+ * max_radius 0 or above PBRS_DOF_MAX_RADIUS; non-zero flags or reserved words; focus not finite or <= 0; scale not finite or < 0.
+ * Then w * h above 2^28: PBRS_E_LIMIT. */
+#define PBRS_DOF_MAX_RADIUS 16u
+typedef struct pbrs_dof_params {
+    uint32_t w, h;        /* image size */
+    uint32_t max_radius;  /* 1 .. PBRS_DOF_MAX_RADIUS: pixels; also the loop's reach */
+    uint32_t flags;       /* 0 */
+    float focus;          /* finite, > 0: the depth AOV's value that is sharp */
+    float scale;          /* finite, >= 0: blur radius in pixels of a point at infinity */
+    uint32_t reserved[2]; /* 0 */
+} pbrs_dof_params;        /* 32 B */
+/* (The three functions' prefix is pbrsf_; the struct and the constant above carry pbrs_.)
+ * Filler: max_radius 8, flags 0, focus 1, scale 0 (a copy until the caller sets a lens), reserved 0; `out` NULL does nothing.
+ * Host code: needs no context. */
+void pbrsf_dof_params_default(uint32_t w, uint32_t h, pbrs_dof_params* out);
+int pbrsf_dof(pbrs_ctx*, const pbrs_dof_params*, const float* rgb_host, const float* depth_host, float* rgb_out_host, float* coc_out_host);
+int pbrsf_dof_device(pbrs_ctx*, const pbrs_dof_params*, const float* rgb_device, const float* depth_device, float* rgb_out_device, float* coc_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -580,6 +580,67 @@ def _bloom_params(bloom):
     return bp
 
 
+class DofParams(C.Structure):
+    """pbrs_dof_params (include/pbrs_gpu.h, "depth of field"): image size, the largest blur radius (also the gather's reach), the depth
+    AOV's value that is sharp and the blur radius in pixels of a point at infinity."""
+    MAX_RADIUS = 16
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("max_radius", C.c_uint32), ("flags", C.c_uint32), ("focus", C.c_float), ("scale", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, w, h, max_radius=8, focus=1.0, scale=0.0):
+        """The defaults are pbrsf_dof_params_default's; api.lens(camera, focus_distance, lens_radius) gives focus and scale."""
+        p = cls()
+        p.w, p.h = w, h
+        p.max_radius, p.focus, p.scale = max_radius, focus, scale
+        return p
+
+    def as_dict(self):
+        return {"w": self.w, "h": self.h, "max_radius": self.max_radius, "flags": self.flags, "focus": self.focus, "scale": self.scale}
+
+
+def lens(camera, focus_distance, lens_radius):
+    """A thin lens in front of the pinhole `camera` (a Camera) -> {"focus": ..., "scale": ...}, DofParams.make's keywords: the plane at
+    `focus_distance` along the view axis (world units) is sharp, and `lens_radius` is the aperture's radius (world units).  The depth
+    AOV is the ray parameter t of the direction c + a x + b y, whose component along the view axis n = normalize(cross(a, b)) is
+    D = |dot(c, n)| for every pixel: focus = focus_distance / D.  A point at depth z spreads over a circle of the world radius
+    lens_radius |z - F| / z on the plane of focus, where one pixel step is |a| focus: scale = lens_radius / (|a| focus).  Computed in
+    f64 and rounded once.  With `upscale`, pass the full-size camera."""
+    a, b, c = (np.array(list(v), dtype=np.float64) for v in (camera.a, camera.b, camera.c))
+    n = np.cross(a, b)
+    norm = float(np.sqrt(n @ n))
+    if not (norm > 0.0 and np.isfinite(norm)):
+        raise ValueError("the camera's a and b do not span an image plane")
+    D = abs(float(c @ (n / norm)))
+    if not (D > 0.0 and focus_distance > 0.0 and lens_radius >= 0.0 and np.isfinite(focus_distance) and np.isfinite(lens_radius)):
+        raise ValueError("lens takes a camera that looks along its axis, a focus_distance > 0 and a lens_radius >= 0")
+    focus = float(focus_distance) / D
+    scale = float(lens_radius) / (float(np.sqrt(a @ a)) * focus)
+    return {"focus": float(np.float32(focus)), "scale": float(np.float32(scale))}
+
+
+def _dof_params(dof):
+    """render_temporal's / render_animation's `dof` -> a function frame index -> DofParams.make's keywords, or None: None or False is
+    the sequence without the step, a dict the keywords of every frame, a list or tuple of dicts one per frame (a focus pull; a sequence
+    longer than the list fails at the frame that has none).  An unknown keyword fails here."""
+    if dof is None or dof is False:
+        return None
+    per_frame = isinstance(dof, (list, tuple))
+    if not (isinstance(dof, dict) or (per_frame and len(dof) and all(isinstance(d, dict) for d in dof))):
+        raise ValueError("dof is None, a dict of DofParams.make's keywords or a list of such dicts, one per frame")
+    frames = [dict(d) for d in (dof if per_frame else [dof])]
+    for d in frames:
+        DofParams.make(1, 1, **d)
+
+    def of_frame(i):
+        if not per_frame:
+            return frames[0]
+        if i >= len(frames):
+            raise ValueError(f"dof holds {len(frames)} frames' keywords: none for frame {i}")
+        return frames[i]
+    return of_frame
+
+
 class SpatialVarianceGuides(C.Structure):
     """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]

@@ -14,13 +14,13 @@ import numpy as np
 
 from .abi import (AOV_NAMES, AOVS, BSDF_OPS, BSDF_QUERY_WORDS, BSDF_RESULT_WORDS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
                   SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, BloomParams, Camera, CompareMaps, CompareParams, CompareResult,
-                  DenoiseGuides, DenoiseParams, DespeckleIO, DespeckleParams, DespeckleResult,
+                  DenoiseGuides, DenoiseParams, DespeckleIO, DespeckleParams, DespeckleResult, DofParams,
                   DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
                   PixelFilter, RenderParams, SceneDesc, SpatialVarianceGuides, SpatialVarianceParams, Stats, TemporalFrame, TemporalGuides, TemporalHistory,
-                  TemporalParams, UpsampleParams, _aov_names, _bloom_params, _DenoiseParamsMixin, _despeckle_params, _display_params, _history_clip, _matte_select, _motion_args, _pass_names,
-                  _reference_frame, _reference_frames, _temporal_struct, _upscale_params, scaled_camera)
+                  TemporalParams, UpsampleParams, _aov_names, _bloom_params, _DenoiseParamsMixin, _despeckle_params, _display_params, _dof_params, _history_clip, _matte_select, _motion_args, _pass_names,
+                  _reference_frame, _reference_frames, _temporal_struct, _upscale_params, lens, scaled_camera)
 from .devmem import DeviceBuffers
-from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_DOF_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
 from .spec import SceneSpec  # noqa: F401
 
 
@@ -71,7 +71,7 @@ def _guide_bytes(guides, w, h, suffix=""):
     return {n + suffix: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}
 
 
-def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False, bloom=False):
+def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False, bloom=False, dof=False):
     """{name: bytes} of the device buffers of a frame sequence (Context._temporal_frames) that runs at w x h and shows fw x fh: the
     frame's image, the filtered one, the two variances; two ping-pong halves ("0", "1") of the guides the next frame is tested against
     and of the history; the other guides once; and what each option that is on adds."""
@@ -94,6 +94,8 @@ def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, re
         sizes["despeckled"], sizes["despeckle"] = 3 * w * h * 4, C.sizeof(DespeckleResult)
     if bloom:
         sizes["bloom"] = 3 * fw * fh * 4
+    if dof:
+        sizes["dof"] = 3 * fw * fh * 4
     return sizes
 
 
@@ -913,6 +915,42 @@ class Context:
         p = BloomParams.make(w, h, **params)
         self._check(self._L.pbrsb_bloom_device(self._h, C.addressof(p), C.c_void_p(src_ptr), C.c_void_p(dst_ptr)), "pbrsb_bloom_device")
 
+    def dof(self, rgb, depth, return_coc=False, focus_pixel=None, **params):
+        """The (h, w, 3) f32 image `rgb` through a thin lens (include/pbrs_gpu.h, pbrsf_dof): every pixel's circle of confusion from the
+        (h, w) f32 depth AOV `depth`, then one gather under the header's occlusion rules -> the (h, w, 3) f32 image; with return_coc
+        also the (h, w) f32 signed circles (near field negative).  params: DofParams.make's keywords (api.lens gives focus and scale).
+        `focus_pixel`: (x, y), takes `focus` from depth[y, x], which must be finite and positive."""
+        rgb, depth = np.ascontiguousarray(rgb, dtype=np.float32), np.ascontiguousarray(depth, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"the image is (h, w, 3), not {rgb.shape}")
+        h, w, _ = rgb.shape
+        if depth.shape != (h, w):
+            raise ValueError(f"the depth is ({h}, {w}) like the image, not {depth.shape}")
+        if focus_pixel is not None:
+            if "focus" in params:
+                raise ValueError("focus_pixel and focus are two ways to say the same thing: give one")
+            x, y = (int(v) for v in focus_pixel)
+            if not (0 <= x < w and 0 <= y < h):
+                raise ValueError(f"focus_pixel {(x, y)} is outside the {w} x {h} image")
+            z = float(depth[y, x])
+            if not (np.isfinite(z) and z > 0.0):
+                raise ValueError(f"the depth at focus_pixel {(x, y)} is {z}: nothing to focus on")
+            params["focus"] = z
+        p = DofParams.make(w, h, **params)
+        out = np.empty((h, w, 3), dtype=np.float32)
+        coc = np.empty((h, w), dtype=np.float32) if return_coc else None
+        self._check(self._L.pbrsf_dof(self._h, C.addressof(p), rgb.ctypes.data, depth.ctypes.data, out.ctypes.data, coc.ctypes.data if return_coc else None),
+                    "pbrsf_dof")
+        return (out, coc) if return_coc else out
+
+    def dof_device(self, rgb_ptr, depth_ptr, out_ptr, w, h, coc_ptr=None, **params):
+        """dof() on caller-owned device memory: (h, w, 3) f32 in and out, which must differ, the (h, w) f32 depth, and the optional
+        (h, w) f32 signed circles.  Runs on the context's stream behind whatever was queued there and does not wait: valid after
+        `collect_stats()`."""
+        p = DofParams.make(w, h, **params)
+        self._check(self._L.pbrsf_dof_device(self._h, C.addressof(p), C.c_void_p(rgb_ptr), C.c_void_p(depth_ptr), C.c_void_p(out_ptr), C.c_void_p(coc_ptr)),
+                    "pbrsf_dof_device")
+
     def _render_guides_device(self, rgb_device_ptr, guide_device_ptrs, seed, camera=None):
         """The full-size first-hit guides of guided upsampling: a one-sample render of `seed` through the path integrator at depth 1 (the
         cheapest route whose first hits are the jittered ones the low-resolution AOVs average; the visualisers shoot through the
@@ -999,8 +1037,14 @@ class Context:
         taken out of `params` likewise): None is that chain, with its allocations and tuples; True, or a dict of BloomParams.make's
         keywords, queues bloom_device on the frame's first image (the full-size one with `upscale`) behind the filter, on the same stream,
         into one more colour buffer: `display` then reads the bloomed image, `reference` keeps scoring the first image as it was, and
-        the stats gain "bloom", the (h, w, 3) f32 bloomed image."""
-        reference, despeckle, bloom = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None)
+        the stats gain "bloom", the (h, w, 3) f32 bloomed image.  `dof` (a keyword taken out of `params` likewise): None is that chain,
+        with its allocations and tuples; a dict of DofParams.make's keywords (api.lens gives focus and scale), or a list of such dicts,
+        one per frame (a focus pull), queues dof_device on the frame's first image and the depth of its size (the frame's depth guide;
+        with `upscale` the full-size guide render's) behind the filter and the upsample, on the same stream, into one more colour
+        buffer: a lens blurs before the sensor glares, so `bloom` then reads the defocused image and `display` reads bloom's or,
+        without bloom, the defocused one; `reference` keeps scoring the first image as it was, and the stats gain "dof", the (h, w, 3)
+        f32 defocused image."""
+        reference, despeckle, bloom, dof = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None), params.pop("dof", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -1011,7 +1055,7 @@ class Context:
             _reference_frame(_reference_frames(reference), 0, self.scene.width, self.scene.height)
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display,
-                                         upscale, reference, despeckle, bloom):
+                                         upscale, reference, despeckle, bloom, dof):
             yield out[:4] if reference is None else out[:4] + out[5:]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
@@ -1025,17 +1069,17 @@ class Context:
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
         are `spatial`, `display`, `upscale` (the motion vectors are then the low-resolution chain's) and the keyword `reference`, whose
-        CompareResult is the last entry, and the keywords `despeckle` and `bloom`."""
-        reference, despeckle, bloom = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None)
+        CompareResult is the last entry, and the keywords `despeckle`, `bloom` and `dof`."""
+        reference, despeckle, bloom, dof = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None), params.pop("dof", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display,
-                                         upscale, reference, despeckle, bloom):
+                                         upscale, reference, despeckle, bloom, dof):
             yield (out[:5] if motion_vectors else out[:4]) + (() if reference is None else out[5:])
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None, display=None, upscale=None, reference=None, despeckle=None, bloom=None):
+                         clip=None, display=None, upscale=None, reference=None, despeckle=None, bloom=None, dof=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None, CompareResult or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  The options are checked here, before
@@ -1052,6 +1096,7 @@ class Context:
         s.reference, s.one_reference = _reference_frames(reference), isinstance(reference, np.ndarray)
         s.despeckle = _despeckle_params(despeckle)
         s.bloom = _bloom_params(bloom)
+        s.dof = _dof_params(dof)
         dev = None
         try:
             cam_prev = scene_prev = None
@@ -1075,9 +1120,11 @@ class Context:
                 ref = None
                 if s.reference is not None and not (s.one_reference and i):  # checked before anything is allocated or queued
                     ref = _reference_frame(s.reference, i, s.fw, s.fh)
+                if s.dof is not None:
+                    s.dof(i)  # a list shorter than the sequence fails here, before the frame is queued
                 if dev is None:
                     dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None,
-                                                          s.reference is not None, s.despeckle is not None, s.bloom is not None), "a temporal sequence")
+                                                          s.reference is not None, s.despeckle is not None, s.bloom is not None, s.dof is not None), "a temporal sequence")
                 if ref is not None:
                     dev.upload("reference", ref)  # the frame before has been waited for: nothing reads the buffer
                 self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table)
@@ -1091,8 +1138,9 @@ class Context:
     def _queue_frame(self, s, dev, i, p, cam, cam_full, cam_prev, table):
         """Frame i of the sequence `s` on the context's stream, nothing waits: the render of `p` with its guides and its variance; the
         despeckle step, into a colour buffer of its own and in place on the variance; the accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
-        on the accumulated variance; the filter; the full-size guides and the upsample; the bloom of the frame's first image, into a colour
-        buffer of its own, which the display transform then reads; the display transform, whose exposure word is
+        on the accumulated variance; the filter; the full-size guides and the upsample; the depth of field of the frame's first image, into a
+        colour buffer of its own; the bloom of that (without the step: of the first image), into a colour buffer of its own; the display
+        transform, which reads the last of the three that exists and whose exposure word is
         read from the second frame on and written by every one; the comparison of the frame's first image with its reference."""
         w, h, cur, old = s.w, s.h, i & 1, (i & 1) ^ 1
         gp = {n: dev.ptr(f"{n}{cur}" if n in s.kept else n) for n in s.guides}
@@ -1116,10 +1164,15 @@ class Context:
         self.denoise_var_device(hist[cur]["rgb"], dev.ptr("out"), w, h, acc_variance, gp, **s.params)
         if s.uparams is not None:
             self._upsample_out_device(dev, gp, s.guides, p.seed, s.fw, s.fh, *s.uparams, camera=cam_full)
+        lit = s.shown  # what the next step of the chain reads: the first image, then the defocused one, then the bloomed one
+        if s.dof is not None:
+            self.dof_device(dev.ptr(lit), dev.ptr("depth_hi") if s.uparams is not None else gp["depth"], dev.ptr("dof"), s.fw, s.fh, **s.dof(i))
+            lit = "dof"
         if s.bloom is not None:
-            self.bloom_device(dev.ptr(s.shown), dev.ptr("bloom"), s.fw, s.fh, **s.bloom)
+            self.bloom_device(dev.ptr(lit), dev.ptr("bloom"), s.fw, s.fh, **s.bloom)
+            lit = "bloom"
         if s.dparams is not None:
-            self.display_device(dev.ptr(s.shown if s.bloom is None else "bloom"), dev.ptr("display"), s.fw, s.fh,
+            self.display_device(dev.ptr(lit), dev.ptr("display"), s.fw, s.fh,
                                 {"exposure_in": dev.ptr("exposure") if i else None, "exposure_out": dev.ptr("exposure")}, **s.dparams)
         if s.reference is not None:
             self.compare_device(dev.ptr(s.shown), dev.ptr("reference"), s.fw, s.fh, dev.ptr("compare"))
@@ -1136,6 +1189,8 @@ class Context:
             stats["low_res"] = (w, h)
         if s.despeckle is not None:
             stats["despeckle"] = DespeckleResult.from_buffer_copy(dev.download("despeckle", C.sizeof(DespeckleResult), np.uint8, "a temporal sequence's despeckle record"))
+        if s.dof is not None:
+            stats["dof"] = dev.download("dof", (s.fh, s.fw, 3), np.float32, "a temporal sequence's defocused image")
         if s.bloom is not None:
             stats["bloom"] = dev.download("bloom", (s.fh, s.fw, 3), np.float32, "a temporal sequence's bloomed image")
         shapes = {s.shown: (h, w, 3) if s.uparams is None else (s.fh, s.fw, 3), f"h_rgb{i & 1}": (h, w, 3), "rgb": (h, w, 3)}

@@ -79,5 +79,8 @@ Refusal check_compare(const pbrs_compare_params* p, const float* a, const float*
 Refusal check_despeckle(const pbrs_despeckle_params* p, const pbrs_despeckle_io* io);
 // pbrsb_bloom* (host/arg_checks_bloom.cpp, beside the filler pbrsb_bloom_params_default).  `rgb_out` may be `rgb`.
 Refusal check_bloom(const pbrs_bloom_params* p, const float* rgb, const float* rgb_out);
+// pbrsf_dof* (host/arg_checks_dof.cpp, beside the filler pbrsf_dof_params_default).  `rgb_out` must not be `rgb`; coc_out, which may
+// be NULL, is not looked at.
+Refusal check_dof(const pbrs_dof_params* p, const float* rgb, const float* depth, const float* rgb_out);
 
 }  // namespace pbrs

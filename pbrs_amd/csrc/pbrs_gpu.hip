@@ -41,6 +41,7 @@
 #include "device/compare.h"
 #include "device/despeckle.h"
 #include "device/bloom.h"
+#include "device/dof.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -163,6 +164,8 @@ enum BufferId {
     // bloom (pbrsb_bloom, device/bloom.h): the pyramid, one chain of levels of a float4 per level pixel, held only by a context that has
     // called it with a strength above 0; and the host variant's staging (the image, which the result replaces)
     BUF_BLOOM, BUF_BLOOM_STAGE,
+    // depth of field (pbrsf_dof, device/dof.h): the host variant's staging (rgb, depth, the output and the circles); the device call holds nothing
+    BUF_DOF_STAGE,
     N_BUFFERS
 };
 
@@ -2007,6 +2010,49 @@ int pbrsb_bloom(pbrs_ctx* c, const pbrs_bloom_params* p, const float* rgb_host, 
     if (rc) return rc;
     Staged s[] = {{rgb_host, 3, rgb_out_host}};  // in place on the staged image
     return run_staged(c, BUF_BLOOM_STAGE, "the bloom staging", s, (size_t)p->w * p->h, [&] { return bloom_launch(c, *p, s[0].as<float>(), s[0].as<float>()); });
+}
+
+// ---- depth of field (include/pbrs_gpu.h, device/dof.h) ----
+static_assert(sizeof(pbrs_dof_params) == 32 && offsetof(pbrs_dof_params, focus) == 16 && offsetof(pbrs_dof_params, reserved) == 24, "pbrs_dof_params is 32 B");
+
+namespace {
+
+using DofKernel = void (*)(Dof);
+// [halo class: 4, 8, 16][both planes 16-byte aligned]
+constexpr DofKernel kDof[3][2] = {{k_dof<4u, false>, k_dof<4u, true>}, {k_dof<8u, false>, k_dof<8u, true>}, {k_dof<16u, false>, k_dof<16u, true>}};
+static_assert(PBRS_DOF_MAX_RADIUS == 16u, "the halo classes end at the largest radius");
+
+// The one launch on the context's stream (arguments checked; device pointers).  scale 0 is the header's step 0: a copy.
+int dof_launch(pbrs_ctx* c, const pbrs_dof_params& p, const float* rgb, const float* depth, float* out, float* coc) {
+    const size_t P = (size_t)p.w * p.h;
+    if (p.scale == 0.0f) {
+        HIPCHK(c, hipMemcpyAsync(out, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        if (coc) HIPCHK(c, hipMemsetAsync(coc, 0, P * sizeof(float), c->stream));
+        return PBRS_OK;
+    }
+    const uint32_t tiles_x = (p.w + kDofTile - 1u) / kDofTile;
+    const uint32_t tiles = tiles_x * ((p.h + kDofTile - 1u) / kDofTile);  // at most 2^28 pixels: at most 2^28 tiles
+    const uint32_t halo = p.max_radius <= 4u ? 0u : (p.max_radius <= 8u ? 1u : 2u);  // the smallest class that holds max_radius
+    const bool aligned = ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(depth)) & 15u) == 0;
+    hipLaunchKernelGGL(kDof[halo][aligned], dim3(tiles), dim3(kDofBlock), 0, c->stream, Dof{rgb, depth, out, coc, p.w, p.h, tiles_x, p.max_radius, p.focus, p.scale});
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrsf_dof_device(pbrs_ctx* c, const pbrs_dof_params* p, const float* rgb_device, const float* depth_device, float* rgb_out_device, float* coc_out_device) {
+    const int rc = enter(c, check_dof(p, rgb_device, depth_device, rgb_out_device));
+    if (rc) return rc;
+    return dof_launch(c, *p, rgb_device, depth_device, rgb_out_device, coc_out_device);
+}
+
+int pbrsf_dof(pbrs_ctx* c, const pbrs_dof_params* p, const float* rgb_host, const float* depth_host, float* rgb_out_host, float* coc_out_host) {
+    const int rc = enter(c, check_dof(p, rgb_host, depth_host, rgb_out_host));
+    if (rc) return rc;
+    Staged s[] = {{rgb_host, 3}, {depth_host, 1}, {nullptr, 3, rgb_out_host}, {nullptr, 1, coc_out_host}};
+    return run_staged(c, BUF_DOF_STAGE, "the depth of field staging", s, (size_t)p->w * p->h,
+                      [&] { return dof_launch(c, *p, s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>()); });
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {

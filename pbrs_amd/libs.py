@@ -79,6 +79,12 @@ GPU_BLOOM_FUNCTIONS = _table({
 }, with_device={
     "pbrsb_bloom": [P] * 4,
 })
+# The depth-of-field call's entry points (include/pbrs_gpu.h, "depth of field"), likewise, under the prefix pbrsf_.
+GPU_DOF_FUNCTIONS = _table({
+    "pbrsf_dof_params_default": ([U32, U32, P], None),
+}, with_device={
+    "pbrsf_dof": [P] * 6,
+})
 HOST_FUNCTIONS = _table({
     "pbrs_host_scene_build": [P, C.POINTER(P)],
     "pbrs_host_scene_free": [P],
@@ -100,6 +106,7 @@ GPU_SYMBOLS, HOST_SYMBOLS = list(GPU_FUNCTIONS), list(HOST_FUNCTIONS)
 GPU_COMPARE_SYMBOLS = list(GPU_COMPARE_FUNCTIONS)
 GPU_DESPECKLE_SYMBOLS = list(GPU_DESPECKLE_FUNCTIONS)
 GPU_BLOOM_SYMBOLS = list(GPU_BLOOM_FUNCTIONS)
+GPU_DOF_SYMBOLS = list(GPU_DOF_FUNCTIONS)
 _host = _gpu = _hip = None
 
 
@@ -134,7 +141,7 @@ def gpu_lib():
         path = os.environ.get("PBRS_GPU_LIB") or lib_paths()[1]
         if not os.path.exists(path):
             raise PbrsError(f"{path} is missing: the HIP extension must be built (make -C pbrs_amd/csrc); there is no CPU fallback")
-        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS, **GPU_BLOOM_FUNCTIONS})
+        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS, **GPU_BLOOM_FUNCTIONS, **GPU_DOF_FUNCTIONS})
     return _gpu
 
 

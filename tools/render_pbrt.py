@@ -60,7 +60,13 @@ despeckled image and variance.  With --frames N --temporal every frame is despec
 pbrsb_bloom; the flag itself takes no value): the part of the image above the luminance T (default 1; 0 = the whole image) goes down a
 pyramid of N levels (1 .. 8, default 6), comes back up and is added to the image S times (default 0.05), or mixed into it
 (--bloom-mix: out = rgb + S (B - rgb), for T = 0 and S <= 1): also writes <out>.bloom.<ext>, and --display then shows the bloomed image.
-With --frames N --temporal every frame's first image is bloomed behind the filter (render_temporal's bloom=), <out>.NNNN.bloom.<ext>."""
+With --frames N --temporal every frame's first image is bloomed behind the filter (render_temporal's bloom=), <out>.NNNN.bloom.<ext>.
+--dof-focus D --dof-lens-radius A [--dof-max-radius R]: depth of field as an image operation (include/pbrs_gpu.h, pbrsf_dof): a thin lens
+of the aperture radius A (world units) focused on the plane at the distance D along the view axis (world units; api.lens turns both into
+the call's focus and scale), the circles clamped to R pixels (1 .. 16, default 8), from the depth AOV of the same samples: also writes
+<out>.dof.<ext>; --bloom and --display then act on the defocused image.  --dof-focus-pixel X Y in the place of --dof-focus focuses on
+what pixel (X, Y) shows (one image only).  With --frames N --temporal every frame's first image is defocused behind the filter and the
+upsample (render_temporal's dof=), <out>.NNNN.dof.<ext>."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -97,7 +103,12 @@ if "--bloom-mix" in sys.argv:
     if bloom is None:
         sys.exit("--bloom-mix goes with --bloom")
     bloom["mix"] = True
-for flag in ("--bloom-threshold", "--bloom-strength", "--bloom-levels", "--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+dof = None  # --dof-*: {"focus": D or None, "lens_radius": A, "max_radius": R, "focus_pixel": (X, Y) or None}
+if "--dof-focus-pixel" in sys.argv:  # takes two values
+    k = sys.argv.index("--dof-focus-pixel")
+    dof = {"focus_pixel": (int(sys.argv[k + 1]), int(sys.argv[k + 2]))}
+    del sys.argv[k:k + 3]
+for flag in ("--dof-focus", "--dof-lens-radius", "--dof-max-radius", "--bloom-threshold", "--bloom-strength", "--bloom-levels", "--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -114,6 +125,8 @@ for flag in ("--bloom-threshold", "--bloom-strength", "--bloom-levels", "--despe
             if bloom is None:
                 sys.exit("--bloom-threshold, --bloom-strength and --bloom-levels go with --bloom")
             bloom[flag[len("--bloom-"):]] = int(value) if flag == "--bloom-levels" else float(value)
+        elif flag in ("--dof-focus", "--dof-lens-radius", "--dof-max-radius"):
+            dof = dict(dof or {}, **{flag[len("--dof-"):].replace("-", "_"): int(value) if flag == "--dof-max-radius" else float(value)})
         elif flag == "--orbit":
             orbit = float(value)
         elif flag == "--spin":
@@ -156,6 +169,8 @@ if display is not None or auto_exposure:
     if display["curve"] not in pbrs_amd.DisplayParams.CURVES or display.get("encode", "srgb") not in pbrs_amd.DisplayParams.ENCODES:
         sys.exit("--display none|reinhard|aces [--encode sqrt|srgb]")
     display["auto"] = auto_exposure
+if dof is not None and ("lens_radius" not in dof or ("focus" in dof) == ("focus_pixel" in dof)):
+    sys.exit("--dof-lens-radius A goes with --dof-focus D or --dof-focus-pixel X Y [--dof-max-radius R]")
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -227,7 +242,11 @@ if frames:
         sys.exit("with --frames N, --despeckle goes with --temporal")
     if bloom is not None and not temporal:
         sys.exit("with --frames N, --bloom goes with --temporal")
+    if dof is not None and (not temporal or "focus_pixel" in dof):
+        sys.exit("with --frames N, --dof-focus goes with --temporal; --dof-focus-pixel goes with one image")
     extra = {} if despeckle is None else {"despeckle": despeckle}  # (a keyword of the sequences only when asked for)
+    if dof is not None:
+        extra["dof"] = dict(pbrs_amd.lens(hs.camera, dof["focus"], dof["lens_radius"]), max_radius=dof.get("max_radius", 8))
     if bloom is not None:
         extra["bloom"] = bloom
     spatial = True if spatial_variance else None
@@ -244,6 +263,8 @@ if frames:
         if temporal:
             pbrs_amd.write_image(f"{stem}.{k:04d}.accumulated{ext}", images[1])
             pbrs_amd.write_image(f"{stem}.{k:04d}.noisy{ext}", images[2])
+        if dof is not None:
+            pbrs_amd.write_image(f"{stem}.{k:04d}.dof{ext}", images[3]["dof"])
         if bloom is not None:
             pbrs_amd.write_image(f"{stem}.{k:04d}.bloom{ext}", images[3]["bloom"])
         if display is not None:
@@ -282,8 +303,22 @@ pbrs_amd.write_image(out, img)
 scored = {"image": img}  # what --compare-strata scores
 stem, ext = (out[:-4], out[-4:]) if out.lower().endswith((".exr", ".png")) else (out, ".exr")
 glare = img  # what --display shows
+if dof is not None:
+    z = buf["depth"] if want_buf else ctx.render_aovs(msaa, msaa, depth, 1, aovs=("depth",), integrator=integrator)[1]["depth"]  # the same samples' first hits
+    if "focus_pixel" in dof:  # the focus in the AOV's units; the scale follows it: lens() at any distance gives focus * scale
+        x, y = dof["focus_pixel"]
+        if not (0 <= x < z.shape[1] and 0 <= y < z.shape[0] and np.isfinite(z[y, x]) and z[y, x] > 0):
+            sys.exit(f"--dof-focus-pixel {x} {y}: nothing to focus on there")
+        unit = pbrs_amd.lens(hs.camera, 1.0, dof["lens_radius"])
+        thin = {"focus": float(z[y, x]), "scale": unit["focus"] * unit["scale"] / float(z[y, x])}
+    else:
+        thin = pbrs_amd.lens(hs.camera, dof["focus"], dof["lens_radius"])
+    thin["max_radius"] = dof.get("max_radius", 8)
+    glare = ctx.dof(img, z, **thin)
+    pbrs_amd.write_image(f"{stem}.dof{ext}", glare)
+    print(f"-> {stem}.dof{ext} ({pbrs_amd.DofParams.make(img.shape[1], img.shape[0], **thin).as_dict()})")
 if bloom is not None:
-    glare = ctx.bloom(img, **bloom)
+    glare = ctx.bloom(glare, **bloom)
     pbrs_amd.write_image(f"{stem}.bloom{ext}", glare)
     print(f"-> {stem}.bloom{ext} ({pbrs_amd.BloomParams.make(img.shape[1], img.shape[0], **bloom).as_dict()})")
 if display is not None:
