@@ -184,7 +184,8 @@ struct AnySel {
 };
 template <bool STATS, uint32_t FEAT>
 struct AnySel<0u, STATS, FEAT> {
-    typedef AnyWalk<STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP))> type;
+    // (k_shadow's: where the TLAS is not scanned, the tree walk passes over the light a ray was aimed at, AnyWalk::skip)
+    typedef AnyWalk<STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP)), !STATS && !(FEAT & PBRS_FEAT_FLAT_TLAS)> type;
 };
 #define PBRS_WALK_ARITY(STATS, FEAT) ((STATS) ? 0u : ((FEAT) & PBRS_FEAT_WIDE) ? 4u : 0u)
 #ifndef PBRS_NODE_STEPS_SHORT  // node steps per round in scenes with short walks: one (two, the second a lean one: C2 -2.3 %, C3 -3.2 %)

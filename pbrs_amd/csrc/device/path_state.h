@@ -30,7 +30,8 @@ struct PathState {
                   // drops at bounce 0, and by run_pass's memset when the pass has no bounce: nobody reads a slot before that.
     // Next-event estimation hand-off.  Shadow rays by position j in the bounce's shadow queue:
     //   sr[0][j] = origin.xyz, t_max        sr[1][j] = dir.xyz, item
-    //   sr[2][j] = lone ray: the path's radiance if the ray is unoccluded (k_shade has stored the occluded outcome in L)
+    //   sr[2][j] = lone ray: the path's radiance if the ray is unoccluded (k_shade has stored the occluded outcome in L); .w: the light
+    //              the ray was aimed at, where k_shadow need not visit it (scene.h, PBRS_SKIP_*; 0: none)
     // item = slot | 1 << 30 for a path's only shadow ray (the lane that traces it finishes the estimate), else
     // slot | ray index << 31: a path that casts both of its rays (the two MIS terms of an area light) cannot be finished
     // by either tracing lane — its terms wait in nee[] (by slot) and k_nee_resolve combines them with the two occlusion bytes.

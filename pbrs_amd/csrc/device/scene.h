@@ -91,6 +91,12 @@ struct DevScene {
 #define PBRS_FEAT_LDS_TOP 128u      // kernels only: the head of DevScene::nodes — a TLAS too large to scan — is copied into the block's LDS (scenes whose arrays do not fit as a whole)
 #define PBRS_FEAT_LDS_SCENE 64u     // kernels only: the arrays the walks read are copied into the block's LDS at kernel start (scenes of a few KB; kernels.h)
 #define PBRS_FEAT_FULL_STEPS 32u    // kernels only (with PBRS_FEAT_LONG_WALKS): a round's further node steps are full steps (kernels.h): scenes outside the guarded range of the division-free box test
+// The light a shadow ray was aimed at, as one word (0: none).  prepare_scene links an area light to the analytic instance that IS the
+// light (same shape, identity matrices); pbrs_upload_scene writes the two halves, as bit patterns, into pad[0] (instance + 1) and pad[1]
+// (flat leaf + 1) of the uploaded copy of the light record; k_shade puts them together in sr[2][j].w of a lone ray whose own test of that
+// instance is false, and k_shadow passes the instance's TLAS leaf over (traverse.h, AnyWalk::skip).
+#define PBRS_SKIP_INST_MASK 0x00ffffffu  // instance + 1 (a scene with more instances sets no links)
+#define PBRS_SKIP_FLAT_SHIFT 24          // above it: index + 1 of the instance's leaf among the leaf copies at DevScene::flat_off; 0 without them
 #define PBRS_FLAT_TLAS_MIN 2u
 // Largest TLAS the wave scans instead of walking (tools/tlas_probe.py, C5's scene family at 960x540, ms per 64 spp, walk vs
 // scan): closest hit 4.84 / 4.74 at 20 instances, 5.10 / 5.28 at 24, 5.66 / 6.15 at 30 — the scan only filters there and every

@@ -73,6 +73,26 @@ PD DevScene stage_shade_scene(const DevScene& G, uint32_t* lds_base) {
 static_assert(sizeof(pbrs_material) % 16 == 0 && sizeof(pbrs_bxdf) % 16 == 0 && sizeof(pbrs_area_light) % 16 == 0 && sizeof(pbrs_delta_light) % 16 == 0 &&
                   sizeof(pbrs_tri_shade) % 16 == 0,
               "stage_shade_scene copies 16-byte pieces");
+// The light a shadow ray was aimed at, for k_shadow to pass over (traverse.h, AnyWalk::skip).  A sample on an area light ends at t_max =
+// 0.999, just short of the light's own surface, so the box of the instance that IS the light passes k_shadow's TLAS test for nearly
+// every such ray, and the walk, having exhausted the terrain, still crossed two instance boundaries to learn that the light does not
+// occlude the sample taken on it.  `Lt` is the chosen light; pad[0] / pad[1] of the uploaded record name the instance that is the light
+// and its flat leaf (PBRS_SKIP_*; pbrs_upload_scene, from PreparedScene::light_link); `r` the ray exactly as it is stored in sr[0] / sr[1]: the
+// instance's own test — the function the walk would call, on the same floats — is evaluated here, where the wave is full and the records
+// are at hand, and the ray is tagged only if the value is FALSE.  Where it is true (a ray that grazes past its sample, a sample seen
+// from inside the light) the ray goes untagged and walks as before.  Lone rays only: a path's two MIS rays have no sr[2] record.
+template <uint32_t SPEC>
+PD uint32_t light_skip_tag(const DevScene& S, const pbrs_area_light& Lt, const ShadowRay& r) {
+    const uint32_t link = __float_as_uint(Lt.pad[0]) | __float_as_uint(Lt.pad[1]) << PBRS_SKIP_FLAT_SHIFT;
+    if (link == 0u) return 0u;
+    Cnt<false> cnt;
+    const pbrs_instance& in = S.inst[(link & PBRS_SKIP_INST_MASK) - 1u];
+    // a linked instance has its light's shape (host/scene_prepare.cpp): known at compile time where every light is a sphere
+    const uint32_t kind = (SPEC & PBRS_SHADE_LIGHT_SPHERE) ? (uint32_t)PBRS_SHAPE_SPHERE : in.shape_kind;
+    const bool own = analytic_occludes(S, in, kind, r.o, r.d, r.t_max, cnt);
+    return own ? 0u : link;
+}
+
 template <uint32_t INTEG, bool TEX, uint32_t SPEC>
 __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : PBRS_SHADE_WAVES) k_shade(DevScene G, PathState st, RenderConst rc, uint32_t bounce, const uint32_t* count, uint32_t n_direct,
                                               uint32_t* count_out, uint32_t* nee_queue, unsigned long long* nee_shadow_count, uint32_t sorted, const uint2* range,
@@ -106,6 +126,13 @@ __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : 
     sr0.o = sr0.d = sr1.o = sr1.d = gray(0.0f);
     sr0.t_max = sr1.t_max = -1.0f;
     f3 L_vis = gray(0.0f);  // a lone shadow ray: the path's radiance if it turns out unoccluded
+    // ... and the light it was aimed at (light_skip_tag).  The chosen area light waits in LDS until the rays are stored: a register
+    // carried through the shading code in between would cost the Lambert variants their sixth wave.  Not in the variants of scenes
+    // whose lights are all triangles (links name analytic instances: there are none) nor in those that carry the Fourier lobe, which
+    // live on spilled registers and would pay for the tag in scratch: their rays go untagged and walk as before.
+    constexpr bool TAGS = !(SPEC & (PBRS_SHADE_LIGHT_TRIANGLE | PBRS_SHADE_FOURIER));
+    __shared__ uint32_t s_light[TAGS ? 256 : 1];  // the chosen area light + 1; 0: none
+    if (TAGS) s_light[threadIdx.x] = 0u;
     // the path's next record, kept until the compaction below has given it a queue position
     f3 next_o = gray(0.0f), next_d = gray(0.0f), next_beta = gray(0.0f);
     uint64_t next_rng = 0;
@@ -319,6 +346,7 @@ __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : 
                     const pbrs_area_light& Lt = S.alights[chosen - S.n_delta];
                     const uint32_t lkind = (SPEC & PBRS_SHADE_LIGHT_SPHERE) ? (uint32_t)PBRS_SHAPE_SPHERE
                                            : (SPEC & PBRS_SHADE_LIGHT_TRIANGLE) ? (uint32_t)PBRS_SHAPE_TRIANGLE : Lt.shape_kind;
+                    if (TAGS) s_light[threadIdx.x] = chosen - S.n_delta + 1u;
                     f3 li, wi;
                     float lpdf;
                     ShadowRay vis;
@@ -500,17 +528,24 @@ __global__ void __launch_bounds__(256, (SPEC & 8u) ? PBRS_FOURIER_SHADE_WAVES : 
         st_stream(&st.q[out][2][j], pack4(next_beta, (uint32_t)(next_rng >> 32)));
     }
     if (both) nee_queue[b_nee + lane_prefix(m_nee)] = slot;
+    uint32_t skip_tag = 0u;  // travels in sr[2][j].w: lone rays (both MIS rays aim at the chosen light; a pair has no sr[2] record)
+    if (TAGS && lone) {
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));  // the word's address is formed again: kept from the write above, it held a register through the bounce code
+        const uint32_t light = s_light[t];
+        if (light != 0u) skip_tag = light_skip_tag<SPEC>(S, S.alights[light - 1u], cast0 ? sr0 : sr1);
+    }
     if (cast0) {
         const size_t j = (size_t)b_sh + lane_prefix(m_c0);
         st_stream(&st.sr[0][j], pack4(sr0.o, sr0.t_max));
         st_stream(&st.sr[1][j], pack4(sr0.d, slot | lone));
-        if (lone) st_stream(&st.sr[2][j], pack4(L_vis, 0.0f));
+        if (lone) st_stream(&st.sr[2][j], pack4(L_vis, skip_tag));
     }
     if (cast1) {
         const size_t j = (size_t)b_sh + s_cnt[wave][2] + lane_prefix(m_c1);
         st_stream(&st.sr[0][j], pack4(sr1.o, sr1.t_max));
         st_stream(&st.sr[1][j], pack4(sr1.d, slot | 0x80000000u | lone));
-        if (lone) st_stream(&st.sr[2][j], pack4(L_vis, 0.0f));
+        if (lone) st_stream(&st.sr[2][j], pack4(L_vis, skip_tag));
     }
 #ifdef PBRS_PROBE_SHADE
     PBRS_SHADE_MARK(7);  // compaction + queue / record writes

@@ -58,8 +58,17 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_WIDE) ? PBR
                     stk.item = idx;
                     const float4 q0 = st.sr[0][idx], q1 = st.sr[1][idx];
                     item = __float_as_uint(q1.w);
-                    if (item & 0x40000000u) l_vis = xyz(st.sr[2][idx]);
+                    uint32_t tag = 0u;
+                    if (item & 0x40000000u) {
+                        const float4 q2 = st.sr[2][idx];
+                        l_vis = xyz(q2);
+                        tag = __float_as_uint(q2.w);  // the light the ray was aimed at, where its own test is known to be false (AnyWalk::skip)
+                    }
                     walk.start(S, mk3(q0.x, q0.y, q0.z), mk3(q1.x, q1.y, q1.z), q0.w, stk);
+                    if constexpr (!STATS) {
+                        walk.skip = tag & PBRS_SKIP_INST_MASK;  // read by the walks of a TLAS that is not scanned
+                        walk.skip_scanned(tag);                 // ... and where it is: out of the mask the scan is about to hand the lane
+                    }
                     nrays++;
                     PBRS_KP_LANE(2, true);
                 }

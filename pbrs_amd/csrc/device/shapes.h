@@ -391,6 +391,40 @@ PD bool mesh_tri_pred(const pbrs_tri_verts& tv, f3 o, f3 d, float t_max) {
     return (s0 && s1 && s2) || (!s0 && !s1 && !s2);
 }
 
+// Instance::occludes (tlas/src/instance.rs:68-72) for an analytic instance: the world-space ray (o, d, t_max) into the shape's space by the
+// literal products, as the reference makes them, then the shape's own predicate.  Pure arithmetic on the ray and the records: whoever
+// evaluates it on the same floats gets the same value — the any-hit walks when they visit the instance's TLAS leaf
+// (traverse.h, AnyWalk::analytic_visit), and k_shade on the shadow ray it has just built towards a light that IS this instance
+// (shade.h, light_skip_tag), which is how a ray comes to pass such a leaf over.
+template <bool STATS>
+PD bool analytic_occludes(const DevScene& S, const pbrs_instance& in, uint32_t kind, f3 wo, f3 wd, float t_max, Cnt<STATS>& cnt) {
+    const f3 o = xf_apply(in.inv, wo, 1.0f), d = xf_apply(in.inv, wd, 0.0f);
+    const float* p = S.shapes[in.shape_index].p;
+    bool hit;
+    switch (kind) {
+        case PBRS_SHAPE_SPHERE:
+            CNT(spheres);
+            hit = sphere_occludes(ld3(p), p[3], o, d, t_max);
+            break;
+        case PBRS_SHAPE_QUAD:
+            CNT(quads);
+            hit = quad_occludes(ld3(p), ld3(p + 3), ld3(p + 6), o, d, t_max);
+            break;
+        case PBRS_SHAPE_CUBOID:  // Q14: the bbox slab test
+            CNT(cuboids);
+            hit = slab_test(ld3(p), ld3(p + 3), o, d, t_max);
+            break;
+        case PBRS_SHAPE_DISK:
+            CNT(disks);
+            hit = disk_occludes(ld3(p), ld3(p + 3), ld3(p + 6), o, d);
+            break;
+        default:  // a mesh or an IsolatedTriangle is not tested here
+            hit = false;
+            break;
+    }
+    return hit;
+}
+
 // A per-lane stack in LDS: entry `level` of a lane at base[level * 256] (lane-major rows of the 256-thread block:
 // a wave's 64 accesses to one level hit 64 consecutive dwords — no bank conflicts; the constant stride folds the
 // index arithmetic into the ds_read/ds_write address).

@@ -757,7 +757,7 @@ struct ClosestWalk {
 // the visiting order cannot change the answer and nothing is carried between instances, so BLAS children
 // are visited near-first (by the sign of the ray direction on the split axis), which reaches an occluder
 // sooner than the reference's left-first recursion.
-template <bool STATS, uint32_t FEAT>
+template <bool STATS, uint32_t FEAT, bool SKIP = false>  // SKIP: the tree walk passes the instance `skip` names over (k_shadow's walks; below)
 struct AnyWalk {
     RaySpace C;
     float t_max;
@@ -766,10 +766,26 @@ struct AnyWalk {
     uint32_t cand;  // leaves of the leaf copies at DevScene::flat_off still to visit: their boxes passed the shared scan (0 on a tree walk)
     bool in_blas, occluded, moved;  // moved: C is not the world ray (inst_kind bit 8: only its origin differs)
     uint32_t mode;
+    // The light the ray was aimed at.  The answer is an OR over the TLAS leaves the ray reaches of (the leaf's box passes AND the
+    // instance's own test passes); k_shade has evaluated the own test of one analytic instance — the one that is the light it sampled —
+    // on the very floats of this ray record (analytic_occludes, shapes.h) and tagged the ray only where the value was FALSE: that term is
+    // false whatever its box does, and the leaf need not be visited.  On a scanned TLAS the leaf's bit of `cand` is cleared in the
+    // refill: a lane that waits for the scan holds the bit in `cand` (skip_scanned; the field is idle until then, and the tag costs the
+    // scan no register of its own), scan_wave takes it out of the mask it hands the lane, and nothing of the tag outlives the refill.
+    // A walk of a scene whose TLAS is not scanned (SKIP) keeps instance + 1 in `skip` (0: none) and passes the leaf over in the node
+    // step that pops it.  A ray that walks the tree of a scanned TLAS (outside the guarded range: rare) is not worth a register of the
+    // scanning kernels: it visits the light as before.  The counting instantiations never skip: their counts are the oracle's.
+    uint32_t skip;
+    PD bool skips(uint32_t inst) const { return SKIP && !STATS && inst + 1u == skip; }
+    PD void skip_scanned(uint32_t tag) {  // between start() and scan_wave(), a lane that has just been given a ray; tag: PBRS_SKIP_* (scene.h)
+        const uint32_t leaf = tag >> PBRS_SKIP_FLAT_SHIFT;  // flat-leaf index + 1
+        if (!STATS && mode == PBRS_WALK_SCAN && leaf != 0u) cand = 1u << (leaf - 1u);
+    }
     PBRS_TP_FIELDS
 
     PD void start(const DevScene& S, f3 o, f3 d, float tmax, LaneStack stk) {
         C = make_space(o, d, S.fast_slab != 0);
+        skip = 0u;
         moved = false;
         t_max = tmax;
         in_blas = false;
@@ -794,7 +810,7 @@ struct AnyWalk {
         const uint32_t mine = FlatScan::run(S, mode == PBRS_WALK_SCAN, C, t_max, tested);
         if (STATS) cnt.c.tlas_nodes += tested;
         if (mode == PBRS_WALK_SCAN) {
-            cand = mine;
+            cand = mine & ~cand;  // (cand: the leaf the ray need not visit, skip_scanned; else 0)
             mode = PBRS_WALK_NODE;
         }
     }
@@ -846,6 +862,7 @@ struct AnyWalk {
             leaf_end = node.a + (node.b & ~PBRS_LEAF_FLAG);
             if (leaf_end != leaf_a) mode = PBRS_WALK_LEAF;
         } else {
+            if (skips(node.a)) return;  // passed over: the next pending entry is the next step's
             leaf_a = node.a;  // the instance, until xfer_step replaces it by the held primitive
             inst_kind = (node.b >> PBRS_TLAS_LEAF_KIND_SHIFT) & 7u;
             mode = PBRS_WALK_XFER;
@@ -879,6 +896,7 @@ struct AnyWalk {
             leaf_end = node.a + (node.b & ~PBRS_LEAF_FLAG);
             if (leaf_end != leaf_a) mode = PBRS_WALK_LEAF;
         } else {
+            if (skips(node.a)) return;
             leaf_a = node.a;
             inst_kind = (node.b >> PBRS_TLAS_LEAF_KIND_SHIFT) & 7u;
             mode = PBRS_WALK_XFER;
@@ -958,34 +976,8 @@ struct AnyWalk {
     // Instance::occludes (instance.rs:68-72) for an analytic shape in one go, see ClosestWalk::analytic_visit; an occluder
     // ends the walk (mode DONE, occluded set).
     PD void analytic_visit(const DevScene& S, const pbrs_instance& in, Cnt<STATS>& cnt) {
-        bool hit;
-        {
-            if (!(FEAT & PBRS_FEAT_ANALYTIC)) return;
-            const f3 o = xf_apply(in.inv, C.o, 1.0f), d = xf_apply(in.inv, C.d, 0.0f);
-            const float* p = S.shapes[in.shape_index].p;
-            switch (inst_kind) {
-                case PBRS_SHAPE_SPHERE:
-                    CNT(spheres);
-                    hit = sphere_occludes(ld3(p), p[3], o, d, t_max);
-                    break;
-                case PBRS_SHAPE_QUAD:
-                    CNT(quads);
-                    hit = quad_occludes(ld3(p), ld3(p + 3), ld3(p + 6), o, d, t_max);
-                    break;
-                case PBRS_SHAPE_CUBOID:  // Q14: the bbox slab test
-                    CNT(cuboids);
-                    hit = slab_test(ld3(p), ld3(p + 3), o, d, t_max);
-                    break;
-                case PBRS_SHAPE_DISK:
-                    CNT(disks);
-                    hit = disk_occludes(ld3(p), ld3(p + 3), ld3(p + 6), o, d);
-                    break;
-                default:  // PBRS_SHAPE_TRIANGLE never gets here
-                    hit = false;
-                    break;
-            }
-        }
-        if (hit) {
+        if (!(FEAT & PBRS_FEAT_ANALYTIC)) return;
+        if (analytic_occludes(S, in, inst_kind, C.o, C.d, t_max, cnt)) {  // (shapes.h: the function k_shade runs on a ray aimed at this instance)
             occluded = true;
             mode = PBRS_WALK_DONE;
         }

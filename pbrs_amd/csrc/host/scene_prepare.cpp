@@ -130,6 +130,23 @@ uint32_t split_planes(const std::vector<pbrs_node>& nodes, uint32_t x) {
     return pbrs_plane_pack(qd, qu);
 }
 
+// The analytic instance that IS area light `L` (prepare_scene, PreparedScene::light_link): an instance of the light's shape kind whose shape parameters are the light's
+// world-space ones bit for bit and whose two matrices are bit-exactly the identity — so that a sample on the light lies on the instance.
+// What the kinds compare: a sphere's centre and radius, a disk's centre, normal and radial, a quad's origin and two sides.
+bool is_light_instance(const pbrs_scene_desc& d, const pbrs_area_light& L, const pbrs_instance& in) {
+    const uint32_t k = L.shape_kind;
+    if (!(k == PBRS_SHAPE_SPHERE || k == PBRS_SHAPE_DISK || k == PBRS_SHAPE_QUAD) || in.shape_kind != k || in.shape_index >= d.n_shapes) return false;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t one = pn_bits(r == c ? 1.0f : 0.0f);
+            if (pn_bits(in.inv[r][c]) != one || pn_bits(in.fwd[r][c]) != one) return false;
+        }
+    const float* p = d.shapes[in.shape_index].p;
+    for (uint32_t j = 0, n = k == PBRS_SHAPE_SPHERE ? 4u : 9u; j < n; ++j)
+        if (pn_bits(p[j]) != pn_bits(L.p[j])) return false;
+    return true;
+}
+
 }  // namespace
 
 // Host-side shape checks: every index the kernels dereference must be in range before any launch.
@@ -413,6 +430,19 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
         if (same && k0 == PBRS_SHAPE_SPHERE) f.light_spec = PBRS_SHADE_LIGHT_SPHERE;
         if (same && k0 == PBRS_SHAPE_TRIANGLE) f.light_spec = PBRS_SHADE_LIGHT_TRIANGLE;
     }
+    // The light a shadow ray is aimed at (device/scene.h, PBRS_SKIP_*): per area light, the first instance that is the light itself, and
+    // that instance's leaf among the leaf copies where k_shadow scans them.  Which instance a light is linked to only decides where
+    // the saving lies: k_shade tags a ray only where the linked instance's own test is false for it (device/shade.h, light_skip_tag).
+    P.light_link.assign(d.n_area_lights, 0u);
+    for (uint32_t l = 0; l < d.n_area_lights; ++l)
+        for (uint32_t i = 0; i < d.n_instances && i + 1u <= PBRS_SKIP_INST_MASK; ++i) {
+            if (!is_light_instance(d, d.area_lights[l], d.instances[i])) continue;
+            uint32_t leaf = 0u;
+            for (uint32_t k = S.n_flat; k-- > 0u;)
+                if (nodes[S.flat_off + k].a == i) leaf = k + 1u;
+            P.light_link[l] = (i + 1u) | leaf << PBRS_SKIP_FLAT_SHIFT;
+            break;
+        }
     // what the traversal kernels may stage in LDS next to the stack rows (choose_kernels)
     f.stack_bytes = (size_t)lv.stack * kBlock * sizeof(uint32_t);
     f.wide_stack_bytes = (size_t)S.wide_cap * kBlock * sizeof(uint32_t);
@@ -451,6 +481,16 @@ uint32_t pack_wide_leaves(PreparedScene& P) {
             ++packed;
         }
     return packed;
+}
+
+// What pbrs_upload_scene does to its copy of the area lights: the links ride in the records' two padding words, as bit patterns
+// (pad[0]: instance + 1, pad[1]: flat leaf + 1; 0: none).  The description's own records are not written.
+void write_light_links(const PreparedScene& P, std::vector<pbrs_area_light>& lights) {
+    for (size_t l = 0; l < lights.size() && l < P.light_link.size(); ++l) {
+        const uint32_t inst = P.light_link[l] & PBRS_SKIP_INST_MASK, leaf = P.light_link[l] >> PBRS_SKIP_FLAT_SHIFT;
+        std::memcpy(&lights[l].pad[0], &inst, sizeof inst);
+        std::memcpy(&lights[l].pad[1], &leaf, sizeof leaf);
+    }
 }
 
 }  // namespace pbrs

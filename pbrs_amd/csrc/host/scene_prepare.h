@@ -36,6 +36,7 @@ struct PreparedScene {
     std::vector<pbrs_instance> inst; // DevScene::inst: pad[0] the shading class, pad[1] the wide root, blas_root and flags as the walks read them
     std::vector<pbrs_wnode> wide;    // DevScene::wnodes; empty where the scene keeps the binary walks (S.wnodes stays null)
     std::vector<uint32_t> tri_leaf;  // DevScene::tri_leaf: per triangle record, the BLAS leaf of `nodes` that holds it; built with the wide nodes, empty without them
+    std::vector<uint32_t> light_link;  // per area light: the analytic instance that is the light, as a PBRS_SKIP_* word (device/scene.h); 0: none
     uint32_t wide_levels = 0;        // wide nodes on the longest way down a BLAS (0: no wide nodes)
     SceneFacts facts;
     uint32_t stack_depth = 0;      // entries of a lane's traversal stack
@@ -47,5 +48,7 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& levels,
 // What pbrs_upload_scene does to `P.wide` before it uploads it: the references to leaves of one to four triangles take the form that names
 // the triangles themselves (device/scene.h, PBRS_WREF_PACKED).  Returns how many it rewrote.
 uint32_t pack_wide_leaves(PreparedScene& P);
+// ... and to its copy of the description's area lights before it uploads that: `P.light_link` into the records' padding words.
+void write_light_links(const PreparedScene& P, std::vector<pbrs_area_light>& lights);
 
 }  // namespace pbrs

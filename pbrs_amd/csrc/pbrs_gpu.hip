@@ -1131,7 +1131,11 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     if ((rc = upload(c, d->tri_shade, d->n_triangles, &S.ts))) return rc;
     if ((rc = upload(c, d->materials, d->n_materials, &S.mats))) return rc;
     if ((rc = upload(c, d->bxdfs, d->n_bxdfs, &S.bxdfs))) return rc;
-    if ((rc = upload(c, d->area_lights, d->n_area_lights, &S.alights))) return rc;
+    {  // the lights' links to the instances that are the lights ride in the padding of the uploaded copy (host/scene_prepare.h)
+        std::vector<pbrs_area_light> lights(d->area_lights, d->area_lights + d->n_area_lights);
+        write_light_links(P, lights);
+        if ((rc = upload(c, lights.data(), lights.size(), &S.alights))) return rc;
+    }
     if ((rc = upload(c, d->delta_lights, d->n_delta_lights, &S.dlights))) return rc;
     if ((rc = upload(c, d->textures, d->n_textures, &S.textures))) return rc;
     if ((rc = upload(c, d->tex_floats, d->n_tex_floats, &S.tex_floats))) return rc;
