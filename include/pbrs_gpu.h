@@ -1406,6 +1406,83 @@ void pbrsf_dof_params_default(uint32_t w, uint32_t h, pbrs_dof_params* out);
 int pbrsf_dof(pbrs_ctx*, const pbrs_dof_params*, const float* rgb_host, const float* depth_host, float* rgb_out_host, float* coc_out_host);
 int pbrsf_dof_device(pbrs_ctx*, const pbrs_dof_params*, const float* rgb_device, const float* depth_device, float* rgb_out_device, float* coc_out_device);
 
+/* ---- motion blur ------------------------------------------------------------------------------------------------- */
+/* A shutter as an image operation: every frame of a sequence is an instantaneous exposure, and this call smears it afterwards along
+ * the motion vector AOV (pbrs_motion_vectors above: per pixel, where the surface point was one frame ago minus where it is, in pixels,
+ * through the camera's motion and each instance's).  It is not a plain directional blur: a fast object smears over a static background,
+ * a static object in front keeps its edge against a moving background, and a moving object's thinning edge lets the background show
+ * through.  That takes the depth, every pixel's own speed and a dominant velocity per neighbourhood (McGuire et al. 2012, "A
+ * reconstruction filter for plausible motion blur"; Jimenez 2014, "Next generation post processing in Call of Duty: Advanced
+ * Warfare").  An image operation like pbrsf_dof: it needs a context (device, stream) and no uploaded scene.  rgb and rgb_out are w * h
+ * pixels, row-major, 3 floats each; depth is w * h floats as pbrs_aov_buffers writes it, +inf where nothing was hit; motion is w * h
+ * pixels of 2 floats, exactly what pbrs_motion_vectors writes.  All arithmetic is f32 without fused multiply-add, in the order written;
+ * divisions and square roots are correctly rounded; pn_* is include/pbrs_numeric.h.  No sum here depends on the launch shape or on
+ * arrival order: a CPU model of this text gives the same bytes.  R = max_radius, S = taps.
+ *   0. shutter == 0 comes before everything else: rgb_out gets rgb's bits (a copy) and velocity_out, where given, +0.
+ *   1. Velocity, the half-exposure vector: the exposure is centred on the frame, so a point is seen from -v to +v.  k = shutter * 0.5f;
+ *      v(p) = (motion(p).x * k, motion(p).y * k).  A component of motion(p) that does not pass pn_isfinite gives v = (+0, +0).
+ *      ll = v.x * v.x + v.y * v.y; len = sqrt(ll).  If len > (float)R: s = (float)R / len; v = (v.x * s, v.y * s); ll and len are
+ *      computed again from that v; and len = len < (float)R ? len : (float)R.
+ *   2. The dominant velocity of a tile.  Tiles are 16 x 16 pixels, anchored at (0, 0): part of the contract.  vn(tile) is v(q) of the
+ *      pixel q with the largest ll over the tile grown by R pixels on every side and cut at the image; among equal ll the lowest
+ *      row-major index y * w + x wins.  (ll, index) is a total order (ll is never NaN), so the maximum is the same in any reduction
+ *      shape.  Every pixel whose smear can reach a pixel of the tile has len <= R and lies in that window, which is why R ends at the
+ *      tile's size.  If len(q) <= 0.5 for that q, every pixel of the tile gets its rgb bits.
+ *   3. Gather, for a pixel p of any other tile.  A p with a channel that does not pass pn_isfinite passes through with its bits.
+ *      zeff(p) = depth(p) > 0 ? depth(p) : +inf (zero, negative, NaN: unknown, taken as far).  j = 0, or with PBRS_MOTION_BLUR_JITTER
+ *      j = ((float)M[y & 3][x & 3] + 0.5f) / 16.0f - 0.5f with the display transform's 4 x 4 Bayer matrix M.  Start from
+ *      acc = (+0, +0, +0), W = +0, n = 0, and for i = 0 .. S - 1:
+ *        t = (((float)i + 0.5f) + j) / (float)S * 2.0f - 1.0f.
+ *        dx = (int)pn_floor(vn.x * t + 0.5f), dy = (int)pn_floor(vn.y * t + 0.5f), q = p + (dx, dy); |dx|, |dy| <= R.
+ *        (dx, dy) == (0, 0): left out.  q outside the image: left out.  rgb(q) has a channel that does not pass pn_isfinite: left out.
+ *        dist = sqrt((float)(dx * dx + dy * dy)).
+ *        f = 1.0f where zeff(q) <= zeff(p); otherwise a = 1.0f - (zeff(q) - zeff(p)) / (z_rel * zeff(p)); f = a > 0 ? a : +0.  An
+ *            unordered comparison is false.  A q in front of p or level with it gives 1; f falls to 0 as q goes behind p by the
+ *            fraction z_rel of p's depth.
+ *        cyl(d, l) = c = (l - d) + 0.5f; c = c > 0 ? c : +0; c = c < 1.0f ? c : 1.0f: a line of the length l with a one-pixel soft end.
+ *        wgt = f * cyl(dist, len(q)) + (1.0f - f) * cyl(dist, len(p)).  A tap in front spreads by its own speed; a tap behind shows
+ *            only as far as p itself is smeared thin.
+ *        wgt <= 0: left out.  Otherwise acc.c = acc.c + wgt * rgb(q).c per channel; W = W + wgt; n = n + 1.
+ *      n == 0 gives rgb(p)'s bits; otherwise out.c = (acc.c + ((float)S - W) * rgb(p).c) / (float)S.  The slices of the exposure that
+ *      no tap claims show the pixel itself: coverage is the share of the line's taps, not a ratio of heuristic weights.
+ *   4. velocity_out, optional (NULL: not wanted), w * h pixels of 2 floats: v(p) of step 1.
+ * Rules.  (a) With rgb times 2^j the output is 2^j times the output, bit for bit, while nothing overflows or becomes a nonzero value
+ * below the smallest normal f32.  (b) With depth times 2^j, likewise, nothing changes.  (c) Where every len is <= 0.5 the output is rgb,
+ * bit for bit.  (d) A pixel with v = 0 takes nothing from a pixel behind it (f == 0): its weight is cyl(dist, 0) with dist >= 1.
+ * (e) A tap that is left out is not added at all, so an implementation may cut its loops wherever it can prove wgt <= 0, and nothing
+ * changes.
+ * What the method cannot know: the background hidden behind a moving object is taken from its visible neighbours; the motion within
+ * the exposure is taken as linear and centred on the frame; shadows and reflections of movers have no vectors (the limit the temporal
+ * section states), so they stay sharp.
+ * Pointers are host memory for pbrsm_motion_blur, which stages the planes on first use (44 B per pixel) and synchronises before it
+ * returns; device memory for pbrsm_motion_blur_device, which runs on the context's stream (pbrs_set_stream honoured) and does not wait:
+ * one launch, no scratch, no allocation.  rgb_out must not be rgb: a gather reads its neighbours.  Any other overlap is the caller's
+ * error.
+ * Refused, in this order, with PBRS_E_INVALID (the context stays usable): NULL params, rgb, depth, motion or rgb_out; rgb_out == rgb;
+ * w or h 0; max_radius 0 or above PBRS_MOTION_BLUR_MAX_RADIUS; taps below 2 or above PBRS_MOTION_BLUR_MAX_TAPS; flag bits other than
+ * PBRS_MOTION_BLUR_JITTER; a non-zero reserved word; shutter not finite or outside 0 .. 1; z_rel not finite or <= 0.  Then w * h above
+ * 2^28: PBRS_E_LIMIT. */
+#define PBRS_MOTION_BLUR_MAX_RADIUS 16u
+#define PBRS_MOTION_BLUR_MAX_TAPS 64u
+#define PBRS_MOTION_BLUR_JITTER 1u /* flags: each pixel shifts its taps by a 4 x 4 ordered offset, banding becomes a fine pattern */
+typedef struct pbrs_motion_blur_params {
+    uint32_t w, h;       /* image size */
+    uint32_t max_radius; /* 1 .. PBRS_MOTION_BLUR_MAX_RADIUS: pixels, the longest half-exposure vector */
+    uint32_t taps;       /* 2 .. PBRS_MOTION_BLUR_MAX_TAPS: samples along the line from -vn to +vn */
+    uint32_t flags;      /* 0 or PBRS_MOTION_BLUR_JITTER */
+    float shutter;       /* finite, 0 .. 1: the open fraction of the frame interval, centred on the frame */
+    float z_rel;         /* finite, > 0: the relative depth difference over which a tap goes from level to behind */
+    uint32_t reserved;   /* 0 */
+} pbrs_motion_blur_params; /* 32 B */
+/* (The three functions' prefix is pbrsm_; the struct and the constants above carry pbrs_.)
+ * Filler: max_radius 16, taps 16, flags 0, shutter 0.5 (a 180 degree shutter), z_rel 0.05, reserved 0: choices, not measurements;
+ * `out` NULL does nothing.  Host code: needs no context. */
+void pbrsm_motion_blur_params_default(uint32_t w, uint32_t h, pbrs_motion_blur_params* out);
+int pbrsm_motion_blur(pbrs_ctx*, const pbrs_motion_blur_params*, const float* rgb_host, const float* depth_host, const float* motion_host,
+                      float* rgb_out_host, float* velocity_out_host);
+int pbrsm_motion_blur_device(pbrs_ctx*, const pbrs_motion_blur_params*, const float* rgb_device, const float* depth_device,
+                             const float* motion_device, float* rgb_out_device, float* velocity_out_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -641,6 +641,50 @@ def _dof_params(dof):
     return of_frame
 
 
+class MotionBlurParams(C.Structure):
+    """pbrs_motion_blur_params (include/pbrs_gpu.h, "motion blur"): image size, the longest half-exposure vector in pixels (also the
+    gather's reach), the taps along the line, the jitter flag, the open fraction of the frame interval and the relative depth
+    difference over which a tap goes from level to behind."""
+    MAX_RADIUS, MAX_TAPS, JITTER = 16, 64, 1
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("max_radius", C.c_uint32), ("taps", C.c_uint32), ("flags", C.c_uint32), ("shutter", C.c_float),
+                ("z_rel", C.c_float), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def make(cls, w, h, max_radius=16, taps=16, jitter=False, shutter=0.5, z_rel=0.05):
+        """The defaults are pbrsm_motion_blur_params_default's."""
+        p = cls()
+        p.w, p.h = w, h
+        p.max_radius, p.taps, p.flags, p.shutter, p.z_rel = max_radius, taps, cls.JITTER if jitter else 0, shutter, z_rel
+        return p
+
+    def as_dict(self):
+        return {"w": self.w, "h": self.h, "max_radius": self.max_radius, "taps": self.taps, "flags": self.flags, "shutter": self.shutter, "z_rel": self.z_rel}
+
+
+def _motion_blur_params(motion_blur):
+    """render_temporal's / render_animation's `motion_blur` -> a function frame index -> MotionBlurParams.make's keywords, or None: None
+    or False is the sequence without the step, True the defaults, a dict the keywords of every frame, a list or tuple of dicts one per
+    frame (a sequence longer than the list fails at the frame that has none).  An unknown keyword fails here."""
+    if motion_blur is None or motion_blur is False:
+        return None
+    if motion_blur is True:
+        motion_blur = {}
+    per_frame = isinstance(motion_blur, (list, tuple))
+    if not (isinstance(motion_blur, dict) or (per_frame and len(motion_blur) and all(isinstance(d, dict) for d in motion_blur))):
+        raise ValueError("motion_blur is None, True, a dict of MotionBlurParams.make's keywords or a list of such dicts, one per frame")
+    frames = [dict(d) for d in (motion_blur if per_frame else [motion_blur])]
+    for d in frames:
+        MotionBlurParams.make(1, 1, **d)
+
+    def of_frame(i):
+        if not per_frame:
+            return frames[0]
+        if i >= len(frames):
+            raise ValueError(f"motion_blur holds {len(frames)} frames' keywords: none for frame {i}")
+        return frames[i]
+    return of_frame
+
+
 class SpatialVarianceGuides(C.Structure):
     """pbrs_spatial_variance_guides: depth, normal and instance of the frame; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("depth", "normal", "instance")]

@@ -15,12 +15,12 @@ import numpy as np
 from .abi import (AOV_NAMES, AOVS, BSDF_OPS, BSDF_QUERY_WORDS, BSDF_RESULT_WORDS, DENOISE_GUIDES, HIT_DTYPE, INTEGRATORS, MATTE_LAYERS, NUMERIC_FNS, NUMERIC_K_FNS, PASS_CHANNELS, PASSES,  # noqa: F401
                   SPATIAL_VARIANCE_PLANES, TEMPORAL_FRAME, TEMPORAL_GUIDES, TEMPORAL_HISTORY, VARIANCE, AovBuffers, BloomParams, Camera, CompareMaps, CompareParams, CompareResult,
                   DenoiseGuides, DenoiseParams, DespeckleIO, DespeckleParams, DespeckleResult, DofParams,
-                  DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, Node, PassBuffers,
+                  DenoiseVarGuides, DenoiseVarParams, DisplayIO, DisplayParams, HistoryClipParams, InstanceMotion, MatteBuffers, MatteParams, MotionBlurParams, Node, PassBuffers,
                   PixelFilter, RenderParams, SceneDesc, SpatialVarianceGuides, SpatialVarianceParams, Stats, TemporalFrame, TemporalGuides, TemporalHistory,
-                  TemporalParams, UpsampleParams, _aov_names, _bloom_params, _DenoiseParamsMixin, _despeckle_params, _display_params, _dof_params, _history_clip, _matte_select, _motion_args, _pass_names,
+                  TemporalParams, UpsampleParams, _aov_names, _bloom_params, _DenoiseParamsMixin, _despeckle_params, _display_params, _dof_params, _history_clip, _matte_select, _motion_args, _motion_blur_params, _pass_names,
                   _reference_frame, _reference_frames, _temporal_struct, _upscale_params, lens, scaled_camera)
 from .devmem import DeviceBuffers
-from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_DOF_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_DOF_SYMBOLS, GPU_MOTION_BLUR_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
 from .spec import SceneSpec  # noqa: F401
 
 
@@ -71,7 +71,8 @@ def _guide_bytes(guides, w, h, suffix=""):
     return {n + suffix: DENOISE_GUIDES[n][0] * w * h * 4 for n in guides}
 
 
-def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False, bloom=False, dof=False):
+def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, reference=False, despeckle=False, bloom=False, dof=False,
+                      motion_blur=False):
     """{name: bytes} of the device buffers of a frame sequence (Context._temporal_frames) that runs at w x h and shows fw x fh: the
     frame's image, the filtered one, the two variances; two ping-pong halves ("0", "1") of the guides the next frame is tested against
     and of the history; the other guides once; and what each option that is on adds."""
@@ -96,6 +97,10 @@ def _sequence_buffers(w, h, fw, fh, guides, motion_vectors, upscale, display, re
         sizes["bloom"] = 3 * fw * fh * 4
     if dof:
         sizes["dof"] = 3 * fw * fh * 4
+    if motion_blur:
+        sizes["mblur"] = 3 * fw * fh * 4
+        if upscale or not motion_vectors:  # the step needs vectors of the full size: the "motion" buffer is the chain's, at its size
+            sizes["mblur_motion"] = 2 * fw * fh * 4
     return sizes
 
 
@@ -951,6 +956,35 @@ class Context:
         self._check(self._L.pbrsf_dof_device(self._h, C.addressof(p), C.c_void_p(rgb_ptr), C.c_void_p(depth_ptr), C.c_void_p(out_ptr), C.c_void_p(coc_ptr)),
                     "pbrsf_dof_device")
 
+    def motion_blur(self, rgb, depth, motion, return_velocity=False, **params):
+        """The (h, w, 3) f32 image `rgb` through a shutter (include/pbrs_gpu.h, pbrsm_motion_blur): smeared along the (h, w, 2) f32
+        motion vector AOV `motion` of the same frame (motion_vectors(): where each surface point was one frame ago minus where it is,
+        in pixels), with the (h, w) f32 depth AOV `depth` deciding what covers what -> the (h, w, 3) f32 image; with return_velocity
+        also the (h, w, 2) f32 clamped half-exposure vectors.  params: MotionBlurParams.make's keywords."""
+        rgb, depth = np.ascontiguousarray(rgb, dtype=np.float32), np.ascontiguousarray(depth, dtype=np.float32)
+        motion = np.ascontiguousarray(motion, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"the image is (h, w, 3), not {rgb.shape}")
+        h, w, _ = rgb.shape
+        if depth.shape != (h, w):
+            raise ValueError(f"the depth is ({h}, {w}) like the image, not {depth.shape}")
+        if motion.shape != (h, w, 2):
+            raise ValueError(f"the motion vectors are ({h}, {w}, 2) like the image, not {motion.shape}")
+        p = MotionBlurParams.make(w, h, **params)
+        out = np.empty((h, w, 3), dtype=np.float32)
+        vel = np.empty((h, w, 2), dtype=np.float32) if return_velocity else None
+        self._check(self._L.pbrsm_motion_blur(self._h, C.addressof(p), rgb.ctypes.data, depth.ctypes.data, motion.ctypes.data, out.ctypes.data,
+                                              vel.ctypes.data if return_velocity else None), "pbrsm_motion_blur")
+        return (out, vel) if return_velocity else out
+
+    def motion_blur_device(self, rgb_ptr, depth_ptr, motion_ptr, out_ptr, w, h, velocity_ptr=None, **params):
+        """motion_blur() on caller-owned device memory: (h, w, 3) f32 in and out, which must differ, the (h, w) f32 depth, the
+        (h, w, 2) f32 motion vectors and the optional (h, w, 2) f32 velocities.  Runs on the context's stream behind whatever was
+        queued there and does not wait: valid after `collect_stats()`."""
+        p = MotionBlurParams.make(w, h, **params)
+        self._check(self._L.pbrsm_motion_blur_device(self._h, C.addressof(p), C.c_void_p(rgb_ptr), C.c_void_p(depth_ptr), C.c_void_p(motion_ptr),
+                                                     C.c_void_p(out_ptr), C.c_void_p(velocity_ptr)), "pbrsm_motion_blur_device")
+
     def _render_guides_device(self, rgb_device_ptr, guide_device_ptrs, seed, camera=None):
         """The full-size first-hit guides of guided upsampling: a one-sample render of `seed` through the path integrator at depth 1 (the
         cheapest route whose first hits are the jittered ones the low-resolution AOVs average; the visualisers shoot through the
@@ -1043,8 +1077,16 @@ class Context:
         with `upscale` the full-size guide render's) behind the filter and the upsample, on the same stream, into one more colour
         buffer: a lens blurs before the sensor glares, so `bloom` then reads the defocused image and `display` reads bloom's or,
         without bloom, the defocused one; `reference` keeps scoring the first image as it was, and the stats gain "dof", the (h, w, 3)
-        f32 defocused image."""
+        f32 defocused image.  `motion_blur` (a keyword taken out of `params` likewise): None is that chain, with its allocations and
+        tuples; True, a dict of MotionBlurParams.make's keywords, or a list of such dicts, one per frame, queues motion_blur_device
+        between the depth of field and the bloom, on the same stream, into one more colour buffer: it reads the defocused image (or the
+        first one), the depth of its size and the motion vectors of its size against the previous frame's camera (the chain's own
+        where render_animation's motion_vectors is on and there is no `upscale`; otherwise motion_vectors_device into a buffer of the
+        step's, with `upscale` from the full-size guide render's depth and instance ids through the full-size cameras), `bloom` and
+        `display` then read the blurred image, and the stats gain "motion_blur", the (h, w, 3) f32 image.  The first frame has no
+        previous one: its "motion_blur" is a copy of what the step read."""
         reference, despeckle, bloom, dof = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None), params.pop("dof", None)
+        motion_blur = params.pop("motion_blur", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides:
             raise ValueError("render_temporal reprojects through the depth AOV: guides must hold \"depth\"")
@@ -1055,7 +1097,7 @@ class Context:
             _reference_frame(_reference_frames(reference), 0, self.scene.width, self.scene.height)
         frames = [(None, cam, seed) for cam, seed in zip(cameras, seeds)]
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, False, spatial, clip, display,
-                                         upscale, reference, despeckle, bloom, dof):
+                                         upscale, reference, despeckle, bloom, dof, motion_blur):
             yield out[:4] if reference is None else out[:4] + out[5:]
 
     def render_animation(self, frames, strata_x, strata_y, depth, guides=("albedo", "normal", "depth", "instance"), samples_per_pass=0,
@@ -1069,17 +1111,19 @@ class Context:
         there is none).  `guides` must hold "depth" and "instance"; every scene must have the first one's film size.  Lights that move and the
         shadows of moving instances are not followed (include/pbrs_gpu.h) unless `clip` bounds their lag: as render_temporal's, and so
         are `spatial`, `display`, `upscale` (the motion vectors are then the low-resolution chain's) and the keyword `reference`, whose
-        CompareResult is the last entry, and the keywords `despeckle`, `bloom` and `dof`."""
+        CompareResult is the last entry, and the keywords `despeckle`, `bloom`, `dof` and `motion_blur` (whose vectors follow the
+        instances through the frame's motion table)."""
         reference, despeckle, bloom, dof = params.pop("reference", None), params.pop("despeckle", None), params.pop("bloom", None), params.pop("dof", None)
+        motion_blur = params.pop("motion_blur", None)
         self._denoise_guide_names(guides)
         if "depth" not in guides or "instance" not in guides:
             raise ValueError("render_animation reprojects through the depth AOV and the instance ids: guides must hold \"depth\" and \"instance\"")
         for out in self._temporal_frames(frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial, clip, display,
-                                         upscale, reference, despeckle, bloom, dof):
+                                         upscale, reference, despeckle, bloom, dof, motion_blur):
             yield (out[:5] if motion_vectors else out[:4]) + (() if reference is None else out[5:])
 
     def _temporal_frames(self, frames, strata_x, strata_y, depth, guides, samples_per_pass, temporal, params, motion_vectors, spatial=None,
-                         clip=None, display=None, upscale=None, reference=None, despeckle=None, bloom=None, dof=None):
+                         clip=None, display=None, upscale=None, reference=None, despeckle=None, bloom=None, dof=None, motion_blur=None):
         """The device chain of render_temporal and render_animation over (HostScene or None, Camera or None, seed) -> (denoised,
         accumulated, noisy, stats, motion vectors or None, CompareResult or None) per frame.  A scene that is given is uploaded and, from the second one on,
         brings its motion table; None keeps the uploaded scene (no table: only the camera moves).  The options are checked here, before
@@ -1097,9 +1141,10 @@ class Context:
         s.despeckle = _despeckle_params(despeckle)
         s.bloom = _bloom_params(bloom)
         s.dof = _dof_params(dof)
+        s.mblur = _motion_blur_params(motion_blur)
         dev = None
         try:
-            cam_prev = scene_prev = None
+            cam_prev = cam_full_prev = scene_prev = None
             for i, (scene, cam, seed) in enumerate(frames):
                 table = None
                 if scene is not None:
@@ -1122,25 +1167,31 @@ class Context:
                     ref = _reference_frame(s.reference, i, s.fw, s.fh)
                 if s.dof is not None:
                     s.dof(i)  # a list shorter than the sequence fails here, before the frame is queued
+                if s.mblur is not None:
+                    s.mblur(i)  # likewise
                 if dev is None:
                     dev = DeviceBuffers(_sequence_buffers(s.w, s.h, s.fw, s.fh, guides, motion_vectors, s.uparams is not None, s.dparams is not None,
-                                                          s.reference is not None, s.despeckle is not None, s.bloom is not None, s.dof is not None), "a temporal sequence")
+                                                          s.reference is not None, s.despeckle is not None, s.bloom is not None, s.dof is not None,
+                                                          s.mblur is not None), "a temporal sequence")
                 if ref is not None:
                     dev.upload("reference", ref)  # the frame before has been waited for: nothing reads the buffer
-                self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table)
+                self._queue_frame(s, dev, i, self._params(strata_x, strata_y, depth, seed, tile, samples_per_pass), cam, cam_full, cam_prev, table,
+                                  cam_full_prev)
                 stats = self.collect_stats()  # waits for the stream
-                cam_prev = cam
+                cam_prev, cam_full_prev = cam, cam_full
                 yield self._read_frame(s, dev, i, stats)
         finally:
             if dev is not None:
                 dev.free()
 
-    def _queue_frame(self, s, dev, i, p, cam, cam_full, cam_prev, table):
+    def _queue_frame(self, s, dev, i, p, cam, cam_full, cam_prev, table, cam_full_prev=None):
         """Frame i of the sequence `s` on the context's stream, nothing waits: the render of `p` with its guides and its variance; the
         despeckle step, into a colour buffer of its own and in place on the variance; the accumulation into this frame's ping-pong half against the other one; the motion vectors; the spatial variance estimate, in place
         on the accumulated variance; the filter; the full-size guides and the upsample; the depth of field of the frame's first image, into a
-        colour buffer of its own; the bloom of that (without the step: of the first image), into a colour buffer of its own; the display
-        transform, which reads the last of the three that exists and whose exposure word is
+        colour buffer of its own; the motion blur of that (without the step: of the first image), into a colour buffer of its own, from
+        the vectors against `cam_prev` (with `upscale`: `cam_full_prev`), a copy for the first frame; the bloom of that (without those
+        steps: of the first image), into a colour buffer of its own; the display
+        transform, which reads the last of the four that exists and whose exposure word is
         read from the second frame on and written by every one; the comparison of the frame's first image with its reference."""
         w, h, cur, old = s.w, s.h, i & 1, (i & 1) ^ 1
         gp = {n: dev.ptr(f"{n}{cur}" if n in s.kept else n) for n in s.guides}
@@ -1168,6 +1219,20 @@ class Context:
         if s.dof is not None:
             self.dof_device(dev.ptr(lit), dev.ptr("depth_hi") if s.uparams is not None else gp["depth"], dev.ptr("dof"), s.fw, s.fh, **s.dof(i))
             lit = "dof"
+        if s.mblur is not None:
+            full = s.uparams is not None
+            depth_ptr = dev.ptr("depth_hi") if full else gp["depth"]
+            own = full or not s.motion_vectors  # (otherwise the chain's own vectors are this size and have been queued above)
+            vectors = dev.ptr("mblur_motion" if own else "motion")
+            if i and own:
+                if full:
+                    self.motion_vectors_device(depth_ptr, vectors, s.fw, s.fh, cam_full, cam_full_prev,
+                                               (dev.ptr("instance_hi") if "instance" in s.guides else None) if table else None, table)
+                else:
+                    self.motion_vectors_device(depth_ptr, vectors, w, h, cam, cam_prev, gp.get("instance") if table else None, table)
+            # frame 0 has no previous frame and no vectors: shutter 0 is the call's copy, which reads neither the depth nor the vectors
+            self.motion_blur_device(dev.ptr(lit), depth_ptr, vectors, dev.ptr("mblur"), s.fw, s.fh, **(s.mblur(i) if i else dict(s.mblur(i), shutter=0.0)))
+            lit = "mblur"
         if s.bloom is not None:
             self.bloom_device(dev.ptr(lit), dev.ptr("bloom"), s.fw, s.fh, **s.bloom)
             lit = "bloom"
@@ -1191,6 +1256,8 @@ class Context:
             stats["despeckle"] = DespeckleResult.from_buffer_copy(dev.download("despeckle", C.sizeof(DespeckleResult), np.uint8, "a temporal sequence's despeckle record"))
         if s.dof is not None:
             stats["dof"] = dev.download("dof", (s.fh, s.fw, 3), np.float32, "a temporal sequence's defocused image")
+        if s.mblur is not None:
+            stats["motion_blur"] = dev.download("mblur", (s.fh, s.fw, 3), np.float32, "a temporal sequence's motion-blurred image")
         if s.bloom is not None:
             stats["bloom"] = dev.download("bloom", (s.fh, s.fw, 3), np.float32, "a temporal sequence's bloomed image")
         shapes = {s.shown: (h, w, 3) if s.uparams is None else (s.fh, s.fw, 3), f"h_rgb{i & 1}": (h, w, 3), "rgb": (h, w, 3)}

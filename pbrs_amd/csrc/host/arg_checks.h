@@ -82,5 +82,8 @@ Refusal check_bloom(const pbrs_bloom_params* p, const float* rgb, const float* r
 // pbrsf_dof* (host/arg_checks_dof.cpp, beside the filler pbrsf_dof_params_default).  `rgb_out` must not be `rgb`; coc_out, which may
 // be NULL, is not looked at.
 Refusal check_dof(const pbrs_dof_params* p, const float* rgb, const float* depth, const float* rgb_out);
+// pbrsm_motion_blur* (host/arg_checks_motion_blur.cpp, beside the filler pbrsm_motion_blur_params_default).  `rgb_out` must not be
+// `rgb`; velocity_out, which may be NULL, is not looked at.
+Refusal check_motion_blur(const pbrs_motion_blur_params* p, const float* rgb, const float* depth, const float* motion, const float* rgb_out);
 
 }  // namespace pbrs

@@ -42,6 +42,7 @@
 #include "device/despeckle.h"
 #include "device/bloom.h"
 #include "device/dof.h"
+#include "device/motion_blur.h"
 
 // the host-only upload steps (host/scene_prepare.h, host/kernel_choice.h), argument checks (host/arg_checks.h) and pass driver's decisions (host/pass_plan.h)
 using namespace pbrs;
@@ -166,6 +167,8 @@ enum BufferId {
     BUF_BLOOM, BUF_BLOOM_STAGE,
     // depth of field (pbrsf_dof, device/dof.h): the host variant's staging (rgb, depth, the output and the circles); the device call holds nothing
     BUF_DOF_STAGE,
+    // motion blur (pbrsm_motion_blur, device/motion_blur.h): the host variant's staging (rgb, depth, motion, the output and the velocities); the device call holds nothing
+    BUF_MOTION_BLUR_STAGE,
     N_BUFFERS
 };
 
@@ -2057,6 +2060,57 @@ int pbrsf_dof(pbrs_ctx* c, const pbrs_dof_params* p, const float* rgb_host, cons
     Staged s[] = {{rgb_host, 3}, {depth_host, 1}, {nullptr, 3, rgb_out_host}, {nullptr, 1, coc_out_host}};
     return run_staged(c, BUF_DOF_STAGE, "the depth of field staging", s, (size_t)p->w * p->h,
                       [&] { return dof_launch(c, *p, s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>()); });
+}
+
+// ---- motion blur (include/pbrs_gpu.h, device/motion_blur.h) ----
+static_assert(sizeof(pbrs_motion_blur_params) == 32 && offsetof(pbrs_motion_blur_params, shutter) == 20 && offsetof(pbrs_motion_blur_params, reserved) == 28,
+              "pbrs_motion_blur_params is 32 B");
+
+namespace {
+
+using MotionBlurKernel = void (*)(MotionBlur);
+// [halo class: 4, 8, 16][rgb and depth 16-byte aligned][PBRS_MOTION_BLUR_JITTER]
+constexpr MotionBlurKernel kMotionBlur[3][2][2] = {
+    {{k_motion_blur<4u, false, false>, k_motion_blur<4u, false, true>}, {k_motion_blur<4u, true, false>, k_motion_blur<4u, true, true>}},
+    {{k_motion_blur<8u, false, false>, k_motion_blur<8u, false, true>}, {k_motion_blur<8u, true, false>, k_motion_blur<8u, true, true>}},
+    {{k_motion_blur<16u, false, false>, k_motion_blur<16u, false, true>}, {k_motion_blur<16u, true, false>, k_motion_blur<16u, true, true>}}};
+static_assert(PBRS_MOTION_BLUR_MAX_RADIUS == 16u, "the halo classes end at the largest radius");
+
+// The one launch on the context's stream (arguments checked; device pointers).  shutter 0 is the header's step 0: a copy.
+int motion_blur_launch(pbrs_ctx* c, const pbrs_motion_blur_params& p, const float* rgb, const float* depth, const float* motion, float* out, float* velocity) {
+    const size_t P = (size_t)p.w * p.h;
+    if (p.shutter == 0.0f) {
+        HIPCHK(c, hipMemcpyAsync(out, rgb, 3 * P * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        if (velocity) HIPCHK(c, hipMemsetAsync(velocity, 0, 2 * P * sizeof(float), c->stream));
+        return PBRS_OK;
+    }
+    const uint32_t tiles_x = (p.w + kMotionBlurTile - 1u) / kMotionBlurTile;
+    const uint32_t tiles = tiles_x * ((p.h + kMotionBlurTile - 1u) / kMotionBlurTile);  // at most 2^28 pixels: at most 2^28 tiles
+    const uint32_t halo = p.max_radius <= 4u ? 0u : (p.max_radius <= 8u ? 1u : 2u);    // the smallest class that holds max_radius
+    const bool aligned = ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(depth)) & 15u) == 0;
+    const bool jitter = (p.flags & PBRS_MOTION_BLUR_JITTER) != 0u;
+    hipLaunchKernelGGL(kMotionBlur[halo][aligned][jitter], dim3(tiles), dim3(kMotionBlurBlock), 0, c->stream,
+                       MotionBlur{rgb, depth, motion, out, velocity, p.w, p.h, tiles_x, p.max_radius, p.taps, p.shutter * 0.5f, p.z_rel});
+    HIPCHK(c, hipGetLastError());
+    return PBRS_OK;
+}
+
+}  // namespace
+
+int pbrsm_motion_blur_device(pbrs_ctx* c, const pbrs_motion_blur_params* p, const float* rgb_device, const float* depth_device, const float* motion_device,
+                             float* rgb_out_device, float* velocity_out_device) {
+    const int rc = enter(c, check_motion_blur(p, rgb_device, depth_device, motion_device, rgb_out_device));
+    if (rc) return rc;
+    return motion_blur_launch(c, *p, rgb_device, depth_device, motion_device, rgb_out_device, velocity_out_device);
+}
+
+int pbrsm_motion_blur(pbrs_ctx* c, const pbrs_motion_blur_params* p, const float* rgb_host, const float* depth_host, const float* motion_host, float* rgb_out_host,
+                      float* velocity_out_host) {
+    const int rc = enter(c, check_motion_blur(p, rgb_host, depth_host, motion_host, rgb_out_host));
+    if (rc) return rc;
+    Staged s[] = {{rgb_host, 3}, {depth_host, 1}, {motion_host, 2}, {nullptr, 3, rgb_out_host}, {nullptr, 2, velocity_out_host}};
+    return run_staged(c, BUF_MOTION_BLUR_STAGE, "the motion blur staging", s, (size_t)p->w * p->h,
+                      [&] { return motion_blur_launch(c, *p, s[0].as<float>(), s[1].as<float>(), s[2].as<float>(), s[3].as<float>(), s[4].as<float>()); });
 }
 
 int pbrs_collect_stats(pbrs_ctx* c, pbrs_stats* stats_out) {

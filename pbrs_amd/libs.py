@@ -85,6 +85,12 @@ GPU_DOF_FUNCTIONS = _table({
 }, with_device={
     "pbrsf_dof": [P] * 6,
 })
+# The motion-blur call's entry points (include/pbrs_gpu.h, "motion blur"), likewise, under the prefix pbrsm_.
+GPU_MOTION_BLUR_FUNCTIONS = _table({
+    "pbrsm_motion_blur_params_default": ([U32, U32, P], None),
+}, with_device={
+    "pbrsm_motion_blur": [P] * 7,
+})
 HOST_FUNCTIONS = _table({
     "pbrs_host_scene_build": [P, C.POINTER(P)],
     "pbrs_host_scene_free": [P],
@@ -107,6 +113,7 @@ GPU_COMPARE_SYMBOLS = list(GPU_COMPARE_FUNCTIONS)
 GPU_DESPECKLE_SYMBOLS = list(GPU_DESPECKLE_FUNCTIONS)
 GPU_BLOOM_SYMBOLS = list(GPU_BLOOM_FUNCTIONS)
 GPU_DOF_SYMBOLS = list(GPU_DOF_FUNCTIONS)
+GPU_MOTION_BLUR_SYMBOLS = list(GPU_MOTION_BLUR_FUNCTIONS)
 _host = _gpu = _hip = None
 
 
@@ -141,7 +148,8 @@ def gpu_lib():
         path = os.environ.get("PBRS_GPU_LIB") or lib_paths()[1]
         if not os.path.exists(path):
             raise PbrsError(f"{path} is missing: the HIP extension must be built (make -C pbrs_amd/csrc); there is no CPU fallback")
-        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS, **GPU_BLOOM_FUNCTIONS, **GPU_DOF_FUNCTIONS})
+        _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS, **GPU_BLOOM_FUNCTIONS, **GPU_DOF_FUNCTIONS,
+                            **GPU_MOTION_BLUR_FUNCTIONS})
     return _gpu
 
 

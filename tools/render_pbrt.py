@@ -66,7 +66,13 @@ of the aperture radius A (world units) focused on the plane at the distance D al
 the call's focus and scale), the circles clamped to R pixels (1 .. 16, default 8), from the depth AOV of the same samples: also writes
 <out>.dof.<ext>; --bloom and --display then act on the defocused image.  --dof-focus-pixel X Y in the place of --dof-focus focuses on
 what pixel (X, Y) shows (one image only).  With --frames N --temporal every frame's first image is defocused behind the filter and the
-upsample (render_temporal's dof=), <out>.NNNN.dof.<ext>."""
+upsample (render_temporal's dof=), <out>.NNNN.dof.<ext>.
+--motion-blur [--shutter S] [--motion-blur-taps N] [--motion-blur-radius R] [--motion-blur-jitter] (with --frames N --temporal; the flag
+itself takes no value): a shutter as an image operation (include/pbrs_gpu.h, pbrsm_motion_blur; render_temporal's motion_blur=): every
+frame from the second on is smeared along its motion vectors against the frame before (the camera's orbit, and with --spin the
+instances'), open for the fraction S of the frame interval (0 .. 1, default 0.5), N taps along the line (2 .. 64, default 16), the
+vectors clamped to R pixels (1 .. 16, default 16), behind the depth of field and in front of the bloom: also writes
+<out>.NNNN.motion_blur.<ext>; --bloom and --display then act on the blurred image."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -103,12 +109,21 @@ if "--bloom-mix" in sys.argv:
     if bloom is None:
         sys.exit("--bloom-mix goes with --bloom")
     bloom["mix"] = True
+motion_blur = None  # MotionBlurParams.make's keywords
+if "--motion-blur" in sys.argv:  # takes no value, like --despeckle
+    sys.argv.remove("--motion-blur")
+    motion_blur = {}
+if "--motion-blur-jitter" in sys.argv:
+    sys.argv.remove("--motion-blur-jitter")
+    if motion_blur is None:
+        sys.exit("--motion-blur-jitter goes with --motion-blur")
+    motion_blur["jitter"] = True
 dof = None  # --dof-*: {"focus": D or None, "lens_radius": A, "max_radius": R, "focus_pixel": (X, Y) or None}
 if "--dof-focus-pixel" in sys.argv:  # takes two values
     k = sys.argv.index("--dof-focus-pixel")
     dof = {"focus_pixel": (int(sys.argv[k + 1]), int(sys.argv[k + 2]))}
     del sys.argv[k:k + 3]
-for flag in ("--dof-focus", "--dof-lens-radius", "--dof-max-radius", "--bloom-threshold", "--bloom-strength", "--bloom-levels", "--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
+for flag in ("--shutter", "--motion-blur-taps", "--motion-blur-radius", "--dof-focus", "--dof-lens-radius", "--dof-max-radius", "--bloom-threshold", "--bloom-strength", "--bloom-levels", "--despeckle-gain", "--despeckle-rank", "--despeckle-radius", "--compare-strata", "--frames", "--orbit", "--spin", "--spin-deg", "--history-clip", "--history-clip-radius", "--display", "--encode", "--exposure", "--upscale", "--upscale-radius", "--denoise-iterations", "--denoise-sigma", "--denoise-sigma-luminance", "--matte", "--matte-slots", "--matte-select"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         value = sys.argv[k + 1]
@@ -125,6 +140,10 @@ for flag in ("--dof-focus", "--dof-lens-radius", "--dof-max-radius", "--bloom-th
             if bloom is None:
                 sys.exit("--bloom-threshold, --bloom-strength and --bloom-levels go with --bloom")
             bloom[flag[len("--bloom-"):]] = int(value) if flag == "--bloom-levels" else float(value)
+        elif flag in ("--shutter", "--motion-blur-taps", "--motion-blur-radius"):
+            if motion_blur is None:
+                sys.exit("--shutter, --motion-blur-taps and --motion-blur-radius go with --motion-blur")
+            motion_blur[{"--shutter": "shutter", "--motion-blur-taps": "taps", "--motion-blur-radius": "max_radius"}[flag]] = float(value) if flag == "--shutter" else int(value)
         elif flag in ("--dof-focus", "--dof-lens-radius", "--dof-max-radius"):
             dof = dict(dof or {}, **{flag[len("--dof-"):].replace("-", "_"): int(value) if flag == "--dof-max-radius" else float(value)})
         elif flag == "--orbit":
@@ -171,6 +190,8 @@ if display is not None or auto_exposure:
     display["auto"] = auto_exposure
 if dof is not None and ("lens_radius" not in dof or ("focus" in dof) == ("focus_pixel" in dof)):
     sys.exit("--dof-lens-radius A goes with --dof-focus D or --dof-focus-pixel X Y [--dof-max-radius R]")
+if motion_blur is not None and not (frames and temporal):
+    sys.exit("--motion-blur goes with --frames N --temporal: it smears a frame along its motion against the frame before")
 scene, out = sys.argv[1], sys.argv[2]
 msaa = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 5  # src/main.rs:205
@@ -247,6 +268,8 @@ if frames:
     extra = {} if despeckle is None else {"despeckle": despeckle}  # (a keyword of the sequences only when asked for)
     if dof is not None:
         extra["dof"] = dict(pbrs_amd.lens(hs.camera, dof["focus"], dof["lens_radius"]), max_radius=dof.get("max_radius", 8))
+    if motion_blur is not None:
+        extra["motion_blur"] = motion_blur
     if bloom is not None:
         extra["bloom"] = bloom
     spatial = True if spatial_variance else None
@@ -265,6 +288,8 @@ if frames:
             pbrs_amd.write_image(f"{stem}.{k:04d}.noisy{ext}", images[2])
         if dof is not None:
             pbrs_amd.write_image(f"{stem}.{k:04d}.dof{ext}", images[3]["dof"])
+        if motion_blur is not None:
+            pbrs_amd.write_image(f"{stem}.{k:04d}.motion_blur{ext}", images[3]["motion_blur"])
         if bloom is not None:
             pbrs_amd.write_image(f"{stem}.{k:04d}.bloom{ext}", images[3]["bloom"])
         if display is not None:
