@@ -300,6 +300,26 @@ int pbrs_set_stream(pbrs_ctx*, void* hip_stream);
  * event brackets include the time its kernels share the chip with the other stream's). */
 int pbrs_set_pass_overlap(pbrs_ctx*, int enabled);
 
+/* Entry nodes of the camera rays.  The rays of a pixel share their origin and differ by less than a pixel in direction; in a scene whose
+ * deepest mesh qualifies (a BLAS of at least twelve levels with every child box inside its parent's, under an instance that is the identity
+ * or a pure translation, coordinates inside the guarded range of the division-free box test) a pre-pass of one lane per pixel finds, once
+ * per render, up to eight nodes of that BLAS under which every leaf a ray of the pixel can reach must lie, and the first bounce's
+ * closest-hit walks enter the mesh there instead of at its root.  The walks visit the same leaves in the same order with the same
+ * extents: the image does not depend on it, bit for bit.  On by default; 0 walks every ray from the root.  An instrumented render
+ * (collect_counters) never uses the table: its node counts are the reference's. */
+int pbrse_set_entry_nodes(pbrs_ctx*, int enabled);
+/* What the pre-pass of the last render queued on the context found (all zero where it did not run: the feature off, a scene without a
+ * qualifying mesh, an instrumented render, a pass without a bounce).  Waits for that render. */
+typedef struct pbrs_entry_info {
+    uint32_t pixels_with_entries; /* pixels whose rays enter the mesh at the pixel's entries              */
+    uint32_t pixels_empty;        /* ... whose rays cannot reach the mesh at all: an empty list           */
+    uint32_t pixels_from_root;    /* ... without a table: a direction component that is zero or changes   */
+                                  /* sign inside the pixel, a ray outside the guarded range, no stack rows */
+    uint32_t entries;             /* entries written, over the pixels with entries                         */
+} pbrs_entry_info;
+int pbrse_last_entry_info(pbrs_ctx*, pbrs_entry_info* out);
+/* (The two functions' prefix is pbrse_; the struct carries pbrs_.) */
+
 /* Copies the flattened scene into HBM.  Stands for building `Scene` (scene/src/lib.rs:36-63). */
 int pbrs_upload_scene(pbrs_ctx*, const pbrs_scene_desc*);
 

@@ -20,7 +20,7 @@ from .abi import (AOV_NAMES, AOVS, BSDF_OPS, BSDF_QUERY_WORDS, BSDF_RESULT_WORDS
                   TemporalParams, UpsampleParams, _aov_names, _bloom_params, _DenoiseParamsMixin, _despeckle_params, _display_params, _dof_params, _history_clip, _matte_select, _motion_args, _motion_blur_params, _pass_names,
                   _reference_frame, _reference_frames, _temporal_struct, _upscale_params, lens, scaled_camera)
 from .devmem import DeviceBuffers
-from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_DOF_SYMBOLS, GPU_MOTION_BLUR_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
+from .libs import GPU_BLOOM_SYMBOLS, GPU_COMPARE_SYMBOLS, GPU_DESPECKLE_SYMBOLS, GPU_DOF_SYMBOLS, GPU_ENTRY_SYMBOLS, GPU_MOTION_BLUR_SYMBOLS, GPU_SYMBOLS, HOST_SYMBOLS, PbrsError, gpu_lib, hip_runtime, host_lib, lib_paths  # noqa: F401
 from .spec import SceneSpec  # noqa: F401
 
 
@@ -247,6 +247,16 @@ class Context:
     def set_pass_overlap(self, enabled):
         """Late bounces of a pass beside the next pass's first bounces, on a second stream (default on; include/pbrs_gpu.h)."""
         self._check(self._L.pbrs_set_pass_overlap(self._h, int(bool(enabled))), "pbrs_set_pass_overlap")
+
+    def set_entry_nodes(self, enabled):
+        """Camera rays enter the scene's deep mesh at per-pixel entry nodes instead of at its root (default on; include/pbrs_gpu.h)."""
+        self._check(self._L.pbrse_set_entry_nodes(self._h, int(bool(enabled))), "pbrse_set_entry_nodes")
+
+    def last_entry_info(self):
+        """What the entry-node pre-pass of the last render found (include/pbrs_gpu.h, pbrs_entry_info); waits for that render."""
+        v = (C.c_uint32 * 4)()
+        self._check(self._L.pbrse_last_entry_info(self._h, C.addressof(v)), "pbrse_last_entry_info")
+        return {"pixels_with_entries": int(v[0]), "pixels_empty": int(v[1]), "pixels_from_root": int(v[2]), "entries": int(v[3])}
 
     def upload(self, host_scene):
         self._check(self._L.pbrs_upload_scene(self._h, C.addressof(host_scene.desc)), "pbrs_upload_scene")

@@ -230,10 +230,15 @@ PD DevScene stage_top(const DevScene& G, uint32_t* lds_base) {
 // handed a new ray at the next refill, the walks of the other lanes continue where they were.
 // `indirect` (binary-walk kernels working off a slow list): the queue positions to trace, `count` of them.  (k_extend walks binary
 // only: the host passes null for `indirect` and the slow list.)
-template <bool STATS, uint32_t FEAT>
+// ENTRY: nothing, or — bounce 0 of a render with an entry table (device/entry_nodes.h; kernel_tables.h, extend_entry_fn_t) — one EntryArgs:
+// camera rays then enter the table instance's BLAS at their pixel's entry nodes.  (A pack, so that every other k_extend keeps its arguments,
+// and with them its instructions.)
+template <bool STATS, uint32_t FEAT, class... ENTRY>
 __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_SHADING_CHECK) ? PBRS_TRAV_WAVES : PBRS_LEAN_EXTEND_WAVES)
     k_extend(DevScene G, PathState st, uint32_t set, const uint32_t* count, uint32_t n_direct, uint32_t* next, GlobalCounters* gc, const uint32_t* indirect,
-             uint32_t* slow_list, uint32_t* slow_count, uint32_t split) {
+             uint32_t* slow_list, uint32_t* slow_count, uint32_t split, ENTRY... entry) {
+    static_assert(sizeof...(ENTRY) <= 1, "at most the entry table's arguments");
+    constexpr bool HAS_ENTRY = sizeof...(ENTRY) != 0;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
     const DevScene S = (!STATS && (FEAT & PBRS_FEAT_LDS_SCENE)) ? stage_scene(G, lds_stack) : (!STATS && (FEAT & PBRS_FEAT_LDS_TOP)) ? stage_top(G, lds_stack) : G;
     const uint32_t n = count ? *count : n_direct;
@@ -243,7 +248,8 @@ __global__ void __launch_bounds__(256, STATS ? 3 : (FEAT & PBRS_FEAT_SHADING_CHE
     Cnt<STATS> cnt;
     cnt.init();
     uint32_t nrays = 0, nhit = 0;
-    ClosestWalk<STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP | PBRS_FEAT_EXTENT))> walk;
+    ClosestWalk<STATS, (FEAT & (PBRS_FEAT_ALL | PBRS_FEAT_LDS_TOP | PBRS_FEAT_EXTENT)), HAS_ENTRY> walk;
+    if constexpr (HAS_ENTRY) walk.a = (entry, ...);
     walk.mode = PBRS_WALK_IDLE;
     PBRS_KP_DECL(walk);
     PBRS_TT_DECL;

@@ -2,6 +2,7 @@
 // slot order of a pass, the stream loads and stores of the records, the instrumented kernels' counters and the LDS staging copy.
 // (The stages: device/kernels.h.)
 #pragma once
+#include "entry_nodes.h"
 #include "shapes.h"  // dmath.h, scene.h, pbrs_f4v
 
 struct PathState {
@@ -54,6 +55,13 @@ struct RenderConst {
     uint32_t band_rows, band_count, band_index;  // interleaved row bands (pbrs_render_params)
     uint32_t integrator;                         // PBRS_INTEGRATOR_*
     uint64_t seed;
+};
+
+// What k_extend<.., EntryArgs> is given beside the arguments of every k_extend (device/entry_nodes.h): the table k_entry_nodes wrote, by pixel
+// of the pass's pixel order, and the pass's slot order (sample_of_slot), which leads from a camera ray's queue position to that pixel.
+struct EntryArgs {
+    const uint4* table;
+    uint32_t n_pixels, k_count, chunk;
 };
 
 // Byte / word columns by path slot (the nee hand-off's occlusion bytes).  Slots stay below 2^28 (check_params).
@@ -114,6 +122,15 @@ PD uint32_t order_of_pixel(uint32_t pix, uint32_t w, uint32_t tiles8_per_row) {
     if (tiles8_per_row == 0u) return pix;
     const uint32_t y = pix / w, x = pix - y * w;
     return (((y >> 3) * tiles8_per_row + (x >> 3)) << 6) + ((y & 7u) << 3) + (x & 7u);
+}
+
+// Film coordinates of the q-th pixel of a pass's pixel order (what sample_of_slot yields): the tile's 8 x 8 blocks, its offset, and the
+// interleaved row bands of a render that traces one band in band_count.  k_raygen's mapping; k_entry_nodes makes the same one.
+PD void film_pixel_of_order(const RenderConst& rc, uint32_t q, uint32_t& col, uint32_t& row) {
+    const uint32_t pix = pixel_of_order(q, rc.w, rc.tiles8_per_row);
+    const uint32_t vrow = pix / rc.w;
+    col = rc.x0 + pix % rc.w;
+    row = rc.y0 + (rc.band_count > 1 ? ((vrow / rc.band_rows) * rc.band_count + rc.band_index) * rc.band_rows + vrow % rc.band_rows : vrow);
 }
 
 struct GlobalCounters {  // instrumented variant only

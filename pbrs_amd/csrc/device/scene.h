@@ -42,6 +42,9 @@ struct DevScene {
     uint32_t features;   // PBRS_FEAT_*: what the traversal kernels must be able to do for this scene
     uint32_t refill_below;  // a wave of a traversal kernel takes new rays when fewer of its lanes than this are walking
     uint32_t refill_below_shadow;  // ... of k_shadow (any-hit walks end at the first occluder: later, larger refills)
+    // The mesh instance whose BLAS the camera rays enter at per-pixel entry nodes (device/entry_nodes.h; prepare_scene), or
+    // PBRS_ENTRY_NONE.  (Like n_wnodes below, this word fills what was padding: the layout of every other member stays.)
+    uint32_t entry_inst;
     // texture/src/lib.rs (device/textures.h) and the environment light (scene/src/lib.rs:105-117)
     const pbrs_texture* textures;
     const float* tex_floats;

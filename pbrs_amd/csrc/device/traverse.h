@@ -30,7 +30,7 @@
 // component, an origin component that is tiny but non-zero) take the reference's literal divisions instead;
 // pbrs_upload_scene checks the node coordinates once.
 #pragma once
-#include "shapes.h"
+#include "path_state.h"  // shapes.h; sample_of_slot, EntryArgs
 
 #include "probes.h"
 
@@ -40,6 +40,8 @@ struct RaySpace {
     bool fast;
 };
 // Branch-free (one unsigned compare per range; `&`, not `&&`): six short-circuit branches here cost more than the tests.
+// (The pre-pass of the entry nodes states the same two ranges in plain C++, device/entry_nodes.h: pbrs_en_dir_in_range,
+// pbrs_en_origin_in_range; change them together.)
 PD uint32_t dir_in_range(float x) {  // normal, 2^-40 <= |x| <= 2^40
     uint32_t e = (pn_bits(x) >> 23) & 0xffu;
     return (e - (127u - 40u) <= 80u) ? 1u : 0u;
@@ -314,8 +316,17 @@ struct FlatScan {
     PD static uint32_t run_filter(const DevScene& S, bool fresh, const RaySpace& R, uint32_t& tested) { return scan<Filter>(S, fresh, R, pn_inf(), tested); }
 };
 
-template <bool STATS, uint32_t FEAT>
-struct ClosestWalk {
+// What the walk of a camera ray holds of k_extend<.., EntryArgs>'s EntryArgs (path_state.h); empty in every other walk.
+template <bool ENTRY>
+struct EntryView {};
+template <>
+struct EntryView<true> {
+    EntryArgs a;
+};
+
+template <bool STATS, uint32_t FEAT, bool ENTRY = false>
+struct ClosestWalk : EntryView<ENTRY> {  // (an empty base: every other walk keeps its layout)
+    static_assert(!ENTRY || (!STATS && !(FEAT & (PBRS_FEAT_EXTENT | PBRS_FEAT_LDS_TOP))), "the entry variant: a walk that carries the split-plane cull");
     RaySpace C;  // the space the lane is walking in (the world ray in the TLAS, the instance's ray below a TLAS leaf): one
                  // box-test call serves lanes in either tree.  The world ray is read again on the way out (reload_world).
     Hit best;       // best.t stays +inf until the first candidate: `!(best.t < t)` then accepts it, as Option::None does
@@ -628,6 +639,30 @@ struct ClosestWalk {
         mt = pn_inf();
         if (kind == PBRS_SHAPE_MESH) {
             inst_info = kind | (H.mesh_flags << 3) | (space == PBRS_SPACE_TRANSLATED ? 0x40000000u : 0u);
+            if constexpr (ENTRY) {
+                // A camera ray enters the table instance's BLAS at its pixel's entry nodes (device/entry_nodes.h, which says why no bit
+                // moves): the root is tested here, against the incoming extent, as node_step would test it; where it passes, the entries are
+                // pushed last-first in its stead (unused slots come last in the record, are written first and overwritten) and the extent
+                // becomes the mesh-local best, as after any passing node.  Where it fails nothing is pushed: the next node step leaves.
+                // The ray's pixel follows from its queue position, which at bounce 0 is its slot.
+                if (cur_inst == S.entry_inst && C.fast && space != PBRS_SPACE_MOVED) {
+                    uint32_t k, pix;
+                    sample_of_slot(stk.item, this->a.n_pixels, this->a.k_count, this->a.chunk, k, pix);
+                    const uint4 e0 = this->a.table[2u * pix], e1 = this->a.table[2u * pix + 1u];
+                    if (e0.x != PBRS_ENTRY_ROOT) {
+                        if (slab_rs(walk_node<FEAT>(S, H.blas_root), C, lt)) {
+                            const uint32_t e[PBRS_ENTRY_MAX] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+#pragma unroll
+                            for (int i = (int)PBRS_ENTRY_MAX - 1; i >= 0; --i) {
+                                stk.put(sp, e[i]);
+                                sp += e[i] != PBRS_ENTRY_UNUSED ? 1 : 0;
+                            }
+                            lt = mt;
+                        }
+                        return;
+                    }
+                }
+            }
             stk.put(sp++, H.blas_root);
         } else if (kind == PBRS_SHAPE_TRIANGLE) {
             // IsolatedTriangle (simple.rs:417-426): one triangle record, no boxes, no shading frame

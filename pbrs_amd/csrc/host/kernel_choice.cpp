@@ -27,6 +27,7 @@ KernelChoice choose_kernels(const SceneFacts& f, const DevOverrides& dev) {
         p.extend[0] = {(f.features & PBRS_FEAT_ALL) | steps | p.lds_staging, staged};
         p.extend[1] = {kStatsKey | PBRS_FEAT_ALL, stack};
     }
+    p.entry_extend = f.entry_nodes && extend_entry_ok(p.extend[0].key);
     const uint32_t shadow_feat = (f.features & PBRS_FEAT_ANALYTIC) | (f.tlas_scanned ? PBRS_FEAT_FLAT_TLAS : 0u) | steps;
     if (p.wide_shadow) {
         p.shadow[0] = {shadow_feat | PBRS_FEAT_WIDE, f.wide_stack_bytes};

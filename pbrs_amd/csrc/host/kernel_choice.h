@@ -40,6 +40,7 @@ struct SceneFacts {
     bool exact_extent = false;  // DevScene::exact_extent: the closest-hit walks follow ray.t_max to the letter (PBRS_FEAT_EXTENT)
     bool long_walks = false;    // a walk of PBRS_LONG_WALK_HEIGHT levels or more: the PBRS_FEAT_LONG_WALKS kernels
     bool full_steps = false;    // ... whose further node steps are full ones (PBRS_FEAT_FULL_STEPS): coordinates outside the guarded range of the division-free box test
+    bool entry_nodes = false;   // DevScene::entry_inst names an instance: camera rays may enter its BLAS at per-pixel entry nodes (device/entry_nodes.h)
     bool wide_ok = false;       // k_shadow may walk the four-wide nodes (a scanned TLAS, built wide nodes, a BLAS deep enough)
     size_t stack_bytes = 0;     // a block's stack rows: DevScene::lds_off_words
     size_t wide_stack_bytes = 0;  // ... of the four-wide walk: DevScene::wide_cap rows
@@ -76,6 +77,26 @@ constexpr bool extend_key_ok(uint32_t k) {
     if ((f & PBRS_FEAT_LDS_TOP) && (f & (PBRS_FEAT_LDS_SCENE | PBRS_FEAT_FULL_STEPS | PBRS_FEAT_FLAT_TLAS))) return false;  // a TLAS too large to scan
     return true;
 }
+// The k_extend instantiations that also exist as the entry variant (k_extend<.., EntryArgs>: bounce 0 enters the table instance's BLAS at the
+// pixel's entry nodes, device/entry_nodes.h): those that carry the split-plane cull and walk long — not the instrumented ones (their node
+// counts are the oracle's), not the walks that follow the extent, not the kernels that stage the scene or the TLAS in LDS, and not the
+// kernels with full further node steps (PBRS_FEAT_FULL_STEPS: a scene outside the guarded range, which gets no table).  The entry
+// variants follow the plain ones in what extend_fns() returns: entry_key(k).
+// A variant must keep the waves per SIMD of its plain kernel (a wave is worth 8 % of k_extend on C4): kEntryKeysLosingAWave
+// lists the keys whose variant does not — their scenes walk every bounce from the root — and `tools/isa_stats.py --check-entry-waves`
+// fails when a variant that IS instantiated has fewer waves than its plain kernel.
+//    9 (analytic shapes, TLAS walked as a tree):  70 -> 75 VGPRs, 7 -> 6 waves
+//   14 (shading check, scanned TLAS):             79 -> 85 VGPRs, 6 -> 5 waves
+constexpr uint32_t kEntryKeysLosingAWave[] = {PBRS_FEAT_LONG_WALKS | PBRS_FEAT_ANALYTIC, PBRS_FEAT_LONG_WALKS | PBRS_FEAT_SHADING_CHECK | PBRS_FEAT_FLAT_TLAS};
+constexpr bool extend_entry_ok(uint32_t k) {
+    for (uint32_t lost : kEntryKeysLosingAWave)
+        if (k == lost) return false;
+    return k < kTraversalKeys && extend_key_ok(k) &&
+           !(k & (kStatsKey | PBRS_FEAT_EXTENT | PBRS_FEAT_LDS_TOP | PBRS_FEAT_LDS_SCENE | PBRS_FEAT_FULL_STEPS)) && (k & PBRS_FEAT_LONG_WALKS);
+}
+static_assert(extend_entry_ok(13u) && !extend_entry_ok(9u) && !extend_entry_ok(14u) && !extend_entry_ok(45u), "the entry variants' keys");
+constexpr uint32_t kExtendKeys = 2u * kTraversalKeys;
+constexpr uint32_t entry_key(uint32_t k) { return kTraversalKeys + k; }
 constexpr bool shadow_key_ok(uint32_t k) {
     const uint32_t f = k & ~kStatsKey;
     if (k & kStatsKey) return f == kShadowStatsFeatures;
@@ -140,6 +161,7 @@ struct KernelChoice {
     TraversalKey shadow[2];
     bool wide_shadow = false;     // the timed k_shadow walks four-wide nodes ...
     TraversalKey shadow_slow;     // ... and this binary-walk kernel works off the rays it refused
+    bool entry_extend = false;    // bounce 0 launches the entry variant of extend[0] (extend_entry_ok; pbrse_set_entry_nodes may still turn it off)
     bool split_queue = false;     // k_extend may split the path integrator's queue (one shading class; run_pass decides)
     uint32_t lds_staging = 0;     // PBRS_FEAT_LDS_SCENE, PBRS_FEAT_LDS_TOP or 0: what the traversal kernels stage in LDS
     IntegratorChoice integ[PBRS_INTEGRATOR_NORMALS + 1];

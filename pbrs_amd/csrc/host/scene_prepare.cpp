@@ -9,6 +9,7 @@
 
 #include "../../../include/pbrs_numeric.h"
 #include "../../../include/pbrs_scene_spec.h"
+#include "../device/entry_nodes.h"
 #include "../device/split_planes.h"
 
 namespace pbrs {
@@ -128,6 +129,25 @@ uint32_t split_planes(const std::vector<pbrs_node>& nodes, uint32_t x) {
     if (!coord_ok(pbrs_plane_down(qd, step, lo))) qd = 0u;
     if (!coord_ok(pbrs_plane_up(qu, step, hi))) qu = 0u;
     return pbrs_plane_pack(qd, qu);
+}
+
+// Does every child box of the BLAS under `root` lie inside its parent's?  (device/entry_nodes.h; `nodes`: absolute links, children after
+// their parent.)  A NaN coordinate fails every comparison.
+bool blas_nested(const std::vector<pbrs_node>& nodes, uint32_t root) {
+    std::vector<uint32_t> todo = {root};
+    while (!todo.empty()) {
+        const uint32_t x = todo.back();
+        todo.pop_back();
+        const pbrs_node& X = nodes[x];
+        if (X.b & PBRS_LEAF_FLAG) continue;
+        for (uint32_t c : {x + 1u, X.a}) {
+            const pbrs_node& C = nodes[c];
+            for (int a = 0; a < 3; ++a)
+                if (!(X.min[a] <= C.min[a] && C.min[a] <= C.max[a] && C.max[a] <= X.max[a])) return false;
+            todo.push_back(c);
+        }
+    }
+    return true;
 }
 
 // The analytic instance that IS area light `L` (prepare_scene, PreparedScene::light_link): an instance of the light's shape kind whose shape parameters are the light's
@@ -403,6 +423,26 @@ PreparedScene prepare_scene(const pbrs_scene_desc& d, const SceneLevels& lv, con
             S.features |= PBRS_FEAT_ANALYTIC;
         }
     }
+    // Entry nodes of the camera rays (device/entry_nodes.h): at most one instance per scene gets a table — the mesh instance with the
+    // deepest BLAS (the first of equals), if that BLAS has PBRS_LONG_WALK_HEIGHT levels or more, the instance is the identity or a pure
+    // translation, the scene lies inside the guarded range of the division-free box test, and EVERY child box of that BLAS lies inside
+    // its parent's (the argument rests on the nesting of whole subtrees; split_planes asks it node by node and only gives up its planes).
+    S.entry_inst = PBRS_ENTRY_NONE;
+    if (S.fast_slab != 0u && !lv.exact_extent) {
+        std::vector<uint32_t> h;
+        tree_heights(nodes.data(), (uint32_t)nodes.size(), h);
+        uint32_t best = PBRS_ENTRY_NONE;
+        for (uint32_t i = 0; i < d.n_instances; ++i)
+            if (inst[i].shape_kind == PBRS_SHAPE_MESH && (best == PBRS_ENTRY_NONE || h[inst[i].blas_root] > h[inst[best].blas_root])) best = i;
+        // (PBRS_INSTANCE_TRANSLATION: set above from the matrix's own bits, the identity included)
+        if (best != PBRS_ENTRY_NONE && h[inst[best].blas_root] >= PBRS_LONG_WALK_HEIGHT && (inst[best].flags & PBRS_INSTANCE_TRANSLATION) &&
+            blas_nested(nodes, inst[best].blas_root)) {
+            S.entry_inst = best;
+            P.entry_height = h[inst[best].blas_root];
+            P.entry_rows = lv.stack - (lv.tlas - 1u);
+        }
+    }
+    f.entry_nodes = S.entry_inst != PBRS_ENTRY_NONE;
     f.features = S.features;
     f.exact_extent = lv.exact_extent;
     f.n_classes = S.n_classes;

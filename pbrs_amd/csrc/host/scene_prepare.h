@@ -40,6 +40,9 @@ struct PreparedScene {
     uint32_t wide_levels = 0;        // wide nodes on the longest way down a BLAS (0: no wide nodes)
     SceneFacts facts;
     uint32_t stack_depth = 0;      // entries of a lane's traversal stack
+    // The instance with the entry table (DevScene::entry_inst, device/entry_nodes.h), if any: the levels of its BLAS, and the stack rows
+    // a lane has left when it enters it (the stack less the TLAS entries that may wait below the instance)
+    uint32_t entry_height = 0, entry_rows = 0;
     bool has_vis_records = false;  // every material names its pbrs_material::vis_bxdf record (normal_visualizer)
     uint64_t walk_bytes = 0;       // what the walks read: nodes, wide nodes, tri_leaf, triangle vertices, instance records (pbrs_ctx::overlap_from)
 };

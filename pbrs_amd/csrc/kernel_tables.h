@@ -19,6 +19,8 @@
 namespace pbrs {
 
 typedef void (*extend_fn_t)(DevScene, PathState, uint32_t, const uint32_t*, uint32_t, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
+// k_extend<.., EntryArgs>: the same arguments and the entry table's.  extend_fns() hands these out as extend_fn_t; cast back before the launch.
+typedef void (*extend_entry_fn_t)(DevScene, PathState, uint32_t, const uint32_t*, uint32_t, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*, uint32_t, EntryArgs);
 typedef void (*shadow_fn_t)(DevScene, PathState, const uint32_t*, uint32_t*, GlobalCounters*, const uint32_t*, uint32_t*, uint32_t*);
 typedef void (*shade_fn_t)(DevScene, PathState, RenderConst, uint32_t, const uint32_t*, uint32_t, uint32_t*, uint32_t*, unsigned long long*, uint32_t, const uint2*,
                            const uint32_t*);
@@ -26,7 +28,7 @@ typedef void (*intersect_fn_t)(DevScene, uint32_t, const float4*, const float4*,
 typedef void (*bsdf_eval_fn_t)(DevScene, uint32_t, uint32_t, const uint32_t*, uint32_t*);
 
 // traverse.hip: the traversal kernels, one per valid key (host/kernel_choice.h: extend_key_ok, shadow_key_ok; null elsewhere), kTraversalKeys
-// each; and k_intersect_rays, its occlusion queries through the four-wide any-hit walk or through the binary one.
+// each — and behind k_extend's, at entry_key(k), the entry variants of the keys that have one (extend_entry_ok; kExtendKeys in all); and k_intersect_rays, its occlusion queries through the four-wide any-hit walk or through the binary one.
 const extend_fn_t* extend_fns();
 const shadow_fn_t* shadow_fns();
 intersect_fn_t intersect_fn(bool wide_any);

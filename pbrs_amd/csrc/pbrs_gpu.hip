@@ -100,6 +100,7 @@ struct IntegratorPlan {
 struct KernelPlan {
     KernelChoice choice;  // (its integ[] are the IntegratorPlans' choices)
     extend_fn_t extend[2] = {};  // [instrumented]
+    extend_entry_fn_t extend_entry = nullptr;  // where choice.entry_extend: bounce 0's k_extend<.., EntryArgs> (device/entry_nodes.h)
     shadow_fn_t shadow[2] = {};
     shadow_fn_t shadow_slow = nullptr;  // where choice.wide_shadow
     IntegratorPlan integ[PBRS_INTEGRATOR_NORMALS + 1];
@@ -121,6 +122,8 @@ enum BufferId {
     // first-hit AOVs (pbrs_render_tile_aovs*, device/aov.h): the per-pixel running state k_aov folds every pass into (PBRS_AOV_STATE_WORDS per
     // pixel, planar), and the host variant's staging for the finished buffers (the seven of pbrs_aov_buffers, one after the other)
     BUF_AOV_STATE, BUF_AOV_OUT,
+    // entry nodes of the camera rays (device/entry_nodes.h): a pbrs_entry_record per pixel of the traced region, then k_entry_nodes' four counts
+    BUF_ENTRY_TABLE,
     // filtered film (pbrs_render_tile_filtered*, device/film.h): S.rgb and W of every tile pixel, planar
     BUF_FILTER_SUM,
     // denoisers (pbrs_denoise*, pbrs_denoise_var*, device/denoise.h): two ping-pong colour planes, the guide plane and the instance ids (16 +
@@ -206,6 +209,14 @@ struct pbrs_ctx {
     int cur_set = 0;
     hipStream_t main_stream = nullptr;  // the stream of set 0: the context's own, or the caller's (pbrs_set_stream)
     hipStream_t second_stream = nullptr;  // the late stream: the context's own, high priority, ordered against the main one by events
+    // Entry nodes of the camera rays (device/entry_nodes.h): pbrse_set_entry_nodes; of the uploaded scene's table instance, the levels of
+    // its BLAS and the stack rows a lane has left there (PreparedScene); the table of the render being queued (null: none) and whether the
+    // last render had one (pbrse_last_entry_info reads the counts behind the table)
+    bool entry_nodes = true;
+    uint32_t entry_height = 0, entry_rows = 0;
+    const uint4* entry_table = nullptr;
+    bool last_entry = false;
+    uint32_t last_entry_pixels = 0;
     bool overlap_passes = true;  // pbrs_set_pass_overlap (DevOverrides::overlap_passes): every pass on the main stream, as in rounds 1-3
     // The bounce from which a pass moves to the late stream (and the next pass starts behind it on the main one).  Same-box A/B lines in
     // profiles/r04m_ab_pass_overlap.log: scenes that live in every XCD's L2 gain most from bounce 2 on (C2 +1.9 %, C3 +1.5 %, C5 +3.3 %
@@ -596,7 +607,8 @@ bool bind_kernels(const KernelChoice& ch, KernelPlan& p) {
         p.shadow[s] = shadow_fns()[ch.shadow[s].key];
     }
     if (ch.wide_shadow) p.shadow_slow = shadow_fns()[ch.shadow_slow.key];
-    bool ok = p.extend[0] && p.extend[1] && p.shadow[0] && p.shadow[1] && (!ch.wide_shadow || p.shadow_slow);
+    if (ch.entry_extend) p.extend_entry = reinterpret_cast<extend_entry_fn_t>(extend_fns()[entry_key(ch.extend[0].key)]);
+    bool ok = p.extend[0] && p.extend[1] && p.shadow[0] && p.shadow[1] && (!ch.wide_shadow || p.shadow_slow) && (!ch.entry_extend || p.extend_entry);
     for (uint32_t i = 0; i <= PBRS_INTEGRATOR_NORMALS; ++i) {
         IntegratorPlan& ip = p.integ[i];
         ip.choice = ch.integ[i];
@@ -686,8 +698,13 @@ int run_pass(pbrs_ctx* c, RenderConst rc, uint32_t first, uint32_t kc, bool stat
         const BouncePlan bp = bounce_plan(rc.integrator, choice.split_queue, ip.choice, c->split_decision, b);
         const uint32_t qsplit = bp.split;
         if (tm.begin(1)) return fail(c, PBRS_E_DEVICE, "event record failed");
-        hipLaunchKernelGGL(plan.extend[stats], dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, set.st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr,
-                           nullptr, nullptr, qsplit);
+        // bounce 0 of a render with an entry table (render_common): camera rays enter the table instance's BLAS at their pixel's entry nodes
+        if (b == 0 && c->entry_table && !stats)
+            hipLaunchKernelGGL(plan.extend_entry, dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, set.st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr,
+                               nullptr, nullptr, qsplit, EntryArgs{c->entry_table, P, kc, rc.chunk_pixels});
+        else
+            hipLaunchKernelGGL(plan.extend[stats], dim3(pgrid), dim3(kBlock), xk.lds, c->stream, xS, set.st, b & 1u, cnt_in, N, xhead + b * kHeadWords, c->gcnt, nullptr,
+                               nullptr, nullptr, qsplit);
         c->pending.kernel_features_extend = reported_features(xk);
         tm.end();
         // First-hit AOVs: bounce 0's rays (q[0], at their slots) and hit records, before bounce 1 overwrites them (k_shade writes set 0
@@ -797,6 +814,25 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
     if (moments) HIPCHK(c, hipMemsetAsync(moments, 0, PBRS_MOMENT_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
     if (matte) HIPCHK(c, hipMemsetAsync(matte, 0, PBRS_MATTE_STATE_WORDS(t.matte->slots) * (size_t)P * sizeof(uint32_t), c->stream));
     if (pass_state) HIPCHK(c, hipMemsetAsync(pass_state, 0, PBRS_PASS_STATE_WORDS * (size_t)P * sizeof(float), c->stream));
+    // Entry nodes of the camera rays (device/entry_nodes.h): one record per pixel of the traced region, written once, read by every
+    // pass's bounce 0.  The instrumented render walks from the root (its node counts are the oracle's).  Without memory for the table the
+    // render goes on without it.
+    c->entry_table = nullptr;
+    c->last_entry = false;
+    if (c->entry_nodes && c->plan.extend_entry && !stats && bounce_count(rc.integrator, rc.max_depth) > 0) {
+        DeviceBuffer& eb = c->buf[BUF_ENTRY_TABLE];
+        const size_t table_bytes = (size_t)P * sizeof(pbrs_entry_record);
+        if (eb.grow(c, table_bytes + 4 * sizeof(uint32_t), "the entry-node table") == PBRS_OK) {
+            uint32_t* info = reinterpret_cast<uint32_t*>(static_cast<char*>(eb.p) + table_bytes);
+            HIPCHK(c, hipMemsetAsync(info, 0, 4 * sizeof(uint32_t), c->stream));
+            hipLaunchKernelGGL(k_entry_nodes, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, rc, c->entry_height, c->entry_rows, eb.as<uint4>(), info);
+            c->entry_table = eb.as<uint4>();
+            c->last_entry = true;
+            c->last_entry_pixels = P;
+        } else {
+            c->error.clear();
+        }
+    }
     uint32_t passes = 0;
     // Where the render has more than one pass, passes alternate between the two pass sets and hand their late bounces to the second
     // stream: those are near-empty launches that end with the latency of their longest walks (C4: 47 ms per frame in kernels that leave
@@ -813,10 +849,12 @@ int render_common(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_render_params*
         const int rcode = run_pass(c, rc, first, kc, stats, tm, two, t);
         if (rcode) {
             use_pass_set(c, 0);
+            c->entry_table = nullptr;
             return rcode;
         }
         ++passes;
     }
+    c->entry_table = nullptr;  // the table is this render's: a pass queued by anything else (pbrs_render_sample_radiance) walks from the root
     if (two) {
         const hipEvent_t last = cur(c).accumulated;
         use_pass_set(c, 0);
@@ -898,8 +936,9 @@ int configure_kernels(pbrs_ctx* c) {
     if (c->device < 64 && g_kernel_cfg_done[c->device]) return PBRS_OK;
     const int cap = (int)(kLdsBytesPerCU / 2);
     std::vector<const void*> traversal_kernels = {reinterpret_cast<const void*>(intersect_fn(false)), reinterpret_cast<const void*>(intersect_fn(true))};
-    for (uint32_t k = 0; k < kTraversalKeys; ++k) {
+    for (uint32_t k = 0; k < kExtendKeys; ++k)
         if (extend_fns()[k]) traversal_kernels.push_back(reinterpret_cast<const void*>(extend_fns()[k]));
+    for (uint32_t k = 0; k < kTraversalKeys; ++k) {
         if (shadow_fns()[k]) traversal_kernels.push_back(reinterpret_cast<const void*>(shadow_fns()[k]));
     }
     for (const void* k : traversal_kernels) HIPCHK(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
@@ -1104,6 +1143,24 @@ int pbrs_set_pass_overlap(pbrs_ctx* c, int enabled) {
     return PBRS_OK;
 }
 
+int pbrse_set_entry_nodes(pbrs_ctx* c, int enabled) {
+    if (!c) return PBRS_E_INVALID;
+    c->entry_nodes = enabled != 0;
+    return PBRS_OK;
+}
+
+int pbrse_last_entry_info(pbrs_ctx* c, pbrs_entry_info* out) {
+    if (!c || !out) return PBRS_E_INVALID;
+    *out = pbrs_entry_info{};
+    if (!c->last_entry) return PBRS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->main_stream));
+    uint32_t v[4];
+    HIPCHK(c, hipMemcpy(v, static_cast<const char*>(c->buf[BUF_ENTRY_TABLE].p) + (size_t)c->last_entry_pixels * sizeof(pbrs_entry_record), sizeof v, hipMemcpyDeviceToHost));
+    *out = pbrs_entry_info{v[0], v[1], v[2], v[3]};
+    return PBRS_OK;
+}
+
 // Check, prepare and choose on the host (host/scene_prepare.h, host/kernel_choice.h), then bind, and only then touch the device: a
 // refusal leaves the context's previous scene in place.  A failing hipMalloc or copy leaves the context without a scene.
 int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
@@ -1159,6 +1216,10 @@ int pbrs_upload_scene(pbrs_ctx* c, const pbrs_scene_desc* d) {
     c->material_flags.resize(d->n_materials);
     for (uint32_t i = 0; i < d->n_materials; ++i) c->material_flags[i] = d->materials[i].flags;
     c->stack_depth = P.stack_depth;
+    c->entry_height = P.entry_height;
+    c->entry_rows = P.entry_rows;
+    c->entry_table = nullptr;
+    c->last_entry = false;
     c->has_scene = true;
     c->split_decision = 0;  // (the streams were synchronised above: no probe of the previous scene is in flight)
     c->split_probe_in_flight = false;
@@ -2292,6 +2353,7 @@ int pbrs_render_sample_radiance(pbrs_ctx* c, const pbrs_camera* cam, const pbrs_
     k.tiles8_per_row = 0u;  // one sample index, exported by pixel: slot = pixel
     Timer tm{c, false};
     HIPCHK(c, hipMemsetAsync(c->sum, 0, 3 * (size_t)P * sizeof(float), c->stream));
+    c->entry_table = nullptr;  // (no pre-pass here: every ray walks from the root)
     rc = run_pass(c, k, sample_index, 1, false, tm, false, RenderTargets{});
     if (rc) return rc;
     hipLaunchKernelGGL(k_export_radiance, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, cur(c).st, P, c->rgb_dev);

@@ -25,8 +25,11 @@ namespace {
 
 // The traversal kernels, one per valid key (host/kernel_choice.h: extend_key_ok, shadow_key_ok), in tables filled at compile time.
 template <uint32_t K>
-constexpr extend_fn_t extend_fn_of() {
-    if constexpr (extend_key_ok(K)) return &k_extend<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
+extend_fn_t extend_fn_of() {  // (no constant expression: the entry kernels are handed out under k_extend's pointer type)
+    if constexpr (K >= kTraversalKeys) {
+        if constexpr (extend_entry_ok(K - kTraversalKeys)) return reinterpret_cast<extend_fn_t>(static_cast<extend_entry_fn_t>(&k_extend<false, K - kTraversalKeys, EntryArgs>));
+        else return nullptr;
+    } else if constexpr (extend_key_ok(K)) return &k_extend<(K & kStatsKey) != 0u, (K & ~kStatsKey)>;
     else return nullptr;
 }
 template <uint32_t K>
@@ -49,7 +52,7 @@ const shadow_fn_t* shadow_table(std::integer_sequence<uint32_t, K...>) {
 
 namespace pbrs {
 
-const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
+const extend_fn_t* extend_fns() { return extend_table(std::make_integer_sequence<uint32_t, kExtendKeys>{}); }
 const shadow_fn_t* shadow_fns() { return shadow_table(std::make_integer_sequence<uint32_t, kTraversalKeys>{}); }
 intersect_fn_t intersect_fn(bool wide_any) { return wide_any ? &k_intersect_rays<true> : &k_intersect_rays<false>; }
 

@@ -91,6 +91,11 @@ GPU_MOTION_BLUR_FUNCTIONS = _table({
 }, with_device={
     "pbrsm_motion_blur": [P] * 7,
 })
+# The entry nodes' switch and report (include/pbrs_gpu.h, "entry nodes of the camera rays"), likewise, under the prefix pbrse_.
+GPU_ENTRY_FUNCTIONS = _table({
+    "pbrse_set_entry_nodes": [P, INT],
+    "pbrse_last_entry_info": [P, P],
+})
 HOST_FUNCTIONS = _table({
     "pbrs_host_scene_build": [P, C.POINTER(P)],
     "pbrs_host_scene_free": [P],
@@ -114,6 +119,7 @@ GPU_DESPECKLE_SYMBOLS = list(GPU_DESPECKLE_FUNCTIONS)
 GPU_BLOOM_SYMBOLS = list(GPU_BLOOM_FUNCTIONS)
 GPU_DOF_SYMBOLS = list(GPU_DOF_FUNCTIONS)
 GPU_MOTION_BLUR_SYMBOLS = list(GPU_MOTION_BLUR_FUNCTIONS)
+GPU_ENTRY_SYMBOLS = list(GPU_ENTRY_FUNCTIONS)
 _host = _gpu = _hip = None
 
 
@@ -149,7 +155,7 @@ def gpu_lib():
         if not os.path.exists(path):
             raise PbrsError(f"{path} is missing: the HIP extension must be built (make -C pbrs_amd/csrc); there is no CPU fallback")
         _gpu = _load(path, {**GPU_FUNCTIONS, **GPU_COMPARE_FUNCTIONS, **GPU_DESPECKLE_FUNCTIONS, **GPU_BLOOM_FUNCTIONS, **GPU_DOF_FUNCTIONS,
-                            **GPU_MOTION_BLUR_FUNCTIONS})
+                            **GPU_MOTION_BLUR_FUNCTIONS, **GPU_ENTRY_FUNCTIONS})
     return _gpu
 
 

@@ -2,7 +2,10 @@
 """Developer tool: static instruction mix and register use per kernel, from the device assembly of the library's translation units
 (pbrs_amd/csrc/Makefile, `asm`: the Makefile's flags and units, nothing repeated here).
 
-    python tools/isa_stats.py [--json PATH] [extra hipcc flags ...]     (CPU only; hipcc cross-compiles gfx950)
+    python tools/isa_stats.py [--json PATH] [--check-entry-waves] [extra hipcc flags ...]     (CPU only; hipcc cross-compiles gfx950)
+
+--check-entry-waves exits non-zero when an entry variant of k_extend (k_extend<.., EntryArgs>, device/entry_nodes.h) has fewer waves per
+SIMD than its plain kernel, or scratch: the keys whose variant would are listed in host/kernel_choice.h and are not instantiated.
 
 --json PATH also writes, per kernel, the static instruction mix bench.py prices the vector issue share with (pbrs_amd/roofline.py):
 vector instructions in all, those in a 32-bit encoding (`_e32`: VOP1 / VOP2 / VOPC forms without a literal — 2.7 issue cycles per
@@ -40,6 +43,9 @@ def demangle(names):
 def main():
     argv = sys.argv[1:]
     json_path = None
+    check_entry = "--check-entry-waves" in argv
+    if check_entry:
+        argv.remove("--check-entry-waves")
     if "--json" in argv:
         k = argv.index("--json")
         json_path = argv[k + 1]
@@ -82,6 +88,12 @@ def main():
         n = names[k].split("(")[0].replace("void ", "")
         print("%-44s %5d %5d %7d %4d | " % (n[:44], c["@NumVgprs"], c.get("@TotalNumSgprs", c["@NumSgprs"]), c["@ScratchSize"], c["@Occupancy"]) +
               " ".join("%7d" % c[f] for f in cols))
+    if check_entry:  # an entry variant of k_extend keeps its plain kernel's waves (host/kernel_choice.h, kEntryKeysLosingAWave) and has no scratch
+        occ = {names[k].split("(")[0].replace("void ", ""): (c["@Occupancy"], c["@ScratchSize"]) for k, c in kernels.items() if "@NumVgprs" in c}
+        bad = [n for n, (o, sc) in occ.items() if n.endswith(", EntryArgs>") and (sc != 0 or o < occ[n.replace(", EntryArgs>", ">")][0])]
+        if bad:
+            sys.exit("entry variants with fewer waves than their plain kernel, or with scratch: " + ", ".join(sorted(bad)))
+        print("entry variants: %d, each with its plain kernel's waves per SIMD and no scratch" % sum(n.endswith(", EntryArgs>") for n in occ))
     if json_path:
         import json
         sys.path.insert(0, ROOT)

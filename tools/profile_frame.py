@@ -17,6 +17,8 @@ def main():
     ap.add_argument("--frames", type=int, default=1)
     ap.add_argument("--strata", type=int, nargs=2, default=None)
     ap.add_argument("--no-warm", action="store_true")
+    ap.add_argument("--serial", action="store_true", help="every pass on one stream (pbrs_set_pass_overlap off): per-launch durations are exclusive times")
+    ap.add_argument("--entry-nodes", type=int, default=None, help="0: camera rays walk from the root (pbrse_set_entry_nodes)")
     a = ap.parse_args()
     import torch
 
@@ -28,6 +30,10 @@ def main():
     hs = pbrs_amd.HostScene(sb)
     ctx = pbrs_amd.Context(0)
     ctx.upload(hs)
+    if a.serial:
+        ctx.set_pass_overlap(False)
+    if a.entry_nodes is not None:
+        ctx.set_entry_nodes(bool(a.entry_nodes))
     out = torch.empty((cfg["height"], cfg["width"], 3), dtype=torch.float32, device="cuda:0")
     st = None
     for k in range(a.frames + (0 if a.no_warm else 1)):
